@@ -32,11 +32,16 @@ samples of the configs[0] and configs[1] shapes).
 
 `python bench.py --gpus N` without a torchrun environment starts its own N ranks
 (torch.distributed.run on 127.0.0.1) and relays rank 0's JSON line.
+
+`--dump-outputs DIR` (rank 0) writes what the last of the K timed steps handed back - its loss values and every model's
+state_dict after it - to DIR/<name>.npy, so that two builds can be compared output for output (the inputs, the initial
+parameters and the batch, are seeded).
 """
 import argparse
 import ctypes
 import json
 import os
+import re
 import sys
 import time
 
@@ -390,6 +395,29 @@ def dp_path_world_of_one(args, headline_ms):
         return {"error": repr(e)[:200]}
 
 
+def dump_outputs(path, trainer, vals, limit=60 << 20):
+    """`--dump-outputs`: the loss values of one step (loss.<key>.npy, float64) and the state_dict of every model after it
+    (<model>.<key>.npy: parameters and buffers, float32; float64 and integer buffers as float64).  Should the arrays
+    exceed `limit` bytes in all (64 MB less room for the files' headers), each is cut to the same fraction of its flattened
+    elements, picked by a fixed seed."""
+    out = {f"loss.{k}": np.asarray(float(v), dtype=np.float64) for k, v in sorted(vals.items())}
+    for name, m in trainer.model.items():
+        for k, v in m.state_dict().items():
+            a = v.detach().cpu()
+            out[f"{name}.{k}"] = (a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()).numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > limit:
+        rs = np.random.RandomState(0)
+        for k, a in out.items():
+            n = max(1, a.size * limit // total)
+            if n < a.size:
+                out[k] = a.reshape(-1)[np.sort(rs.choice(a.size, n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, re.sub(r"[^A-Za-z0-9._-]", "_", k) + ".npy"), a)
+    return {"dir": path, "arrays": len(out), "bytes": sum(a.nbytes for a in out.values()), "sampled": total > limit}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -407,7 +435,11 @@ def main():
                          "trainer.train_graphed / conf hip_graph; N>1: a chain of graphs with the collectives between them)")
     ap.add_argument("--force-dist", action="store_true",
                     help="N=1 only: a process group of one rank (backend nccl = RCCL) with the data-parallel code path on")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss values and the models' state after the last timed step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(respawn_under_torchrun(args.gpus))
@@ -475,17 +507,23 @@ def main():
         if not parallel.agree_on_capture(graphed is not None):
             graphed = None
 
+    last = {}  # what the last step of a run() handed back
+
     def run(k, replay=True):
         barrier()
         t0 = time.perf_counter()
         for _ in range(k):
-            graphed.step() if (graphed is not None and replay) else trainer.train(batch)
+            last["vals"] = graphed.step() if (graphed is not None and replay) else trainer.train(batch)
         barrier()
         return time.perf_counter() - t0
 
+    vals = None
     for _ in range(args.warmup):
         vals = graphed.step() if graphed is not None else trainer.train(batch)
     dt = run(args.steps)
+    if vals is None:  # (--warmup 0)
+        vals = last["vals"]
+    dump = dump_outputs(args.dump_outputs, trainer, last["vals"]) if args.dump_outputs and rank == 0 else None
     dt_eager = run(args.steps, replay=False) if graphed is not None else dt
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if torch.distributed.get_backend() == "nccl" else "cpu")
@@ -518,6 +556,8 @@ def main():
     }
     if args.force_dist:
         out["forced_dist_world_of_one"] = True
+    if dump is not None:
+        out["dump_outputs"] = dump
 
     if not args.no_roofline:
         L = _lib.lib()
