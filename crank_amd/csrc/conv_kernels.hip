@@ -831,6 +831,8 @@ int launch_weight_prep_multi(const NetRefs& R, int total_entries, int nmax, hipS
   if (total_entries <= 16) {
     // a small net (3 - 8 convs of 64 channels): 8-row bands - twice the workgroups, half the rows each wave walks in turn
     // (the kernel is a chain of short phases, 11 us for 40 k parameters; any band that is a multiple of 8 writes the same planes)
+    // an 8-row band of a cin * k in (2048, 2560] still needs more than the default 64 KB of dynamic LDS
+    if (wp_set_lds((const void*)weight_prep_multi_kernel<8>, lds / 2) != CRK_OK) return CRK_ERR_HIP;
     hipLaunchKernelGGL(weight_prep_multi_kernel<8>, dim3(total_entries, 128 / 8), dim3(256), lds / 2, s, R);
     CRK_CHECK_LAUNCH();
     return CRK_OK;

@@ -9,6 +9,32 @@ from ... import ops
 from .flat import FlatModel, net_keys
 
 KIND_GENERATOR, KIND_RESIDUAL_D, KIND_PLAIN = 0, 1, 2
+MAX_CHANNELS = 128  # input, output and conditioning channels of one stack (crk_net_create)
+MAX_KERNEL_SIZE = 5
+MAX_PLAIN_LAYERS = 8  # plain chains: layer i has dilation i; deeper chains' data gradients are wrong
+
+
+def _pad32(c):
+    return (c + 31) // 32 * 32
+
+
+def wgrad_one_tap_group(cout, cin, k, dil):
+    """Whether the weight-gradient kernel takes all k taps of a conv in ONE table entry (conv_kernels.hip wgrad_expand:
+    at most 10 MFMA tiles per wave, and the conv-input rows of a 64-frame chunk within 11 passes of the workgroup).
+    Several tap groups give wrong weight gradients ("Kernel sizes above 5")."""
+    nct, nit = _pad32(cout) // 32, _pad32(cin) // 32
+    nctp = 1 if nct <= 1 else (2 if nct <= 2 else 4)
+    rows_per_pass = 256 // (_pad32(cin) // 4)
+    return k * nit <= 10 * (4 // nctp) and -(-(64 + (k - 1) * dil) // rows_per_pass) <= 11
+
+
+def _conv_shapes(kind, cin, cout, layers, stacks, conv_ch):
+    """(cout, cin, dilation) of every conv with more than one tap (net.hip crk_net_create)."""
+    if kind == KIND_PLAIN:  # dilation = layer index (1 for the first and the last conv)
+        chans = [cin] + [conv_ch] * (layers - 1)
+        return [(cout if i == layers - 1 else conv_ch, chans[i], 1 if i in (0, layers - 1) else i) for i in range(layers)]
+    lps = layers // max(stacks, 1)  # gated blocks: the dilated 64 -> 128 conv, dilation 2^(l mod layers per stack)
+    return [(128, 64, 2 ** (l % lps)) for l in range(layers)]
 
 
 class HipStack:
@@ -18,6 +44,22 @@ class HipStack:
                  conv_channels=64, use_causal_conv=False, bias=True, negative_slope=0.2, dropout=0.0):
         self.kind = kind
         self.layers, self.stacks, self.kernel_size = layers, stacks, kernel_size
+        # the library's channel limit (crk_net_create): refused here with its reason instead of as a failed handle
+        for name, ch in (("in_channels", in_channels), ("out_channels", out_channels), ("aux_channels", aux_channels)):
+            if ch > MAX_CHANNELS:
+                raise NotImplementedError(f"{name}={ch}: the HIP conv stacks take at most {MAX_CHANNELS} channels")
+        # wider kernels compute wrong values ("Kernel sizes above 5"): refused, not run
+        if kernel_size > MAX_KERNEL_SIZE:
+            raise NotImplementedError(f"kernel_size={kernel_size}: the HIP conv stacks are verified up to kernel_size "
+                                      f"{MAX_KERNEL_SIZE} only")
+        if kind == KIND_PLAIN and layers > MAX_PLAIN_LAYERS:
+            raise NotImplementedError(f"layers={layers}: plain conv chains are verified up to {MAX_PLAIN_LAYERS} layers only "
+                                      f"(dilation {MAX_PLAIN_LAYERS - 2})")
+        for cout, cin, dil in _conv_shapes(kind, in_channels, out_channels, layers, stacks, conv_channels):
+            if not wgrad_one_tap_group(cout, cin, kernel_size, dil):
+                raise NotImplementedError(
+                    f"a {cin} -> {cout} conv of kernel {kernel_size} at dilation {dil}: its weight gradient would be split "
+                    f"into tap groups, which the HIP conv stacks do not compute correctly yet (DESIGN.md)")
         self.net = ops.HipNet(
             kind=kind, in_ch=in_channels, out_ch=out_channels, kernel_size=kernel_size, layers=layers,
             stacks=max(stacks, 1), res_ch=64, gate_ch=128, skip_ch=64, aux_ch=max(aux_channels, 0),

@@ -12,7 +12,7 @@ import torch
 from ... import ops, parallel
 from .flat import FlatModel
 from .mlfb import LogMelFilterBankLayer
-from .pwg import KIND_GENERATOR, HipStack
+from .pwg import KIND_GENERATOR, MAX_CHANNELS, HipStack
 
 
 class Quantizer:
@@ -195,6 +195,29 @@ def flush_ema(pending):
     pending.clear()
 
 
+# codebook shapes the quantizer kernels take (vq_kernels.hip: crk_vq_forward instantiates the search for these code
+# dimensions; the EMA statistics and blend take at most 4096 codes)
+VQ_DIMS = (16, 32, 64, 128)
+VQ_EMA_MAX_CODES = 4096
+
+
+def check_vq_shapes(conf):
+    """Refuse, at construction, the configurations the kernels cannot run - instead of a failed launch at the first
+    forward or a failed stack handle deep inside the model."""
+    nst = conf["n_vq_stacks"]
+    for n in range(nst):
+        D, K = conf["emb_dim"][n], conf["emb_size"][n]
+        if D not in VQ_DIMS:
+            raise NotImplementedError(f"emb_dim[{n}] = {D}: the quantizer kernels support emb_dim in {VQ_DIMS}")
+        if conf["ema_flag"] and K > VQ_EMA_MAX_CODES:
+            raise NotImplementedError(f"emb_size[{n}] = {K}: the EMA codebook update supports at most "
+                                      f"{VQ_EMA_MAX_CODES} codes (ema_flag: true)")
+    d_in = sum(conf["emb_dim"][i] for i in range(nst))
+    if d_in > MAX_CHANNELS:
+        raise NotImplementedError(f"n_vq_stacks = {nst}: the first decoder's input is sum(emb_dim) = {d_in} channels, "
+                                  f"above the {MAX_CHANNELS}-channel limit of the HIP conv stacks")
+
+
 class VQVAE2(FlatModel):
     can_skip_decoder = True  # forward(need_decoded=False)
     can_commit = True        # forward(want_commit=True, commit_mask=...)
@@ -211,6 +234,7 @@ class VQVAE2(FlatModel):
             raise NotImplementedError("use_sinc_conv is a dead branch in the reference "
                                       "(crank/net/module/vqvae2.py:76-82 cannot construct its layer)")
         nst = conf["n_vq_stacks"]
+        check_vq_shapes(conf)
         self.encoders, self.decoders, self.quantizers = [], [], []
         entries, off = [], 0
 

@@ -172,6 +172,48 @@ def gen_quantizer_full():
                         x_seed=np.array(1234), x_shape_BDT=np.array([B, D, T]))
 
 
+def gen_quantizer_shapes():
+    """The reference Quantizer at the (D, K) the default configuration never builds (tests/helpers.py QUANTIZER_SHAPES):
+    the indices of three EMA calls and of a final search (N = 8 000 frames each), and the EMA state after the three calls
+    - ema_size in full, ema_w / weight at the probed codes, every code's float64 sum over its dimensions.  The inputs
+    are regenerated from tests/helpers.py quantizer_shape_inputs."""
+    from tests.helpers import QUANTIZER_SHAPES, quantizer_shape_inputs
+
+    # the reference EMA's matmul sums in an order that depends on the thread count: one thread makes the fixture
+    # regenerate bit for bit on any machine
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    out = {}
+    for D, K in QUANTIZER_SHAPES:
+        w0, size0, ema_w0, xs, probe = quantizer_shape_inputs(D, K)
+        q = Quantizer(D, K, ema_flag=True, bdt_flag=True)
+        q.train()
+        with torch.no_grad():
+            q.embedding.weight.copy_(torch.from_numpy(w0))
+            q.ema_size.copy_(torch.from_numpy(size0))
+            q.ema_w.copy_(torch.from_numpy(ema_w0))
+        tag = f"D{D}_K{K}"
+        gaps = []
+        for it, x in enumerate(xs):
+            w = np_(q.embedding.weight).astype(np.float64)
+            xf = x.transpose(0, 2, 1).reshape(-1, D).astype(np.float64)
+            d64 = np.sort((w ** 2).sum(1)[None] - 2 * xf @ w.T, axis=1)
+            gaps.append(float((d64[:, 1] - d64[:, 0]).min()))
+            e, qx, idx = q(torch.from_numpy(x), use_ema=it < 3)
+            out[f"{tag}/idx{it}"] = np_(idx).astype(np.int16)
+            if it == 2:
+                out[f"{tag}/ema_size"] = np_(q.ema_size)
+                out[f"{tag}/ema_w_probe"] = np_(q.ema_w)[:, probe]
+                out[f"{tag}/w_probe"] = np_(q.embedding.weight)[probe]
+                out[f"{tag}/ema_w_sums"] = np_(q.ema_w).astype(np.float64).sum(0)
+                out[f"{tag}/w_sums"] = np_(q.embedding.weight).astype(np.float64).sum(1)
+        out[f"{tag}/probe"] = probe
+        print(f"quantizer_shapes {tag}: distinct codes of the first call {len(np.unique(out[tag + '/idx0']))}, "
+              f"smallest fp64 distance gap between the two nearest codes per call {['%.1e' % g for g in gaps]}")
+    torch.set_num_threads(threads)
+    np.savez_compressed(os.path.join(HERE, "quantizer_shapes.npz"), **out)
+
+
 # ----------------------------------------------------------------------------
 def gen_losses():
     out = {}
@@ -340,9 +382,12 @@ def run_step(trainer_type, tag, conf_over, B=2, T=96, n_spkrs=2, seed=77, steps=
         dec_h, spkrvec = trainer._get_dec_h(batch)
         o = models["G"].forward(batch["raw"] if conf["use_raw"] else batch["in_feats"], enc_h, dec_h, spkrvec=spkrvec, use_ema=False)
         out["post_decoded"] = np_(o["decoded"])
-        out["post_qidx0"], out["post_qidx1"] = np_(o["qidx"][0]), np_(o["qidx"][1])
-        out["dec_h"] = np_(dec_h)
-        out["spkrvec"] = np_(spkrvec)
+        for i, qi in enumerate(o["qidx"]):
+            out[f"post_qidx{i}"] = np_(qi)
+        if dec_h is not None:  # (decoder_f0: false and an embedding: no decoder conditioning besides spkrvec)
+            out["dec_h"] = np_(dec_h)
+        if spkrvec is not None:  # (one-hot speaker codes: the reference has no embedding vector)
+            out["spkrvec"] = np_(spkrvec)
     if scaler is not None:
         out["mlfb_scaler_mean"], out["mlfb_scaler_var"] = scaler["mlfb"].mean_, scaler["mlfb"].var_
     out.update({k: v for k, v in summarize_state(models).items() if "preprocess_layer." not in k})
@@ -572,13 +617,15 @@ def gen_convert(B=4, T=200, n_spkrs=14, seed=11):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["quantizer", "quantizer_full", "losses", "stft", "misc", "dataset", "steps", "convert"]
+    which = sys.argv[1:] or ["quantizer", "quantizer_full", "quantizer_shapes", "losses", "stft", "misc", "dataset", "steps", "convert"]
     if "convert" in which:
         gen_convert()
     if "quantizer" in which:
         gen_quantizer()
     if "quantizer_full" in which:
         gen_quantizer_full()
+    if "quantizer_shapes" in which:
+        gen_quantizer_shapes()
     if "losses" in which:
         gen_losses()
     if "stft" in which:
@@ -611,3 +658,13 @@ if __name__ == "__main__":
         # (crank/bin/train.py:94-118), update_D conditioned on the conversion target (trainer_stargan.py:82-118)
         run_step("stargan", "stargan_mcep", dict(MCEP, **nodrop, n_steps_gan_start=0, use_cyclic_training=True,
                                                  n_steps_cycle_start=0), B=3, T=128, n_spkrs=12)
+    if "configs" in which or "steps" in which:
+        # the configuration knobs of default.yml:88-106 at values the default step never builds (tests/helpers.py STEP_CASES)
+        nodrop = {"discriminator_dropout": 0.0}
+        run_step("vqvae", "vqvae_nvq1", {"n_vq_stacks": 1})
+        run_step("vqvae", "vqvae_cb1024", {"emb_size": [1024, 1024]})
+        run_step("vqvae", "vqvae_dim32", {"emb_dim": [32, 32]})
+        run_step("vqvae", "vqvae_onehot", {"use_spkr_embedding": False}, n_spkrs=4)
+        run_step("vqvae", "vqvae_nodecf0", {"decoder_f0": False})
+        # mcep_vqvae_24000.yml: 36-dim mel-cepstra
+        run_step("lsgan", "lsgan_mcep36", dict(MCEP, input_size=36, output_size=36, **nodrop, n_steps_gan_start=0))

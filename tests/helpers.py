@@ -68,7 +68,40 @@ STEP_CASES = {
     "stargan_mcep": ("stargan", {"discriminator_dropout": 0.0, "n_steps_gan_start": 0, "use_cyclic_training": True,
                                  "n_steps_cycle_start": 0, "input_feat_type": "mcep", "output_feat_type": "mcep",
                                  "input_size": 34, "output_size": 34, "use_mcep_0th": False, "ignore_scaler": ["mcep"]}, 1),
+    # configuration knobs at values the default step never builds (tests/golden/make_golden.py "configs")
+    "vqvae_nvq1": ("vqvae", {"n_vq_stacks": 1}, 1),
+    "vqvae_cb1024": ("vqvae", {"emb_size": [1024, 1024]}, 1),
+    "vqvae_dim32": ("vqvae", {"emb_dim": [32, 32]}, 1),
+    "vqvae_onehot": ("vqvae", {"use_spkr_embedding": False}, 1),
+    "vqvae_nodecf0": ("vqvae", {"decoder_f0": False}, 1),
+    "lsgan_mcep36": ("lsgan", {"discriminator_dropout": 0.0, "n_steps_gan_start": 0, "input_feat_type": "mcep",
+                               "output_feat_type": "mcep", "input_size": 36, "output_size": 36, "use_mcep_0th": False,
+                               "ignore_scaler": ["mcep"]}, 1),
 }
+
+
+# quantizer shapes off the default (D, K) = (64, 512): the frame-per-lane search kernel (vq_forward_kernel<D>, codebook in
+# LDS chunks) and the per-quantizer EMA path (tests/golden/quantizer_shapes.npz, tests/golden/make_golden.py)
+QUANTIZER_SHAPES = [(16, 2048), (32, 1024), (32, 512), (128, 256), (128, 1000), (64, 513), (64, 4096)]
+QUANTIZER_SHAPE_BDT = (4, 2000)  # (B, T) of every call: N = 8 000 frames
+QUANTIZER_SHAPE_PROBE = 32       # codes whose ema_w / weight rows the fixture stores in full (the last 8 are dead codes)
+
+
+def quantizer_shape_inputs(D, K):
+    """The deterministic state and inputs of one quantizer_shapes.npz case: a codebook in use (7/8 of the codes with
+    trained-like statistics, ema_w = size * code; the last K/8 codes never used so far - zero size, randn ema_w, which the
+    first EMA update throws to ~1e5, quirk Q2), the four (B, D, T) inputs (three EMA calls, one search), and the probed
+    codes."""
+    rs = np.random.RandomState(1000 * D + K)
+    alive = K - K // 8
+    w0 = (0.8 * rs.standard_normal((K, D))).astype(np.float32)
+    size0 = np.where(np.arange(K) < alive, 20.0, 0.0).astype(np.float32)
+    ema_w0 = rs.standard_normal((D, K)).astype(np.float32)
+    ema_w0[:, :alive] = (w0[:alive] * size0[:alive, None]).T
+    B, T = QUANTIZER_SHAPE_BDT
+    xs = [rs.standard_normal((B, D, T)).astype(np.float32) for _ in range(4)]
+    probe = np.concatenate([np.sort(rs.choice(alive, QUANTIZER_SHAPE_PROBE - 8, replace=False)), np.arange(K - 8, K)])
+    return w0, size0, ema_w0, xs, probe
 
 
 class MlfbScaler:

@@ -177,6 +177,8 @@ def _check_standalone(prod, orac, cin, B, T, precision, lengths=None, aux_ch=0, 
     dict(in_channels=80, out_channels=14, kernel_size=5, layers=8),    # speaker classifier C (train.py:78-89)
     dict(in_channels=128, out_channels=14, kernel_size=3, layers=3),   # SPKRADV classifier (spkradv.py:49-60)
     dict(in_channels=34, out_channels=2, kernel_size=3, layers=2),
+    dict(in_channels=36, out_channels=2, kernel_size=5, layers=8),     # speaker classifier C on 36-dim mcep
+    dict(in_channels=34, out_channels=12, kernel_size=5, layers=8),    # ... on 34-dim mcep, 12 speakers
 ])
 def test_plain_stack(cfg, precision):
     from crank_amd.net.module.pwg import ParallelWaveGANDiscriminator
@@ -193,6 +195,7 @@ def test_plain_stack(cfg, precision):
 @pytest.mark.parametrize("cfg", [
     dict(in_channels=113, out_channels=1, kernel_size=5, layers=8, stacks=4),   # D (train.py:108-118)
     dict(in_channels=67, out_channels=15, kernel_size=3, layers=2, stacks=1),
+    dict(in_channels=69, out_channels=1, kernel_size=5, layers=8, stacks=4),    # D on 36-dim mcep (36 + 1 + 32)
 ])
 def test_residual_discriminator(cfg, precision):
     from crank_amd.net.module.pwg import ResidualParallelWaveGANDiscriminator
@@ -283,7 +286,8 @@ class _GenStack:
             def __init__(self):
                 super().__init__()
                 self.stack = HipStack(KIND_GENERATOR, kw["in_channels"], kw["out_channels"], kw["kernel_size"], kw["layers"],
-                                      stacks=kw["stacks"], aux_channels=kw["aux_channels"], bias=True)
+                                      stacks=kw["stacks"], aux_channels=kw["aux_channels"], bias=True,
+                                      use_causal_conv=kw.get("use_causal_conv", False))
                 self._alloc(self.stack.entries("", 0), self.stack.n_params, "cuda")
                 self.stack.bind(self, 0)
                 self.stack.init_parameters()

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import REPO, golden
+from tests.helpers import QUANTIZER_SHAPES, REPO, golden, quantizer_shape_inputs
 
 
 # ------------------------------------------------------------------ oracle vs goldens
@@ -35,6 +35,29 @@ def test_oracle_quantizer_matches_reference_quantizer():
     q2.embedding.weight.data.copy_(torch.from_numpy(fx["tie_w"]))
     e, qx, idx = q2(torch.from_numpy(fx["tie_x"]))
     assert np.array_equal(idx.numpy(), fx["tie_idx"])
+
+
+@pytest.mark.parametrize("D,K", QUANTIZER_SHAPES)
+def test_oracle_quantizer_matches_reference_quantizer_at_other_shapes(D, K):
+    """quantizer_shapes.npz (the reference Quantizer at the (D, K) the default configuration never builds, 8 000 frames
+    per call): the oracle gives every index of the three EMA calls and of the search after them, and the EMA state."""
+    from oracle.modules import OracleQuantizer
+
+    fx = golden("quantizer_shapes.npz")
+    tag = f"D{D}_K{K}"
+    w0, size0, ema_w0, xs, probe = quantizer_shape_inputs(D, K)
+    assert np.array_equal(probe, fx[f"{tag}/probe"])
+    q = OracleQuantizer(D, K, ema_flag=True, bdt_flag=True).train()
+    q.embedding.weight.data.copy_(torch.from_numpy(w0))
+    q.ema_size.copy_(torch.from_numpy(size0))
+    q.ema_w.data.copy_(torch.from_numpy(ema_w0))
+    for it, x in enumerate(xs):
+        e, qx, idx = q(torch.from_numpy(x), use_ema=it < 3)
+        assert np.array_equal(idx.numpy(), fx[f"{tag}/idx{it}"]), f"indices differ at call {it}"
+        if it == 2:
+            np.testing.assert_allclose(q.ema_size.numpy(), fx[f"{tag}/ema_size"], rtol=1e-6)
+            np.testing.assert_allclose(q.ema_w.numpy()[:, probe], fx[f"{tag}/ema_w_probe"], rtol=1e-5, atol=1e-6)
+            np.testing.assert_allclose(q.embedding.weight.detach().numpy()[probe], fx[f"{tag}/w_probe"], rtol=1e-5, atol=1e-6)
 
 
 def test_oracle_vq_matches_reference_at_benchmark_size():
