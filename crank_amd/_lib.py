@@ -109,6 +109,11 @@ SIGNATURES = {
     "crk_decode_f0": (I, [P, P, I, I, P, P, D, D, I, P, P, P, P, P, P]),
     "crk_mcd_scratch_bytes": (LL, [I, I, I, I, I]),
     "crk_mcd_fastdtw": (I, [P, P, P, P, I, I, I, I, I, P, P, P, LL, P, P, P]),
+    "crk_voc_create": (P, [I, I, I, I, P, I, P]),
+    "crk_voc_destroy": (None, [P]),
+    "crk_voc_workspace_bytes": (LL, [P, I, I]),
+    "crk_voc_forward": (I, [P, P, P, I, I, P, P, P, LL, I, P]),
+    "crk_voc_upsample": (I, [P, P, P, I, I, P, P, LL, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

@@ -1134,6 +1134,8 @@ extern "C" long long crk_net_scratch_bytes(void* h, int B, int T) {
   return (q.need_s + q.need_p) * 4;
 }
 extern "C" long long crk_debug_alloc_count(void) { return g_net_allocs; }
+// vocoder_kernels.hip counts its handles' allocations here too
+long long crk_count_alloc_(void) { return ++g_net_allocs; }
 // which kernel generation the compute entry points pick for a batch shape (the predicates they share): bit 0 the generator
 // stack runs channel-split in plain bf16 (stack2_fwd_kernel / stack2_bwd_kernel), bit 1 its bf16x3f forward runs on the
 // channel-split split-operand kernel (stack2x_fwd_kernel), bit 2 the discriminator's blocks and chain run channel-split,

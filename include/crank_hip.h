@@ -430,6 +430,35 @@ int crk_debug_vq_flags(unsigned long long* host_out3, int reset);
  * pass in place no kernel finds its producer's output in a cache (tools/mall_ab.sh). */
 int crk_debug_flush_before(long long bytes);
 
+/* ---- Parallel WaveGAN vocoder inference (recipe stage 6) ----------------------
+ * Replaces `parallel-wavegan-decode` (egs/vaevc/template/run.sh:217-226, voc=PWG, run.sh:39): the third-party
+ * ParallelWaveGANGenerator.inference(c, x) with a ConvInUpsampleNetwork, non-causal, 64 / 128 / 64 channels, kernel 3,
+ * for a ragged batch of utterances, forward only.
+ *
+ * crk_voc_create: one handle per generator; `params` is a HOST fp32 block with weight norm already folded (g v / ||v||),
+ * torch layouts, in this order:
+ *   first_conv weight [64], bias [64]; upsample_net.conv_in weight [aux][aux][2 win + 1];
+ *   per upsample scale s: the (1, 2s+1) Conv2d kernel [2s + 1];
+ *   per layer: conv weight [128][64][3], conv bias [128], conv1x1_aux weight [128][aux], conv1x1_out weight [64][64],
+ *              bias [64], conv1x1_skip weight [64][64], bias [64];
+ *   last_conv_layers.1 weight [64][64], bias [64]; last_conv_layers.3 weight [64], bias [1].
+ * Lays the weights out for the kernels and allocates the handle's device memory (this is the one allocation; it
+ * synchronises the device).  NULL on an unsupported configuration: aux > 128, a scale outside 1..16, more than 8 scales.
+ *
+ * c: fp32 [total_frames][aux] row-major, frames of utterance u = rows frame_offsets[u] .. frame_offsets[u+1]-1
+ * (frame_offsets: DEVICE int64 [n_utts + 1], frame_offsets[0] = 0, every utterance >= 1 frame); noise / out: fp32
+ * [total_frames * hop], the samples of utterance u at frame_offsets[u] * hop.  workspace: device memory of at least
+ * crk_voc_workspace_bytes(voc, n_utts, total_frames) bytes.  The compute entries never allocate.
+ * flags: CRK_FLAG_PRECISE - split hi + lo bf16 operands (bf16x3; forward only, so bf16x3f is the same); else plain bf16. */
+void* crk_voc_create(int layers, int stacks, int aux_ch, int aux_window, const int* scales, int n_scales, const float* params);
+void crk_voc_destroy(void* voc);
+long long crk_voc_workspace_bytes(void* voc, int n_utts, int total_frames);
+int crk_voc_forward(void* voc, const float* c, const long long* frame_offsets, int n_utts, int total_frames,
+                    const float* noise, float* out, void* workspace, long long workspace_bytes, int flags, void* stream);
+/* the aux path alone (conv_in + upsampling network, fp32): out fp32 [total_frames * hop][aux] */
+int crk_voc_upsample(void* voc, const float* c, const long long* frame_offsets, int n_utts, int total_frames, float* out,
+                     void* workspace, long long workspace_bytes, void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 
