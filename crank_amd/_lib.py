@@ -114,6 +114,13 @@ SIGNATURES = {
     "crk_voc_workspace_bytes": (LL, [P, I, I]),
     "crk_voc_forward": (I, [P, P, P, I, I, P, P, P, LL, I, P]),
     "crk_voc_upsample": (I, [P, P, P, I, I, P, P, LL, P]),
+    "crk_world_create": (P, [I, I, D, D, I, I, I]),
+    "crk_world_destroy": (None, [P]),
+    "crk_world_reserve": (I, [P, LL]),
+    "crk_world_workspace_bytes": (LL, [P, I, LL, LL]),
+    "crk_world_synthesis": (I, [P, P, P, P, P, I, I, P, P, I, LL, LL, LL, P, P, P, LL, P]),
+    "crk_world_frames": (I, [P, P, P, P, I, I, LL, P, P, P, LL, P]),
+    "crk_world_pulses": (I, [P, P, P, P, I, P, P, P, P, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

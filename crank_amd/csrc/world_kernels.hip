@@ -1,0 +1,687 @@
+// WORLD waveform synthesis for mel-cepstral models on the device (recipe stage 5 with output_feat_type mcep; gfx950).
+//
+// Replaces the reference's world2wav (sprocket Synthesizer.synthesis: mod_power, pysptk mc2sp, pyworld
+// decode_aperiodicity + synthesize) for a ragged batch of utterances, all in float64.  The oracle is the CPU restatement
+// tests/world_synth_ref.py; parity with pyworld / pysptk is unpinned.  Structure:
+//  * world_energy_kernel: one wave per (frame, mcep or rmcep): c = freqt(mc, 1024, -alpha) through the precomputed
+//    matrix, then SPTK c2ir's recursion h[n] = sum_k k c_k h[n-k] / n with h in LDS and a wave reduction per n; writes
+//    sum h^2 (mc2e).  Only with rmcep (power modification).
+//  * world_frame_kernel: one thread per (frame, bin): log sp = W . mc' (W = the cosine sum of mc2sp composed with freqt,
+//    mc'_0 = mc_0 + log(e_r / e_cv) / 2) and the decoded aperiodicity.
+//  * world_timebase_kernel: one workgroup per utterance.  F0 / vuv interpolated in parallel per 2048-sample chunk, the
+//    phase accumulated by one thread in sample order (fp contract off: pulse positions are bit-identical to the
+//    restatement), fmod, pulse detection and an ordered compaction into the utterance's slots.
+//  * world_pulse_kernel: one workgroup per pulse: envelope and ratio, both minimum-phase spectra, the noise spectrum and
+//    both inverse transforms in four 1024-point fp64 LDS FFTs (two real sequences per complex transform); writes the
+//    pulse's response.
+//  * world_ola_kernel: one thread per output sample sums the responses that cover it, in pulse order (no atomics).
+#include "common.h"
+#include "../../include/crank_hip.h"
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <vector>
+
+#define W_N 1024
+#define W_K (W_N / 2 + 1)
+#define W_LOGN 10
+#define W_IRLEN 1024
+#define W_MAX_ORDER1 128
+#define W_CHUNK 2048
+#define W_THREADS 256
+#define W_SAFE 1e-12
+#define W_DEFAULT_F0 500.0
+
+long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
+
+struct World {
+  int fs, m1, bands, capacity;
+  double shiftms, fp, alpha;
+  double* tables;  // one device block: at [m1][W_IRLEN], wt [m1][W_K], tw cos [W_N/2], tw sin [W_N/2], dc [W_N]
+  const double *at, *wt, *twc, *tws, *dcw;
+  double* noise;
+  long long noise_len;
+};
+
+static int w_bands(int fs) { return (int)(fmin(15000.0, fs / 2.0 - 3000.0) / 3000.0); }
+static size_t w_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---------------------------------------------------------------------------------------------------------- helpers
+__device__ __forceinline__ double w_wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// deterministic workgroup sum (W_THREADS threads): wave sums, then the four partials in order
+__device__ double w_block_sum(double v, double* red) {
+  v = w_wave_sum(v);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wv] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ int w_find(const long long* off, int n, long long v) {  // largest u with off[u] <= v
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= v) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// cos(x) for x in [0, pi] as the Taylor polynomial in x^2 (16 terms, Horner), each operation rounded on its own.
+// WORLD's delay takes sin as sqrt(1 - cos^2), which turns a last-bit difference of cos at small x into a large one of
+// sin; tests/world_synth_ref.py evaluates the same polynomial, so both get the same bits.
+static __constant__ double W_COS[16] = {1.0, -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05, -2.755731922398589e-07, 2.08767569878681e-09, -1.1470745597729725e-11, 4.779477332387385e-14, -1.5619206968586225e-16, 4.110317623312165e-19, -8.896791392450574e-22, 1.6117375710961184e-24, -2.4795962632247976e-27, 3.279889237069838e-30, -3.7699876288159054e-33};
+__device__ double w_cos(double x) {
+#pragma clang fp contract(off)
+  const double x2 = x * x;
+  double r = W_COS[15];
+  for (int n = 14; n >= 0; --n) r = r * x2 + W_COS[n];
+  return r;
+}
+
+__device__ __forceinline__ int w_brev(int n) { return (int)(__brev((unsigned)n) >> (32 - W_LOGN)); }
+
+// in-place radix-2 DIT FFT of W_N points in LDS, input in bit-reversed order; sign -1 forward, +1 inverse (unnormalised)
+__device__ void w_fft(double2* x, const double* twc, const double* tws, double sign) {
+  for (int half = 1; half < W_N; half <<= 1) {
+    const int stride = W_N / (2 * half);
+    for (int b = threadIdx.x; b < W_N / 2; b += W_THREADS) {
+      const int pos = b & (half - 1);
+      const int i = ((b - pos) << 1) + pos, j = i + half;
+      const double c = twc[pos * stride], s = sign * tws[pos * stride];
+      const double2 xj = x[j], xi = x[i];
+      const double tr = c * xj.x - s * xj.y, ti = c * xj.y + s * xj.x;
+      x[j] = make_double2(xi.x - tr, xi.y - ti);
+      x[i] = make_double2(xi.x + tr, xi.y + ti);
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- per frame
+// mc2e of every frame of mcep (which 0) and rmcep (which 1): e[f * 2 + which].  One wave per item; lane l holds
+// k c_k for k = l + 64 j in registers and reads h from its wave's LDS row.
+__global__ __launch_bounds__(W_THREADS) void world_energy_kernel(const double* __restrict__ mcep,
+                                                                 const double* __restrict__ rmcep, int m1, long long F,
+                                                                 const double* __restrict__ at, double* __restrict__ e) {
+  __shared__ double hs[W_THREADS / 64][W_IRLEN];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long item = (long long)blockIdx.x * (W_THREADS / 64) + wv;
+  if (item >= 2 * F) return;
+  const long long f = item >> 1;
+  const double* mc = ((item & 1) ? rmcep : mcep) + f * m1;
+  double* h = hs[wv];
+  double kc[W_IRLEN / 64];
+#pragma unroll
+  for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] = 0.0;
+  for (int i = 0; i < m1; ++i) {
+    const double v = mc[i];
+    const double* row = at + (size_t)i * W_IRLEN + lane;
+#pragma unroll
+    for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] = fma(row[64 * j], v, kc[j]);
+  }
+  const double c0 = __shfl(kc[0], 0);
+#pragma unroll
+  for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] *= (double)(lane + 64 * j);
+  double h0 = exp(c0);
+  if (lane == 0) h[0] = h0;
+  double en = h0 * h0;
+  for (int n = 1; n < W_IRLEN; ++n) {
+    __builtin_amdgcn_wave_barrier();
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < W_IRLEN / 64; ++j) {
+      const int k = lane + 64 * j;
+      if (64 * j <= n && k >= 1 && k <= n) acc = fma(kc[j], h[n - k], acc);
+    }
+    const double hn = w_wave_sum(acc) / n;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) h[n] = hn;
+    en = fma(hn, hn, en);
+  }
+  if (lane == 0) e[item] = en;
+}
+
+// sp and decoded ap of every frame: one thread per (frame, bin)
+__global__ void world_frame_kernel(const double* __restrict__ mcep, const double* __restrict__ cap, int m1, int bands,
+                                   long long F, int fs, const double* __restrict__ wt, const double* __restrict__ e,
+                                   double* __restrict__ sp, double* __restrict__ ap) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= F * W_K) return;
+  const long long f = idx / W_K;
+  const int k = (int)(idx % W_K);
+  const double* mc = mcep + f * m1;
+  double acc = 0.0;
+  for (int i = 0; i < m1; ++i) {
+    double v = mc[i];
+    if (i == 0 && e) v += log(e[2 * f + 1] / e[2 * f]) / 2.0;
+    acc = fma(wt[(size_t)i * W_K + k], v, acc);
+  }
+  sp[idx] = exp(acc);
+  // WORLD DecodeAperiodicity: knots (0, -60 dB), (3000 b, cap[b-1]), (fs / 2, -1e-12); unvoiced frames 1 - 1e-12
+  const double* cp = cap + f * bands;
+  double mean = 0.0;
+  for (int b = 0; b < bands; ++b) mean += cp[b];
+  mean /= bands;
+  double a = 1.0 - W_SAFE;
+  if (!(mean > -0.5)) {
+    const double fk = (double)fs / W_N * k;
+    int j = 0;
+    while (j + 1 <= bands && 3000.0 * (j + 1) <= fk) ++j;  // the last knot at or below fk, at most `bands`
+    const double x0 = 3000.0 * j, x1 = j + 1 <= bands ? 3000.0 * (j + 1) : fs / 2.0;
+    const double y0 = j == 0 ? -60.0 : cp[j - 1], y1 = j + 1 <= bands ? cp[j] : -W_SAFE;
+    const double s = (fk - x0) / (x1 - x0);
+    a = pow(10.0, (y0 + s * (y1 - y0)) / 20.0);
+  }
+  ap[idx] = a;
+}
+
+// ---------------------------------------------------------------------------------------------------------- time base
+struct WTime {
+  const double* f0; const long long* foff; const long long* soff;
+  int* ppos; double* pshift; unsigned char* pvuv; long long* pcount;
+  int fs; double fp;
+};
+
+__global__ __launch_bounds__(W_THREADS) void world_timebase_kernel(WTime a) {
+#pragma clang fp contract(off)
+  __shared__ double ph[W_CHUNK];       // phase increment, then total phase
+  __shared__ double wr[W_CHUNK + 1];   // wrapped phase; [0] = the previous chunk's last sample
+  __shared__ unsigned char vv[W_CHUNK + 1];
+  __shared__ int cnt[W_THREADS];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const long long F0 = a.foff[u], S0 = a.soff[u];
+  const int T = (int)(a.foff[u + 1] - F0);
+  const long long Y = a.soff[u + 1] - S0;
+  if (T < 2 || Y < 1) {
+    if (tid == 0) a.pcount[u] = 0;
+    return;
+  }
+  const double fsd = (double)a.fs, fp = a.fp, two_pi = 2.0 * M_PI;
+  const double lowest = (double)(a.fs / W_N) + 1.0;
+  const double* f0 = a.f0 + F0;
+  auto cf = [&](int j) {  // coarse F0 / vuv at knot j (j == T: the extrapolated point)
+    if (j < T) return f0[j] < lowest ? 0.0 : f0[j];
+    const double p = f0[T - 1] < lowest ? 0.0 : f0[T - 1], q = f0[T - 2] < lowest ? 0.0 : f0[T - 2];
+    return p * 2 - q;
+  };
+  auto cv = [&](int j) {
+    if (j < T) return cf(j) == 0.0 ? 0.0 : 1.0;
+    return (cf(T - 1) == 0.0 ? 0.0 : 1.0) * 2 - (cf(T - 2) == 0.0 ? 0.0 : 1.0);
+  };
+  double total = 0.0;  // thread 0's running phase
+  long long base = 0;  // pulses written so far
+  for (long long c0 = 0; c0 < Y; c0 += W_CHUNK) {
+    const int n = (int)min((long long)W_CHUNK, Y - c0);
+    for (int t = tid; t < n; t += W_THREADS) {
+      const long long i = c0 + t;
+      const double xi = (double)i / fsd;
+      int j = (int)(xi / fp);
+      j = max(0, min(j, T - 1));
+      while (j > 0 && (double)j * fp > xi) --j;
+      while (j + 1 < T && (double)(j + 1) * fp <= xi) ++j;
+      const double x0 = (double)j * fp, x1 = (double)(j + 1) * fp;
+      const double s = (xi - x0) / (x1 - x0);
+      const double v0 = cv(j), v1 = cv(j + 1);
+      const double v = v0 + s * (v1 - v0) > 0.5 ? 1.0 : 0.0;
+      double fr = W_DEFAULT_F0;
+      if (v != 0.0) {
+        const double g0 = cf(j), g1 = cf(j + 1);
+        fr = g0 + s * (g1 - g0);
+      }
+      ph[t] = two_pi * fr / fsd;
+      vv[t + 1] = (unsigned char)(v != 0.0);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int t = 0; t < n; ++t) {
+        total = total + ph[t];
+        ph[t] = total;
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < n; t += W_THREADS) wr[t + 1] = fmod(ph[t], two_pi);
+    __syncthreads();
+    // pulse at sample i = c0 + t - 1 when |wrap[i + 1] - wrap[i]| > pi (t >= 1 in the first chunk)
+    const int per = W_CHUNK / W_THREADS, t0 = tid * per, t1 = min(t0 + per, n);
+    const int tstart = c0 == 0 ? 1 : 0;
+    int mine = 0;
+    for (int t = max(t0, tstart); t < t1; ++t) mine += fabs(wr[t + 1] - wr[t]) > M_PI;
+    cnt[tid] = mine;
+    __syncthreads();
+    if (tid == 0) {
+      int run = 0;
+      for (int q = 0; q < W_THREADS; ++q) {
+        const int c = cnt[q];
+        cnt[q] = run;
+        run += c;
+      }
+    }
+    __syncthreads();
+    long long at = base + cnt[tid];
+    for (int t = max(t0, tstart); t < t1; ++t) {
+      if (fabs(wr[t + 1] - wr[t]) > M_PI) {
+        const double y1 = wr[t] - two_pi, y2 = wr[t + 1];
+        a.ppos[S0 + at] = (int)(c0 + t - 1);
+        a.pshift[S0 + at] = -y1 / (y2 - y1) / fsd;
+        a.pvuv[S0 + at] = vv[t];
+        ++at;
+      }
+    }
+    const int last = cnt[W_THREADS - 1] + (tid == W_THREADS - 1 ? mine : 0);
+    __syncthreads();
+    if (tid == W_THREADS - 1) cnt[0] = last;  // the chunk's pulse count
+    if (tid == 0) {
+      wr[0] = wr[n];
+      vv[0] = vv[n];
+    }
+    __syncthreads();
+    base += cnt[0];
+    __syncthreads();
+  }
+  if (tid == 0) a.pcount[u] = base;
+}
+
+// exclusive scan of the per-utterance pulse counts; poff[n_utts] is the batch's pulse count
+__global__ void world_offsets_kernel(const long long* pcount, int n_utts, long long* poff) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  long long s = 0;
+  for (int u = 0; u < n_utts; ++u) {
+    poff[u] = s;
+    s += pcount[u];
+  }
+  poff[n_utts] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------------- per pulse
+struct WPulse {
+  const double* sp; const double* ap;
+  const long long* foff; const long long* soff; const long long* poff; int n_utts;
+  const int* ppos; const double* pshift; const unsigned char* pvuv;
+  const double* noise; long long noise_len;
+  const double* twc; const double* tws; const double* dcw;
+  double* resp; long long p0;
+  int fs; double fp;
+};
+
+__global__ __launch_bounds__(W_THREADS) void world_pulse_kernel(WPulse a) {
+#pragma clang fp contract(off)  // 1 - c * c below: a fused c * c would differ from the restatement at small angles
+  __shared__ double2 Z[W_N];
+  __shared__ double2 Yb[W_N];
+  __shared__ double env[W_K], rat[W_K];
+  __shared__ double tc[W_N / 2], ts[W_N / 2];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const long long p = a.p0 + blockIdx.x;
+  const int u = w_find(a.poff, a.n_utts, p);
+  const long long pu0 = a.poff[u], pu1 = a.poff[u + 1];
+  const long long slot = a.soff[u] + (p - pu0);
+  const int s = a.ppos[slot];
+  const int ns = p + 1 < pu1 ? a.ppos[slot + 1] - s : 0;
+  const double shift = a.pshift[slot];
+  const double vuv = a.pvuv[slot] ? 1.0 : 0.0;
+  const long long nbase = s - a.ppos[a.soff[u]];
+  const long long F0 = a.foff[u];
+  const int T = (int)(a.foff[u + 1] - F0);
+  double* out = a.resp + (size_t)blockIdx.x * W_N;
+
+  for (int m = tid; m < W_N / 2; m += W_THREADS) { tc[m] = a.twc[m]; ts[m] = a.tws[m]; }
+  // envelope and aperiodic ratio at t = s / fs (WORLD GetSpectralEnvelope / GetAperiodicRatio)
+  const double q = (double)s / (double)a.fs / a.fp;
+  const int lo = min(T - 1, (int)floor(q)), hi = min(T - 1, (int)ceil(q));
+  const double w1 = q - lo;
+  const double* sl = a.sp + (F0 + lo) * W_K;
+  const double* sh = a.sp + (F0 + hi) * W_K;
+  const double* al = a.ap + (F0 + lo) * W_K;
+  const double* ah = a.ap + (F0 + hi) * W_K;
+  for (int k = tid; k < W_K; k += W_THREADS) {
+    const double ql = fmax(0.001, fmin(0.999999999999, al[k]));
+    if (lo == hi) {
+      env[k] = fabs(sl[k]);
+      rat[k] = ql * ql;
+    } else {
+      const double qh = fmax(0.001, fmin(0.999999999999, ah[k]));
+      env[k] = (1.0 - w1) * fabs(sl[k]) + w1 * fabs(sh[k]);
+      const double r = (1.0 - w1) * ql + w1 * qh;
+      rat[k] = r * r;
+    }
+  }
+  __syncthreads();
+  const bool per_on = vuv > 0.5 && rat[0] <= 0.999 && ns > 0;
+  if (ns <= 0) {  // the last pulse of an utterance: no noise, periodic part times sqrt(0)
+    for (int i = tid; i < W_N; i += W_THREADS) out[i] = 0.0;
+    return;
+  }
+  // both log amplitudes as one complex even sequence: FFT -> (periodic cepstrum, aperiodic cepstrum)
+  for (int n = tid; n < W_N; n += W_THREADS) {
+    const int k = n <= W_N / 2 ? n : W_N - n;
+    const double la = per_on ? log(env[k] * (1.0 - rat[k]) + W_SAFE) / 2.0 : 0.0;
+    const double lb = vuv != 0.0 ? log(env[k] * rat[k] + W_SAFE) / 2.0 : log(env[k] + W_SAFE) / 2.0;
+    Z[w_brev(n)] = make_double2(la, lb);
+  }
+  __syncthreads();
+  w_fft(Z, tc, ts, -1.0);
+  // fold (c0, 2 c_1 .. 2 c_{N/2-1}, c_{N/2}, zeros) and transform both folded cepstra at once
+  for (int n = tid; n < W_N; n += W_THREADS) {
+    double2 c = make_double2(0.0, 0.0);
+    if (n <= W_N / 2) {
+      const double g = (n == 0 || n == W_N / 2) ? 1.0 : 2.0;
+      c = make_double2(g * Z[n].x, g * Z[n].y);
+    }
+    Yb[w_brev(n)] = c;
+  }
+  __syncthreads();
+  w_fft(Yb, tc, ts, -1.0);
+  // zero-mean noise of min(ns, N) samples from the fixed randn stream, zero padded
+  const int m = min(ns, W_N);
+  double part = 0.0;
+  for (int n = tid; n < m; n += W_THREADS) part += a.noise[min(nbase + n, a.noise_len - 1)];
+  const double mean = w_block_sum(part, red) / m;
+  for (int n = tid; n < W_N; n += W_THREADS)
+    Z[w_brev(n)] = make_double2(n < m ? a.noise[min(nbase + n, a.noise_len - 1)] - mean : 0.0, 0.0);
+  __syncthreads();
+  w_fft(Z, tc, ts, -1.0);
+  // spectra: periodic P = exp(A / N) e^{-i theta}, aperiodic Q = exp(B / N) * noise; V = P + i Q, Hermitian halves
+  const double coef = 2.0 * M_PI * shift * a.fs / W_N;
+  double2 P[3], Q[3];  // k = tid + 256 r
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int k = tid + W_THREADS * r;
+    if (k > W_N / 2) break;
+    const double2 yk = Yb[k], ym = Yb[(W_N - k) & (W_N - 1)];
+    const double Ar = 0.5 * (yk.x + ym.x), Ai = 0.5 * (yk.y - ym.y);
+    const double dr = yk.x - ym.x, di = yk.y + ym.y;
+    const double Br = 0.5 * di, Bi = -0.5 * dr;
+    double2 pk = make_double2(0.0, 0.0);
+    if (per_on) {
+      const double ea = exp(Ar / W_N), re = ea * cos(Ai / W_N), im = ea * sin(Ai / W_N);
+      const double c = w_cos(coef * k), sn = sqrt(fmax(1.0 - c * c, 0.0));
+      pk = make_double2(re * c + im * sn, im * c - re * sn);
+    }
+    const double eb = exp(Br / W_N), mr = eb * cos(Bi / W_N), mi = eb * sin(Bi / W_N);
+    const double2 nzk = Z[k];
+    double2 qk = make_double2(mr * nzk.x - mi * nzk.y, mr * nzk.y + mi * nzk.x);
+    if (k == 0 || k == W_N / 2) { pk.y = 0.0; qk.y = 0.0; }  // a real inverse transform ignores them
+    P[r] = pk;
+    Q[r] = qk;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int k = tid + W_THREADS * r;
+    if (k > W_N / 2) break;
+    const double2 pk = P[r], qk = Q[r];
+    Z[w_brev(k)] = make_double2(pk.x - qk.y, pk.y + qk.x);
+    if (k > 0 && k < W_N / 2) Z[w_brev(W_N - k)] = make_double2(pk.x + qk.y, -pk.y + qk.x);
+  }
+  __syncthreads();
+  w_fft(Z, tc, ts, 1.0);
+  // fftshift; the periodic part's DC removal; (periodic sqrt(ns) + aperiodic) / N
+  double dcp = 0.0;
+  if (per_on) {
+    for (int n = tid; n < W_N / 2; n += W_THREADS) dcp += Z[n].x;
+    dcp = w_block_sum(dcp, red);
+  }
+  const double sq = sqrt((double)ns);
+  for (int i = tid; i < W_N; i += W_THREADS) {
+    const double2 v = Z[(i + W_N / 2) & (W_N - 1)];
+    double per = 0.0;
+    if (per_on) per = i < W_N / 2 ? -dcp * a.dcw[i] : v.x - dcp * a.dcw[i];
+    out[i] = (per * sq + v.y) / W_N;
+  }
+}
+
+// y[g] += the responses of the chunk's pulses that cover sample g, in pulse order
+__global__ void world_ola_kernel(const long long* __restrict__ soff, const long long* __restrict__ poff, int n_utts,
+                                 long long S, const int* __restrict__ ppos, const double* __restrict__ resp, long long p0,
+                                 long long p1, double* __restrict__ y) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= S) return;
+  const int u = w_find(soff, n_utts, g);
+  const long long i = g - soff[u];
+  const long long a0 = max(poff[u], p0), a1 = min(poff[u + 1], p1);
+  if (a0 >= a1) return;
+  const long long base = soff[u] - poff[u];  // ppos[base + p]: the sample of the utterance's global pulse p
+  long long lo = a0, hi = a1;                 // the first pulse with sample >= i - N/2
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (ppos[base + mid] < i - W_N / 2) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= a1 || ppos[base + lo] > i + W_N / 2 - 1) return;
+  double acc = y[g];
+  for (long long p = lo; p < a1 && ppos[base + p] <= i + W_N / 2 - 1; ++p) {
+    const long long off = ppos[base + p] - W_N / 2 + 1;
+    acc = acc + resp[(size_t)(p - p0) * W_N + (i - off)];
+  }
+  y[g] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------- host side
+// SPTK freqt of the unit vectors: at[i][n] = freqt(e_i, W_IRLEN, -alpha)[n] (n < W_IRLEN; rows 0..N/2 are
+// freqt(., N/2, -alpha) too: g_m does not depend on the order)
+static void w_freqt_matrix(int m1, double alpha, std::vector<double>& at) {
+  at.assign((size_t)m1 * W_IRLEN, 0.0);
+  const double a = -alpha, b = 1.0 - a * a;
+  std::vector<double> g(W_IRLEN + 1), d(W_IRLEN + 1);
+  for (int col = 0; col < m1; ++col) {
+    std::fill(g.begin(), g.end(), 0.0);
+    for (int i = m1 - 1; i >= 0; --i) {
+      d = g;
+      g[0] = (i == col ? 1.0 : 0.0) + a * d[0];
+      g[1] = b * d[0] + a * d[1];
+      for (int m = 2; m <= W_IRLEN; ++m) g[m] = d[m - 1] + a * (d[m] - g[m - 1]);
+    }
+    for (int n = 0; n < W_IRLEN; ++n) at[(size_t)col * W_IRLEN + n] = g[n];
+  }
+}
+
+extern "C" void* crk_world_create(int fs, int fftl, double shiftms, double alpha, int order1, int bands, int pulse_capacity) {
+  if (fftl != W_N || fs < 8000 || fs > 192000 || !(shiftms > 0.0) || !(fabs(alpha) < 1.0) || order1 < 1 ||
+      order1 > W_MAX_ORDER1 || bands != w_bands(fs) || bands < 1 || pulse_capacity < 1 || pulse_capacity > (1 << 20))
+    return nullptr;
+  World* w = new World();
+  w->fs = fs; w->m1 = order1; w->bands = bands; w->capacity = pulse_capacity;
+  w->shiftms = shiftms; w->fp = shiftms / 1000.0; w->alpha = alpha;
+  std::vector<double> at;
+  w_freqt_matrix(order1, alpha, at);
+  // log sp_k = 2 c0 + 2 sum_{n=1}^{N/2-1} c_n cos(2 pi k n / N) + c_{N/2} cos(pi k), c = at . mc
+  std::vector<double> cosn(W_N);
+  for (int m = 0; m < W_N; ++m) cosn[m] = cos(2.0 * M_PI * m / W_N);
+  std::vector<double> wt((size_t)order1 * W_K, 0.0);
+  for (int i = 0; i < order1; ++i)
+    for (int k = 0; k < W_K; ++k) {
+      double acc = 0.0;
+      for (int n = 0; n <= W_N / 2; ++n) {
+        const double g = n == W_N / 2 ? 1.0 : 2.0;
+        acc += g * cosn[((size_t)k * n) % W_N] * at[(size_t)i * W_IRLEN + n];
+      }
+      wt[(size_t)i * W_K + k] = acc;
+    }
+  std::vector<double> dcw(W_N);
+  double dc = 0.0;
+  for (int i = 0; i < W_N / 2; ++i) {
+    dcw[i] = 0.5 - 0.5 * cos(2.0 * M_PI * (i + 1.0) / (1.0 + W_N));
+    dcw[W_N - i - 1] = dcw[i];
+    dc += dcw[i] * 2.0;
+  }
+  for (int i = 0; i < W_N / 2; ++i) {
+    dcw[i] /= dc;
+    dcw[W_N - i - 1] = dcw[i];
+  }
+  std::vector<double> host;
+  host.insert(host.end(), at.begin(), at.end());
+  host.insert(host.end(), wt.begin(), wt.end());
+  for (int m = 0; m < W_N / 2; ++m) host.push_back(cos(2.0 * M_PI * m / W_N));
+  for (int m = 0; m < W_N / 2; ++m) host.push_back(sin(2.0 * M_PI * m / W_N));
+  host.insert(host.end(), dcw.begin(), dcw.end());
+  if (hipMalloc(&w->tables, host.size() * sizeof(double)) != hipSuccess) {
+    delete w;
+    return nullptr;
+  }
+  crk_count_alloc_();
+  if (hipMemcpy(w->tables, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(w->tables);
+    delete w;
+    return nullptr;
+  }
+  w->at = w->tables;
+  w->wt = w->at + at.size();
+  w->twc = w->wt + wt.size();
+  w->tws = w->twc + W_N / 2;
+  w->dcw = w->tws + W_N / 2;
+  return w;
+}
+
+extern "C" void crk_world_destroy(void* h) {
+  World* w = (World*)h;
+  if (!w) return;
+  (void)hipFree(w->tables);
+  if (w->noise) (void)hipFree(w->noise);
+  delete w;
+}
+
+// WORLD randn after randn_reseed, max_samples values (one allocation when the table grows; synchronises)
+extern "C" int crk_world_reserve(void* h, long long max_samples) {
+  World* w = (World*)h;
+  if (!w || max_samples < 1 || max_samples > (1LL << 31)) return CRK_ERR_ARG;
+  if (max_samples <= w->noise_len) return CRK_OK;
+  std::vector<double> v(max_samples);
+  uint32_t x = 123456789u, y = 362436069u, z = 521288629u, ww = 88675123u;
+  for (long long i = 0; i < max_samples; ++i) {
+    uint32_t acc = 0;
+    for (int r = 0; r < 12; ++r) {
+      const uint32_t t = x ^ (x << 11);
+      x = y; y = z; z = ww;
+      ww = (ww ^ (ww >> 19)) ^ (t ^ (t >> 8));
+      acc += ww >> 4;
+    }
+    v[i] = acc / 268435456.0 - 6.0;
+  }
+  double* d = nullptr;
+  if (hipMalloc(&d, max_samples * sizeof(double)) != hipSuccess) return CRK_ERR_HIP;
+  crk_count_alloc_();
+  if (hipMemcpy(d, v.data(), max_samples * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return CRK_ERR_HIP;
+  }
+  if (w->noise) (void)hipFree(w->noise);
+  w->noise = d;
+  w->noise_len = max_samples;
+  return CRK_OK;
+}
+
+struct WWs {
+  double *e, *sp, *ap, *pshift, *resp;
+  int* ppos; unsigned char* pvuv; long long *pcount, *poff;
+  size_t bytes;
+};
+
+static WWs w_ws(const World* w, int n_utts, long long F, long long S, unsigned char* base) {
+  WWs r;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += w_align(bytes); return p; };
+  r.e = (double*)take((size_t)F * 2 * sizeof(double));
+  r.sp = (double*)take((size_t)F * W_K * sizeof(double));
+  r.ap = (double*)take((size_t)F * W_K * sizeof(double));
+  r.ppos = (int*)take((size_t)S * sizeof(int));
+  r.pshift = (double*)take((size_t)S * sizeof(double));
+  r.pvuv = (unsigned char*)take((size_t)S);
+  r.pcount = (long long*)take((size_t)n_utts * sizeof(long long));
+  r.poff = (long long*)take((size_t)(n_utts + 1) * sizeof(long long));
+  r.resp = (double*)take((size_t)w->capacity * W_N * sizeof(double));
+  r.bytes = o;
+  return r;
+}
+
+extern "C" long long crk_world_workspace_bytes(void* h, int n_utts, long long total_frames, long long total_samples) {
+  World* w = (World*)h;
+  if (!w || n_utts < 1 || total_frames < 2 || total_samples < 1) return -1;
+  return (long long)w_ws(w, n_utts, total_frames, total_samples, nullptr).bytes;
+}
+
+static int w_frames(World* w, const double* mcep, const double* rmcep, const double* cap, long long F, double* e,
+                    double* sp, double* ap, hipStream_t st) {
+  if (rmcep) {
+    const long long blocks = (2 * F + W_THREADS / 64 - 1) / (W_THREADS / 64);
+    world_energy_kernel<<<dim3((unsigned)blocks), dim3(W_THREADS), 0, st>>>(mcep, rmcep, w->m1, F, w->at, e);
+    CRK_CHECK_LAUNCH();
+  }
+  const long long n = F * W_K;
+  world_frame_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(mcep, cap, w->m1, w->bands, F, w->fs,
+                                                                             w->wt, rmcep ? e : nullptr, sp, ap);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+static int w_pulses(World* w, const double* f0, const long long* foff, const long long* soff, int n_utts, int* ppos,
+                    double* pshift, unsigned char* pvuv, long long* pcount, hipStream_t st) {
+  WTime a{f0, foff, soff, ppos, pshift, pvuv, pcount, w->fs, w->fp};
+  world_timebase_kernel<<<dim3(n_utts), dim3(W_THREADS), 0, st>>>(a);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+extern "C" int crk_world_frames(void* h, const double* mcep, const double* rmcep, const double* cap, int order1,
+                                int bands, long long total_frames, double* sp, double* ap, void* workspace,
+                                long long workspace_bytes, void* stream) {
+  World* w = (World*)h;
+  if (!w || !mcep || !cap || !sp || !ap || total_frames < 1 || !workspace) return CRK_ERR_ARG;
+  if (order1 != w->m1 || bands != w->bands) return CRK_ERR_UNSUPPORTED;
+  if (workspace_bytes < (long long)w_align((size_t)total_frames * 2 * sizeof(double))) return CRK_ERR_ARG;
+  return w_frames(w, mcep, rmcep, cap, total_frames, (double*)workspace, sp, ap, (hipStream_t)stream);
+}
+
+extern "C" int crk_world_pulses(void* h, const double* f0, const long long* frame_offsets, const long long* sample_offsets,
+                                int n_utts, int* pulse_pos, double* pulse_shift, unsigned char* pulse_vuv,
+                                long long* pulse_count, void* stream) {
+  World* w = (World*)h;
+  if (!w || !f0 || !frame_offsets || !sample_offsets || n_utts < 1 || !pulse_pos || !pulse_shift || !pulse_vuv ||
+      !pulse_count)
+    return CRK_ERR_ARG;
+  return w_pulses(w, f0, frame_offsets, sample_offsets, n_utts, pulse_pos, pulse_shift, pulse_vuv, pulse_count,
+                  (hipStream_t)stream);
+}
+
+extern "C" int crk_world_synthesis(void* h, const double* f0, const double* mcep, const double* rmcep, const double* cap,
+                                   int order1, int bands, const long long* frame_offsets, const long long* sample_offsets,
+                                   int n_utts, long long total_frames, long long total_samples, long long max_samples,
+                                   double* y, long long* n_pulses, void* workspace, long long workspace_bytes,
+                                   void* stream) {
+  World* w = (World*)h;
+  if (!w || !f0 || !mcep || !cap || !frame_offsets || !sample_offsets || !y || !workspace || n_utts < 1 ||
+      total_frames < 2 || total_samples < 1 || max_samples < 1 || max_samples > total_samples)
+    return CRK_ERR_ARG;
+  if (order1 != w->m1 || bands != w->bands) return CRK_ERR_UNSUPPORTED;
+  if (max_samples > w->noise_len) return CRK_ERR_ARG;  // crk_world_reserve(max_samples) first
+  WWs ws = w_ws(w, n_utts, total_frames, total_samples, (unsigned char*)workspace);
+  if (workspace_bytes < (long long)ws.bytes) return CRK_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(y, 0, (size_t)total_samples * sizeof(double), st) != hipSuccess) return CRK_ERR_HIP;
+  int rc = w_frames(w, mcep, rmcep, cap, total_frames, ws.e, ws.sp, ws.ap, st);
+  if (rc) return rc;
+  rc = w_pulses(w, f0, frame_offsets, sample_offsets, n_utts, ws.ppos, ws.pshift, ws.pvuv, ws.pcount, st);
+  if (rc) return rc;
+  world_offsets_kernel<<<1, 1, 0, st>>>(ws.pcount, n_utts, ws.poff);
+  CRK_CHECK_LAUNCH();
+  // the one device-to-host read of a call: the batch's pulse count sizes the pulse launches
+  long long P = 0;
+  if (hipMemcpyAsync(&P, ws.poff + n_utts, sizeof(long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return CRK_ERR_HIP;
+  if (n_pulses) *n_pulses = P;
+  for (long long p0 = 0; p0 < P; p0 += w->capacity) {
+    const long long np = std::min((long long)w->capacity, P - p0);
+    WPulse a{ws.sp, ws.ap, frame_offsets, sample_offsets, ws.poff, n_utts, ws.ppos, ws.pshift, ws.pvuv,
+             w->noise, w->noise_len, w->twc, w->tws, w->dcw, ws.resp, p0, w->fs, w->fp};
+    world_pulse_kernel<<<dim3((unsigned)np), dim3(W_THREADS), 0, st>>>(a);
+    CRK_CHECK_LAUNCH();
+    world_ola_kernel<<<dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st>>>(
+        sample_offsets, ws.poff, n_utts, total_samples, ws.ppos, ws.resp, p0, p0 + np, y);
+    CRK_CHECK_LAUNCH();
+  }
+  return CRK_OK;
+}

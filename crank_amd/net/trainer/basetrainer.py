@@ -694,3 +694,23 @@ class BaseTrainer(object):
                 d["rmcep"] = rden[n, :L] if rden is not None else None
             out.append(d)
         return out
+
+    def _save_decoded_world(self, dicts, tdir):
+        """basetrainer.py:419-433: every converted utterance of an mcep model as a WAV through WORLD synthesis
+        (crank_amd.world, clipped to [-1, 1], 16-bit PCM), named <flbl>_org-<org>_cv-<cv>.wav as basetrainer.py:358
+        names it.  `dicts`: the lists of _store_features, or a dict of them per target speaker.  Returns the paths."""
+        from ...world import WorldSynthesizer, write_pcm16
+
+        fc = self.conf["feature"]
+        if isinstance(dicts, dict):
+            dicts = [d for v in dicts.values() for d in v]
+        syn = WorldSynthesizer(fc["fs"], fc["fftl"], fc["shiftms"], fc["mcep_alpha"], device=self.device)
+        tdir = Path(tdir)
+        tdir.mkdir(parents=True, exist_ok=True)
+        paths = []
+        for d, y in zip(dicts, syn.vocode_eval_outputs(dicts)):
+            path = tdir / f"{d['flbl']}_org-{d['org_spkr_name']}_cv-{d['cv_spkr_name']}.wav"
+            path.parent.mkdir(parents=True, exist_ok=True)  # flbl may hold a speaker directory
+            write_pcm16(path, y.cpu().numpy(), fc["fs"])
+            paths.append(path)
+        return paths

@@ -459,6 +459,44 @@ int crk_voc_forward(void* voc, const float* c, const long long* frame_offsets, i
 int crk_voc_upsample(void* voc, const float* c, const long long* frame_offsets, int n_utts, int total_frames, float* out,
                      void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- WORLD waveform synthesis for mel-cepstral models (recipe stage 5, output_feat_type mcep) ---------------------
+ * Replaces the reference's world2wav (sprocket Synthesizer.synthesis: mod_power, pysptk mc2sp, pyworld
+ * decode_aperiodicity + synthesize), all in float64, for a ragged batch of utterances.  Parity with pyworld / pysptk is
+ * unpinned; the oracle is tests/world_synth_ref.py.  CRANK_AMD_PRECISION does not apply.
+ *
+ * crk_world_create: one handle per (fs, fftl, shiftms, alpha, mcep order + 1, bands); precomputes the freqt / mc2sp
+ * matrices, FFT twiddles and the DC remover and allocates them (one allocation; synchronises).  NULL unless fftl = 1024,
+ * order1 <= 128 and bands = int(min(15000, fs/2 - 3000) / 3000).  pulse_capacity: pulses per response buffer (the
+ * workspace holds pulse_capacity * 1024 doubles; a call with more pulses runs several rounds of it, in order).
+ * crk_world_reserve: WORLD's randn stream (reseeded, as every synthesis reseeds) for utterances of up to max_samples
+ * output samples; allocates (synchronises) only when the table grows.
+ *
+ * f0: [total_frames] (Hz, 0 unvoiced); mcep, rmcep: [total_frames][order1] (rmcep NULL: no power modification); cap:
+ * [total_frames][bands] (dB); frames of utterance u = rows frame_offsets[u] .. frame_offsets[u+1]-1, at least 2 per
+ * utterance.  sample_offsets: utterance u owns y[sample_offsets[u] .. sample_offsets[u+1]), its length
+ * int(frames * shiftms * fs / 1000) (the caller computes it).  Both offset arrays: DEVICE int64 [n_utts + 1].
+ * workspace: device memory of at least crk_world_workspace_bytes(h, n_utts, total_frames, total_samples) bytes.  The
+ * compute entries never allocate.  crk_world_synthesis reads the batch's pulse count back to the host once (it sizes
+ * the pulse launches; the call synchronises its stream there) and stores it in *n_pulses when that is not NULL;
+ * max_samples is the longest utterance's sample count (at most what crk_world_reserve covered). */
+void* crk_world_create(int fs, int fftl, double shiftms, double alpha, int order1, int bands, int pulse_capacity);
+void crk_world_destroy(void* world);
+int crk_world_reserve(void* world, long long max_samples);
+long long crk_world_workspace_bytes(void* world, int n_utts, long long total_frames, long long total_samples);
+int crk_world_synthesis(void* world, const double* f0, const double* mcep, const double* rmcep, const double* cap,
+                        int order1, int bands, const long long* frame_offsets, const long long* sample_offsets, int n_utts,
+                        long long total_frames, long long total_samples, long long max_samples, double* y,
+                        long long* n_pulses, void* workspace, long long workspace_bytes, void* stream);
+/* the per-frame stage alone: sp, ap [total_frames][513] (power-modified sp when rmcep is given); uses the first
+ * 16 * total_frames bytes of the workspace */
+int crk_world_frames(void* world, const double* mcep, const double* rmcep, const double* cap, int order1, int bands,
+                     long long total_frames, double* sp, double* ap, void* workspace, long long workspace_bytes, void* stream);
+/* the time base alone: utterance u's pulses at pulse_pos / pulse_shift (seconds) / pulse_vuv [sample_offsets[u] + i],
+ * i < pulse_count[u] (pulse_pos: the sample within the utterance); the slot arrays hold total_samples entries */
+int crk_world_pulses(void* world, const double* f0, const long long* frame_offsets, const long long* sample_offsets,
+                     int n_utts, int* pulse_pos, double* pulse_shift, unsigned char* pulse_vuv, long long* pulse_count,
+                     void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 
