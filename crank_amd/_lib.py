@@ -52,7 +52,6 @@ SIGNATURES = {
     "crk_net_scratch_bytes": (LL, [P, I, I]),
     "crk_debug_alloc_count": (LL, []),
     "crk_debug_net_paths": (I, [P, I, I]),
-    "crk_net_set_wgrad_stream": (I, [P, P]),
     "crk_seed_next": (I, [P, P, P]),
     "crk_nets_wnorm_bwd": (I, [I, P, P]),
     "crk_nets_prepare": (I, [I, P, P, ULL, P, P]),

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <deque>
 #include <vector>
 
 #include "conv_kernels.h"
@@ -58,58 +59,69 @@ static int not_reserved(const char* what) {
   return CRK_ERR_ARG;
 }
 
+#define PS_MAXL 16
+// host copies of the fused plain-conv chain tables (pstack_kernels.hip): [0] first/forward, [1] head forward / backward,
+// [2] head backward, [3] first backward; w: the weight-gradient table
+struct PsTables { PsLayer t[4][PS_MAXL]; int L[4]; PwLayer w[PS_MAXL]; int nw; int max_wa, max_wb, max_tiles; double wflops_per_frame; };
+// what a batch shape needs: scratch / partial-sum floats and the slot counts of the two weight-gradient regions
+struct ShapeNeed { long long need_s, need_p; int Gs, Gg, cpg; };
+// The kernels a net runs at a batch shape in one arithmetic (route_of).  It depends on the net, the shape, the arithmetic and
+// the process-wide switches only, never on a call's pointers, so a backward always reads the plane layout its forward wrote.
+// Every other path computes the same values, only slower.
+struct Route {
+  bool fused;       // forward, data-gradient chain and weight gradient on the fused kernels (else one kernel per layer)
+  bool gen_split;   // generator, plain bf16: forward and chain channel-split, gate planes in the lane-record layout
+  bool x3f;         // generator: a bf16x3f forward ahead of this (plain) route's backward runs channel-split too
+  bool disc_split;  // discriminator, plain bf16: blocks and chain channel-split, gate planes in the lane-record layout
+};
+// Everything batch shape (B, T) needs besides the growing buffers, made by crk_net_reserve: plane offsets are multiples of
+// N = B*T, partial-sum offsets of the slot counts Gs / Gg.
+struct Shape {
+  int B, T;
+  ShapeNeed q;
+  Route route[2];                    // [precise]
+  std::vector<ConvEntry> abs;        // the conv entries with absolute partial offsets and slot counts ...
+  ConvEntry* d_ents = nullptr;       // ... on the device
+  PsTables ps;                       // fused plain-conv chain tables (nets of at most PS_MAXL layers) ...
+  PsLayer* d_ps = nullptr;           // ... on the device: [4][PS_MAXL]
+  PwLayer* d_pw = nullptr;           // [PS_MAXL]
+  StackWLayer* d_wlayers = nullptr;  // gated nets: fused weight-gradient layer table
+};
+
 struct Net {
   crk_net_desc d;
   std::vector<ConvEntry> ents;
   std::vector<ConvMeta> meta;
-  ConvEntry* d_ents = nullptr;
+  ConvEntry* d_ents = nullptr;  // the table weight preparation reads (it reads no partial-sum offsets)
   long long n_params = 0;
   long long wprep_elems = 0, norm_elems = 0;
   uint16_t *whi = nullptr, *wlo = nullptr;
   float* norms = nullptr;
   unsigned long long prepared_version = ~0ull;
   const float* prepared_params = nullptr;
-  // weight-norm backward deferred by CRK_FLAG_DEFER_WNORM: the per-group partial sums wait in `partials`
-  bool wn_pending = false; const float* wn_params = nullptr; float* wn_grads = nullptr;
+  // weight-norm backward deferred by CRK_FLAG_DEFER_WNORM (wn_shape: pending, for that shape): the per-group partial sums
+  // wait in `partials`
+  const Shape* wn_shape = nullptr; const float* wn_params = nullptr; float* wn_grads = nullptr;
   // ... and, with it, the weight gradients of the plain convs around a gated stack (first conv, head): their planes stay in
   // `scratch` / the caller's `saved` until the group call
-  bool pw_pending = false; int pw_B = 0, pw_T = 0; const uint16_t* pw_a = nullptr; const uint16_t* pw_b = nullptr;
-  // grown on demand
+  const Shape* pw_shape = nullptr; PwP pw_params;
+  // grown by crk_net_reserve
   float* partials = nullptr; long long partial_cap = 0;
   float* scratch = nullptr; long long scratch_cap = 0;
-  std::vector<long long> pt_per_utt;  // per entry partial floats per utterance (0 if shared)
   // weight-gradient partial sums: two regions with their own slot counts - the gated blocks'
   // convs (utterance groups, stack_wgrad_kernel) and everything else (chunk groups, table kernel)
   long long pt_floats_stack = 0, pt_floats_gen = 0;
-  std::vector<ConvEntry> abs_ents;  // the uploaded table (absolute partial offsets, slot counts)
-  int Gs = 0, Gg = 0, cpg_gen = 1;
   int L = 0;
   int idx_first = -1, idx_last1 = -1, idx_last2 = -1;
   std::vector<int> idx_conv, idx_aux, idx_out, idx_skip, idx_plain;
   StackLayer* d_layers = nullptr;  // fused-forward layer table (kinds 0/1)
   StackBLayer* d_blayers = nullptr;  // fused data-gradient layer table
-  StackWLayer* d_wlayers = nullptr;  // fused weight-gradient layer table (partial offsets for wl_G groups)
-  int wl_G = 0;
-  // fused plain-conv chains (pstack_kernels.hip): device layer tables, rebuilt when the batch shape changes
-  PsLayer* d_ps = nullptr;   // [4][PS_MAXL]: kind 2: forward, backward; gated: first fwd | head fwd | head bwd | first bwd
-  PwLayer* d_pw = nullptr;   // [PS_MAXL] weight-gradient table
-  long long ps_N = -1; int ps_Gg = -1;
-  // optional side stream for the weight gradients (crk_net_set_wgrad_stream): they only read planes the
-  // data-gradient chain has finished writing, so they overlap the next stack's chain on the main stream
-  hipStream_t wg_stream = nullptr;
-  hipEvent_t ev_chain = nullptr, ev_wg = nullptr;
-  bool wg_pending = false;
-  // Device tables depend on the batch shape (plane offsets are multiples of N = B*T, partial-sum offsets of the slot counts
-  // Gs / Gg).  Every shape gets tables of its own that live as long as the net: d_ents / d_ps / d_pw / d_wlayers above are
-  // the CURRENT shape's (switching is a host-side pointer swap), so a captured HIP graph - which holds the pointers of the
-  // shape it was captured with - keeps seeing that shape's tables whatever ran in between (a short last batch of an
-  // epoch, a dev batch).  Buffers that grow are retired, not freed, for the same reason.  Growth is bounded by the number of
-  // DISTINCT (B, T) a run feeds a net: training has one (batch_len is fixed, dataset.py crops / pads to it), decoding one per
-  // flag (batch_len = longest utterance); a table set is a few KB, so nothing is evicted - a captured graph may hold any of them.
-  struct EntSet { int Gs, Gg; ConvEntry* d; std::vector<ConvEntry> abs; };
-  struct PsSet { long long N; int Gs, Gg; PsLayer* d_ps; PwLayer* d_pw; };
-  struct WlSet { int G, Gg; StackWLayer* d; };
-  std::vector<EntSet> ent_sets; std::vector<PsSet> ps_sets; std::vector<WlSet> wl_sets;
+  // One record per reserved batch shape, looked up once per compute call.  Records live as long as the net, so a captured HIP
+  // graph - which holds the pointers of the shape it was captured with - keeps seeing that shape's tables whatever ran in
+  // between (a short last batch of an epoch, a dev batch).  Buffers that grow are retired, not freed, for the same reason.
+  // Growth is bounded by the number of DISTINCT (B, T) a run feeds a net: training has one (batch_len is fixed, dataset.py
+  // crops / pads to it), decoding one per flag (batch_len = longest utterance); a record is a few KB, so nothing is evicted.
+  std::deque<Shape> shapes;  // (a deque: deferred work points at its record)
   std::vector<void*> retired;  // outgrown partial-sum / scratch buffers (freed with the net)
   // How each recent forward laid out the planes in the caller's `saved` workspace (keyed by its address; the last 32 calls):
   // mode 0 plain bf16, 1 split operands with hi + lo planes (CRK_FLAG_PRECISE), 2 split-operand forward that saved what a
@@ -117,9 +129,6 @@ struct Net {
   // crk_net_backward checks its flags against the tag instead of trusting the caller to pair the two calls.
   struct FwdTag { const float* saved; int B, T; unsigned char mode; bool x3f; };
   FwdTag fwd_tags[32]; int fwd_tag_next = 0; int fwd_tag_count = 0;
-  // deferred plain-conv weight gradients: the launch parameters of the shape they were deferred for
-  PwP pw_params; int pw_nw = 0, pw_max_wa = 0, pw_max_wb = 0, pw_max_tiles = 0; double pw_flops = 0.0;
-  const ConvEntry* wn_ents = nullptr;  // table of the shape the pending weight-norm backward belongs to
   std::vector<WgradP> jobs;  // weight-gradient problems queued by the running backward
   WgradP* d_jobs = nullptr;
   // pinned upload ring for the job table (a slot is reused only after its copy completed)
@@ -156,7 +165,11 @@ static long long alloc_pt(Net* n, long long floats_per_group, bool stack) {
   return o;
 }
 
-static int upload_entries(Net* n, int Gs, int Gg);
+// a host table copied into a new device allocation (*d is set as soon as it is allocated: the caller frees it on failure)
+template <class E> static int upload(E** d, const E* h, size_t count) {
+  if (NET_MALLOC(d, sizeof(E) * count) != hipSuccess) return CRK_ERR_HIP;
+  return hipMemcpy(*d, h, sizeof(E) * count, hipMemcpyHostToDevice) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
+}
 extern "C" void* crk_net_create(const crk_net_desc* desc) {
   AllocScope may_allocate;
   if (!desc) return nullptr;
@@ -289,8 +302,7 @@ extern "C" void* crk_net_create(const crk_net_desc* desc) {
       y.dil = n->meta[n->idx_conv[l]].dilation;
       y.off0 = d.causal ? -(ec.k - 1) * y.dil : -((ec.k - 1) / 2) * y.dil;
     }
-    ok = NET_MALLOC(&n->d_layers, sizeof(StackLayer) * n->L) == hipSuccess &&
-         hipMemcpy(n->d_layers, lt.data(), sizeof(StackLayer) * n->L, hipMemcpyHostToDevice) == hipSuccess;
+    ok = upload(&n->d_layers, lt.data(), n->L) == CRK_OK;
     std::vector<StackBLayer> bt(n->L);
     for (int l = 0; l < n->L; l++) {
       const ConvEntry& ec = n->ents[n->idx_conv[l]];
@@ -304,10 +316,9 @@ extern "C" void* crk_net_create(const crk_net_desc* desc) {
       y.f_conv = ec.bfr_off; y.f_os = eo.bfr_off;
       y.f_aux = d.aux_ch > 0 ? n->ents[n->idx_aux[l]].bfr_off : -1;
     }
-    ok = ok && NET_MALLOC(&n->d_blayers, sizeof(StackBLayer) * n->L) == hipSuccess &&
-         hipMemcpy(n->d_blayers, bt.data(), sizeof(StackBLayer) * n->L, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && upload(&n->d_blayers, bt.data(), n->L) == CRK_OK;
   }
-  ok = ok && upload_entries(n, 1, 1) == CRK_OK;  // (the table weight preparation reads; batch shapes get their own in crk_net_reserve)
+  ok = ok && upload(&n->d_ents, n->ents.data(), n->ents.size()) == CRK_OK;  // (batch shapes get their own in crk_net_reserve)
   if (!ok) {
     fprintf(stderr, "[crank_hip] net_create: device allocation failed\n");
     delete n;
@@ -316,39 +327,15 @@ extern "C" void* crk_net_create(const crk_net_desc* desc) {
   return n;
 }
 
-// partial offsets are per group; the device table needs absolute offsets for the slot counts of a
-// given batch shape: [stack region: entry block x Gs slots][generic region: entry block x Gg slots]
-static int upload_entries(Net* n, int Gs, int Gg) {
-  for (auto& es : n->ent_sets)
-    if (es.Gs == Gs && es.Gg == Gg) { n->d_ents = es.d; n->abs_ents = es.abs; n->Gs = Gs; n->Gg = Gg; return CRK_OK; }
-  if (!g_may_alloc) return not_reserved("conv-entry table");
-  Net::EntSet es; es.Gs = Gs; es.Gg = Gg; es.d = nullptr;
-  es.abs = n->ents;
-  for (auto& e : es.abs) {
-    const bool stack = e.pt_groups != 0;
-    const long long base = stack ? 0 : n->pt_floats_stack * Gs;
-    const int G = stack ? Gs : Gg;
-    e.pt_off = base + e.pt_off * G; e.pb_off = base + e.pb_off * G; e.pt_groups = G;
-  }
-  if (NET_MALLOC(&es.d, sizeof(ConvEntry) * es.abs.size()) != hipSuccess) return CRK_ERR_HIP;
-  if (hipMemcpy(es.d, es.abs.data(), sizeof(ConvEntry) * es.abs.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(es.d);
-    return CRK_ERR_HIP;  // (e.g. a new batch shape first seen inside a stream capture: run it eagerly once)
-  }
-  n->ent_sets.push_back(es);
-  n->d_ents = es.d; n->abs_ents = es.abs; n->Gs = Gs; n->Gg = Gg;
-  return CRK_OK;
+static void free_shape(Shape& r) {
+  (void)hipFree(r.d_ents); (void)hipFree(r.d_ps); (void)hipFree(r.d_pw); (void)hipFree(r.d_wlayers);
 }
-
 extern "C" void crk_net_destroy(void* h) {
   Net* n = (Net*)h;
   if (!n) return;
-  for (auto& es : n->ent_sets) (void)hipFree(es.d);
-  for (auto& ps : n->ps_sets) { (void)hipFree(ps.d_ps); (void)hipFree(ps.d_pw); }
-  for (auto& ws : n->wl_sets) (void)hipFree(ws.d);
+  for (Shape& r : n->shapes) free_shape(r);
   for (void* q : n->retired) (void)hipFree(q);
-  (void)hipFree(n->whi); (void)hipFree(n->wlo); (void)hipFree(n->norms);
-  if (n->ev_chain) { (void)hipEventDestroy(n->ev_chain); (void)hipEventDestroy(n->ev_wg); }
+  (void)hipFree(n->whi); (void)hipFree(n->wlo); (void)hipFree(n->norms); (void)hipFree(n->d_ents);
   for (int k = 0; k < 4; k++) if (n->h_slot[k]) { (void)hipHostFree(n->h_slot[k]); (void)hipEventDestroy(n->slot_ev[k]); }
   (void)hipFree(n->partials); (void)hipFree(n->scratch); (void)hipFree(n->d_jobs); (void)hipFree(n->d_layers); (void)hipFree(n->d_blayers);
   delete n;
@@ -374,7 +361,6 @@ static int stack_aux_pad(const Net* n) { return n->d.aux_ch > 0 ? n->ents[n->idx
 //   gated : fp32 planes X | TA | SB | Z | SKIP | H1 (TA, SB, Z, H1: per-layer fallback only), then bf16:
 //           Xb Zb Tb Sg (block input, z, tanh, sigmoid; hi[L] lo[L], [N,64] each), Cb_hi Cb_lo ([N,aux_pad]), F_hi F_lo (first-conv input [N,kpF]),
 //           head_hi = S|H1 ([N,64] each), head_lo
-#define PS_MAXL 16
 static long long saved_f32_floats(const Net* n, long long N) {
   if (n->d.kind == 2) return (long long)(n->L - 1) * N * n->d.conv_ch;
   return (long long)(4 * n->L + 2) * N * 64;
@@ -412,44 +398,6 @@ static long long saved_floats(const Net* n, long long N) {
 }
 extern "C" long long crk_net_saved_bytes(void* h, int B, int T) { return saved_floats((Net*)h, (long long)B * T) * 4; }
 
-extern "C" int crk_net_set_wgrad_stream(void* h, void* stream) {
-  Net* n = (Net*)h;
-  if (!n) return CRK_ERR_ARG;
-  if (n->wg_pending && n->ev_wg && hipEventSynchronize(n->ev_wg) != hipSuccess) return CRK_ERR_HIP;
-  n->wg_pending = false;
-  n->wg_stream = (hipStream_t)stream;
-  if (stream && !n->ev_chain) {
-    if (hipEventCreateWithFlags(&n->ev_chain, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&n->ev_wg, hipEventDisableTiming) != hipSuccess) return CRK_ERR_HIP;
-  }
-  return CRK_OK;
-}
-// the main stream must not touch what earlier side-stream weight gradients of this handle still use
-// (scratch planes, partial sums, the weight-norm factors) before they are done
-static int wait_side_work(Net* n, hipStream_t s) {
-  if (n->wg_pending) {
-    if (hipStreamWaitEvent(s, n->ev_wg, 0) != hipSuccess) return CRK_ERR_HIP;
-    n->wg_pending = false;
-  }
-  return CRK_OK;
-}
-// stream for the weight gradients of the running backward: the side stream, ordered after everything
-// the main stream has enqueued so far
-static int fork_wgrad(Net* n, hipStream_t s, hipStream_t* ws) {
-  *ws = s;
-  if (!n->wg_stream || n->wg_stream == s) return CRK_OK;
-  if (hipEventRecord(n->ev_chain, s) != hipSuccess || hipStreamWaitEvent(n->wg_stream, n->ev_chain, 0) != hipSuccess)
-    return CRK_ERR_HIP;
-  *ws = n->wg_stream;
-  return CRK_OK;
-}
-static int join_wgrad(Net* n, hipStream_t s, hipStream_t ws) {
-  if (ws == s) return CRK_OK;
-  if (hipEventRecord(n->ev_wg, ws) != hipSuccess) return CRK_ERR_HIP;
-  n->wg_pending = true;
-  return CRK_OK;
-}
-
 static int net_nmax(const Net* n) {  // largest cin * k of the net's convs
   int m = 1;
   for (const auto& e : n->ents) if (e.cin * e.k > m) m = e.cin * e.k;
@@ -457,7 +405,6 @@ static int net_nmax(const Net* n) {  // largest cin * k of the net's convs
 }
 static int ensure_prepared(Net* n, const float* params, unsigned long long version, hipStream_t s) {
   if (n->prepared_version == version && n->prepared_params == params) return CRK_OK;
-  { int rc = wait_side_work(n, s); if (rc) return rc; }
   int rc = launch_weight_prep(n->d_ents, (int)n->ents.size(), net_nmax(n), params, n->whi, n->wlo, n->norms, s);
   if (rc) return rc;
   n->prepared_version = version;
@@ -466,17 +413,17 @@ static int ensure_prepared(Net* n, const float* params, unsigned long long versi
 }
 
 // partial sums -> dg / dv / dbias: now, or (deferred) when the caller finishes all its nets with crk_nets_wnorm_bwd
-static int finish_wnorm(Net* n, const float* params, float* grads, bool defer, hipStream_t s) {
-  if (defer) { n->wn_pending = true; n->wn_params = params; n->wn_grads = grads; n->wn_ents = n->d_ents; return CRK_OK; }
-  return launch_wnorm_bwd(n->d_ents, (int)n->ents.size(), params, grads, n->partials, n->norms, s);
+static int finish_wnorm(Net* n, const Shape* r, const float* params, float* grads, bool defer, hipStream_t s) {
+  if (defer) { n->wn_shape = r; n->wn_params = params; n->wn_grads = grads; return CRK_OK; }
+  return launch_wnorm_bwd(r->d_ents, (int)n->ents.size(), params, grads, n->partials, n->norms, s);
 }
 static int flush_pending_plain_wgrad(Net* n, hipStream_t s);
 static int flush_pending_wnorm(Net* n, hipStream_t s) {
-  if (!n->wn_pending) return CRK_OK;
+  if (!n->wn_shape) return CRK_OK;
   { int rc = flush_pending_plain_wgrad(n, s); if (rc) return rc; }
-  n->wn_pending = false;
-  { int rc = wait_side_work(n, s); if (rc) return rc; }  // the partial sums may still be in flight on the side stream
-  return launch_wnorm_bwd(n->wn_ents ? n->wn_ents : n->d_ents, (int)n->ents.size(), n->wn_params, n->wn_grads, n->partials, n->norms, s);
+  const Shape* r = n->wn_shape;
+  n->wn_shape = nullptr;
+  return launch_wnorm_bwd(r->d_ents, (int)n->ents.size(), n->wn_params, n->wn_grads, n->partials, n->norms, s);
 }
 
 static ConvP base_conv(const Net* n, int B, int T) {
@@ -486,9 +433,6 @@ static ConvP base_conv(const Net* n, int B, int T) {
   p.slope = n->d.slope;
   p.B = B; p.T = T; p.tiles_per_utt = ceil_div(T, CRK_TM);
   p.ktaps = 1; p.dil = 1; p.off0 = 0;
-  static int dbg = -1;
-  if (dbg < 0) dbg = 0;
-  p.dbg = dbg;
   return p;
 }
 static void set_fw_weights(const Net* n, ConvP& p, const ConvEntry& e, const float* params) {
@@ -531,9 +475,9 @@ static PsLayer ps_layer_bwd(const Net* n, int ei, int epi) {  // the conv transp
   y.f_off = e.bfr_mode == 1 ? e.bfr_off : -1;
   return y;
 }
-static PwLayer pw_layer(const Net* n, int ei, long long a_hi, long long a_lo, long long b_hi, long long b_lo) {
+static PwLayer pw_layer(const Net* n, const ConvEntry* abs, int ei, long long a_hi, long long a_lo, long long b_hi, long long b_lo) {
   const ConvEntry& e = n->ents[ei];
-  const ConvEntry& a = n->abs_ents[ei];
+  const ConvEntry& a = abs[ei];
   PwLayer y; memset(&y, 0, sizeof(y));
   y.a_hi = a_hi; y.a_lo = a_lo; y.b_hi = b_hi; y.b_lo = b_lo;
   y.wa = e.bw_kp; y.wb = e.fw_kp; y.ca = e.cout; y.cb = e.cin;
@@ -556,9 +500,8 @@ static GatedS16 gated_s16(const Net* n, long long N) {
   g.hb_hi = g.dsb_lo + P; g.hb_lo = g.hb_hi + hb; g.total = g.hb_lo + hb;
   return g;
 }
-// host copies of the chain tables: [0] first/forward, [1] head forward / backward, [2] head backward, [3] first backward
-struct PsTables { PsLayer t[4][PS_MAXL]; int L[4]; PwLayer w[PS_MAXL]; int nw; int max_wa, max_wb; double wflops_per_frame; };
-static void ps_build(const Net* n, long long N, PsTables& T) {
+// the chain tables of a batch shape; abs: the conv entries of its slot counts (the weight-gradient table's partial offsets)
+static void ps_build(const Net* n, long long N, const ConvEntry* abs, PsTables& T) {
   memset(&T, 0, sizeof(T));
   const crk_net_desc& d = n->d;
   if (d.kind == 2) {
@@ -575,7 +518,7 @@ static void ps_build(const Net* n, long long N, PsTables& T) {
       T.t[1][j] = ps_layer_bwd(n, n->idx_plain[i], i > 0 ? 2 + ACT_LRELU : 0);
       T.t[1][j].save_plane = goff[i];
       if (i > 0) { T.t[1][j].mask_plane = ooff[i]; T.t[1][j].mask_w = n->ents[n->idx_plain[i]].fw_kp; }
-      T.w[i] = pw_layer(n, n->idx_plain[i], goff[i], N * gw + goff[i], ooff[i], N * ow + ooff[i]);
+      T.w[i] = pw_layer(n, abs, n->idx_plain[i], goff[i], N * gw + goff[i], ooff[i], N * ow + ooff[i]);
     }
     T.L[0] = T.L[1] = L; T.nw = L;
   } else {
@@ -590,14 +533,16 @@ static void ps_build(const Net* n, long long N, PsTables& T) {
     T.t[2][1] = ps_layer_bwd(n, n->idx_last1, 2 + hact); T.t[2][1].mask_plane = 0; T.t[2][1].mask_w = 64; T.t[2][1].save_plane = N * kpY;
     T.L[2] = 2;
     T.t[3][0] = ps_layer_bwd(n, n->idx_first, 0); T.L[3] = 1;
-    T.w[0] = pw_layer(n, n->idx_first, gs.dxb_hi, gs.dxb_lo, gf.f_hi, gf.f_lo);
-    T.w[1] = pw_layer(n, n->idx_last1, gs.hb_hi + N * kpY, gs.hb_lo + N * kpY, gf.head_hi, gf.head_lo);
-    T.w[2] = pw_layer(n, n->idx_last2, gs.hb_hi, gs.hb_lo, gf.head_hi + P, gf.head_lo + P);
+    T.w[0] = pw_layer(n, abs, n->idx_first, gs.dxb_hi, gs.dxb_lo, gf.f_hi, gf.f_lo);
+    T.w[1] = pw_layer(n, abs, n->idx_last1, gs.hb_hi + N * kpY, gs.hb_lo + N * kpY, gf.head_hi, gf.head_lo);
+    T.w[2] = pw_layer(n, abs, n->idx_last2, gs.hb_hi, gs.hb_lo, gf.head_hi + P, gf.head_lo + P);
     T.nw = 3;
   }
   for (int i = 0; i < T.nw; i++) {
     if (T.w[i].wa > T.max_wa) T.max_wa = T.w[i].wa;
     if (T.w[i].wb > T.max_wb) T.max_wb = T.w[i].wb;
+    const int tiles = ((T.w[i].ca + 31) / 32) * ((T.w[i].cb + 31) / 32) * T.w[i].k;  // (tap, cin band, cout band) tiles
+    if (tiles > T.max_tiles) T.max_tiles = tiles;
     T.wflops_per_frame += 2.0 * T.w[i].ca * T.w[i].cb * T.w[i].k;
   }
 }
@@ -605,35 +550,6 @@ static double ps_flops(const PsLayer* t, int L, long long N) {
   double f = 0.0;
   for (int i = 0; i < L; i++) f += 2.0 * (double)N * t[i].rows * t[i].kp * t[i].k;
   return f;
-}
-// upload the tables for this batch shape / slot counts (cached)
-static int ps_upload(Net* n, long long N) {
-  if (n->ps_N == N && n->ps_Gg == n->Gg * 1000 + n->Gs) return CRK_OK;
-  for (auto& ps : n->ps_sets)
-    if (ps.N == N && ps.Gs == n->Gs && ps.Gg == n->Gg) {
-      n->d_ps = ps.d_ps; n->d_pw = ps.d_pw; n->ps_N = N; n->ps_Gg = n->Gg * 1000 + n->Gs;
-      return CRK_OK;
-    }
-  if (!g_may_alloc) return not_reserved("plain-chain tables");
-  PsTables T;
-  ps_build(n, N, T);
-  Net::PsSet ps; ps.N = N; ps.Gs = n->Gs; ps.Gg = n->Gg; ps.d_ps = nullptr; ps.d_pw = nullptr;
-  if (NET_MALLOC(&ps.d_ps, sizeof(PsLayer) * 4 * PS_MAXL) != hipSuccess) return CRK_ERR_HIP;
-  if (NET_MALLOC(&ps.d_pw, sizeof(PwLayer) * PS_MAXL) != hipSuccess) { (void)hipFree(ps.d_ps); return CRK_ERR_HIP; }
-  if (hipMemcpy(ps.d_ps, T.t, sizeof(PsLayer) * 4 * PS_MAXL, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(ps.d_pw, T.w, sizeof(PwLayer) * PS_MAXL, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(ps.d_ps); (void)hipFree(ps.d_pw);
-    return CRK_ERR_HIP;
-  }
-  n->ps_sets.push_back(ps);
-  n->d_ps = ps.d_ps; n->d_pw = ps.d_pw;
-  n->ps_N = N; n->ps_Gg = n->Gg * 1000 + n->Gs;
-  return CRK_OK;
-}
-static int ps_chain_version() {
-  static int v = -1;
-  if (v < 0) v = crk_sw().ps_v;
-  return v;
 }
 static PsP ps_base(const Net* n, int B, int T, const float* params) {
   PsP p; memset(&p, 0, sizeof(p));
@@ -644,7 +560,7 @@ static PsP ps_base(const Net* n, int B, int T, const float* params) {
 // can this kind-2 net / the first conv and head of this gated net run through the fused chains?
 static bool plain_chains_ok(const Net* n, int B, int T, bool precise) {
   PsTables Tb;
-  ps_build(n, (long long)B * T, Tb);
+  ps_build(n, (long long)B * T, n->ents.data(), Tb);  // (relative partial offsets: the planners do not read them)
   const int nchains = n->d.kind == 2 ? 2 : 4;
   for (int c = 0; c < nchains; c++) {
     if (Tb.L[c] > PS_MAXL) return false;
@@ -657,9 +573,6 @@ static bool plain_chains_ok(const Net* n, int B, int T, bool precise) {
   return true;
 }
 
-// One decision for the whole stack and shape: forward, data-gradient chain and weight gradient
-// run fused together or not at all (the fused kernels exchange bf16 planes the generic kernels
-// do not produce).  CRK_NO_FUSE=1 selects the per-layer kernels (debugging / A-B timing).
 static void stack_halo(const Net* n, int* hl, int* hr, int* max_off, int* max_dil) {
   *hl = *hr = *max_off = 0; *max_dil = 1;
   for (int l = 0; l < n->L; l++) {
@@ -672,92 +585,67 @@ static void stack_halo(const Net* n, int* hl, int* hr, int* max_off, int* max_di
     if (dil > *max_dil) *max_dil = dil;
   }
 }
-static bool stack_fused(const Net* n, int B, int T, bool precise) {
-  static int no_fuse = -1;
-  if (no_fuse < 0) no_fuse = crk_sw().no_fuse;
-  if (no_fuse || n->L > PS_MAXL) return false;
-  if (n->d.kind == 2) return plain_chains_ok(n, B, T, precise);
-  int hl, hr, mo, md;
-  stack_halo(n, &hl, &hr, &mo, &md);
+// the shape parts of a gated stack's launch parameters: the launches add the pointers, the planners the window
+static StackP stack_fwd_shape(const Net* n, int B, int T) {
   StackP sp; memset(&sp, 0, sizeof(sp));
-  sp.B = B; sp.T = T; sp.L = n->L; sp.ktaps = n->d.kernel_size; sp.hl = hl; sp.hr = hr; sp.max_off = mo;
+  int md;
+  stack_halo(n, &sp.hl, &sp.hr, &sp.max_off, &md);
+  sp.B = B; sp.T = T; sp.L = n->L; sp.ktaps = n->d.kernel_size;
   sp.aux_ch = n->d.aux_ch > 0 ? n->d.aux_ch : 0; sp.aux_pad = stack_aux_pad(n);
+  return sp;
+}
+static StackBP stack_bwd_shape(const Net* n, int B, int T) {
   StackBP bp; memset(&bp, 0, sizeof(bp));
-  bp.B = B; bp.T = T; bp.L = n->L; bp.ktaps = n->d.kernel_size; bp.hl = hr; bp.hr = hl; bp.max_off = mo;
-  bp.aux_ch = sp.aux_ch;
-  return stack_fwd_plan(sp, precise) == CRK_OK && stack_bwd_plan(bp, precise) == CRK_OK &&
-         stack_wgrad_supported(n->d.kernel_size, md, sp.aux_ch) && plain_chains_ok(n, B, T, precise);
+  int hl, hr, md;
+  stack_halo(n, &hl, &hr, &bp.max_off, &md);
+  bp.hl = hr; bp.hr = hl;  // the data gradient looks the other way
+  bp.B = B; bp.T = T; bp.L = n->L; bp.ktaps = n->d.kernel_size;
+  bp.aux_ch = n->d.aux_ch > 0 ? n->d.aux_ch : 0;
+  return bp;
 }
 
-// Generator stacks in plain bf16: forward and data-gradient chain both run channel-split (stack2_kernels.hip,
-// stack2b_kernels.hip) and exchange the tanh / sigmoid planes in the lane-record layout.  ONE predicate for both calls - it
-// depends on the net, the batch shape and process-wide switches only, never on a call's pointers - so a backward always reads
-// the layout its forward wrote.  (Misaligned tensors then fail loudly in the call instead of taking another path.)
-static bool gen_split_path(const Net* n, int B, int T, bool precise) {
+// The kernel path of net n at batch shape (B, T) in one arithmetic: the one place where the planners decide.  crk_net_reserve
+// keeps both arithmetics' routes in the shape's record; the compute entry points read them there.
+static Route route_of(const Net* n, int B, int T, bool precise) {
+  Route r = {false, false, false, false};
   const crk_net_desc& d = n->d;
-  static int sk_v = -1, skb_v = -1;
-  if (sk_v < 0) sk_v = crk_sw().sk_v;
-  if (skb_v < 0) skb_v = crk_sw().skb_v;
-  if (precise || d.kind != 0 || d.dropout != 0.f || sk_v != 2 || skb_v != 2) return false;
-  if (d.in_ch % 8 || d.out_ch % 8 || d.out_ch > 128) return false;
-  if (!stack_fused(n, B, T, precise)) return false;
-  const ConvEntry& ef = n->ents[n->idx_first];
-  const ConvEntry& e1 = n->ents[n->idx_last1];
-  const ConvEntry& e2 = n->ents[n->idx_last2];
-  if (ef.fr_off < 0 || e1.fr_off < 0 || e2.fr_off < 0 || ef.bfr_off < 0 || e1.bfr_off < 0 || e2.bfr_off < 0 ||
-      n->ents[n->idx_conv[0]].bfr_off < 0) return false;
-  int hl, hr, mo, md;
-  stack_halo(n, &hl, &hr, &mo, &md);
-  StackP sp; memset(&sp, 0, sizeof(sp));
-  sp.B = B; sp.T = T; sp.L = n->L; sp.ktaps = d.kernel_size; sp.hl = hl; sp.hr = hr; sp.max_off = mo;
-  sp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0; sp.aux_pad = stack_aux_pad(n);
-  sp.x_in = reinterpret_cast<const float*>(n);  // (any non-null value: folded, the plan sizes the first conv's input tile)
-  sp.in_ch = d.in_ch; sp.kp_first = ef.fw_kp;
-  StackBP bp; memset(&bp, 0, sizeof(bp));
-  bp.B = B; bp.T = T; bp.L = n->L; bp.ktaps = d.kernel_size; bp.hl = hr; bp.hr = hl; bp.max_off = mo; bp.aux_ch = sp.aux_ch;
-  return stack2_fwd_plan(sp) == CRK_OK && stack2_bwd_plan(bp) == CRK_OK;
-}
-
-// bf16x3f (forward in split-operand arithmetic, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN; backward in plain bf16,
-// CRK_FLAG_FWD_PRECISE): generator stacks run the channel-split split-operand forward (stack2x_kernels.hip), which leaves the
-// hi planes in the plain path's layout, and the plain path's backward kernels behind it.  ONE predicate for both calls, like
-// gen_split_path.  CRK_S2X=0: the round-4 pairing (frame-split stack_fwd_kernel<PRECISE>, frame-split chain on row planes).
-static bool gen_x3f_path(const Net* n, int B, int T) {
-  static int s2x = -1;
-  if (s2x < 0) s2x = crk_sw().s2x;
-  if (!s2x || !gen_split_path(n, B, T, false)) return false;
-  const crk_net_desc& d = n->d;
-  int hl, hr, mo, md;
-  stack_halo(n, &hl, &hr, &mo, &md);
-  StackP sp; memset(&sp, 0, sizeof(sp));
-  sp.B = B; sp.T = T; sp.L = n->L; sp.ktaps = d.kernel_size; sp.hl = hl; sp.hr = hr; sp.max_off = mo;
-  sp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0; sp.aux_pad = stack_aux_pad(n);
-  sp.x_in = reinterpret_cast<const float*>(n);  // (any non-null value: folded; stack2_fwd_plan, called first, sizes the input tile)
-  sp.in_ch = d.in_ch; sp.kp_first = n->ents[n->idx_first].fw_kp;
-  return stack2x_fwd_plan(sp) == CRK_OK;
-}
-
-// The discriminator (kind 1, no conditioning) in plain bf16, dropout or not: the forward's gated blocks (stack2_fwd_kernel, not
-// folded: first conv and head keep their own launches) and the data-gradient chain (stack2_bwd_kernel<.., FOLD = false>) run
-// channel-split and exchange the gate planes in the lane-record layout.  One predicate for both calls, like gen_split_path.
-// CRK_DISC_SPLIT=0: the round-3 pairing (channel-split forward, frame-split chain, row-layout planes).
-static bool disc_split_path(const Net* n, int B, int T, bool precise) {
-  const crk_net_desc& d = n->d;
-  static int sk_v = -1, skb_v = -1, dsp = -1;
-  if (sk_v < 0) sk_v = crk_sw().sk_v;
-  if (skb_v < 0) skb_v = crk_sw().skb_v;
-  if (dsp < 0) dsp = crk_sw().disc_split;
-  if (precise || d.kind != 1 || d.aux_ch > 0 || sk_v != 2 || skb_v != 2 || !dsp) return false;
-  if (!stack_fused(n, B, T, precise)) return false;
-  if (n->ents[n->idx_conv[0]].bfr_off < 0 || n->ents[n->idx_out[0]].bfr_off < 0 || n->ents[n->idx_conv[0]].fr_off < 0 ||
-      n->ents[n->idx_out[0]].fr_off < 0) return false;
-  int hl, hr, mo, md;
-  stack_halo(n, &hl, &hr, &mo, &md);
-  StackP sp; memset(&sp, 0, sizeof(sp));
-  sp.B = B; sp.T = T; sp.L = n->L; sp.ktaps = d.kernel_size; sp.hl = hl; sp.hr = hr; sp.max_off = mo; sp.drop_p = d.dropout;
-  StackBP bp; memset(&bp, 0, sizeof(bp));
-  bp.B = B; bp.T = T; bp.L = n->L; bp.ktaps = d.kernel_size; bp.hl = hr; bp.hr = hl; bp.max_off = mo;
-  return stack2_fwd_plan(sp) == CRK_OK && stack2_bwd_plan(bp) == CRK_OK;
+  const CrkSwitches& sw = crk_sw();
+  // forward, data-gradient chain and weight gradient run fused together or not at all (the fused kernels exchange bf16
+  // planes the generic kernels do not produce).  CRK_NO_FUSE=1 selects the per-layer kernels (debugging / A-B timing).
+  if (sw.no_fuse || n->L > PS_MAXL) return r;
+  if (d.kind == 2) { r.fused = plain_chains_ok(n, B, T, precise); return r; }
+  int hl, hr, mo, max_dil;
+  stack_halo(n, &hl, &hr, &mo, &max_dil);
+  StackP sp = stack_fwd_shape(n, B, T);
+  StackBP bp = stack_bwd_shape(n, B, T);
+  r.fused = stack_fwd_plan(sp, precise) == CRK_OK && stack_bwd_plan(bp, precise) == CRK_OK &&
+            stack_wgrad_supported(d.kernel_size, max_dil, sp.aux_ch) && plain_chains_ok(n, B, T, precise);
+  if (!r.fused || precise || sw.sk_v != 2 || sw.skb_v != 2) return r;
+  if (d.kind == 0 && d.dropout == 0.f && d.in_ch % 8 == 0 && d.out_ch % 8 == 0) {
+    // Generator stacks in plain bf16: forward and data-gradient chain both run channel-split (stack2_kernels.hip,
+    // stack2b_kernels.hip), first conv and head folded in, and exchange the tanh / sigmoid planes in the lane-record layout.
+    StackP f = stack_fwd_shape(n, B, T);
+    f.x_in = reinterpret_cast<const float*>(n);  // (any non-null value: folded, the plan sizes the first conv's input tile)
+    f.in_ch = d.in_ch; f.kp_first = n->ents[n->idx_first].fw_kp;
+    StackP fx = f;
+    StackBP b = stack_bwd_shape(n, B, T);
+    r.gen_split = stack2_fwd_plan(f) == CRK_OK && stack2_bwd_plan(b) == CRK_OK;
+    // bf16x3f (forward in split-operand arithmetic, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN; backward in plain bf16,
+    // CRK_FLAG_FWD_PRECISE): the channel-split split-operand forward (stack2x_kernels.hip) leaves the hi planes in this route's
+    // layout for this route's backward.  CRK_S2X=0: the round-4 pairing (frame-split stack_fwd_kernel<PRECISE>, frame-split
+    // chain on row planes).
+    r.x3f = r.gen_split && sw.s2x && stack2x_fwd_plan(fx) == CRK_OK;
+  }
+  if (d.kind == 1 && d.aux_ch == 0 && sw.disc_split) {
+    // The discriminator (no conditioning) in plain bf16, dropout or not: the forward's gated blocks (stack2_fwd_kernel, not
+    // folded: first conv and head keep their own launches) and the data-gradient chain (stack2_bwd_kernel<.., FOLD = false>)
+    // run channel-split.  CRK_DISC_SPLIT=0: the round-3 pairing (channel-split forward, frame-split chain, row-layout planes).
+    StackP f = stack_fwd_shape(n, B, T);
+    f.drop_p = d.dropout;
+    StackBP b = stack_bwd_shape(n, B, T);
+    r.disc_split = stack2_fwd_plan(f) == CRK_OK && stack2_bwd_plan(b) == CRK_OK;
+  }
+  return r;
 }
 
 static void tag_forward(Net* n, const float* saved, int B, int T, int flags, bool x3f) {
@@ -785,10 +673,11 @@ static int check_forward_tag(const Net* n, const float* saved, int B, int T, int
   }
   return CRK_OK;
 }
-// what a batch shape needs: scratch / partial-sum floats and the slot counts of the two weight-gradient regions
-struct ShapeNeed { long long need_s, need_p; int Gs, Gg, cpg; };
-static ShapeNeed shape_need(const Net* n, int B, int T);
-static int select_shape(Net* n, const ShapeNeed& q);
+static const Shape* find_shape(const Net* n, int B, int T) {
+  for (const Shape& r : n->shapes)
+    if (r.B == B && r.T == T) return &r;
+  return nullptr;
+}
 extern "C" int crk_net_forward(void* h, const float* params, unsigned long long version, const float* x, int ldx,
                                const float* c, int ldc, float* y, int ldy, float* saved, int B, int T, int flags,
                                unsigned long long seed, void* stream) {
@@ -800,33 +689,33 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
   const unsigned long long* seed_ptr = (flags & CRK_FLAG_SEED_ON_DEVICE) ? reinterpret_cast<const unsigned long long*>((uintptr_t)seed) : nullptr;
   const unsigned long long seed_val = (flags & CRK_FLAG_SEED_ON_DEVICE) ? 0ull : seed;
   const crk_net_desc& d = n->d;
+  const Shape* r = find_shape(n, B, T);
+  if (!r) return not_reserved("crk_net_forward");
+  const Route& rt = r->route[precise];
+  // bf16x3f: split-operand arithmetic that saves the plain route's planes
+  const bool x3f = precise && (flags & CRK_FLAG_BWD_PLAIN) && r->route[0].x3f;
   RUN(ensure_prepared(n, params, version, s));
-  RUN(select_shape(n, shape_need(n, B, T)));  // this shape's tables (a pointer swap; CRK_ERR_ARG: the shape was not reserved)
-  tag_forward(n, saved, B, T, flags, precise && (flags & CRK_FLAG_BWD_PLAIN) && n->d.kind == 0 && gen_x3f_path(n, B, T));
+  tag_forward(n, saved, B, T, flags, x3f);
   const long long N = (long long)B * T;
-  if (d.kind == 2 && stack_fused(n, B, T, precise)) {
+  const PsTables& Tb = r->ps;
+  if (d.kind == 2 && rt.fused) {
     // the whole stack in one launch; every conv's input operand is kept as a bf16 plane
     if (!saved && !(flags & CRK_FLAG_NO_SAVE)) return CRK_ERR_ARG;
-    RUN(ps_upload(n, N));
-    PsTables Tb;
-    ps_build(n, N, Tb);
     PsP p = ps_base(n, B, T, params);
     p.x = x; p.ldx = ldx; p.cin = d.in_ch; p.y = y; p.ldy = ldy;
     if (!(flags & CRK_FLAG_NO_SAVE)) {
       p.save_hi = reinterpret_cast<uint16_t*>(saved + saved_f32_floats(n, N));
       p.save_lo = p.save_hi + N * plain_planes_w(n);
     }
-    p.layers = n->d_ps; p.L = Tb.L[0];
-    if (!precise && ps_chain_version() == 2) {  // channel-split chain (pstack2_kernels.hip); CRK_PS_V=1: the frame-split one
+    p.layers = r->d_ps; p.L = Tb.L[0];
+    if (!precise && crk_sw().ps_v == 2) {  // channel-split chain (pstack2_kernels.hip); CRK_PS_V=1: the frame-split one
       PsP q = p;
       if (pstack2_plan(q, Tb.t[0]) == CRK_OK) return launch_pstack2(q, ps_flops(Tb.t[0], Tb.L[0], N), s);
     }
-    if (precise && (flags & CRK_FLAG_BWD_PLAIN) && ps_chain_version() == 2) {  // bf16x3f: split-operand forward, hi planes only
-      static int s2x = -1;
-      if (s2x < 0) s2x = crk_sw().s2x;
+    if (precise && (flags & CRK_FLAG_BWD_PLAIN) && crk_sw().ps_v == 2) {  // bf16x3f: split-operand forward, hi planes only
       PsP q = p;
       q.save_lo = nullptr;
-      if (s2x && pstack2x_plan(q, Tb.t[0]) == CRK_OK) return launch_pstack2x(q, ps_flops(Tb.t[0], Tb.L[0], N), s);
+      if (crk_sw().s2x && pstack2x_plan(q, Tb.t[0]) == CRK_OK) return launch_pstack2x(q, ps_flops(Tb.t[0], Tb.L[0], N), s);
     }
     RUN(pstack_plan(p, Tb.t[0], precise));
     return launch_pstack(p, precise, ps_flops(Tb.t[0], Tb.L[0], N), s);
@@ -860,23 +749,18 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
   float* SKIP = Z + (long long)L * P;
   float* H1 = SKIP + P;
   const int head_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
-  const bool fused = stack_fused(n, B, T, precise);
-  PsTables Tb;
+  const bool fused = rt.fused;
   uint16_t* b16 = reinterpret_cast<uint16_t*>(saved + saved_f32_floats(n, N));
   const GatedB16 gf = gated_b16(n, N);
   const bool keep = !(flags & CRK_FLAG_NO_SAVE);
   // plain bf16, generator stacks: first conv, gated blocks and head in ONE launch (stack2_kernels.hip)
   bool folded = false;
-  const bool x3f = precise && (flags & CRK_FLAG_BWD_PLAIN) && d.kind == 0 && gen_x3f_path(n, B, T);
   if ((fused && !precise && d.kind == 0) || x3f) {
-    static int sk_v = -1;
-    if (sk_v < 0) sk_v = crk_sw().sk_v;
     const ConvEntry& ef = n->ents[n->idx_first];
     const ConvEntry& e1 = n->ents[n->idx_last1];
     const ConvEntry& e2 = n->ents[n->idx_last2];
-    StackP sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.c = c; sp.ldc = ldc; sp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0; sp.aux_pad = stack_aux_pad(n);
+    StackP sp = stack_fwd_shape(n, B, T);
+    sp.c = c; sp.ldc = ldc;
     sp.params = params;
     if (keep) {
       sp.saved = saved;
@@ -886,16 +770,15 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
     }
     sp.skip = SKIP;  // (unused by the folded kernel; a valid base for its dummy descriptors)
     sp.whi = n->whi; sp.wlo = n->wlo; sp.layers = n->d_layers;
-    sp.B = B; sp.T = T; sp.L = L; sp.ktaps = d.kernel_size;
-    int md;
-    stack_halo(n, &sp.hl, &sp.hr, &sp.max_off, &md);
     sp.x_in = x; sp.ldx_in = ldx; sp.in_ch = d.in_ch; sp.kp_first = ef.fw_kp;
     sp.f_first = ef.fr_off; sp.b_first = ef.off_b;
     sp.f_h1 = e1.fr_off; sp.b_h1 = e1.off_b; sp.f_h2 = e2.fr_off; sp.b_h2 = e2.off_b;
     sp.y = y; sp.ldy = ldy; sp.out_ch = d.out_ch; sp.head_scale = (float)sqrt(1.0 / L);
-    const bool shape_ok = (d.in_ch % 8 == 0) && (ldx % 4 == 0) && (d.out_ch % 4 == 0) && (ldy % 4 == 0) && d.out_ch <= 128 &&
-                          ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)y) & 15) == 0) && ef.fr_off >= 0 && e1.fr_off >= 0 && e2.fr_off >= 0;
-    const bool split = x3f || gen_split_path(n, B, T, precise);
+    // per call: the folded kernels read x and write y in 16-byte pieces; without that the stack takes the unfolded path, or
+    // (a channel-split route, whose backward reads the lane-record planes only this forward writes) the call fails
+    const bool shape_ok = (d.in_ch % 8 == 0) && (ldx % 4 == 0) && (d.out_ch % 4 == 0) && (ldy % 4 == 0) &&
+                          ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)y) & 15) == 0);
+    const bool split = x3f || rt.gen_split;
     if (split && !shape_ok) {
       fprintf(stderr, "[crank_hip] crk_net_forward: x / y must be 16-byte aligned with row strides that are multiples of 4 floats\n");
       return CRK_ERR_ARG;
@@ -905,19 +788,17 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
       RUN(stack2x_fwd_plan(sp));
       RUN(launch_stack2x_fwd(sp, s));
       folded = true;
-    } else if (sk_v == 2 && shape_ok && d.dropout == 0.f && stack2_fwd_plan(sp) == CRK_OK) {
+    } else if (crk_sw().sk_v == 2 && shape_ok && d.dropout == 0.f && stack2_fwd_plan(sp) == CRK_OK) {
       RUN(launch_stack2_fwd(sp, s));
       folded = true;
-    } else if (split) return CRK_ERR_UNSUPPORTED;  // (cannot happen: the predicate implies the plan)
+    } else if (split) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
   }
   if (folded) return CRK_OK;
   if (fused) {  // first conv (1x1; kind 1: + LeakyReLU) -> X_0, its input kept as a bf16 plane
-    RUN(ps_upload(n, N));
-    ps_build(n, N, Tb);
     PsP p = ps_base(n, B, T, params);
     p.x = x; p.ldx = ldx; p.cin = d.in_ch; p.y = X; p.ldy = 64;
     if (keep) { p.save_hi = b16 + gf.f_hi; p.save_lo = b16 + gf.f_lo; }
-    p.layers = n->d_ps; p.L = 1;
+    p.layers = r->d_ps; p.L = 1;
     RUN(pstack_plan(p, Tb.t[0], precise));
     RUN(launch_pstack(p, precise, ps_flops(Tb.t[0], 1, N), s));
   } else
@@ -930,10 +811,8 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
     RUN(conv_go(p, MODE_PLAIN, precise, s));
   }
   if (fused) {
-    StackP sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.x0 = X; sp.c = c; sp.ldc = ldc; sp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
-    sp.aux_pad = stack_aux_pad(n);
+    StackP sp = stack_fwd_shape(n, B, T);
+    sp.x0 = X; sp.c = c; sp.ldc = ldc;
     sp.skip = SKIP; sp.params = params;
     if (keep) {
       sp.saved = saved;
@@ -942,18 +821,13 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
       if (d.aux_ch > 0) { sp.cb_hi = b16 + gf.cb_hi; sp.cb_lo = b16 + gf.cb_lo; }
     }
     sp.whi = n->whi; sp.wlo = n->wlo; sp.layers = n->d_layers;
-    sp.B = B; sp.T = T; sp.L = L; sp.ktaps = d.kernel_size;
-    int md;
-    stack_halo(n, &sp.hl, &sp.hr, &sp.max_off, &md);
     if (d.dropout > 0.f) { sp.drop_p = d.dropout; sp.drop_seed = seed_val; sp.drop_seed_ptr = seed_ptr; }
     // plain bf16: the channel-split kernel (stack2_kernels.hip); bf16x3 and CRK_SK_V=1: the frame-split one
-    static int sk_v = -1;
-    if (sk_v < 0) sk_v = crk_sw().sk_v;
-    if (disc_split_path(n, B, T, precise)) sp.ts_stride = ts_plane_stride(N);  // (its data-gradient chain reads lane records)
-    if (!precise && sk_v != 1 && stack2_fwd_plan(sp) == CRK_OK) {
+    if (rt.disc_split) sp.ts_stride = ts_plane_stride(N);  // (its data-gradient chain reads lane records)
+    if (!precise && crk_sw().sk_v != 1 && stack2_fwd_plan(sp) == CRK_OK) {
       RUN(launch_stack2_fwd(sp, s));
     } else {
-      if (sp.ts_stride) return CRK_ERR_UNSUPPORTED;  // (cannot happen: the predicate implies the plan)
+      if (sp.ts_stride) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
       RUN(stack_fwd_plan(sp, precise));
       RUN(launch_stack_fwd(sp, precise, s));
     }
@@ -986,7 +860,7 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
     p.x = SKIP; p.ldx = 64; p.cin = 64; p.in_scale = (float)sqrt(1.0 / L); p.in_act = head_act;
     p.y = y; p.ldy = ldy;
     if (keep) { p.save_hi = b16 + gf.head_hi; p.save_lo = b16 + gf.head_lo; }
-    p.layers = n->d_ps + PS_MAXL; p.L = 2;
+    p.layers = r->d_ps + PS_MAXL; p.L = 2;
     RUN(pstack_plan(p, Tb.t[1], precise));
     RUN(launch_pstack(p, precise, ps_flops(Tb.t[1], 2, N), s));
   } else
@@ -1057,74 +931,68 @@ static ShapeNeed shape_need(const Net* n, int B, int T) {
   q.need_p = n->pt_floats_stack * q.Gs + n->pt_floats_gen * q.Gg;
   return q;
 }
-// the current tables become those of batch shape (B, T); nothing is allocated unless inside crk_net_reserve
-static int select_shape(Net* n, const ShapeNeed& q) {
-  n->cpg_gen = q.cpg;
-  if (n->Gs != q.Gs || n->Gg != q.Gg) { RUN(upload_entries(n, q.Gs, q.Gg)); n->wl_G = 0; }
+// a buffer that must hold `need` floats: outgrown ones are retired, not freed (a captured graph may still hold the pointer)
+static int grow(Net* n, float** buf, long long* cap, long long need) {
+  if (need <= *cap) return CRK_OK;
+  if (*buf) n->retired.push_back(*buf);
+  *buf = nullptr; *cap = 0;
+  if (NET_MALLOC(buf, need * 4) != hipSuccess) return CRK_ERR_HIP;
+  *cap = need;
   return CRK_OK;
 }
-static int ensure_bwd_buffers(Net* n, int B, int T) {
-  const ShapeNeed q = shape_need(n, B, T);
-  if ((q.need_s > n->scratch_cap || q.need_p > n->partial_cap || !n->d_jobs) && !g_may_alloc) return not_reserved("crk_net_backward");
-  if (q.need_s > n->scratch_cap) {
-    if (n->scratch) n->retired.push_back(n->scratch);  // (a captured graph may still hold the pointer)
-    n->scratch = nullptr; n->scratch_cap = 0;
-    if (NET_MALLOC(&n->scratch, q.need_s * 4) != hipSuccess) return CRK_ERR_HIP;
-    n->scratch_cap = q.need_s;
-  }
-  if (q.need_p > n->partial_cap) {
-    if (n->partials) n->retired.push_back(n->partials);
-    n->partials = nullptr; n->partial_cap = 0;
-    if (NET_MALLOC(&n->partials, q.need_p * 4) != hipSuccess) return CRK_ERR_HIP;
-    n->partial_cap = q.need_p;
-  }
-  RUN(select_shape(n, q));
-  if (!n->d_jobs) {
-    if (NET_MALLOC(&n->d_jobs, sizeof(WgradP) * 256) != hipSuccess) return CRK_ERR_HIP;
-  }
-  return CRK_OK;
-}
-
-// fused weight-gradient layer table of a gated stack for G utterance groups (built once per count, kept: see Net::ent_sets)
-static int ensure_wl_table(Net* n, int G) {
-  if (n->wl_G == G) return CRK_OK;
+static int build_shape(Net* n, Shape& r) {
   const crk_net_desc& d = n->d;
-  const int L = n->L;
-  StackWLayer* found = nullptr;
-  for (auto& ws : n->wl_sets) if (ws.G == G && ws.Gg == n->Gg) found = ws.d;
-  if (!found) {
-    if (!g_may_alloc) return not_reserved("weight-gradient layer table");
-    std::vector<StackWLayer> wt(L);
-    for (int l = 0; l < L; l++) {
+  // partial offsets are per group; the device table needs absolute offsets for the shape's slot counts:
+  // [stack region: entry block x Gs slots][generic region: entry block x Gg slots]
+  r.abs = n->ents;
+  for (auto& e : r.abs) {
+    const bool stack = e.pt_groups != 0;
+    const long long base = stack ? 0 : n->pt_floats_stack * r.q.Gs;
+    const int G = stack ? r.q.Gs : r.q.Gg;
+    e.pt_off = base + e.pt_off * G; e.pb_off = base + e.pb_off * G; e.pt_groups = G;
+  }
+  RUN(upload(&r.d_ents, r.abs.data(), r.abs.size()));
+  if (n->L <= PS_MAXL) {
+    ps_build(n, (long long)r.B * r.T, r.abs.data(), r.ps);
+    RUN(upload(&r.d_ps, &r.ps.t[0][0], 4 * PS_MAXL));
+    RUN(upload(&r.d_pw, r.ps.w, PS_MAXL));
+  }
+  if (d.kind != 2) {  // the fused weight-gradient layer table of the gated stack (partial offsets of the Gs utterance groups)
+    std::vector<StackWLayer> wt(n->L);
+    for (int l = 0; l < n->L; l++) {
       const ConvEntry& ec = n->ents[n->idx_conv[l]];
       const ConvEntry& eo = n->ents[n->idx_out[l]];
+      const ConvEntry& ac = r.abs[n->idx_conv[l]];
+      const ConvEntry& ao = r.abs[n->idx_out[l]];
       StackWLayer& y = wt[l];
-      const ConvEntry& ac = n->abs_ents[n->idx_conv[l]];
-      const ConvEntry& ao = n->abs_ents[n->idx_out[l]];
       y.pt_conv = ac.pt_off; y.pb_conv = ec.off_b >= 0 ? ac.pb_off : -1;
       y.pt_os = ao.pt_off; y.pb_os = eo.off_b >= 0 ? ao.pb_off : -1;
-      y.pt_aux = d.aux_ch > 0 ? n->abs_ents[n->idx_aux[l]].pt_off : 0;
+      y.pt_aux = d.aux_ch > 0 ? r.abs[n->idx_aux[l]].pt_off : 0;
       y.dil = n->meta[n->idx_conv[l]].dilation;
       y.off0 = fwd_off0(n, ec.k, y.dil);
     }
-    Net::WlSet ws; ws.G = G; ws.Gg = n->Gg; ws.d = nullptr;
-    if (NET_MALLOC(&ws.d, sizeof(StackWLayer) * L) != hipSuccess) return CRK_ERR_HIP;
-    if (hipMemcpy(ws.d, wt.data(), sizeof(StackWLayer) * L, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(ws.d); return CRK_ERR_HIP; }
-    n->wl_sets.push_back(ws);
-    found = ws.d;
+    RUN(upload(&r.d_wlayers, wt.data(), wt.size()));
   }
-  n->d_wlayers = found;
-  n->wl_G = G;
   return CRK_OK;
 }
-
 extern "C" int crk_net_reserve(void* h, int B, int T) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return CRK_ERR_ARG;
+  if (find_shape(n, B, T)) return CRK_OK;
   AllocScope may_allocate;
-  RUN(ensure_bwd_buffers(n, B, T));
-  if (n->d.kind != 2) RUN(ensure_wl_table(n, stack_groups(n, B, T)));
-  if (n->L <= PS_MAXL) RUN(ps_upload(n, (long long)B * T));
+  Shape r{};
+  r.B = B; r.T = T; r.q = shape_need(n, B, T);
+  r.route[0] = route_of(n, B, T, false);
+  r.route[1] = route_of(n, B, T, true);
+  RUN(grow(n, &n->scratch, &n->scratch_cap, r.q.need_s));
+  RUN(grow(n, &n->partials, &n->partial_cap, r.q.need_p));
+  if (!n->d_jobs && NET_MALLOC(&n->d_jobs, sizeof(WgradP) * 256) != hipSuccess) return CRK_ERR_HIP;
+  const int rc = build_shape(n, r);
+  if (rc != CRK_OK) {  // (e.g. a new batch shape first seen inside a stream capture: run it eagerly once)
+    free_shape(r);
+    return rc;
+  }
+  n->shapes.push_back(r);
   return CRK_OK;
 }
 extern "C" long long crk_net_scratch_bytes(void* h, int B, int T) {
@@ -1136,20 +1004,16 @@ extern "C" long long crk_net_scratch_bytes(void* h, int B, int T) {
 extern "C" long long crk_debug_alloc_count(void) { return g_net_allocs; }
 // vocoder_kernels.hip counts its handles' allocations here too
 long long crk_count_alloc_(void) { return ++g_net_allocs; }
-// which kernel generation the compute entry points pick for a batch shape (the predicates they share): bit 0 the generator
-// stack runs channel-split in plain bf16 (stack2_fwd_kernel / stack2_bwd_kernel), bit 1 its bf16x3f forward runs on the
-// channel-split split-operand kernel (stack2x_fwd_kernel), bit 2 the discriminator's blocks and chain run channel-split,
-// bit 3 the net is a chain of plain convs that runs fused (pstack kernels).  Every fallback computes the same values, only
-// slower: a test pins the bits at the benchmark shape so that a plan that starts failing does not pass as a timing.
+// which kernel generation the compute entry points pick for a batch shape (its route): bit 0 the generator stack runs
+// channel-split in plain bf16 (stack2_fwd_kernel / stack2_bwd_kernel), bit 1 its bf16x3f forward runs on the channel-split
+// split-operand kernel (stack2x_fwd_kernel), bit 2 the discriminator's blocks and chain run channel-split, bit 3 the net is a
+// chain of plain convs that runs fused (pstack kernels).  Every fallback computes the same values, only slower: a test pins
+// the bits at the benchmark shape so that a plan that starts failing does not pass as a timing.
 extern "C" int crk_debug_net_paths(void* h, int B, int T) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return -1;
-  int r = 0;
-  if (n->d.kind == 0 && gen_split_path(n, B, T, false)) r |= 1;
-  if (n->d.kind == 0 && gen_x3f_path(n, B, T)) r |= 2;
-  if (n->d.kind == 1 && disc_split_path(n, B, T, false)) r |= 4;
-  if (n->d.kind == 2 && stack_fused(n, B, T, false)) r |= 8;
-  return r;
+  const Route r = route_of(n, B, T, false);
+  return (int)r.gen_split | (int)r.x3f << 1 | (int)r.disc_split << 2 | (int)(n->d.kind == 2 && r.fused) << 3;
 }
 
 static WgradP base_wgrad(const Net* n, int B, int T) {
@@ -1160,14 +1024,14 @@ static WgradP base_wgrad(const Net* n, int B, int T) {
   w.dbg = 0;
   return w;
 }
-// partial-sum slots of conv entry ei: pointers into the partial block, chunks per group, group count
-static void wgrad_slots(const Net* n, int ei, int B, int T, WgradP& w) {
-  const ConvEntry& a = n->abs_ents[ei];
+// partial-sum slots of conv entry ei at shape r: pointers into the partial block, chunks per group, group count
+static void wgrad_slots(const Net* n, const Shape* r, int ei, WgradP& w) {
+  const ConvEntry& a = r->abs[ei];
   const bool stack = n->ents[ei].pt_groups != 0;
   w.partial = n->partials + a.pt_off;
   w.bias_partial = a.off_b >= 0 ? n->partials + a.pb_off : nullptr;
   w.ngroups = a.pt_groups;
-  w.cpg = stack ? stack_cpg(n, B, T) : n->cpg_gen;
+  w.cpg = stack ? stack_cpg(n, r->B, r->T) : r->q.cpg;
 }
 // queue one weight-gradient problem; launched with the rest of the stack's by wgrad_flush
 static int wgrad_go(Net* n, WgradP& w, bool precise) {
@@ -1196,33 +1060,22 @@ static int wgrad_flush(Net* n, int B, int T, bool precise, hipStream_t s) {
   return rc;
 }
 
-// weight gradients of the plain convs of a net from the bf16 planes of its fused chains
-static PwP plain_wgrad_params(Net* n, int B, int T, const uint16_t* abase, const uint16_t* bbase) {
+// weight gradients of the plain convs of a net from the bf16 planes of its fused chains at shape r
+static PwP plain_wgrad_params(const Net* n, const Shape* r, const uint16_t* abase, const uint16_t* bbase) {
   PwP wp; memset(&wp, 0, sizeof(wp));
-  wp.layers = n->d_pw; wp.abase = abase; wp.bbase = bbase; wp.partials = n->partials;
-  wp.B = B; wp.T = T; wp.cpg = n->cpg_gen; wp.G = n->Gg;
+  wp.layers = r->d_pw; wp.abase = abase; wp.bbase = bbase; wp.partials = n->partials;
+  wp.B = r->B; wp.T = r->T; wp.cpg = r->q.cpg; wp.G = r->q.Gg;
   return wp;
 }
-static int ps_max_tiles(const PsTables& Tb) {  // largest (tap, cin band, cout band) tile count of a conv of the table
-  int mt = 0;
-  for (int i = 0; i < Tb.nw; i++) {
-    const int t = ((Tb.w[i].ca + 31) / 32) * ((Tb.w[i].cb + 31) / 32) * Tb.w[i].k;
-    if (t > mt) mt = t;
-  }
-  return mt;
-}
-static int plain_wgrad(Net* n, int B, int T, const uint16_t* abase, const uint16_t* bbase, bool precise, hipStream_t s) {
-  PsTables Tb;
-  ps_build(n, (long long)B * T, Tb);
-  const PwP wp = plain_wgrad_params(n, B, T, abase, bbase);
-  return launch_pstack_wgrad(wp, Tb.nw, Tb.max_wa, Tb.max_wb, precise, Tb.wflops_per_frame * B * T, s, ps_max_tiles(Tb));
+static int launch_plain_wgrad(const Shape* r, const PwP& wp, bool precise, hipStream_t s) {
+  const PsTables& Tb = r->ps;
+  return launch_pstack_wgrad(wp, Tb.nw, Tb.max_wa, Tb.max_wb, precise, Tb.wflops_per_frame * r->B * r->T, s, Tb.max_tiles);
 }
 static int flush_pending_plain_wgrad(Net* n, hipStream_t s) {
-  if (!n->pw_pending) return CRK_OK;
-  n->pw_pending = false;
-  PsTables Tb;
-  ps_build(n, (long long)n->pw_B * n->pw_T, Tb);
-  return launch_pstack_wgrad(n->pw_params, Tb.nw, Tb.max_wa, Tb.max_wb, false, Tb.wflops_per_frame * n->pw_B * n->pw_T, s, ps_max_tiles(Tb));
+  if (!n->pw_shape) return CRK_OK;
+  const Shape* r = n->pw_shape;
+  n->pw_shape = nullptr;
+  return launch_plain_wgrad(r, n->pw_params, false, s);
 }
 
 // flags bit0: precise; bit1: skip parameter gradients (they would be discarded);
@@ -1247,9 +1100,7 @@ extern "C" int crk_net_backward_scaled(void* h, const float* params, unsigned lo
                                        int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
                                        float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
                                        unsigned long long seed, const float* dy_num, const float* dy_den, void* stream) {
-  Net* n = (Net*)h;
-  if (!n || !dy_num || !dy_den) return CRK_ERR_ARG;
-  if (n->d.kind != 2 || !stack_fused(n, B, T, flags & 1)) return CRK_ERR_UNSUPPORTED;
+  if (!h || !dy_num || !dy_den) return CRK_ERR_ARG;
   return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, dc, lddc, saved, B, T, flags,
                            seed, dy_num, dy_den, stream);
 }
@@ -1259,12 +1110,18 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
                              unsigned long long seed, const float* dy_num, const float* dy_den, void* stream) {
   Net* n = (Net*)h;
   if (!n || !params || !x || !dy || B <= 0 || T <= 0) return CRK_ERR_ARG;
+  const Shape* r = find_shape(n, B, T);
+  if (!r) return not_reserved("crk_net_backward");
   hipStream_t s = (hipStream_t)stream;
   const bool precise = flags & CRK_FLAG_PRECISE;
+  const Route& rt = r->route[precise];
+  if (dy_num && !(n->d.kind == 2 && rt.fused)) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_scaled)
   // CRK_FLAG_FWD_PRECISE: how the forward laid its planes out - unless that forward was the channel-split split-operand one
-  // (generator stacks of the bf16x3f mode), which writes the plain path's planes
-  const bool expects_x3f = !precise && (flags & CRK_FLAG_FWD_PRECISE) && n->d.kind == 0 && gen_x3f_path(n, B, T);
+  // (generator stacks of the bf16x3f mode), which writes the plain route's planes
+  const bool expects_x3f = !precise && (flags & CRK_FLAG_FWD_PRECISE) && r->route[0].x3f;
   const bool planes_precise = precise || ((flags & CRK_FLAG_FWD_PRECISE) && !expects_x3f);
+  // the channel-split chains read gate planes in the lane-record layout, which only the plain-plane forwards write
+  const bool gen_split = rt.gen_split && !planes_precise, disc_split = rt.disc_split && !planes_precise;
   RUN(check_forward_tag(n, saved, B, T, flags, expects_x3f));
   const bool want_w = !(flags & CRK_FLAG_NO_PARAM_GRAD) && grads;
   const bool defer_wn = flags & CRK_FLAG_DEFER_WNORM;
@@ -1273,20 +1130,15 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
   const crk_net_desc& d = n->d;
   RUN(flush_pending_wnorm(n, s));  // a second backward of this net reuses the partial-sum buffer and the gradient planes
   RUN(ensure_prepared(n, params, version, s));
-  RUN(wait_side_work(n, s));
-  RUN(ensure_bwd_buffers(n, B, T));
   const long long N = (long long)B * T;
   float* PT = n->partials;
-  const int G = stack_groups(n, B, T);
   n->jobs.clear();
+  const PsTables& Tb = r->ps;
 
-  if (d.kind == 2 && stack_fused(n, B, T, precise)) {
+  if (d.kind == 2 && rt.fused) {
     // data-gradient chain in one launch (output-gradient planes kept), then all weight gradients in one
     if (!saved) return CRK_ERR_ARG;
     const long long cw = d.conv_ch > d.out_ch ? d.conv_ch : d.out_ch;
-    RUN(ps_upload(n, N));
-    PsTables Tb;
-    ps_build(n, N, Tb);
     const uint16_t* f16 = reinterpret_cast<const uint16_t*>(saved + saved_f32_floats(n, N));
     uint16_t* g16 = reinterpret_cast<uint16_t*>(n->scratch + (long long)n->L * N * cw);
     PsP p = ps_base(n, B, T, params);
@@ -1294,13 +1146,13 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     p.in_num = dy_num; p.in_den = dy_den;
     p.save_hi = g16; p.save_lo = g16 + N * plain_gplanes_w(n);
     p.mask_hi = f16;
-    p.layers = n->d_ps + PS_MAXL; p.L = Tb.L[1];
-    // nobody wants the input gradient (the classifier's input is data, the adversarial net's is detached in its own
+    p.layers = r->d_ps + PS_MAXL; p.L = Tb.L[1];
+    // per call: nobody wants the input gradient (the classifier's input is data, the adversarial net's is detached in its own
     // update): the chain stops at the output-gradient plane of the first conv - its weight gradient needs that - and the
     // transposed first conv, the widest layer of the chain, is not computed
     if (!dx && p.L >= 2) { p.L -= 1; p.tail = 1; }
     bool done = false;
-    if (!precise && ps_chain_version() == 2) {
+    if (!precise && crk_sw().ps_v == 2) {
       PsP q = p;
       if (pstack2_plan(q, Tb.t[1]) == CRK_OK) { RUN(launch_pstack2(q, ps_flops(Tb.t[1], p.L, N), s)); done = true; }
     }
@@ -1309,11 +1161,8 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       RUN(launch_pstack(p, precise, ps_flops(Tb.t[1], p.L, N), s));
     }
     if (want_w) {
-      hipStream_t ws;
-      RUN(fork_wgrad(n, s, &ws));
-      RUN(plain_wgrad(n, B, T, g16, f16, precise, ws));
-      RUN(finish_wnorm(n, params, grads, defer_wn, ws));
-      RUN(join_wgrad(n, s, ws));
+      RUN(launch_plain_wgrad(r, plain_wgrad_params(n, r, g16, f16), precise, s));
+      RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
     }
     return CRK_OK;
   }
@@ -1332,7 +1181,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
         w.a1 = dcur; w.lda1 = ldcur; w.ca1 = e.cout; w.ca = e.cout;
         w.x = in; w.ldx = ldin; w.cx = e.cin; w.act_in = (i == 0) ? ACT_NONE : ACT_LRELU;
         w.ktaps = e.k; w.dil = dil; w.off0 = -((e.k - 1) / 2) * dil;
-        wgrad_slots(n, ei, B, T, w);
+        wgrad_slots(n, r, ei, w);
         RUN(wgrad_go(n, w, precise));
       }
       if (i > 0 || dx) {
@@ -1354,7 +1203,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     }
     if (want_w) {
       RUN(wgrad_flush(n, B, T, precise, s));
-      RUN(finish_wnorm(n, params, grads, defer_wn, s));
+      RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
     }
     return CRK_OK;
   }
@@ -1376,8 +1225,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
   const float sL = (float)sqrt(1.0 / L);
   const float rs = 0.70710678118654752440f;
 
-  const bool fused = stack_fused(n, B, T, precise);
-  PsTables Tb;
+  const bool fused = rt.fused;
   const uint16_t* f16 = reinterpret_cast<const uint16_t*>(saved + saved_f32_floats(n, N));
   uint16_t* s16 = reinterpret_cast<uint16_t*>(n->scratch + N * 64 * (3LL * L + 3));
   const GatedB16 gf = gated_b16(n, N);
@@ -1385,21 +1233,18 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
   // plain bf16, generator stacks: the head's and the first conv's data gradients run inside the chain's launch
   bool bfold = false;
   if (fused && !precise && d.kind == 0 && d.dropout == 0.f) {
-    static int sk_v = -1;
-    if (sk_v < 0) sk_v = crk_sw().sk_v;
-    const bool splitp = gen_split_path(n, B, T, planes_precise);
-    // (the channel-split chain also takes a dy whose rows are only 4-byte aligned: a column slice of a wider gradient)
-    const bool ok_y = (d.out_ch % 8 == 0) && (splitp || ((lddy % 4 == 0) && ((((uintptr_t)dy) & 15) == 0))) && ((((uintptr_t)dy) & 3) == 0);
+    // per call: the folds read dy and write dx in 16-byte pieces (the channel-split chain also takes a dy whose rows are
+    // only 4-byte aligned: a column slice of a wider gradient)
+    const bool ok_y = (d.out_ch % 8 == 0) && (gen_split || ((lddy % 4 == 0) && ((((uintptr_t)dy) & 15) == 0))) && ((((uintptr_t)dy) & 3) == 0);
     const bool ok_x = !dx || ((d.in_ch % 4 == 0) && (lddx % 4 == 0) && ((((uintptr_t)dx) & 15) == 0));
-    bfold = sk_v == 2 && ok_y && ok_x && (stack_bwd_waves(precise) == 8 || splitp);
+    bfold = crk_sw().sk_v == 2 && ok_y && ok_x && (stack_bwd_waves(precise) == 8 || gen_split);
   }
-  if (fused) { RUN(ps_upload(n, N)); ps_build(n, N, Tb); }
   if (fused && !bfold) {  // head backward: dy -> dH1 -> dS in one launch; dy and dH1 kept as bf16 planes
     PsP p = ps_base(n, B, T, params);
     p.x = dy; p.ldx = lddy; p.cin = d.out_ch; p.y = dS; p.ldy = 64; p.out_scale = sL;
     p.save_hi = s16 + gs.hb_hi; p.save_lo = s16 + gs.hb_lo;
     p.mask_hi = f16 + gf.head_hi;
-    p.layers = n->d_ps + 2 * PS_MAXL; p.L = 2;
+    p.layers = r->d_ps + 2 * PS_MAXL; p.L = 2;
     RUN(pstack_plan(p, Tb.t[2], precise));
     RUN(launch_pstack(p, precise, ps_flops(Tb.t[2], 2, N), s));
   } else if (!fused)
@@ -1409,7 +1254,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       WgradP w = base_wgrad(n, B, T);
       w.a1 = dy; w.lda1 = lddy; w.ca1 = e2.cout; w.ca = e2.cout;
       w.x = H1; w.ldx = 64; w.cx = 64; w.act_in = head_act;
-      wgrad_slots(n, n->idx_last2, B, T, w);
+      wgrad_slots(n, r, n->idx_last2, w);
       RUN(wgrad_go(n, w, precise));
     }
     ConvP p = base_conv(n, B, T);
@@ -1422,7 +1267,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       WgradP w = base_wgrad(n, B, T);
       w.a1 = dH1; w.lda1 = 64; w.ca1 = 64; w.ca = 64;
       w.x = SKIP; w.ldx = 64; w.cx = 64; w.sx = sL; w.act_in = head_act;
-      wgrad_slots(n, n->idx_last1, B, T, w);
+      wgrad_slots(n, r, n->idx_last1, w);
       RUN(wgrad_go(n, w, precise));
     }
     ConvP q = base_conv(n, B, T);
@@ -1431,27 +1276,21 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     q.y = dS; q.ldy = 64; q.dmask = SKIP; q.ldm = 64; q.dmask_act = head_act; q.out_scale = sL;
     RUN(conv_go(q, MODE_PLAIN, precise, s));
   }
-  hipStream_t ws = s;  // stream of the weight-gradient launches (the side stream once the fused chain has forked)
   const float* dxo = nullptr;  // gradient wrt the block output; the last block's x output is unused
   if (fused) {
-    StackBP bp;
-    memset(&bp, 0, sizeof(bp));
+    StackBP bp = stack_bwd_shape(n, B, T);
     bp.dS = dS; bp.saved = saved; bp.dX0 = dXall;
     bp.tb_hi = f16 + gf.tb_hi; bp.tb_lo = f16 + gf.tb_lo; bp.sg_hi = f16 + gf.sg_hi; bp.sg_lo = f16 + gf.sg_lo;
     bp.gb_hi = s16 + gs.gb_hi; bp.gb_lo = s16 + gs.gb_lo;
     bp.dxb_hi = s16 + gs.dxb_hi; bp.dxb_lo = s16 + gs.dxb_lo;
     bp.dsb_hi = s16 + gs.dsb_hi; bp.dsb_lo = s16 + gs.dsb_lo;
-    bp.dc = (dc && d.aux_ch > 0) ? dc : nullptr; bp.lddc = lddc; bp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
+    bp.dc = (dc && d.aux_ch > 0) ? dc : nullptr; bp.lddc = lddc;
     bp.whi = n->whi; bp.wlo = n->wlo; bp.layers = n->d_blayers;
-    bp.B = B; bp.T = T; bp.L = L; bp.ktaps = d.kernel_size;
-    int fhl, fhr, md;
-    stack_halo(n, &fhl, &fhr, &bp.max_off, &md);
-    bp.hl = fhr; bp.hr = fhl;  // the data gradient looks the other way
     if (d.dropout > 0.f) { bp.drop_p = d.dropout; bp.drop_seed = seed_val; bp.drop_seed_ptr = seed_ptr; }
     bp.mask_l0 = d.kind == 1; bp.slope = d.slope;
     RUN(stack_bwd_plan(bp, precise));
     bool split = false;  // the channel-split chain (stack2b_kernels.hip): folded generator stacks, plain bf16
-    if (bfold && (bp.nw == 8 || gen_split_path(n, B, T, planes_precise))) {
+    if (bfold && (bp.nw == 8 || gen_split)) {
       const ConvEntry& ef = n->ents[n->idx_first];
       const ConvEntry& e1 = n->ents[n->idx_last1];
       const ConvEntry& e2 = n->ents[n->idx_last2];
@@ -1459,23 +1298,23 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       bp.w_h2 = e2.bw_off; bp.w_h1 = e1.bw_off; bp.w_first = ef.bw_off;
       bp.hmask_hi = f16 + gf.head_hi; bp.hb_hi = s16 + gs.hb_hi; bp.head_scale = sL;
       bp.dx = dx; bp.lddx = lddx; bp.in_ch = d.in_ch; bp.in_rows = ef.bw_rows; bp.dx_scale = dx_scale;
-      // CRK_SKB_V=1: the frame-split chain (A/B timing, the bitwise test); see gen_split_path
+      // CRK_SKB_V=1: the frame-split chain (A/B timing, the bitwise test); see route_of
       bp.f_h2 = e2.bfr_off; bp.f_h1 = e1.bfr_off; bp.f_first = ef.bfr_off;
-      if (gen_split_path(n, B, T, planes_precise)) {
+      if (gen_split) {
         StackBP q = bp;
         q.ts_stride = ts_plane_stride(N);
         if (stack2_bwd_plan(q) == CRK_OK) { bp = q; split = true; }
       }
     } else
       bfold = false;
-    if (!split && disc_split_path(n, B, T, planes_precise)) {  // the discriminator: the same chain without the folds
+    if (!split && disc_split) {  // the discriminator: the same chain without the folds
       StackBP q = bp;
       q.ts_stride = ts_plane_stride(N);
       q.dy = nullptr;
-      if (stack2_bwd_plan(q) != CRK_OK) return CRK_ERR_UNSUPPORTED;  // (cannot happen: the predicate implies the plan)
+      if (stack2_bwd_plan(q) != CRK_OK) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
       bp = q; split = true;
     }
-    if (!split && gen_split_path(n, B, T, planes_precise)) {
+    if (!split && gen_split) {
       // the forward wrote the gate planes for the channel-split chain: nothing else can read them
       fprintf(stderr, "[crank_hip] crk_net_backward: dy / dx must be 16-byte aligned with row strides that are multiples of 4 floats\n");
       return CRK_ERR_ARG;
@@ -1485,10 +1324,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     bp.rec = (split && N % 4 == 0) ? 1 : 0;
     if (split) RUN(launch_stack2_bwd(bp, s));
     else RUN(launch_stack_bwd(bp, precise, s));
-    if (want_w) {
-      RUN(fork_wgrad(n, s, &ws));  // everything the weight gradients read is written by now
-      // weight gradients of every block: one launch over (utterance group, block)
-      RUN(ensure_wl_table(n, G));
+    if (want_w) {  // weight gradients of every block: one launch over (utterance group, block)
       StackWP wp;
       memset(&wp, 0, sizeof(wp));
       wp.xb_hi = f16 + gf.xb_hi; wp.xb_lo = f16 + gf.xb_lo; wp.zb_hi = f16 + gf.zb_hi; wp.zb_lo = f16 + gf.zb_lo;
@@ -1496,11 +1332,11 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       if (d.aux_ch > 0) { wp.cb_hi = f16 + gf.cb_hi; wp.cb_lo = f16 + gf.cb_lo; }
       wp.gb_hi = bp.gb_hi; wp.gb_lo = bp.gb_lo; wp.dxb_hi = bp.dxb_hi; wp.dxb_lo = bp.dxb_lo;
       wp.dsb_hi = bp.dsb_hi; wp.dsb_lo = bp.dsb_lo;
-      wp.layers = n->d_wlayers; wp.partials = PT;
+      wp.layers = r->d_wlayers; wp.partials = PT;
       wp.B = B; wp.T = T; wp.L = L; wp.ktaps = d.kernel_size; wp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
-      wp.cpg = stack_cpg(n, B, T); wp.G = G;
+      wp.cpg = stack_cpg(n, B, T); wp.G = r->q.Gs;
       wp.rec_g = bp.rec;
-      RUN(launch_stack_wgrad(wp, precise, ws));
+      RUN(launch_stack_wgrad(wp, precise, s));
     }
     dxo = dXall;
   }
@@ -1526,16 +1362,16 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       w.x = X + l * P; w.ldx = 64; w.cx = 64;
       if (d.dropout > 0.f) { w.drop_p = d.dropout; w.drop_seed = layer_seed(seed_val, l); w.drop_seed_ptr = seed_ptr; }
       w.ktaps = ec.k; w.dil = dil; w.off0 = off0;
-      wgrad_slots(n, n->idx_conv[l], B, T, w);
+      wgrad_slots(n, r, n->idx_conv[l], w);
       if (d.aux_ch > 0) {
         const ConvEntry& ea = n->ents[n->idx_aux[l]];
-        w.has_aux = 1; w.xc = c; w.ldc = ldc; w.cc = ea.cin; w.partial_aux = PT + n->abs_ents[n->idx_aux[l]].pt_off;
+        w.has_aux = 1; w.xc = c; w.ldc = ldc; w.cc = ea.cin; w.partial_aux = PT + r->abs[n->idx_aux[l]].pt_off;
       }
       RUN(wgrad_go(n, w, precise));
       WgradP v = base_wgrad(n, B, T);  // 1x1 out | skip on z
       v.a1 = dxo; v.lda1 = 64; v.ca1 = 64; v.a2 = dS; v.lda2 = 64; v.ca2 = 64; v.ca = 128;
       v.x = Z + l * P; v.ldx = 64; v.cx = 64;
-      wgrad_slots(n, n->idx_out[l], B, T, v);
+      wgrad_slots(n, r, n->idx_out[l], v);
       RUN(wgrad_go(n, v, precise));
     }
     if (dc && d.aux_ch > 0) {  // conditioning gradient, accumulated over layers
@@ -1565,16 +1401,16 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     if (dx && !bfold) {
       PsP p = ps_base(n, B, T, params);
       p.x = dxo; p.ldx = 64; p.cin = 64; p.y = dx; p.ldy = lddx; p.out_scale = dx_scale;
-      p.layers = n->d_ps + 3 * PS_MAXL; p.L = 1;
+      p.layers = r->d_ps + 3 * PS_MAXL; p.L = 1;
       RUN(pstack_plan(p, Tb.t[3], precise));
       RUN(launch_pstack(p, precise, ps_flops(Tb.t[3], 1, N), s));
     }
     if (want_w) {
-      if (defer_wn && !precise && ws == s) {  // with the weight-norm backward: one launch for all stacks of the model
-        n->pw_pending = true; n->pw_B = B; n->pw_T = T; n->pw_a = s16; n->pw_b = f16;
-        n->pw_params = plain_wgrad_params(n, B, T, s16, f16);  // tables / slot counts of THIS shape
+      const PwP wp = plain_wgrad_params(n, r, s16, f16);
+      if (defer_wn && !precise) {  // with the weight-norm backward: one launch for all stacks of the model
+        n->pw_shape = r; n->pw_params = wp;
       } else {
-        RUN(plain_wgrad(n, B, T, s16, f16, precise, ws));
+        RUN(launch_plain_wgrad(r, wp, precise, s));
       }
     }
   } else
@@ -1584,7 +1420,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       WgradP w = base_wgrad(n, B, T);
       w.a1 = dxo; w.lda1 = 64; w.ca1 = 64; w.ca = 64;
       w.x = x; w.ldx = ldx; w.cx = e.cin;
-      wgrad_slots(n, n->idx_first, B, T, w);
+      wgrad_slots(n, r, n->idx_first, w);
       RUN(wgrad_go(n, w, precise));
     }
     if (dx) {
@@ -1596,9 +1432,8 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
     }
   }
   if (want_w) {
-    RUN(wgrad_flush(n, B, T, precise, ws));
-    RUN(finish_wnorm(n, params, grads, defer_wn, ws));
-    RUN(join_wgrad(n, s, ws));
+    RUN(wgrad_flush(n, B, T, precise, s));
+    RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
   }
   return CRK_OK;
 }
@@ -1629,24 +1464,21 @@ static int flush_plain_wgrads(int n_nets, void* const* nets, hipStream_t s) {
     for (int i = 0; i < n_nets; i++) {
       Net* n = (Net*)nets[i];
       if (!n) return CRK_ERR_ARG;
-      if (!n->pw_pending) continue;
+      const Shape* r = n->pw_shape;
+      if (!r) continue;
       if (M.n == CRK_MAX_NETS_PW) { RUN(flush_pending_plain_wgrad(n, s)); continue; }
-      PsTables Tb;
-      ps_build(n, (long long)n->pw_B * n->pw_T, Tb);
+      const PsTables& Tb = r->ps;
       M.q[M.n] = n->pw_params;
       M.first[M.n] = layers;
       layers += Tb.nw;
       if (n->pw_params.G > max_G) max_G = n->pw_params.G;
       if (Tb.max_wa > max_wa) max_wa = Tb.max_wa;
       if (Tb.max_wb > max_wb) max_wb = Tb.max_wb;
-      for (int j = 0; j < Tb.nw; j++) {
-        const int tiles = ((Tb.w[j].ca + 31) / 32) * ((Tb.w[j].cb + 31) / 32) * Tb.w[j].k;
-        if (tiles > max_tiles) max_tiles = tiles;
-      }
-      flops += Tb.wflops_per_frame * n->pw_B * n->pw_T;
-      bytes += 2.0 * (Tb.max_wa + Tb.max_wb) * (double)n->pw_B * n->pw_T * Tb.nw;
+      if (Tb.max_tiles > max_tiles) max_tiles = Tb.max_tiles;
+      flops += Tb.wflops_per_frame * r->B * r->T;
+      bytes += 2.0 * (Tb.max_wa + Tb.max_wb) * (double)r->B * r->T * Tb.nw;
       M.n++;
-      n->pw_pending = false;
+      n->pw_shape = nullptr;
     }
     M.first[M.n] = layers;
     if (M.n > 0) RUN(launch_pstack_wgrad_multi(M, layers, max_G, max_wa, max_wb, max_tiles, flops, bytes, s));
@@ -1662,17 +1494,16 @@ extern "C" int crk_nets_wnorm_bwd(int n_nets, void* const* nets, void* stream) {
   for (int i = 0; i < n_nets; i++) {
     Net* n = (Net*)nets[i];
     if (!n) return CRK_ERR_ARG;
-    if (!n->wn_pending) continue;
-    RUN(wait_side_work(n, s));  // (weight gradients on a side stream: their partial sums first)
+    if (!n->wn_shape) continue;
     if (R.n == CRK_MAX_NETS) {  // more nets than one launch holds: this one goes alone
       RUN(flush_pending_wnorm(n, s));
       continue;
     }
     NetRef& q = R.r[R.n++];
-    q.ents = n->wn_ents ? n->wn_ents : n->d_ents; q.n_ents = (int)n->ents.size(); q.first = total;
+    q.ents = n->wn_shape->d_ents; q.n_ents = (int)n->ents.size(); q.first = total;
     q.params = n->wn_params; q.grads = n->wn_grads; q.partials = n->partials; q.norms = n->norms;
     total += q.n_ents;
-    n->wn_pending = false;
+    n->wn_shape = nullptr;
   }
   if (R.n == 0) return CRK_OK;
   return launch_wnorm_bwd_multi(R, total, s);
@@ -1693,8 +1524,6 @@ extern "C" int crk_nets_prepare(int n_nets, void* const* nets, const float* cons
     if (n->prepared_version == version && n->prepared_params == params[i]) continue;
     if (net_nmax(n) > nmax) nmax = net_nmax(n);
     if (R.n == CRK_MAX_NETS) { RUN(ensure_prepared(n, params[i], version, s)); continue; }
-    if (n->Gs == 0) RUN(upload_entries(n, 1, 1));
-    RUN(wait_side_work(n, s));
     NetRef& q = R.r[R.n++];
     q.ents = n->d_ents; q.n_ents = (int)n->ents.size(); q.first = total;
     q.params = params[i]; q.whi = n->whi; q.wlo = n->wlo; q.norms = n->norms;

@@ -74,16 +74,10 @@ long long crk_net_saved_bytes(void* net, int B, int T);
 /* The handle's own device memory for batch shape (B, T) - the backward's gradient planes, the weight-gradient partial sums
  * (crk_net_scratch_bytes of them) and the per-shape descriptor tables - allocated HERE, once per shape and outside the step
  * (it calls hipMalloc / hipMemcpy: a device-wide synchronisation; not inside a stream capture).  crk_net_forward /
- * crk_net_backward* never allocate: at a shape that was not reserved (and that the buffers of a larger reserved shape with
- * the same slot counts do not happen to cover) they launch nothing and return CRK_ERR_ARG.  Buffers outgrown by a later
- * reserve stay alive until crk_net_destroy (a captured HIP graph may still hold them). */
+ * crk_net_backward* never allocate: at a shape that was not reserved they launch nothing and return CRK_ERR_ARG.  Buffers
+ * outgrown by a later reserve stay alive until crk_net_destroy (a captured HIP graph may still hold them). */
 int crk_net_reserve(void* net, int B, int T);
 long long crk_net_scratch_bytes(void* net, int B, int T);
-/* Optional: run the weight gradients of crk_net_backward on `stream` (null: on the call's stream).
- * They only read buffers the data-gradient chain has finished with, so they overlap the next
- * stack's chain.  The caller must make its consumers of `grads` (optimizer, all-reduce) and the
- * release of `saved` wait for that stream; the library orders its own buffers itself. */
-int crk_net_set_wgrad_stream(void* net, void* stream);
 /* y[N,out_ch] = net(x[N,in_ch], c[N,aux_ch]); `saved` (crk_net_saved_bytes) keeps what
  * the backward needs; `version` changes whenever `params` was modified. */
 int crk_net_forward(void* net, const float* params, unsigned long long version, const float* x, int ldx,

@@ -261,7 +261,7 @@ def test_generator_ema_of_quantizers_of_different_shapes_equals_each_alone():
 
 # ------------------------------------------------------------------------------------------------ generator stacks
 # (in, out, k, layers, stacks, aux, causal, T) of the stacks other configurations build, and the kernel generation
-# crk_debug_net_paths must report for them.  bit 0 (gen_split_path, net.hip) needs in and out a multiple of 8, a kernel
+# crk_debug_net_paths must report for them.  bit 0 (route_of, net.hip) needs in and out a multiple of 8, a kernel
 # of 3 or 5 and no conditioning on a kernel-3 stack (stack2_fwd_plan); none of these shapes exceeds its other limits.
 # Where it fails, bit 1 (the bf16x3f split forward) cannot hold either and the stack runs the frame-split kernels.
 GEN_CASES = {

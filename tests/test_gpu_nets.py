@@ -679,6 +679,18 @@ def test_compute_entry_points_never_allocate_and_check_how_they_are_paired(capfd
     assert L.crk_net_reserve(net.handle, B, T) == 0 and L.crk_debug_alloc_count() == a1  # idempotent
     # a smaller batch with other slot counts was not reserved either
     assert fwd(2, 0, saved) == 1
+    # nor was one frame more: the same slot counts as (B, T), but every shape needs its own reserve; buffers sized for it
+    T2 = T + 1
+    x2, dy2 = torch.randn(B, T2, 80, device="cuda"), torch.randn(B, T2, 64, device="cuda")
+    y2, dx2 = torch.empty(B, T2, 64, device="cuda"), torch.empty(B, T2, 80, device="cuda")
+    saved2 = torch.empty(L.crk_net_saved_bytes(net.handle, B, T2) // 4 + 1, device="cuda")
+    a2 = L.crk_debug_alloc_count()
+    assert L.crk_net_forward(net.handle, ptr(params), 1, ptr(x2), 80, None, 0, ptr(y2), 64, ptr(saved2), B, T2, 0, 0,
+                             stream_ptr()) == 1
+    assert L.crk_net_backward(net.handle, ptr(params), 1, ptr(grads), ptr(x2), 80, None, 0, ptr(dy2), 64, ptr(dx2), 80, 1.0,
+                              None, 0, ptr(saved2), B, T2, 0, 0, stream_ptr()) == 1
+    torch.cuda.synchronize()
+    assert L.crk_debug_alloc_count() == a2
     # pairing: plain forward, then a backward that claims the split-operand forward wrote the planes (and the other way round)
     PRECISE, FWD_PRECISE, BWD_PLAIN = 1, 32, 64
     assert fwd(B, 0, saved) == 0
