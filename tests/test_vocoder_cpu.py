@@ -99,7 +99,8 @@ def test_from_checkpoint_refuses_unsupported_options(tmp_path, change):
         ParallelWaveGANVocoder.from_checkpoint(ck, cfg, device="cpu")
 
 
-@pytest.mark.parametrize("scales,window", [([2, 3], 2), ([4, 4], 1), ([2, 4, 4], 0)])
+@pytest.mark.parametrize("scales,window", [([2, 3], 2), ([4, 4], 1), ([2, 4, 4], 0), ([4, 5, 3, 4], 2), ([2, 3, 5], 5),
+                                           ([1, 4, 8], 2), ([16, 16], 0), ([2] * 8, 5)])
 def test_restated_upsampler_matches_brute_force(scales, window):
     """The restated ConvInUpsampleNetwork (replicate pad, conv_in, nearest stretch + (1, 2s+1) conv per stage with zero
     padding at each stage's edges) against explicit loops, on short inputs where the edges dominate."""

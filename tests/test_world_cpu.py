@@ -149,3 +149,30 @@ def test_world2wav_clips():
     y = R.world2wav(f0, mc, cap, fs=22050, shiftms=10, alpha=0.455)
     assert y.shape == (R.y_length(30, 22050, 10),) and np.abs(y).max() <= 1.0
     assert math.isclose(np.abs(y).max(), 1.0)
+
+
+def test_module_refusals_at_the_limits():
+    """The limits of crank_amd.world, refused before the device: order + 1 outside 1..128, a sampling rate without
+    an aperiodicity band (below 12 kHz), and a batch of mixed orders.  The accepted side of each limit reaches the
+    device check (RuntimeError on a CPU synthesizer) instead."""
+    from crank_amd.world import MAX_ORDER1, WorldSynthesizer, n_bands
+
+    assert MAX_ORDER1 == 128
+    assert [n_bands(fs) for fs in (11025, 11999, 12000, 44100, 48000)] == [0, 0, 1, 5, 5]
+    for fs in (8000, 11025, 11999):
+        with pytest.raises(ValueError):
+            WorldSynthesizer(fs, 1024, 10.0, 0.455, device="cpu")
+    assert WorldSynthesizer(12000, 1024, 10.0, 0.455, device="cpu").bands == 1
+    syn = WorldSynthesizer(22050, 1024, 10.0, 0.455, device="cpu")
+    rng = np.random.default_rng(9)
+    f0, _, cap, _ = utterance(rng, 6, 1, 2)
+    for order1 in (0, MAX_ORDER1 + 1):
+        with pytest.raises(ValueError, match="mcep must be"):
+            syn.synthesis(f0, np.zeros((6, order1)), cap)
+    for order1 in (1, MAX_ORDER1):
+        with pytest.raises(RuntimeError, match="device must be the GPU"):
+            syn.synthesis(f0, np.zeros((6, order1)), cap)
+    with pytest.raises(ValueError, match="same order"):
+        syn.synthesis_batch([f0, f0], [np.zeros((6, 35)), np.zeros((6, 36))], [cap, cap])
+    with pytest.raises(RuntimeError, match="device must be the GPU"):
+        syn.synthesis_batch([f0, f0], [np.zeros((6, 36)), np.zeros((6, 36))], [cap, cap])
