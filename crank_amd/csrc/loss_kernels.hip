@@ -6,6 +6,8 @@
 //   multi-resolution STFT loss - crank/net/module/loss.py:50-114
 // All reductions are two-stage (per-workgroup partials, then one finishing block) so
 // results are deterministic; there are no host synchronisations.
+#include <algorithm>
+
 #include "common.h"
 
 __device__ __forceinline__ float block_sum_256(float v, float* sh) {
@@ -412,7 +414,8 @@ __global__ __launch_bounds__(256) void ce_partial_regs(const float* __restrict__
 __global__ __launch_bounds__(256) void scale_by_kernel(float* __restrict__ v, long total,
                                                        const float* __restrict__ gout,
                                                        const float* __restrict__ stat, float* __restrict__ out) {
-  const float g = gout[0] / stat[1];
+  // no frame counted (every target ignored): the gradient is 0 like torch's, not 0 * (g / 0) = NaN
+  const float g = stat[1] != 0.f ? gout[0] / stat[1] : 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = v[i] * g;
 }
 
@@ -1536,15 +1539,20 @@ extern "C" int crk_concat_embed(const float* a, int lda, int ca, const float* b,
 // Two stages, no atomics, fixed summation order (bit-reproducible): a workgroup reduces a run of
 // 256 frames into [rows][E] (each (frame-lane, column) thread owns private LDS accumulators,
 // combined in lane order), then one pass adds the per-run tables in run order.
+// The host picks nsub, the frame lanes per column (256 / E where their accumulators fit in EMB_LDS, fewer where they do
+// not); where even one lane's [n_rows][E] does not fit, the rows are cut into windows of wrows, one per blockIdx.y, and a
+// workgroup accumulates only the labels of its window.  Frame lane sub sums frames sub, sub + nsub, ... in frame order and
+// the lanes are combined in lane order: the order is fixed per (E, n_rows), and unchanged where 256 / E lanes fit.
 #define EMB_FRAMES 256
+#define EMB_LDS (60 * 1024)
 __global__ __launch_bounds__(256) void embed_bwd_partial_kernel(const float* __restrict__ dcat, int ld, int c0, int E,
                                                                 const long long* __restrict__ idx, long run, long N,
-                                                                int n_rows, float* __restrict__ part) {
-  extern __shared__ float acc[];  // [nsub][n_rows][E]
+                                                                int n_rows, int nsub, int wrows, float* __restrict__ part) {
+  extern __shared__ float acc[];  // [nsub][rows of the window][E]
 #define EMB_LABEL(n) idx[run > 1 ? (n) - (n) % run : (n)]
   const int tid = threadIdx.x;
-  const int nsub = 256 / E, tab = n_rows * E;
-  for (int i = tid; i < nsub * tab; i += 256) acc[i] = 0.f;
+  const int row0 = blockIdx.y * wrows, rows = min(wrows, n_rows - row0), tab = n_rows * E, wtab = rows * E;
+  for (int i = tid; i < nsub * wtab; i += 256) acc[i] = 0.f;
   __syncthreads();
   const int e = tid % E, sub = tid / E;
   if (sub < nsub) {
@@ -1559,18 +1567,18 @@ __global__ __launch_bounds__(256) void embed_bwd_partial_kernel(const float* __r
       for (int u = 0; u < 8; u++) { r[u] = EMB_LABEL(n + u * (long)nsub); v[u] = dcat[(n + u * (long)nsub) * ld + c0 + e]; }
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (r[u] >= 0 && r[u] < n_rows) acc[(sub * n_rows + (int)r[u]) * E + e] += v[u];
+        if (r[u] >= row0 && r[u] < row0 + rows) acc[(sub * rows + (int)(r[u] - row0)) * E + e] += v[u];
     }
     for (; n < end; n += nsub) {
       const long r = EMB_LABEL(n);
-      if (r >= 0 && r < n_rows) acc[(sub * n_rows + (int)r) * E + e] += dcat[n * ld + c0 + e];
+      if (r >= row0 && r < row0 + rows) acc[(sub * rows + (int)(r - row0)) * E + e] += dcat[n * ld + c0 + e];
     }
   }
   __syncthreads();
-  for (int i = tid; i < tab; i += 256) {
+  for (int i = tid; i < wtab; i += 256) {
     float s = 0.f;
-    for (int u = 0; u < nsub; u++) s += acc[u * tab + i];
-    part[(long)blockIdx.x * tab + i] = s;
+    for (int u = 0; u < nsub; u++) s += acc[u * wtab + i];
+    part[(long)blockIdx.x * tab + (long)row0 * E + i] = s;
   }
 #undef EMB_LABEL
 }
@@ -1605,13 +1613,15 @@ extern "C" long long crk_embed_bwd_scratch_floats(long long N, int E, int n_rows
 
 extern "C" int crk_embed_bwd_run(const float* dcat, int ld, int c0, int E, const long long* idx, long long run, long long N,
                                  int n_rows, float* dtable, float* scratch, void* stream) {
-  if (!dcat || !idx || !dtable || !scratch || E <= 0 || E > 256 || run < 1) return CRK_ERR_ARG;
-  const int nsub = 256 / E;
-  if ((long long)nsub * n_rows * E * 4 > 60 * 1024) return CRK_ERR_UNSUPPORTED;
+  if (!dcat || !idx || !dtable || !scratch || E <= 0 || E > 256 || n_rows < 1 || run < 1) return CRK_ERR_ARG;
+  const long long row_bytes = (long long)E * sizeof(float);
+  const int wrows = (int)std::min<long long>(n_rows, EMB_LDS / row_bytes);  // >= 60 rows at E <= 256
+  const int nsub = std::min<int>(256 / E, (int)(EMB_LDS / (row_bytes * wrows)));
+  const int nwin = (n_rows + wrows - 1) / wrows;
   const int nb = (int)((N + EMB_FRAMES - 1) / EMB_FRAMES), tab = n_rows * E;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(embed_bwd_partial_kernel, dim3(nb), dim3(256), (size_t)nsub * tab * sizeof(float), s, dcat, ld, c0, E,
-                     idx, (long)run, (long)N, n_rows, scratch);
+  hipLaunchKernelGGL(embed_bwd_partial_kernel, dim3(nb, nwin), dim3(256), (size_t)nsub * wrows * row_bytes, s, dcat, ld, c0,
+                     E, idx, (long)run, (long)N, n_rows, nsub, wrows, scratch);
   hipLaunchKernelGGL(embed_bwd_reduce_kernel, dim3((tab + 255) / 256), dim3(256), 0, s, scratch, nb, tab, dtable);
   CRK_CHECK_LAUNCH();
   return CRK_OK;

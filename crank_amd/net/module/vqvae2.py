@@ -199,6 +199,8 @@ def flush_ema(pending):
 # dimensions; the EMA statistics and blend take at most 4096 codes)
 VQ_DIMS = (16, 32, 64, 128)
 VQ_EMA_MAX_CODES = 4096
+# widest speaker embedding the table-gradient kernel takes (loss_kernels.hip, crk_embed_bwd_run: one lane per column)
+SPKR_EMB_MAX = 256
 
 
 def check_vq_shapes(conf):
@@ -212,6 +214,9 @@ def check_vq_shapes(conf):
         if conf["ema_flag"] and K > VQ_EMA_MAX_CODES:
             raise NotImplementedError(f"emb_size[{n}] = {K}: the EMA codebook update supports at most "
                                       f"{VQ_EMA_MAX_CODES} codes (ema_flag: true)")
+    if conf["use_spkr_embedding"] and conf["spkr_embedding_size"] > SPKR_EMB_MAX:
+        raise NotImplementedError(f"spkr_embedding_size = {conf['spkr_embedding_size']}: the speaker-embedding gradient "
+                                  f"kernel supports at most {SPKR_EMB_MAX} columns")
     d_in = sum(conf["emb_dim"][i] for i in range(nst))
     if d_in > MAX_CHANNELS:
         raise NotImplementedError(f"n_vq_stacks = {nst}: the first decoder's input is sum(emb_dim) = {d_in} channels, "

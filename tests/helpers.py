@@ -112,15 +112,17 @@ class MlfbScaler:
 
 
 def run_golden_case(tag, build_models, build_optim, build_criterion, build_sched, device="cpu", pyseed=1234, optim_type=None,
-                    steps=None):
+                    steps=None, n_spkrs=None):
     """Re-run the scenario of tests/golden/step_<tag>.npz with the given factories and
-    return (loss values per step, models, trainer, fixture).  optim_type / steps: the same scenario with another
-    ``optim.<model>.type`` (crank/net/trainer/utils.py:40-50) / step count - the fixture's values then do not apply."""
+    return (loss values per step, models, trainer, fixture).  optim_type / steps / n_spkrs: the same scenario (B, T and
+    seed of the fixture) with another ``optim.<model>.type`` (crank/net/trainer/utils.py:40-50) / step count / speaker
+    count - the fixture's values then do not apply."""
     from crank_amd.net.trainer import TrainerWrapper
 
     fx = golden(f"step_{tag}.npz")
-    B, T, n_spkrs, seed, fx_steps = [int(v) for v in fx["meta_B_T_nspk_seed_steps"]]
+    B, T, fx_spkrs, seed, fx_steps = [int(v) for v in fx["meta_B_T_nspk_seed_steps"]]
     steps = fx_steps if steps is None else steps
+    n_spkrs = fx_spkrs if n_spkrs is None else n_spkrs
     ttype, over, _ = STEP_CASES[tag]
     random.seed(pyseed)
     np.random.seed(pyseed)

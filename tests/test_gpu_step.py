@@ -222,7 +222,13 @@ def test_first_step_gradients_bf16_match_bf16_emulating_oracle(tag):
 def test_vqvae2_forward_backward_vs_oracle(mode):
     """Forward values (decoded, encoded, indices) against the fp32 oracle in both parity modes; the parameter gradients in
     the mode whose backward is split-operand too (bf16x3f's backward is plain bf16: pinned by
-    test_first_step_gradients_bf16_match_bf16_emulating_oracle)."""
+    test_first_step_gradients_bf16_match_bf16_emulating_oracle).  3 speakers, and 100 (the speaker-embedding table
+    gradient with fewer frame lanes than 256 / E, crk_embed_bwd_run)."""
+    for S in (3, 100):
+        _vqvae2_vs_oracle(mode, S)
+
+
+def _vqvae2_vs_oracle(mode, S):
     from crank_amd import ops
     from crank_amd.net.module.vqvae2 import VQVAE2
     from oracle.modules import OracleVQVAE2
@@ -230,7 +236,7 @@ def test_vqvae2_forward_backward_vs_oracle(mode):
     ops.set_precision(mode)
     try:
         conf = load_yaml(None)
-        B, T, S = 2, 140, 3
+        B, T = 2, 140
         orac = OracleVQVAE2(conf, spkr_size=S).train()
         prod = VQVAE2(conf, spkr_size=S).train()
         fill_models({"G": orac})
@@ -263,10 +269,65 @@ def test_vqvae2_forward_backward_vs_oracle(mode):
             e = _relmax(prod.grad_view(k).cpu().numpy(), p.grad.numpy())
             if e > worst[1]:
                 worst = (k, e)
-        print(mode, "worst G parameter-gradient error", worst)
+        print(mode, S, "worst G parameter-gradient error", worst)
         assert worst[1] < (1e-3 if mode == "bf16x3" else 1e-1), worst
     finally:
         ops.set_precision("bf16")
+
+
+@pytest.mark.parametrize("tag", ["vqvae", "lsgan"])
+def test_trainer_steps_at_100_speakers_vs_oracle(tag):
+    """The scenario at 100 speakers (the jvs_ver1 recipe's count; B, T and seed of the fixture), 3 steps, product trainer
+    (bf16x3) against the CPU oracle trainer: every loss within 2e-3 |v| + 1e-5, and every parameter tensor's MOVEMENT
+    over the run within 5 %, the 100 x 32 speaker-embedding table and the 100-class heads among them.  At 100 rows the
+    table gradient no longer fits 256 / E frame lanes in LDS (crk_embed_bwd_run picks 4).  With RAdam, whose first steps
+    move each weight in proportion to its gradient (Adam's move it by lr * sign(gradient), whatever the gradient's size).
+    Every update is rounded to the fp32 spacing of the weight it changes, in the oracle and the kernels alike: the
+    movement is held to 5 % plus that rounding, steps * spacing per moved element.  (The weight_g of the gated blocks
+    move by one or two spacings over these steps, in the oracle itself: their movement is rounding, not resolved.)"""
+    from crank_amd import ops
+    from tests.helpers import initial_state
+
+    torch.set_num_threads(8)
+    steps, S = 3, 100
+    lo, mo, _, _, _ = run_golden_case(tag, *_oracle_factories(), optim_type="radam", steps=steps, n_spkrs=S)
+    ops.set_precision("bf16x3")
+    try:
+        lh, mh, _, _, _ = run_golden_case(tag, *_hip_factories(), device="cuda", optim_type="radam", steps=steps, n_spkrs=S)
+    finally:
+        ops.set_precision("bf16")
+    for s in range(steps):
+        for k, v in lo[s].items():
+            if v:
+                assert abs(lh[s][k] - v) <= 2e-3 * abs(v) + 1e-5, (s, k, lh[s][k], v)
+    init = initial_state(mo)
+    wide, errs, bad = [], {}, []
+    for m in mo:
+        so, sh = mo[m].state_dict(), mh[m].state_dict()
+        for k in so:
+            name = f"{m}/{k}"
+            if S in tuple(so[k].shape):
+                wide.append(name)
+            w0 = init[m][k].float()
+            do = (so[k].float() - w0).reshape(-1)
+            dh = (sh[k].float().cpu() - w0).reshape(-1)
+            if float(do.norm()) == 0.0:
+                assert float(dh.norm()) == 0.0, name
+                continue
+            moved = ((do != 0) | (dh != 0)).numpy()
+            rounding = steps * float(np.linalg.norm(np.spacing(np.abs(w0.reshape(-1).numpy()[moved])).astype(np.float64)))
+            err, mv = float((dh - do).norm()), float(do.norm())
+            errs[name] = (err / mv, mv / rounding)
+            if not err <= 0.05 * mv + rounding:
+                bad.append((name, err / mv, mv / rounding))
+    assert "G/spkr_embedding.weight" in wide and tuple(mo["G"].state_dict()["spkr_embedding.weight"].shape) == (S, 32)
+    assert any(not w.startswith("G/") for w in wide), wide  # the classifier / adversarial heads
+    assert all(errs[w][1] >= 10.0 for w in wide), {w: errs[w] for w in wide}  # their movement is resolved: 5 % binds
+    resolved = {k: v[0] for k, v in errs.items() if v[1] >= 20.0}
+    print(tag, "100 speakers: tensors with a 100-wide dimension", {w: tuple(round(x, 4) for x in errs[w]) for w in wide},
+          f"| {len(resolved)} of {len(errs)} moved tensors move by >= 20x their rounding, worst relative error",
+          max(resolved.items(), key=lambda t: t[1]))
+    assert not bad, bad
 
 
 def _frame_mcd(a, b):

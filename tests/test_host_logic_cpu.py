@@ -333,6 +333,7 @@ def test_collector_is_held_off_for_a_capture_and_handed_back():
     ({"n_vq_stacks": 3}, "sum\\(emb_dim\\) = 192 channels, above the 128-channel limit"),
     ({"emb_dim": [48, 48]}, "emb_dim\\[0\\] = 48: the quantizer kernels support emb_dim in \\(16, 32, 64, 128\\)"),
     ({"emb_size": [512, 8192]}, "emb_size\\[1\\] = 8192: the EMA codebook update supports at most 4096 codes"),
+    ({"spkr_embedding_size": 257}, "spkr_embedding_size = 257: the speaker-embedding gradient kernel supports at most 256"),
 ])
 def test_generator_refuses_unsupported_shapes_at_construction(over, match):
     """Configurations the kernels cannot run fail when the model is built, naming the limit - not as a failed stack handle
