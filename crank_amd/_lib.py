@@ -120,6 +120,16 @@ SIGNATURES = {
     "crk_world_synthesis": (I, [P, P, P, P, P, I, I, P, P, I, LL, LL, LL, P, P, P, LL, P]),
     "crk_world_frames": (I, [P, P, P, P, I, I, LL, P, P, P, LL, P]),
     "crk_world_pulses": (I, [P, P, P, P, I, P, P, P, P, P]),
+    "crk_wana_create": (P, [I, I, D, D, I]),
+    "crk_wana_destroy": (None, [P]),
+    "crk_wana_reserve": (I, [P, LL]),
+    "crk_wana_workspace_bytes": (LL, [I, LL, LL]),
+    "crk_wana_lowcut": (I, [P, P, P, I, P, I, LL, P, P]),
+    "crk_wana_lowcut_tile": (I, []),
+    "crk_wana_cheaptrick": (I, [P, P, P, P, P, I, LL, LL, LL, P, P, LL, P]),
+    "crk_wana_mcep": (I, [P, P, P, P, P, I, LL, LL, LL, I, P, P, P, LL, P]),
+    "crk_wana_npow": (I, [P, P, P, I, LL, P, P, LL, P]),
+    "crk_wana_frame_shapes": (I, [P, P, P, I, LL, P, P, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

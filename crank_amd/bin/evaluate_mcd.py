@@ -2,8 +2,12 @@
 utterance pairs in one launch: voiced-frame selection on the host (the features come from files), FastDTW
 alignment and the distortion on the device (crk_mcd_fastdtw, one wavefront per pair).
 
-The reference's file handling (HDF5 / WORLD analysis of converted waveforms, feats.scp lookup, per-pair
-summary) is not reproduced; ``mcd_fastdtw`` takes the arrays ``calculate()`` works on.
+The reference's file handling (HDF5, feats.scp lookup, per-pair summary) is not reproduced; ``mcd_fastdtw`` takes the
+arrays ``calculate()`` works on.  ``mcd_fastdtw_from_waveforms`` is the branch for models that write waveforms
+(``output_feat_type: mlfb``; evaluate_mcd.py:26-42, 56-57): low cut and WORLD spectral analysis of all converted
+waveforms in one batch on the device (crank_amd.world.WorldAnalyzer), then ``mcd_fastdtw``.  One stated difference: the
+reference re-estimates F0 from the converted waveform (Harvest); here the caller gives the converted F0 contour, the one
+the eval stage stored with the utterance and the model was conditioned on.
 """
 import numpy as np
 import torch
@@ -54,3 +58,20 @@ def mcd_fastdtw(cv_mceps, cv_f0s, gt_mceps, gt_f0s, radius=1, return_paths=False
     lens = plen.cpu().tolist()
     pc = paths.cpu().numpy()
     return vals, [pc[i, : 2 * lens[i]].reshape(-1, 2) for i in range(P)]
+
+
+def mcd_fastdtw_from_waveforms(cv_waves, cv_f0s, gt_mceps, gt_f0s, conf, radius=1, return_paths=False, device="cuda",
+                               analyzer=None):
+    """MCD of converted WAVEFORMS against ground-truth mel-cepstra.  cv_waves: per-utterance waveforms at
+    conf["feature"]["fs"]; cv_f0s: their F0 contours (one value per analysis frame of shiftms; > 0 voiced), which set the
+    number of frames and select the voiced ones; gt_mceps / gt_f0s as in ``mcd_fastdtw``.  The 0th coefficient stays in,
+    as in the reference."""
+    from crank_amd.world import WorldAnalyzer
+
+    feat = conf["feature"]
+    if analyzer is None:
+        analyzer = WorldAnalyzer(feat["fs"], feat["fftl"], feat["shiftms"], device=device)
+    cv_mceps = analyzer.mcep_batch(cv_waves, cv_f0s, feat["mcep_dim"], feat["mcep_alpha"], low_cut=70)
+    to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
+    return mcd_fastdtw([to_np(m) for m in cv_mceps], [to_np(f) for f in cv_f0s], gt_mceps, gt_f0s, radius, return_paths,
+                       device)

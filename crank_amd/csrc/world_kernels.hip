@@ -17,18 +17,15 @@
 //  * world_ola_kernel: one thread per output sample sums the responses that cover it, in pulse order (no atomics).
 #include "common.h"
 #include "../../include/crank_hip.h"
+#include "world_fft.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
 
-#define W_N 1024
-#define W_K (W_N / 2 + 1)
-#define W_LOGN 10
 #define W_IRLEN 1024
 #define W_MAX_ORDER1 128
 #define W_CHUNK 2048
-#define W_THREADS 256
 #define W_SAFE 1e-12
 #define W_DEFAULT_F0 500.0
 
@@ -44,32 +41,6 @@ struct World {
 };
 
 static int w_bands(int fs) { return (int)(fmin(15000.0, fs / 2.0 - 3000.0) / 3000.0); }
-static size_t w_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// ---------------------------------------------------------------------------------------------------------- helpers
-__device__ __forceinline__ double w_wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// deterministic workgroup sum (W_THREADS threads): wave sums, then the four partials in order
-__device__ double w_block_sum(double v, double* red) {
-  v = w_wave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ int w_find(const long long* off, int n, long long v) {  // largest u with off[u] <= v
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // cos(x) for x in [0, pi] as the Taylor polynomial in x^2 (16 terms, Horner), each operation rounded on its own.
 // WORLD's delay takes sin as sqrt(1 - cos^2), which turns a last-bit difference of cos at small x into a large one of
@@ -81,25 +52,6 @@ __device__ double w_cos(double x) {
   double r = W_COS[15];
   for (int n = 14; n >= 0; --n) r = r * x2 + W_COS[n];
   return r;
-}
-
-__device__ __forceinline__ int w_brev(int n) { return (int)(__brev((unsigned)n) >> (32 - W_LOGN)); }
-
-// in-place radix-2 DIT FFT of W_N points in LDS, input in bit-reversed order; sign -1 forward, +1 inverse (unnormalised)
-__device__ void w_fft(double2* x, const double* twc, const double* tws, double sign) {
-  for (int half = 1; half < W_N; half <<= 1) {
-    const int stride = W_N / (2 * half);
-    for (int b = threadIdx.x; b < W_N / 2; b += W_THREADS) {
-      const int pos = b & (half - 1);
-      const int i = ((b - pos) << 1) + pos, j = i + half;
-      const double c = twc[pos * stride], s = sign * tws[pos * stride];
-      const double2 xj = x[j], xi = x[i];
-      const double tr = c * xj.x - s * xj.y, ti = c * xj.y + s * xj.x;
-      x[j] = make_double2(xi.x - tr, xi.y - ti);
-      x[i] = make_double2(xi.x + tr, xi.y + ti);
-    }
-    __syncthreads();
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------- per frame

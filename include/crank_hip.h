@@ -491,6 +491,52 @@ int crk_world_pulses(void* world, const double* f0, const long long* frame_offse
                      int n_utts, int* pulse_pos, double* pulse_shift, unsigned char* pulse_vuv, long long* pulse_count,
                      void* stream);
 
+/* ---- The spectral half of WORLD analysis (csrc/world_analysis_kernels.hip) ----
+ * What the reference's evaluate_mcd.py runs on a converted waveform, without F0 estimation and aperiodicity: low-cut
+ * FIR, CheapTrick spectral envelope (pyworld cheaptrick), pysptk sp2mc and sprocket spc2npow, all in float64, for a ragged
+ * batch of utterances and a GIVEN F0 contour per utterance.  Parity with pyworld / pysptk is unpinned; the oracle is
+ * tests/world_analysis_ref.py.  CRANK_AMD_PRECISION does not apply.
+ *
+ * crk_wana_create: one handle per (fs, fftl, shiftms, alpha, mcep order + 1); precomputes the FFT twiddles and the freqt
+ * matrix and allocates them (one allocation; synchronises).  NULL unless fftl = 1024 and order1 <= 128.
+ * crk_wana_reserve: WORLD's randn stream (reseeded once per utterance) for utterances that draw up to max_draws values:
+ * a frame draws 2 * half + 1 + 513 values, half = round(1.5 fs / F0) <= 511, so frames * 1536 always suffices.
+ * Allocates (synchronises) only when the table grows.
+ *
+ * x: [total_samples] waveforms, utterance u = x[sample_offsets[u] .. sample_offsets[u+1]); f0: [total_frames] (Hz; at or
+ * below 3 fs / 1021 the frame is analysed at 500 Hz; at most fs / 4), utterance u = rows frame_offsets[u] ..
+ * frame_offsets[u+1]-1, frame i centred at sample round(i * shiftms / 1000 * fs + 0.001).  Both offset arrays: DEVICE int64
+ * [n_utts + 1].  workspace: device memory of at least crk_wana_workspace_bytes(n_utts, total_frames, total_samples) bytes.
+ * The compute entries never allocate and never synchronise; max_draws (the largest draw count of one utterance, or a bound
+ * of it) above what crk_wana_reserve covered is CRK_ERR_ARG. */
+void* crk_wana_create(int fs, int fftl, double shiftms, double alpha, int order1);
+void crk_wana_destroy(void* wana);
+int crk_wana_reserve(void* wana, long long max_draws);
+long long crk_wana_workspace_bytes(int n_utts, long long total_frames, long long total_samples);
+/* y[g] = sum_k taps[k] x[g - k] within the utterance (zero history); taps: DEVICE [n_taps], n_taps <= 256.  One workgroup
+ * filters crk_wana_lowcut_tile() consecutive samples. */
+int crk_wana_lowcut(void* wana, const float* x, const double* taps, int n_taps, const long long* sample_offsets, int n_utts,
+                    long long total_samples, double* y, void* stream);
+int crk_wana_lowcut_tile(void);
+/* sp: [total_frames][513], the spectral envelope */
+int crk_wana_cheaptrick(void* wana, const double* x, const double* f0, const long long* frame_offsets,
+                        const long long* sample_offsets, int n_utts, long long total_frames, long long total_samples,
+                        long long max_draws, double* sp, void* workspace, long long workspace_bytes, void* stream);
+/* mcep: [total_frames][order1] = sp2mc(sp, order1 - 1, alpha), from the envelope's cepstrum; sp (optional, may be NULL)
+ * as above.  order1 must be the handle's. */
+int crk_wana_mcep(void* wana, const double* x, const double* f0, const long long* frame_offsets,
+                  const long long* sample_offsets, int n_utts, long long total_frames, long long total_samples,
+                  long long max_draws, int order1, double* mcep, double* sp, void* workspace, long long workspace_bytes,
+                  void* stream);
+/* npow: [total_frames], 10 log10 of each frame's power over its utterance's mean power */
+int crk_wana_npow(void* wana, const double* sp, const long long* frame_offsets, int n_utts, long long total_frames,
+                  double* npow, void* workspace, long long workspace_bytes, void* stream);
+/* debug: the integers the CheapTrick kernel forms per frame: shapes [total_frames][4] = frame origin (sample), half
+ * window, DC-correction limit, smoothing boundary; draw_offsets [total_frames] = where the frame's randn draws start in
+ * its utterance's stream */
+int crk_wana_frame_shapes(void* wana, const double* f0, const long long* frame_offsets, int n_utts, long long total_frames,
+                          int* shapes, long long* draw_offsets, void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 
