@@ -19,7 +19,7 @@ void conv_prof_bytes(int cls, double bytes);
 
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ raw, int ld_raw, int n_samples, int T,
                                                      int n_fft, int log2n, int hop, int win, const float* __restrict__ window,
-                                                     const float* __restrict__ mel, int n_mels, float eps,
+                                                     const float* __restrict__ mel, int n_mels, float eps, float log_eps,
                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
                                                      float* __restrict__ out, int ldo, int frames_per_block, int center) {
   __shared__ float re[MLFB_MAX_FFT], im[MLFB_MAX_FFT];
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ r
       float acc = 0.f;
       const int k_hi = mel_hi[m];
       for (int k = mel_lo[m]; k < k_hi; k++) acc += re[k] * mel[(long)k * n_mels + m];
-      float v = log10f(fmaxf(acc, eps));
+      float v = acc > eps ? log10f(acc) : log_eps;  // (log_eps: see crk_logmel_fwd)
       if (mean) v = (v - mean[m]) / stdv[m];
       out[((long)b * T + t) * ldo + m] = v;
     }
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64) void lm_prep_kernel(const float* __restrict__ m
 #define LM_ZS 1088  // complex slots per wave: 4 rows x 16 x 17 (padded transposes) >= 1024 (the spectrum)
 __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restrict__ raw, int ld_raw, int n_samples, int T, int hop,
                                                           int win, const float* __restrict__ window, const float* __restrict__ mel,
-                                                          int n_mels, float eps, const float* __restrict__ mean,
+                                                          int n_mels, float eps, float log_eps, const float* __restrict__ mean,
                                                           const float* __restrict__ stdv, float* __restrict__ out, int ldo,
                                                           int pairs_per_wave, int center, int slot) {
   constexpr int N = 1024, NB = 513;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
       } else {
         for (int k = lo; k < hi; k++) { const float w = mel[(long)k * n_mels + m]; sa += mag[wave][0][k] * w; sb += mag[wave][1][k] * w; }
       }
-      float va = log10f(fmaxf(sa, eps)), vb = log10f(fmaxf(sb, eps));
+      float va = sa > eps ? log10f(sa) : log_eps, vb = sb > eps ? log10f(sb) : log_eps;
       if (mean) { va = (va - mean[m]) / stdv[m]; vb = (vb - mean[m]) / stdv[m]; }
       out[((long)b * T + ta) * ldo + m] = va;
       if (tb < T) out[((long)b * T + tb) * ldo + m] = vb;
@@ -292,9 +292,16 @@ extern "C" int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples
   if (!raw || !window || !mel_basis || !out || n_fft > MLFB_MAX_FFT || (n_fft & (n_fft - 1)) || win_length > n_fft ||
       n_mels > 256)
     return CRK_ERR_ARG;
+  // a grid dimension of 0 (B, T), a frame step that never advances (hop), log2n = 0 (n_fft 1: the bit reversal shifts by 32),
+  // an empty window or basis, an output row shorter than its values
+  if (B <= 0 || T <= 0 || hop <= 0 || n_fft < 2 || win_length <= 0 || n_mels <= 0 || n_samples <= 0 || ldo < n_mels || ld_raw < n_samples)
+    return CRK_ERR_ARG;
   if (center && n_samples <= n_fft / 2) return CRK_ERR_ARG;  // reflect padding needs pad < length, like torch.stft
   int log2n = 0;
   while ((1 << log2n) < n_fft) log2n++;
+  // The value of every clamped cell, rounded from double on the host: the device's log10f(1e-10f) is -10.000001f, one ulp
+  // below the correctly rounded -10.0f that torch.log10 returns for the reference's clamp.  Cells above eps are untouched.
+  const float log_eps = (float)log10((double)eps);
   static int wave_env = -1;  // CRK_LOGMEL_WAVE=0: the radix-2 workgroup-per-frame kernel for every size (A/B measurements)
   if (wave_env < 0) wave_env = crk_sw().logmel_wave;
   if (n_fft == 1024 && wave_env) {
@@ -308,7 +315,7 @@ extern "C" int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples
     ppw = ppw < 1 ? 1 : (ppw > 32 ? 32 : ppw);
     dim3 grid((npairs + 4 * ppw - 1) / (4 * ppw), B), block(256);
     hipLaunchKernelGGL(logmel_wave_kernel, grid, block, 0, (hipStream_t)stream, raw, ld_raw, n_samples, T, hop, win_length, window,
-                       mel_basis, n_mels, eps, mean, stdv, out, ldo, ppw, center, slot);
+                       mel_basis, n_mels, eps, log_eps, mean, stdv, out, ldo, ppw, center, slot);
     conv_prof_end(8, (hipStream_t)stream);
     CRK_CHECK_LAUNCH();
     return CRK_OK;
@@ -322,7 +329,7 @@ extern "C" int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples
   conv_prof_bytes(8, 4.0 * B * n_samples + 4.0 * B * T * n_mels);
   conv_prof_begin(8, (double)B * T * (5.0 * n_fft * log2n + 2.0 * (n_fft / 2 + 1) * n_mels), (hipStream_t)stream);
   hipLaunchKernelGGL(logmel_kernel, grid, block, 0, (hipStream_t)stream, raw, ld_raw, n_samples, T, n_fft, log2n, hop,
-                     win_length, window, mel_basis, n_mels, eps, mean, stdv, out, ldo, fpb, center);
+                     win_length, window, mel_basis, n_mels, eps, log_eps, mean, stdv, out, ldo, fpb, center);
   conv_prof_end(8, (hipStream_t)stream);
   CRK_CHECK_LAUNCH();
   return CRK_OK;

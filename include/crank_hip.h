@@ -321,7 +321,10 @@ int crk_embed_bwd_run(const float* dcat, int ld, int c0, int E, const long long*
  * matvec, clamp(eps), log10, optional (x-mean)/std.  center = 0: frame t starts at sample
  * t*hop (the training step, vqvae2.py:60); center = 1: frame t is centred on t*hop over the
  * reflect-padded signal, T = 1 + n_samples / hop (the offline extraction,
- * crank/feature/feature.py:126-145 -> parallel_wavegan logmelfilterbank). */
+ * crank/feature/feature.py:126-145 -> parallel_wavegan logmelfilterbank).
+ * CRK_ERR_ARG, nothing launched: n_fft not a power of two in 2 .. 2048, win_length outside
+ * 1 .. n_fft, n_mels outside 1 .. 256, B, T, hop or n_samples < 1, ldo < n_mels, ld_raw <
+ * n_samples, center with n_samples <= n_fft / 2.  A clamped cell is (float)log10((double)eps). */
 int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples, int T, int n_fft, int hop, int win_length,
                    const float* window, const float* mel_basis /* [n_bins][n_mels] */, int n_mels, float eps,
                    const float* mean, const float* std, float* out, int ldo, int center, void* stream);

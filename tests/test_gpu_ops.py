@@ -862,6 +862,7 @@ def test_logmel_layer_vs_oracle_and_reference_stft():
     got = LogMelFilterBankLayer(**kw)(wav.cuda()).cpu().numpy()
     assert got.shape == ref.shape
     np.testing.assert_allclose(got, ref, rtol=0, atol=2e-3)  # log10 domain; reference tests use decimal=3
+    _logmel_linear_metric("fixture", got)
 
     class Sc:
         mean_, var_ = fx["scaler_mean"], fx["scaler_var"]
@@ -869,6 +870,21 @@ def test_logmel_layer_vs_oracle_and_reference_stft():
     got = LogMelFilterBankLayer(**kw, scaler=Sc)(wav.cuda()).cpu().numpy()
     ref = OracleLogMel(**kw, scaler=Sc)(wav).numpy()
     np.testing.assert_allclose(got, ref, rtol=0, atol=5e-3)
+    _logmel_linear_metric("fixture_scaler", got)
+
+
+def _logmel_linear_metric(name, got):
+    """The fixture's quietest mel cells are 1.4e-4 of their frame's largest, where a log10 bound cannot be tight, so next
+    to the log10 tolerance above: max |10^got - 10^ref64| / (the frame's largest mel energy) against the float64
+    reference of tests/logmel_cases.py, within 10 x the fp32 oracle's own error + 2^-21."""
+    from tests import logmel_cases as C
+
+    case = {c["name"]: c for c in C.cases()}[name]
+    x = C.signal(case)
+    lin, _ = C.metrics(case, got if got.ndim == 3 else got[None], C.mel_energies(case, x))
+    bound = C.bounds(name)[0]
+    print(f"{name}: linear error {lin:.3e} (bound {bound:.3e})")
+    assert lin <= bound, (name, lin, bound)
 
 
 def test_offline_logmel_extraction_centered_reflect():
@@ -892,6 +908,7 @@ def test_offline_logmel_extraction_centered_reflect():
         got = logmelfilterbank(x, fs, fft_size=1024, hop_size=128, win_length=1024, window="hann", num_mels=80, fmin=80, fmax=7600)
         assert got.shape == ref.shape == (1 + n // 128, 80)
         np.testing.assert_allclose(got, ref, rtol=0, atol=2e-3)
+        _logmel_linear_metric(f"fixture_centred_{n}", got)
     with pytest.raises(ValueError):
         logmelfilterbank(fx["wav"][:512], fs, fft_size=1024, hop_size=128, num_mels=80, fmin=80, fmax=7600)
 
