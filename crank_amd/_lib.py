@@ -130,6 +130,13 @@ SIGNATURES = {
     "crk_wana_mcep": (I, [P, P, P, P, P, I, LL, LL, LL, I, P, P, P, LL, P]),
     "crk_wana_npow": (I, [P, P, P, I, LL, P, P, LL, P]),
     "crk_wana_frame_shapes": (I, [P, P, P, I, LL, P, P, P]),
+    "crk_gl_create": (I, [I, I, I, I, I, P, ctypes.POINTER(c_void_p)]),
+    "crk_gl_destroy": (None, [P]),
+    "crk_gl_workspace_bytes": (LL, [I, LL, LL]),
+    "crk_gl_linear_spectrum": (I, [P, P, LL, I, P, P]),
+    "crk_gl_run": (I, [P, P, P, P, P, I, LL, LL, I, I, P, P, LL, P]),
+    "crk_gl_stft": (I, [P, P, P, P, I, LL, LL, P, P]),
+    "crk_gl_istft": (I, [P, P, P, P, I, LL, LL, P, P, LL, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

@@ -714,3 +714,30 @@ class BaseTrainer(object):
             write_pcm16(path, y.cpu().numpy(), fc["fs"])
             paths.append(path)
         return paths
+
+    def _save_decoded_mlfb(self, dicts, tdir, n_iters=None, seed=0):
+        """basetrainer.py:400-417 without the plots: every converted utterance of an mlfb model as a WAV through
+        Griffin-Lim (crank_amd.griffin_lim, clipped to [-1, 1 - 2^-15], 16-bit PCM), named
+        <flbl>_org-<org>_cv-<cv>.wav as basetrainer.py:358 names it.  `dicts`: the lists of _store_features, or a dict of
+        them per target speaker, synthesised as one ragged batch; utterance i starts from the phases of seed + i.
+        `n_iters` defaults to conf["feature"]["n_iteration"] (the reference never reads the key and runs 100).  Returns
+        the paths."""
+        from ...griffin_lim import GriffinLim
+        from ...world import write_pcm16
+
+        fc = self.conf["feature"]
+        if isinstance(dicts, dict):
+            dicts = [d for v in dicts.values() for d in v]
+        if n_iters is None:
+            n_iters = fc.get("n_iteration", 100)
+        gl = GriffinLim(fc["fs"], fc["mlfb_dim"], fc["fftl"], fc["win_length"], fc["hop_size"], fc["fmin"], fc["fmax"],
+                        device=self.device)
+        tdir = Path(tdir)
+        tdir.mkdir(parents=True, exist_ok=True)
+        paths = []
+        for d, y in zip(dicts, gl.vocode_eval_outputs(dicts, n_iters, seed)):
+            path = tdir / f"{d['flbl']}_org-{d['org_spkr_name']}_cv-{d['cv_spkr_name']}.wav"
+            path.parent.mkdir(parents=True, exist_ok=True)  # flbl may hold a speaker directory
+            write_pcm16(path, y.cpu().numpy(), fc["fs"])
+            paths.append(path)
+        return paths

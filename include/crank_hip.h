@@ -540,6 +540,42 @@ int crk_wana_npow(void* wana, const double* sp, const long long* frame_offsets, 
 int crk_wana_frame_shapes(void* wana, const double* f0, const long long* frame_offsets, int n_utts, long long total_frames,
                           int* shapes, long long* draw_offsets, void* stream);
 
+/* ---- Griffin-Lim waveform synthesis for log-mel models (csrc/griffin_lim_kernels.hip) ----
+ * Replaces the reference's mlfb2wav (crank/utils/utils.py:94-107, 210-269: logmelspc_to_linearspc, griffin_lim -> librosa.griffinlim
+ * with momentum 0.99, centred reflect-padded STFT, periodic Hann window; called by BaseTrainer._save_decoded_mlfb,
+ * crank/net/trainer/basetrainer.py:400-417, and crank/bin/griffin_lim.py), all in float64, for a ragged batch of utterances.
+ * Parity with librosa is unpinned; the oracle is tests/griffin_lim_ref.py.  CRANK_AMD_PRECISION does not apply.
+ *
+ * crk_gl_create: one handle per (fs, n_fft, win_length, hop, n_mels, basis); pinv_basis is the HOST float64 pseudo-inverse of
+ * the mel basis, [n_fft / 2 + 1][n_mels] row-major.  Uploads it with the FFT twiddles and the window (one allocation;
+ * synchronises) and stores the handle in *handle.  CRK_ERR_UNSUPPORTED unless n_fft = 1024, 1 <= win_length <= 1024,
+ * 1 <= hop <= 1024 and n_mels <= 256.
+ *
+ * Frames of utterance u = rows frame_offsets[u] .. frame_offsets[u+1]-1 (T_u of them); it owns the samples
+ * sample_offsets[u] .. sample_offsets[u+1], hop * (T_u - 1) of them (the caller computes it), which must exceed n_fft / 2
+ * so that one reflection pads it.  Both offset arrays: DEVICE int64 [n_utts + 1].  Spectra are [total_frames][513],
+ * complex ones as interleaved (re, im) float64.  workspace: device memory of at least
+ * crk_gl_workspace_bytes(n_utts, total_frames, total_samples) bytes; too small is CRK_ERR_ARG and launches nothing.  The
+ * compute entries never allocate and never synchronise. */
+int crk_gl_create(int fs, int n_fft, int win_length, int hop, int n_mels, const double* pinv_basis, void** handle);
+void crk_gl_destroy(void* gl);
+long long crk_gl_workspace_bytes(int n_utts, long long total_frames, long long total_samples);
+/* utils.py:210-234 (logmelspc_to_linearspc): S[f][k] = sum_m 10^mlfb[f][m] pinv_basis[k][m], signed as the reference
+ * returns it; magnitude != 0 stores its absolute value, the np.abs of utils.py:257.  mlfb: [total_frames][n_mels] */
+int crk_gl_linear_spectrum(void* gl, const double* mlfb, long long total_frames, int magnitude, double* S, void* stream);
+/* utils.py:237-269 (griffin_lim): n_iter iterations from the unit phasors angles0 (complex [total_frames][513]), then the
+ * final inverse STFT into y [total_samples]; clip != 0 clips y to [-1, 1 - 2^-15] as utils.py:258-268 does.  n_iter + 2 launches. */
+int crk_gl_run(void* gl, const double* S, const double* angles0, const long long* frame_offsets,
+               const long long* sample_offsets, int n_utts, long long total_frames, long long total_samples, int n_iter,
+               int clip, double* y, void* workspace, long long workspace_bytes, void* stream);
+/* the two projections alone (librosa.stft / librosa.istft as griffinlim calls them): spec complex [total_frames][513].
+ * crk_gl_stft takes waveforms of any length above n_fft / 2: T_u = 1 + length / hop */
+int crk_gl_stft(void* gl, const double* x, const long long* frame_offsets, const long long* sample_offsets, int n_utts,
+                long long total_frames, long long total_samples, double* spec, void* stream);
+int crk_gl_istft(void* gl, const double* spec, const long long* frame_offsets, const long long* sample_offsets, int n_utts,
+                 long long total_frames, long long total_samples, double* y, void* workspace, long long workspace_bytes,
+                 void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 

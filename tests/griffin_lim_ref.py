@@ -1,0 +1,187 @@
+"""CPU restatement (numpy, float64) of what crank_amd/griffin_lim.py computes on the device: the reference's
+``logmelspc_to_linearspc`` and ``griffin_lim`` (crank/utils/utils.py:210-269), the latter through librosa's ``griffinlim``
+with its defaults (momentum 0.99, centred reflect-padded STFT, periodic Hann window zero-padded to the FFT length,
+``istft`` dividing by the window-sum-square envelope above the smallest normal float).  librosa is not installed: the loop
+is restated from its published algorithm, and parity with librosa itself is unpinned.
+
+Every FFT goes through one hook, a transform object with ``rfft`` ((T, 1024) real -> (T, 513) complex) and ``irfft`` (the
+inverse, dropping the imaginary parts of bin 0 and bin 512).  Three are here: ``NumpyFFT``, ``TorchFFT`` and ``Radix2FFT``, a
+plain radix-2 decimation-in-time transform with table twiddles, the class of the kernels' world_fft.h.  The largest pairwise
+distance between the three results of one case is the restatement's own rounding spread; the GPU tests measure the kernels
+against a multiple of it.
+
+Layouts are frames first, (T, 513), also the phases.
+"""
+import numpy as np
+
+N = 1024
+K = N // 2 + 1
+MOMENTUM = 0.99
+CLIP_LO, CLIP_HI = -1.0, 0.999969482421875
+TINY = np.finfo(np.float64).tiny
+
+
+# ------------------------------------------------------------------------------------------------------- transforms
+class NumpyFFT:
+    name = "numpy"
+
+    @staticmethod
+    def rfft(x):
+        return np.fft.rfft(x, axis=-1)
+
+    @staticmethod
+    def irfft(X):
+        return np.fft.irfft(X, n=N, axis=-1)
+
+
+class TorchFFT:
+    name = "torch"
+
+    @staticmethod
+    def rfft(x):
+        import torch
+
+        return torch.fft.rfft(torch.from_numpy(np.ascontiguousarray(x)), dim=-1).numpy()
+
+    @staticmethod
+    def irfft(X):
+        import torch
+
+        return torch.fft.irfft(torch.from_numpy(np.ascontiguousarray(X)), n=N, dim=-1).numpy()
+
+
+class Radix2FFT:
+    """In-place radix-2 DIT over the last axis, bit-reversed input, twiddles read from a table of cos / sin(2 pi m / N)."""
+    name = "radix2"
+    _rev = np.array([int(format(i, "010b")[::-1], 2) for i in range(N)])
+    _tw = np.exp(-2j * np.pi * np.arange(N // 2) / N)
+
+    @classmethod
+    def _fft(cls, z, inverse):
+        z = np.ascontiguousarray(z[..., cls._rev], dtype=np.complex128)
+        tw = np.conj(cls._tw) if inverse else cls._tw
+        half = 1
+        while half < N:
+            v = z.reshape(z.shape[:-1] + (N // (2 * half), 2, half))
+            t = v[..., 1, :] * tw[:: N // (2 * half)]
+            lo = v[..., 0, :].copy()
+            v[..., 0, :] = lo + t
+            v[..., 1, :] = lo - t
+            half *= 2
+        return z
+
+    @classmethod
+    def rfft(cls, x):
+        return cls._fft(np.asarray(x, np.float64).astype(np.complex128), False)[..., :K]
+
+    @classmethod
+    def irfft(cls, X):
+        X = np.asarray(X, np.complex128)
+        full = np.empty(X.shape[:-1] + (N,), np.complex128)
+        full[..., :K] = X
+        full[..., 0] = X[..., 0].real
+        full[..., N // 2] = X[..., N // 2].real
+        full[..., K:] = np.conj(X[..., N // 2 - 1:0:-1])
+        return cls._fft(full, True).real * (1.0 / N)
+
+
+TRANSFORMS = (NumpyFFT, TorchFFT, Radix2FFT)
+
+
+# ------------------------------------------------------------------------------------------------------- projections
+def hann_window(win_length):
+    """The periodic Hann window of win_length, zero-padded symmetrically to N."""
+    w = np.zeros(N)
+    lpad = (N - win_length) // 2
+    w[lpad:lpad + win_length] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length) / win_length)
+    return w
+
+
+def stft(x, hop, win_length, fft=NumpyFFT):
+    """(1 + len(x) // hop, 513): reflect-pad by N / 2, frames of N at every hop, window, rfft."""
+    x = np.asarray(x, np.float64)
+    assert x.ndim == 1 and x.size > N // 2
+    xp = np.pad(x, N // 2, mode="reflect")
+    T = 1 + x.size // hop
+    idx = hop * np.arange(T)[:, None] + np.arange(N)[None, :]
+    return fft.rfft(xp[idx] * hann_window(win_length))
+
+
+def istft(X, hop, win_length, fft=NumpyFFT):
+    """hop * (T - 1) samples: irfft per frame, window, overlap-add in ascending frame order, division by the window-sum-square
+    envelope where it exceeds the smallest normal float, N / 2 samples dropped at each end."""
+    X = np.asarray(X)
+    T = X.shape[0]
+    w = hann_window(win_length)
+    frames = fft.irfft(X) * w
+    y = np.zeros(N + hop * (T - 1))
+    env = np.zeros_like(y)
+    wsq = w * w
+    for t in range(T):
+        y[t * hop:t * hop + N] += frames[t]
+        env[t * hop:t * hop + N] += wsq
+    big = env > TINY
+    y[big] /= env[big]
+    return y[N // 2:N // 2 + hop * (T - 1)]
+
+
+# ------------------------------------------------------------------------------------------------------- Griffin-Lim
+def initial_angles(T, seed):
+    """librosa's random initial phases with random_state=seed, frames first: exp(2 pi i RandomState(seed).rand(513, T)).T"""
+    return np.ascontiguousarray(np.exp(2j * np.pi * np.random.RandomState(seed).rand(K, T)).T)
+
+
+def griffin_lim_snapshots(S, angles0, ks, hop, win_length, fft=NumpyFFT):
+    """{k: the unclipped waveform after k iterations} for every k of `ks`, from one run of max(ks) iterations.  S: (T, 513)
+    magnitudes; angles0: (T, 513) unit phasors."""
+    S = np.abs(np.asarray(S, np.float64))
+    angles = np.array(angles0, np.complex128)
+    ks = sorted(set(int(k) for k in ks))
+    out = {}
+    rebuilt = 0.0
+    c = MOMENTUM / (1 + MOMENTUM)
+    for it in range(ks[-1] + 1):
+        inverse = istft(S * angles, hop, win_length, fft)
+        if it in ks:
+            out[it] = inverse
+        if it == ks[-1]:
+            break
+        tprev = rebuilt
+        rebuilt = stft(inverse, hop, win_length, fft)
+        angles = rebuilt - c * tprev
+        angles /= np.abs(angles) + 1e-16
+    return out
+
+
+def griffin_lim(S, angles0, n_iter, hop, win_length, fft=NumpyFFT, clip=True):
+    y = griffin_lim_snapshots(S, angles0, [n_iter], hop, win_length, fft)[n_iter]
+    return np.clip(y, CLIP_LO, CLIP_HI) if clip else y
+
+
+def linear_spectrum(mlfb, pinv_basis, dtype=np.float64):
+    """logmelspc_to_linearspc: (10 ** mlfb) @ pinv(mel_basis).T, signed.  dtype numpy.longdouble gives the tests' bound
+    reference."""
+    m = np.power(dtype(10.0), np.asarray(mlfb, np.float64).astype(dtype))
+    return m @ np.asarray(pinv_basis, np.float64).astype(dtype).T
+
+
+def mlfb2wav(mlfb, pinv_basis, hop, win_length, n_iter=100, seed=0, fft=NumpyFFT, clip=True):
+    S = np.abs(linear_spectrum(mlfb, pinv_basis))
+    return griffin_lim(S, initial_angles(S.shape[0], seed), n_iter, hop, win_length, fft, clip)
+
+
+def spectral_convergence(y, S, hop, win_length, fft=NumpyFFT):
+    S = np.abs(np.asarray(S, np.float64))
+    return float(np.linalg.norm(np.abs(stft(y, hop, win_length, fft)) - S) / np.linalg.norm(S))
+
+
+def rel_l2(a, b):
+    """||a - b|| / ||b||; 0 when both vanish."""
+    a, b = np.asarray(a), np.asarray(b)
+    d, n = float(np.linalg.norm(a - b)), float(np.linalg.norm(b))
+    return 0.0 if d == 0.0 else (d / n if n else float("inf"))
+
+
+def spread(results):
+    """The largest pairwise relative-L2 distance between the waveforms of one case from the transforms."""
+    return max(rel_l2(a, b) for i, a in enumerate(results) for b in results[i + 1:])
