@@ -58,6 +58,8 @@ SIGNATURES = {
     "crk_net_forward": (I, [P, P, ULL, P, I, P, I, P, I, P, I, I, I, ULL, P]),
     "crk_net_backward": (I, [P, P, ULL, P, P, I, P, I, P, I, P, I, F, P, I, P, I, I, I, ULL, P]),
     "crk_net_backward_scaled": (I, [P, P, ULL, P, P, I, P, I, P, I, P, I, F, P, I, P, I, I, I, ULL, P, P, P]),
+    "crk_net_embed_grad_supported": (I, [P, I, I, I]),
+    "crk_net_backward_embed": (I, [P, P, ULL, P, P, I, P, I, P, I, P, I, F, P, I, I, I, ULL, P, LL, I, I, I, P, P]),
     "crk_vq_forward": (I, [P, I, P, I, I, I, P, P, I, P, I, P]),
     "crk_vq_forward_fused": (I, [P, I, P, I, P, I, P, I, I, I, P, P, I, P, I, P, P, P, P, P]),
     "crk_vq_image_bytes": (LL, [I, I]),

@@ -15,6 +15,8 @@ before the import.  The kernels' own A/B switches (`CRK_*`, read once per proces
     separate_commit         CRANK_AMD_SEPARATE_COMMIT            0         commitment loss outside the quantizer's launch
     recon_dense             CRANK_AMD_RECON_DENSE                0         L1 / MSE / STFT losses of the decoded features unfused
     stft_two_pass           CRANK_AMD_STFT_TWO_PASS              0         STFT loss forward and gradient as two passes
+    cond_sums               CRANK_AMD_COND_SUMS                  1         speaker-table gradient from per-utterance sums inside the
+                                                                           last decoder's backward (0: per-frame dc, then a reduction)
     force_dist              CRANK_AMD_FORCE_DIST                 0         data-parallel code path in a process group of one rank
     dist_backend            CRANK_AMD_DIST_BACKEND               (auto)    gloo: several ranks sharing one GPU (tests)
     dp_graph_collectives    CRANK_AMD_DP_GRAPH_COLLECTIVES       1         RCCL collectives captured with the step (0: chain of graphs)
@@ -43,6 +45,7 @@ def _read():
         separate_commit=_flag("CRANK_AMD_SEPARATE_COMMIT", False),
         recon_dense=_flag("CRANK_AMD_RECON_DENSE", False),
         stft_two_pass=_flag("CRANK_AMD_STFT_TWO_PASS", False),
+        cond_sums=_flag("CRANK_AMD_COND_SUMS", True),
         force_dist=_flag("CRANK_AMD_FORCE_DIST", False),
         dist_backend=_get("CRANK_AMD_DIST_BACKEND") or None,
         dp_graph_collectives=_flag("CRANK_AMD_DP_GRAPH_COLLECTIVES", True),

@@ -261,9 +261,26 @@ struct StackWP {
   float* partials;
   int B, T, L, ktaps, aux_ch, aux_pad, cpg, G;  // cpg: 64-frame chunks per group (runs over the utterances)
   int rec_g;  // the backward planes (gb, dxb[1..], dsb) are 4-frame records (StackBP::rec)
+  // (null: not wanted) column sums of dG per utterance next to the per-group ones of the conv-bias gradient: slot
+  // [group][segment][block][128], segment = the utterance's position in the group's chunk walk (a group may begin or end
+  // inside an utterance: launch_cond_embed_bwd adds an utterance's segments in group order).  nseg: segments per group.
+  float* usums; int nseg;
 };
 int stack_wgrad_supported(int ktaps, int max_dil, int aux_ch);
 int launch_stack_wgrad(const StackWP& p, bool precise, hipStream_t s);
+// ---- gradient of an embedding table behind the conditioning input of a gated stack, from per-utterance dG sums ----
+// The conditioning columns [c0, c0 + E) are table[idx[u * run]] on every frame of utterance u, so
+//   d table[r][e] = sum_l sum_ch Waux_l[ch][c0 + e] * (sum over the frames of the utterances labelled r of dG_l[t][ch]):
+// no per-frame conditioning gradient.  One workgroup per table row, fixed summation order, no atomics.
+struct CondEmbedP {
+  const float* usums; int nseg, cpg;      // StackWP::usums of the same launch geometry
+  const uint16_t *whi, *wlo;              // prepared weights (wlo null: plain bf16, the hi planes alone)
+  const StackBLayer* layers;              // device table [L]: w_aux planes [aux rows][128]
+  const long long* idx; long long run;    // label of utterance u at idx[u * run]
+  int B, T, L, c0, E, n_rows;
+  float* dtable;                          // [n_rows][E], accumulated into
+};
+int launch_cond_embed_bwd(const CondEmbedP& p, hipStream_t s);
 int stack_bwd_plan(StackBP& p, bool precise);
 int stack2_bwd_plan(StackBP& p);
 int launch_stack2_bwd(const StackBP& p, hipStream_t s);

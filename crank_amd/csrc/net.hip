@@ -73,6 +73,8 @@ struct Route {
   bool gen_split;   // generator, plain bf16: forward and chain channel-split, gate planes in the lane-record layout
   bool x3f;         // generator: a bf16x3f forward ahead of this (plain) route's backward runs channel-split too
   bool disc_split;  // discriminator, plain bf16: blocks and chain channel-split, gate planes in the lane-record layout
+  bool usums;       // gated stack with conditioning, fused: an embedding behind the conditioning gets its gradient from the
+                    // weight-gradient launch's per-utterance dG sums (crk_net_backward_embed), the chain computes no dc
 };
 // Everything batch shape (B, T) needs besides the growing buffers, made by crk_net_reserve: plane offsets are multiples of
 // N = B*T, partial-sum offsets of the slot counts Gs / Gg.
@@ -607,7 +609,7 @@ static StackBP stack_bwd_shape(const Net* n, int B, int T) {
 // The kernel path of net n at batch shape (B, T) in one arithmetic: the one place where the planners decide.  crk_net_reserve
 // keeps both arithmetics' routes in the shape's record; the compute entry points read them there.
 static Route route_of(const Net* n, int B, int T, bool precise) {
-  Route r = {false, false, false, false};
+  Route r = {false, false, false, false, false};
   const crk_net_desc& d = n->d;
   const CrkSwitches& sw = crk_sw();
   // forward, data-gradient chain and weight gradient run fused together or not at all (the fused kernels exchange bf16
@@ -620,6 +622,7 @@ static Route route_of(const Net* n, int B, int T, bool precise) {
   StackBP bp = stack_bwd_shape(n, B, T);
   r.fused = stack_fwd_plan(sp, precise) == CRK_OK && stack_bwd_plan(bp, precise) == CRK_OK &&
             stack_wgrad_supported(d.kernel_size, max_dil, sp.aux_ch) && plain_chains_ok(n, B, T, precise);
+  r.usums = r.fused && d.aux_ch > 0;
   if (!r.fused || precise || sw.sk_v != 2 || sw.skb_v != 2) return r;
   if (d.kind == 0 && d.dropout == 0.f && d.in_ch % 8 == 0 && d.out_ch % 8 == 0) {
     // Generator stacks in plain bf16: forward and data-gradient chain both run channel-split (stack2_kernels.hip,
@@ -903,6 +906,17 @@ static int stack_groups(const Net* n, int B, int T) {
   return (total + cpg - 1) / cpg;
 }
 
+// per-utterance dG sums (StackWP::usums) of a gated stack with conditioning: segments per group, floats, and their place
+// behind the gradient planes in `scratch`
+static int usum_nseg(const Net* n, int B, int T) {
+  const int ncpu = (T + 63) / 64;
+  return (stack_cpg(n, B, T) + 2 * ncpu - 2) / ncpu;  // a group of cpg chunks that starts at the last chunk of an utterance
+}
+static long long usum_floats(const Net* n, int B, int T) {
+  if (n->d.kind == 2 || n->d.aux_ch <= 0) return 0;
+  return (long long)stack_groups(n, B, T) * usum_nseg(n, B, T) * n->L * 128;
+}
+static long long usum_off(const Net* n, long long N) { return N * 64 * (3LL * n->L + 3) + (gated_s16(n, N).total + 1) / 2; }
 static ShapeNeed shape_need(const Net* n, int B, int T) {
   ShapeNeed q;
   const long long N = (long long)B * T;
@@ -913,7 +927,7 @@ static ShapeNeed shape_need(const Net* n, int B, int T) {
   // dGb_hi[L] dGb_lo[L] ([N,128]), dXb_hi[L+1] dXb_lo[L+1], dSb_hi dSb_lo ([N,64])
   // (+ head: dy and dH1 bf16 planes);  kind 2: per-layer fp32 gradients (fallback) + bf16 output-gradient planes
   q.need_s = n->d.kind == 2 ? (long long)n->L * N * cw + N * plain_gplanes_w(n)
-                            : N * 64 * (3LL * n->L + 3) + (gated_s16(n, N).total + 1) / 2;
+                            : usum_off(n, N) + usum_floats(n, B, T);
   q.Gs = stack_groups(n, B, T);
   // generic convs: runs of 64-frame chunks, at most 32 groups: short runs = many workgroups hide the latency of the
   // table kernel's load -> MFMA chain, but every group is one more pass of the weight-norm backward over the
@@ -1081,10 +1095,13 @@ static int flush_pending_plain_wgrad(Net* n, hipStream_t s) {
 // flags bit0: precise; bit1: skip parameter gradients (they would be discarded);
 // dx / dc may be null when the corresponding input needs no gradient.
 // dx_scale multiplies the returned input gradient (gradient reversal: -lambda).
+// the embedding table behind the conditioning columns [c0, c0 + E) (crk_net_backward_embed)
+struct CondEmbed { const long long* idx; long long run; int c0, E, n_rows; float* dtable; };
 static int net_backward_impl(void* h, const float* params, unsigned long long version, float* grads, const float* x,
                              int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
                              float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
-                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream);
+                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream,
+                             const CondEmbed* ce = nullptr);
 extern "C" int crk_net_backward(void* h, const float* params, unsigned long long version, float* grads, const float* x,
                                 int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
                                 float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
@@ -1104,10 +1121,38 @@ extern "C" int crk_net_backward_scaled(void* h, const float* params, unsigned lo
   return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, dc, lddc, saved, B, T, flags,
                            seed, dy_num, dy_den, stream);
 }
+// 1: crk_net_backward_embed serves this net at this shape in the arithmetic of `flags` (a gated stack with conditioning on
+// the fused kernels); 0: it returns CRK_ERR_UNSUPPORTED - take dc from crk_net_backward and reduce it (crk_embed_bwd_run).
+extern "C" int crk_net_embed_grad_supported(void* h, int B, int T, int flags) {
+  Net* n = (Net*)h;
+  if (!n || B <= 0 || T <= 0) return 0;
+  const Shape* r = find_shape(n, B, T);
+  return (r ? r->route[(flags & CRK_FLAG_PRECISE) ? 1 : 0] : route_of(n, B, T, flags & CRK_FLAG_PRECISE)).usums ? 1 : 0;
+}
+// crk_net_backward for a conditioning input c = [.. | table[idx[u * run]] | ..] whose columns [c0, c0 + E) are one row of an
+// embedding table per utterance (run == T: every frame of utterance u carries the label idx[u * run]) and whose other
+// columns need no gradient: no per-frame dc.  The weight-gradient launch also leaves the column sums of every block's dG per
+// utterance, and one small launch adds  sum_l Waux_l[:, c0:c0+E]^T . sums  of the utterances of each label, in ascending
+// utterance order, to dtable [n_rows][E].  Same dx and parameter gradients as crk_net_backward; the table gradient differs
+// from the frame sum of dc by fp32 reassociation.  Needs parameter gradients (no CRK_FLAG_NO_PARAM_GRAD).
+extern "C" int crk_net_backward_embed(void* h, const float* params, unsigned long long version, float* grads, const float* x,
+                                      int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
+                                      float dx_scale, const float* saved, int B, int T, int flags, unsigned long long seed,
+                                      const long long* idx, long long run, int c0, int E, int n_rows, float* dtable,
+                                      void* stream) {
+  Net* n = (Net*)h;
+  if (!n || !idx || !dtable || !grads || run != T || c0 < 0 || E < 1 || n_rows < 1 || c0 + E > n->d.aux_ch ||
+      (flags & CRK_FLAG_NO_PARAM_GRAD))
+    return CRK_ERR_ARG;
+  const CondEmbed ce = {idx, run, c0, E, n_rows, dtable};
+  return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, nullptr, 0, saved, B, T, flags,
+                           seed, nullptr, nullptr, stream, &ce);
+}
 static int net_backward_impl(void* h, const float* params, unsigned long long version, float* grads, const float* x,
                              int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
                              float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
-                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream) {
+                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream,
+                             const CondEmbed* ce) {
   Net* n = (Net*)h;
   if (!n || !params || !x || !dy || B <= 0 || T <= 0) return CRK_ERR_ARG;
   const Shape* r = find_shape(n, B, T);
@@ -1115,6 +1160,7 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
   hipStream_t s = (hipStream_t)stream;
   const bool precise = flags & CRK_FLAG_PRECISE;
   const Route& rt = r->route[precise];
+  if (ce && !rt.usums) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_embed)
   if (dy_num && !(n->d.kind == 2 && rt.fused)) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_scaled)
   // CRK_FLAG_FWD_PRECISE: how the forward laid its planes out - unless that forward was the channel-split split-operand one
   // (generator stacks of the bf16x3f mode), which writes the plain route's planes
@@ -1336,7 +1382,17 @@ static int net_backward_impl(void* h, const float* params, unsigned long long ve
       wp.B = B; wp.T = T; wp.L = L; wp.ktaps = d.kernel_size; wp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
       wp.cpg = stack_cpg(n, B, T); wp.G = r->q.Gs;
       wp.rec_g = bp.rec;
+      if (ce) { wp.usums = n->scratch + usum_off(n, N); wp.nseg = usum_nseg(n, B, T); }
       RUN(launch_stack_wgrad(wp, precise, s));
+      if (ce) {
+        CondEmbedP ep;
+        memset(&ep, 0, sizeof(ep));
+        ep.usums = wp.usums; ep.nseg = wp.nseg; ep.cpg = wp.cpg;
+        ep.whi = n->whi; ep.wlo = precise ? n->wlo : nullptr; ep.layers = n->d_blayers;
+        ep.idx = ce->idx; ep.run = ce->run;
+        ep.B = B; ep.T = T; ep.L = L; ep.c0 = ce->c0; ep.E = ce->E; ep.n_rows = ce->n_rows; ep.dtable = ce->dtable;
+        RUN(launch_cond_embed_bwd(ep, s));
+      }
     }
     dxo = dXall;
   }

@@ -1261,6 +1261,8 @@ __global__ __launch_bounds__(512, 2) void stack_wgrad_kernel(const StackWP p) {
     for (int a = 0; a < KT; a++) accv[a][i] = 0.f;
   }
   float bsum = 0.f;  // it == 0: dG column sums of band ct; it == 1: [dX | dS] column sums
+  float usum = 0.f;  // it == 0: the same terms, restarted at every utterance of the chunk walk (StackWP::usums)
+  int seg = 0;
 
   // group g owns the 64-frame chunks [g * cpg, (g + 1) * cpg) of the batch, counted utterance after utterance (an
   // utterance has ceil(T / 64) of them; with FR = 32 a chunk is walked as two halves, the second one empty where it
@@ -1277,9 +1279,10 @@ __global__ __launch_bounds__(512, 2) void stack_wgrad_kernel(const StackWP p) {
     __syncthreads();  // previous chunk's fragments consumed
     SW_COMMIT()
     __syncthreads();
+    bool uend = c + 1 == nchunks;  // this chunk is the group's last of its utterance
     if (c + 1 < nchunks) {
       f0n += FR;
-      if (f0n >= uspan) { f0n = 0; nbn += p.T; }
+      if (f0n >= uspan) { f0n = 0; nbn += p.T; uend = true; }
       SW_FETCH(nbn, f0n)
     }
     const unsigned char* ag_hi = t_hi + O_GT + rowoff * RA + (ct * 32 + coloff) * 2;
@@ -1296,8 +1299,11 @@ __global__ __launch_bounds__(512, 2) void stack_wgrad_kernel(const StackWP p) {
         a_lo = sw_tr_frag(ag_hi + PLANE + kc * 16 * RA, RA);
         d_lo = sw_tr_frag(ad_hi + PLANE + kc * 16 * RA, RA);
       }
-      if (it == 0) bsum += sw_sum8(a_hi) + (PRECISE ? sw_sum8(a_lo) : 0.f);
-      else bsum += sw_sum8(d_hi) + (PRECISE ? sw_sum8(d_lo) : 0.f);
+      if (it == 0) {
+        const float s8 = sw_sum8(a_hi) + (PRECISE ? sw_sum8(a_lo) : 0.f);
+        bsum += s8; usum += s8;
+      } else
+        bsum += sw_sum8(d_hi) + (PRECISE ? sw_sum8(d_lo) : 0.f);
 #pragma unroll
       for (int a = 0; a < KT; a++) {
         const int boff = (kc * 16 + a * LY.dil) * RB;
@@ -1327,6 +1333,11 @@ __global__ __launch_bounds__(512, 2) void stack_wgrad_kernel(const StackWP p) {
           acca = mfma_bf16(a_hi, b_lo, acca);
         }
       }
+    }
+    if (p.usums && uend) {  // (uniform over the workgroup)
+      const float tot = usum + __shfl_xor(usum, 32);
+      if (it == 0 && half == 0 && seg < p.nseg) p.usums[(((long)g * p.nseg + seg) * p.L + l) * 128 + ct * 32 + l31] = tot;
+      usum = 0.f; seg++;
     }
   }
 
@@ -1392,6 +1403,122 @@ int launch_stack_wgrad(const StackWP& p, bool precise, hipStream_t s) {
     else hipLaunchKernelGGL((stack_wgrad_kernel<false, 5>), grid, dim3(512), lds, s, p);
   }
   conv_prof_end(5, s);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+// ---- embedding-table gradient from the per-utterance dG sums of stack_wgrad_kernel (CondEmbedP, conv_kernels.h) ----
+// One workgroup per table row r.  Phase 0: the utterances labelled r, ascending.  Phase 1: S[l][ch] = their dG sums added
+// in that order, an utterance's segments first (ascending group); eight utterances' loads are in flight at a time, the
+// additions keep the order.  Phase 2: dtable[r][e] += sum_l (sum_ch Waux_l[c0 + e][ch] * S[l][ch]): four lanes per (l, e)
+// row take 32 channels each - all of a thread's weight pieces are requested at once, one memory round trip for the whole
+// product (a loop over the blocks with a load in each turn was eight dependent round trips per column: 25 us) - combine in
+// a fixed butterfly, and column e adds its L products in block order.  Nothing depends on how the launch is scheduled.
+#define CE_THREADS 1024
+__device__ __forceinline__ float ce_dot8(const sk_u32x4 w, const float* s) {
+  float a = 0.f;
+  a += __uint_as_float(w.x << 16) * s[0]; a += __uint_as_float(w.x & 0xffff0000u) * s[1];
+  a += __uint_as_float(w.y << 16) * s[2]; a += __uint_as_float(w.y & 0xffff0000u) * s[3];
+  a += __uint_as_float(w.z << 16) * s[4]; a += __uint_as_float(w.z & 0xffff0000u) * s[5];
+  a += __uint_as_float(w.w << 16) * s[6]; a += __uint_as_float(w.w & 0xffff0000u) * s[7];
+  return a;
+}
+__global__ __launch_bounds__(CE_THREADS) void cond_embed_bwd_kernel(const CondEmbedP p) {
+  extern __shared__ __attribute__((aligned(16))) float ce_s[];  // [L][128] sums, [L][E] products, [B] utterance list, [L] plane offsets
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ncpu = (p.T + 63) / 64, W = p.L * 128, LE = p.L * p.E;
+  float* prod = ce_s + W;
+  int* list = reinterpret_cast<int*>(prod + LE);
+  long long* waux = reinterpret_cast<long long*>(ce_s + ((W + LE + p.B + 1) & ~1));  // (8-byte aligned)
+  __shared__ int s_hits;
+  if (wave == 0) {
+    int cnt = 0;
+    for (int u0 = 0; u0 < p.B; u0 += 64) {
+      const int u = u0 + lane;
+      const bool m = u < p.B && p.idx[(long long)u * p.run] == r;
+      const unsigned long long b = __ballot(m);
+      if (m) list[cnt + __popcll(b & ((1ull << lane) - 1ull))] = u;
+      cnt += __popcll(b);
+    }
+    if (lane == 0) s_hits = cnt;
+  } else if (wave == 1) {
+    for (int l = lane; l < p.L; l += 64) waux[l] = p.layers[l].w_aux;
+  }
+  __syncthreads();
+  const int hits = s_hits;
+  if (hits == 0) return;  // (uniform)
+  // the weights do not depend on phase 1: requested first (the first pass of the loop below; the usual launch has one)
+  const int sub = tid & 3;
+  sk_u32x4 wh[4], wl[4];
+  {
+    const int q = tid >> 2;
+    if (q < LE) {
+      const int l = q / p.E, e = q - l * p.E;
+      const long long wo = waux[l] + (long long)(p.c0 + e) * 128 + sub * 32;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        wh[k] = *reinterpret_cast<const sk_u32x4*>(p.whi + wo + k * 8);
+        if (p.wlo) wl[k] = *reinterpret_cast<const sk_u32x4*>(p.wlo + wo + k * 8);
+      }
+    }
+  }
+  for (int i = tid; i < W; i += CE_THREADS) {
+    float acc = 0.f;
+    for (int k0 = 0; k0 < hits; k0 += 8) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        v[k] = 0.f;
+        if (k0 + k < hits) {
+          const int u = list[k0 + k];
+          const int g0 = (u * ncpu) / p.cpg, g1 = ((u + 1) * ncpu - 1) / p.cpg;
+          for (int g = g0; g <= g1; g++) v[k] += p.usums[((long)g * p.nseg + (u - (g * p.cpg) / ncpu)) * W + i];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; k++)
+        if (k0 + k < hits) acc += v[k];
+    }
+    ce_s[i] = acc;
+  }
+  __syncthreads();
+  for (int q0 = 0; q0 < LE; q0 += CE_THREADS / 4) {
+    const int q = q0 + (tid >> 2);
+    float acc = 0.f;
+    if (q < LE) {
+      const int l = q / p.E, e = q - l * p.E;
+      if (q0 > 0) {
+        const long long wo = waux[l] + (long long)(p.c0 + e) * 128 + sub * 32;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          wh[k] = *reinterpret_cast<const sk_u32x4*>(p.whi + wo + k * 8);
+          if (p.wlo) wl[k] = *reinterpret_cast<const sk_u32x4*>(p.wlo + wo + k * 8);
+        }
+      }
+      const float* sv = ce_s + l * 128 + sub * 32;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        acc += ce_dot8(wh[k], sv + k * 8);
+        if (p.wlo) acc += ce_dot8(wl[k], sv + k * 8);
+      }
+    }
+    acc += __shfl_xor(acc, 1);
+    acc += __shfl_xor(acc, 2);
+    if (q < LE && sub == 0) prod[q] = acc;
+  }
+  __syncthreads();
+  for (int e = tid; e < p.E; e += CE_THREADS) {
+    float acc = 0.f;
+    for (int l = 0; l < p.L; l++) acc += prod[l * p.E + e];
+    p.dtable[(long)r * p.E + e] += acc;
+  }
+}
+
+int launch_cond_embed_bwd(const CondEmbedP& p, hipStream_t s) {
+  const size_t lds = (size_t)((p.L * 128 + p.L * p.E + p.B + 1) & ~1) * sizeof(float) + (size_t)p.L * sizeof(long long);
+  if (!p.usums || !p.whi || !p.layers || !p.idx || !p.dtable || p.E < 1 || p.n_rows < 1 || p.cpg < 1 || p.nseg < 1 || lds > 48 * 1024)
+    return CRK_ERR_ARG;
+  hipLaunchKernelGGL(cond_embed_bwd_kernel, dim3(p.n_rows), dim3(CE_THREADS), lds, s, p);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }

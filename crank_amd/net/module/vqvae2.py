@@ -367,6 +367,10 @@ class VQVAE2(FlatModel):
         """dec_h: the conditioning tensor, or a pair of tensors that are to be concatenated (can_pair_f0)."""
         a, b = dec_h if isinstance(dec_h, (tuple, list)) else (dec_h, None)
         if spkrvec is not None:
+            # one label per utterance and features that want no gradient: the last decoder's backward owns the table's
+            # gradient (ops.concat_embed_owned; same forward launch, same values)
+            if torch.is_grad_enabled() and ops.embed_owned_ok(self.decoders[0].net, a, b, spkrvec):
+                return ops.concat_embed_owned(a, b, self.spkr_table, spkrvec, self, self.emb_offset)
             return ops.concat_embed(a, b, self.spkr_table, spkrvec, self, self.emb_offset, self.flat)
         return dec_h if b is None else torch.cat([a, b], dim=-1)
 

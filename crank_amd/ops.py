@@ -152,6 +152,16 @@ class HipNet:
             v = self._saved_bytes[key] = _lib.lib().crk_net_saved_bytes(self.handle, B, T)
         return v
 
+    def embed_grad_supported(self, B, T):
+        """Does crk_net_backward_embed serve this net at (B, T) in the current arithmetic (a gated stack with conditioning
+        on the fused kernels)?  Remembered per batch shape like saved_bytes."""
+        key = ("embed", B, T, _PRECISION)
+        v = self._saved_bytes.get(key)
+        if v is None:
+            self.saved_bytes(B, T)
+            v = self._saved_bytes[key] = bool(_lib.lib().crk_net_embed_grad_supported(self.handle, B, T, _flags(backward=True)))
+        return v
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -165,9 +175,11 @@ class _NetFn(torch.autograd.Function):
     """y = net(x, c).  `owner` supplies the flat parameter / gradient blocks."""
 
     @staticmethod
-    def forward(ctx, x, c, flat, net, owner, offset, dx_scale, no_save=False, ybuf=None, ycol=0):
+    def forward(ctx, x, c, flat, net, owner, offset, dx_scale, no_save=False, ybuf=None, ycol=0, emb=None):
         L = _lib.lib()
         B, T = x.shape[0], x.shape[1]
+        if emb is not None and not (c is not None and emb.run == T and net.embed_grad_supported(B, T)):
+            raise RuntimeError("conditioning built by concat_embed_owned fed to a net that cannot own its table gradient")
         xk, ldx = _rows(x)
         ck, ldc = (None, 0) if c is None else _rows(c)
         if ybuf is None:
@@ -192,6 +204,7 @@ class _NetFn(torch.autograd.Function):
         ctx.save_for_backward(xk, ck if ck is not None else torch.empty(0, device=x.device), flat)
         ctx.saved_ws = saved
         ctx.has_c = c is not None
+        ctx.emb = emb
         return y
 
     @staticmethod
@@ -221,14 +234,28 @@ class _NetFn(torch.autograd.Function):
                 owner._keepalive.append(ctx.saved_ws)
         params = flat.data_ptr() + 4 * ctx.offset
         grads = owner.grad_flat.data_ptr() + 4 * ctx.offset
+        flags = (_flags(skip, precision=ctx.precision, defer_wnorm=defer, backward=True)
+                 | (CRK_FLAG_SEED_ON_DEVICE if ctx.seed is not None else 0))
+        emb = ctx.emb
+        if emb is not None and not skip and not emb.owner.skip_param_grads:
+            # the conditioning is [a | b | table[label of the utterance]] and only the table wants a gradient: this launch
+            # sequence leaves it in the table's rows of the flat gradient block; no per-frame dc exists
+            emb.owner.grads_clean = False
+            g = emb.owner.grad_flat[emb.tab_offset: emb.tab_offset + emb.rows * emb.E]
+            check(
+                L.crk_net_backward_embed(net.handle, params, owner.version, grads, ptr(xk), ldx, ptr(ck), ldc, ptr(dyk), lddy,
+                                         ptr(dx), net.in_ch, float(ctx.dx_scale), ptr(ctx.saved_ws), B, T, flags,
+                                         ptr(ctx.seed), ptr(emb.idx), emb.run, emb.c0, emb.E, emb.rows, ptr(g), stream_ptr()),
+                "crk_net_backward_embed",
+            )
+            return dx, None, None, None, None, None, None, None, None, None, None
         check(
             L.crk_net_backward(net.handle, params, owner.version, grads, ptr(xk), ldx, ptr(ck), ldc, ptr(dyk), lddy,
                                ptr(dx), net.in_ch, float(ctx.dx_scale), ptr(dc), net.aux_ch, ptr(ctx.saved_ws), B, T,
-                               _flags(skip, precision=ctx.precision, defer_wnorm=defer, backward=True) | (CRK_FLAG_SEED_ON_DEVICE if ctx.seed is not None else 0),
-                               ptr(ctx.seed), stream_ptr()),
+                               flags, ptr(ctx.seed), stream_ptr()),
             "crk_net_backward",
         )
-        return dx, dc, None, None, None, None, None, None, None, None
+        return dx, dc, None, None, None, None, None, None, None, None, None
 
 
 class _NetCEFn(torch.autograd.Function):
@@ -319,7 +346,9 @@ def net_apply(net, owner, offset, x, c=None, dx_scale=1.0, out=None):
     """out = (buffer (B,T,W), first column): write the result into that column slice and return the slice."""
     # without autograd nothing will ever read the per-layer activations: tell the library
     ybuf, ycol = out if out is not None else (None, 0)
-    return _NetFn.apply(x, c, owner.flat, net, owner, offset, dx_scale, not torch.is_grad_enabled(), ybuf, ycol)
+    # a conditioning tensor from concat_embed_owned: this net's backward produces the embedding table's gradient
+    emb = getattr(c, "_crk_embed", None) if c is not None else None
+    return _NetFn.apply(x, c, owner.flat, net, owner, offset, dx_scale, not torch.is_grad_enabled(), ybuf, ycol, emb)
 
 
 class _AliasCatFn(torch.autograd.Function):
@@ -1033,23 +1062,30 @@ def _label_runs(idx):
     return idx.contiguous(), 1
 
 
+def _concat_embed_fwd(a, b, table, idx):
+    """cat([a, b, table[idx]], -1) -> (out, label tensor handed to the kernel, run, (ca, cb, E))."""
+    L = _lib.lib()
+    B, T = idx.shape
+    ak, lda = (None, 0) if a is None else _rows(a)
+    bk, ldb = (None, 0) if b is None else _rows(b)
+    ca = 0 if a is None else a.shape[-1]
+    cb = 0 if b is None else b.shape[-1]
+    E = table.shape[1]
+    out = torch.empty(B, T, ca + cb + E, device=idx.device, dtype=torch.float32)
+    ik, run = _label_runs(idx)
+    check(L.crk_concat_embed_run(ptr(ak), lda, ca, ptr(bk), ldb, cb, ptr(table), E, ptr(ik), run, B * T, ptr(out),
+                                 ca + cb + E, stream_ptr()), "crk_concat_embed_run")
+    return out, ik, run, (ca, cb, E)
+
+
 class _ConcatEmbedFn(torch.autograd.Function):
     """out = cat([a, b, table[idx]], -1); backward routes the embedding slice into the
     owner's flat gradient (table lives there) and returns da / db slices."""
 
     @staticmethod
     def forward(ctx, a, b, table, idx, owner, tab_offset, flat):
-        L = _lib.lib()
+        out, ik, run, (ca, cb, E) = _concat_embed_fwd(a, b, table, idx)
         B, T = idx.shape
-        ak, lda = (None, 0) if a is None else _rows(a)
-        bk, ldb = (None, 0) if b is None else _rows(b)
-        ca = 0 if a is None else a.shape[-1]
-        cb = 0 if b is None else b.shape[-1]
-        E = table.shape[1]
-        out = torch.empty(B, T, ca + cb + E, device=idx.device, dtype=torch.float32)
-        ik, run = _label_runs(idx)
-        check(L.crk_concat_embed_run(ptr(ak), lda, ca, ptr(bk), ldb, cb, ptr(table), E, ptr(ik), run, B * T, ptr(out),
-                                     ca + cb + E, stream_ptr()), "crk_concat_embed_run")
         ctx.geom = (ca, cb, E, table.shape[0], run, B * T)
         ctx.owner, ctx.tab_offset = owner, tab_offset
         ctx.save_for_backward(ik)
@@ -1074,6 +1110,35 @@ class _ConcatEmbedFn(torch.autograd.Function):
 
 def concat_embed(a, b, table, idx, owner=None, tab_offset=0, flat=None):
     return _ConcatEmbedFn.apply(a, b, table, idx, owner, tab_offset, flat)
+
+
+class EmbedCond:
+    """What a conditioning tensor from concat_embed_owned carries to the net op that consumes it."""
+    __slots__ = ("idx", "run", "c0", "E", "rows", "owner", "tab_offset")
+
+
+def embed_owned_ok(net, a, b, idx):
+    """May the net that takes cat([a, b, table[idx]]) as its conditioning produce the table's gradient itself
+    (crk_net_backward_embed)?  One label per utterance (the stride-0 view, run == T), nothing else in the conditioning
+    wants a gradient, the net runs the fused kernels at this shape, and the switch is on."""
+    if not cfg.cond_sums or idx.dim() != 2:
+        return False
+    if (a is not None and a.requires_grad) or (b is not None and b.requires_grad):
+        return False
+    B, T = idx.shape
+    return _label_runs(idx)[1] == T and net.embed_grad_supported(B, T)
+
+
+def concat_embed_owned(a, b, table, idx, owner, tab_offset):
+    """concat_embed's values (the same launch) as a tensor outside autograd that names the table: the net op fed with it as
+    conditioning (net_apply) adds the table's gradient to owner.grad_flat in its backward, from per-utterance sums - no
+    per-frame conditioning gradient is computed or reduced.  Only where embed_owned_ok says so, and only for that net."""
+    with torch.no_grad():
+        out, ik, run, (ca, cb, E) = _concat_embed_fwd(a, b, table, idx)
+    e = EmbedCond()
+    e.idx, e.run, e.c0, e.E, e.rows, e.owner, e.tab_offset = ik, run, ca + cb, E, table.shape[0], owner, tab_offset
+    out._crk_embed = e
+    return out
 
 
 def adam_step(flat, grad, exp_avg, exp_avg_sq, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, clear_grads=False,

@@ -98,6 +98,19 @@ int crk_net_backward_scaled(void* net, const float* params, unsigned long long v
                             int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx, float dx_scale,
                             float* dc, int lddc, const float* saved, int B, int T, int flags, unsigned long long seed,
                             const float* dy_num, const float* dy_den, void* stream);
+/* crk_net_backward for a conditioning input whose columns [c0, c0 + E) are table[idx[u * run]] on every frame of utterance u
+ * (run == T; crk_concat_embed_run built it) and whose other columns need no gradient.  No per-frame dc is computed: the
+ * weight-gradient launch also sums every block's gate gradient per utterance, and one small launch adds
+ * sum_l Waux_l[:, c0:c0+E]^T . sums of the utterances of each label, in ascending utterance order, to dtable [n_rows][E]
+ * (fixed order, no atomics).  dx and the parameter gradients are those of crk_net_backward; the table gradient differs from
+ * the frame sum of dc by fp32 reassociation.  Gated stacks with conditioning on the fused kernels only -
+ * crk_net_embed_grad_supported(net, B, T, flags) == 1 - and CRK_ERR_UNSUPPORTED otherwise (crk_net_backward with dc, then
+ * crk_embed_bwd_run).  The sums live in the scratch crk_net_reserve made. */
+int crk_net_embed_grad_supported(void* net, int B, int T, int flags);
+int crk_net_backward_embed(void* net, const float* params, unsigned long long version, float* grads, const float* x, int ldx,
+                           const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx, float dx_scale,
+                           const float* saved, int B, int T, int flags, unsigned long long seed, const long long* idx,
+                           long long run, int c0, int E, int n_rows, float* dtable, void* stream);
 
 /* Dropout seeds on the device (D's ResidualBlock dropout, crank/bin/train.py:114; torch draws its Philox offsets on the
  * host, which a captured graph would freeze): *out = mix(*state), *state advances.  One thread; `state` is a uint64 the
