@@ -132,6 +132,17 @@ SIGNATURES = {
     "crk_wana_mcep": (I, [P, P, P, P, P, I, LL, LL, LL, I, P, P, P, LL, P]),
     "crk_wana_npow": (I, [P, P, P, I, LL, P, P, LL, P]),
     "crk_wana_frame_shapes": (I, [P, P, P, I, LL, P, P, P]),
+    "crk_f0_create": (P, [I, I, P]),
+    "crk_f0_destroy": (None, [P]),
+    "crk_f0_reserve": (I, [P, LL]),
+    "crk_f0_workspace_bytes": (LL, [I, LL, LL, LL]),
+    "crk_f0_harvest": (I, [P, P, P, P, P, P, I, LL, LL, LL, LL, LL, P, P, P, LL, P]),
+    "crk_f0_decimate": (I, [P, P, P, I, LL, P, P, LL, P]),
+    "crk_f0_raw_candidates": (I, [P, P, P, P, P, P, I, LL, LL, LL, P, P, P, LL, P]),
+    "crk_f0_candidates": (I, [P, P, P, I, LL, P, P, LL, P]),
+    "crk_f0_refine": (I, [P, P, P, P, P, I, LL, P, P, P]),
+    "crk_f0_contour": (I, [P, P, P, P, I, LL, P, P, LL, P]),
+    "crk_f0_continuous": (I, [P, P, I, LL, P, P, P, P, P, P, P]),
     "crk_gl_create": (I, [I, I, I, I, I, P, ctypes.POINTER(c_void_p)]),
     "crk_gl_destroy": (None, [P]),
     "crk_gl_workspace_bytes": (LL, [I, LL, LL]),

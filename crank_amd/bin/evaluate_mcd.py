@@ -5,9 +5,9 @@ alignment and the distortion on the device (crk_mcd_fastdtw, one wavefront per p
 The reference's file handling (HDF5, feats.scp lookup, per-pair summary) is not reproduced; ``mcd_fastdtw`` takes the
 arrays ``calculate()`` works on.  ``mcd_fastdtw_from_waveforms`` is the branch for models that write waveforms
 (``output_feat_type: mlfb``; evaluate_mcd.py:26-42, 56-57): low cut and WORLD spectral analysis of all converted
-waveforms in one batch on the device (crank_amd.world.WorldAnalyzer), then ``mcd_fastdtw``.  One stated difference: the
-reference re-estimates F0 from the converted waveform (Harvest); here the caller gives the converted F0 contour, the one
-the eval stage stored with the utterance and the model was conditioned on.
+waveforms in one batch on the device (crank_amd.world.WorldAnalyzer), then ``mcd_fastdtw``.  With ``cv_f0s=None`` the F0 of
+the converted waveform is re-estimated by Harvest (crank_amd.world.HarvestF0) as the reference does; a given contour (the
+one the eval stage stored with the utterance and the model was conditioned on) is used as it is.
 """
 import numpy as np
 import torch
@@ -61,16 +61,21 @@ def mcd_fastdtw(cv_mceps, cv_f0s, gt_mceps, gt_f0s, radius=1, return_paths=False
 
 
 def mcd_fastdtw_from_waveforms(cv_waves, cv_f0s, gt_mceps, gt_f0s, conf, radius=1, return_paths=False, device="cuda",
-                               analyzer=None):
+                               analyzer=None, f0_ranges=None):
     """MCD of converted WAVEFORMS against ground-truth mel-cepstra.  cv_waves: per-utterance waveforms at
     conf["feature"]["fs"]; cv_f0s: their F0 contours (one value per analysis frame of shiftms; > 0 voiced), which set the
     number of frames and select the voiced ones; gt_mceps / gt_f0s as in ``mcd_fastdtw``.  The 0th coefficient stays in,
-    as in the reference."""
+    as in the reference.  cv_f0s=None: the contours are re-estimated from the low-cut converted waveforms, as the reference
+    does, and f0_ranges = [(minf0, maxf0), ...], the target speakers' search ranges, is required."""
     from crank_amd.world import WorldAnalyzer
 
     feat = conf["feature"]
     if analyzer is None:
         analyzer = WorldAnalyzer(feat["fs"], feat["fftl"], feat["shiftms"], device=device)
+    if cv_f0s is None:
+        if f0_ranges is None or len(f0_ranges) != len(cv_waves):
+            raise ValueError("cv_f0s=None needs f0_ranges, one (minf0, maxf0) per converted waveform")
+        cv_f0s, _ = analyzer.analyze_batch(cv_waves, [r[0] for r in f0_ranges], [r[1] for r in f0_ranges], low_cut=70)
     cv_mceps = analyzer.mcep_batch(cv_waves, cv_f0s, feat["mcep_dim"], feat["mcep_alpha"], low_cut=70)
     to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)  # noqa: E731
     return mcd_fastdtw([to_np(m) for m in cv_mceps], [to_np(f) for f in cv_f0s], gt_mceps, gt_f0s, radius, return_paths,

@@ -9,10 +9,13 @@ library every call raises.
 
 ``WorldAnalyzer`` is the other direction, the spectral half of WORLD analysis (csrc/world_analysis_kernels.hip,
 crk_wana_*): what the reference's ``crank/bin/evaluate_mcd.py`` runs on a converted waveform - ``low_cut_filter``, pyworld
-``cheaptrick``, pysptk ``sp2mc``, sprocket ``spc2npow`` - for a ragged batch of waveforms.  It does NOT estimate F0
-(Harvest is not implemented): the caller gives the contour, for converted speech the ``f0`` the eval stage stored with
-the utterance, where the reference re-estimates it from the converted waveform.  Aperiodicity (D4C) is not implemented
-either.  The oracle is tests/world_analysis_ref.py; parity with pyworld / pysptk is unpinned.
+``cheaptrick``, pysptk ``sp2mc``, sprocket ``spc2npow`` - for a ragged batch of waveforms.  Its stage methods take the F0 contour from
+the caller; ``analyze_batch`` estimates it first with ``HarvestF0``, as the reference does.  Aperiodicity (D4C) is not
+implemented.  The oracle is tests/world_analysis_ref.py; parity with pyworld / pysptk is unpinned.
+
+``HarvestF0`` is pyworld ``harvest`` (csrc/f0_kernels.hip, crk_f0_*) for a ragged batch of waveforms with a search range
+each, and ``continuous_f0_batch`` the reference's ``convert_continuos_f0`` with ``lf0`` / ``lcf0``.  The oracle is
+tests/harvest_ref.py; parity with pyworld is unpinned.
 """
 import ctypes
 
@@ -254,6 +257,7 @@ class WorldAnalyzer:
         self._reserved = {}  # handle key -> randn draws its table covers
         self._taps = {}  # cutoff -> device taps
         self._ws = None
+        self._harvest = None
 
     def __del__(self):
         try:
@@ -444,6 +448,255 @@ class WorldAnalyzer:
         if len(waves) != len(outputs):
             raise ValueError("one waveform per eval output is needed")
         return self.mcep_batch(list(waves), [d["f0"] for d in outputs], dim, alpha, low_cut)
+
+
+    def analyze_batch(self, waves, minf0s, maxf0s, low_cut=70):
+        """sprocket ``FeatureExtractor.analyze`` without ``ap`` for each waveform: the reference's low cut (None: none),
+        Harvest at the utterance's search range, CheapTrick at that F0.  Returns (f0s, sps): lists of (T,) and (T, 513)."""
+        if self.shiftms != round(self.shiftms):
+            raise ValueError(f"shiftms {self.shiftms}: Harvest takes an integer frame period")
+        if self._harvest is None:
+            self._harvest = HarvestF0(self.fs, int(self.shiftms), self.device)
+        self._harvest.check(waves, minf0s, maxf0s)
+        xs = [_f64(w, self.device).reshape(-1) for w in waves] if low_cut is None else self.low_cut_batch(waves, low_cut)
+        f0s = self._harvest.harvest_batch(xs, minf0s, maxf0s)
+        return f0s, self.cheaptrick_batch(xs, f0s)
+
+
+HARVEST_MAX_CHANNELS = 192  # F0_MAX_CH
+HARVEST_SLOTS = 112  # candidates per 1 ms frame after the overlap (F0_NS)
+HARVEST_MIN_SAMPLES = 64
+
+
+class HarvestF0:
+    """pyworld ``harvest(x, fs, f0_floor=minf0, f0_ceil=maxf0, frame_period=shiftms)`` for a ragged batch, each utterance
+    with its own search range (the reference takes it per speaker from spkr.yml).  All float64, on the device."""
+
+    def __init__(self, fs=22050, shiftms=5, device="cuda"):
+        if int(fs) != fs or not 8000 <= int(fs) <= 48000:
+            raise ValueError(f"fs {fs}: Harvest takes 8000 .. 48000 Hz")
+        if int(shiftms) != shiftms or not 1 <= int(shiftms) <= 1000:
+            raise ValueError(f"shiftms {shiftms}: Harvest takes an integer frame period in ms")
+        self.fs, self.shiftms = int(fs), int(shiftms)
+        self.device = torch.device(device)
+        self.r = int(min(12, max(1, np.floor(self.fs / 8000.0 + 0.5))))
+        self.fs_d = self.fs / self.r
+        self._h = None
+        self._ws = None
+        self._events = 0
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().crk_f0_destroy(self._h)
+        except Exception:
+            pass
+
+    def handle(self):
+        if self._h is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("Harvest runs in the HIP kernels: the device must be the GPU")
+            from scipy.signal import cheby1
+
+            b, a = cheby1(3, 0.05, 0.8 / self.r)
+            co = (ctypes.c_double * 8)(*[float(v) for v in list(b) + list(a)])
+            self._h = _lib.lib().crk_f0_create(self.fs, self.shiftms, co)
+            if not self._h:
+                raise RuntimeError("libcrank_hip: crk_f0_create failed (unsupported configuration or HIP error)")
+        return self._h
+
+    # -- inputs
+    def check(self, waves, minf0s, maxf0s):
+        """The supported envelope, before any launch."""
+        n = len(waves)
+        if n < 1 or len(minf0s) != n or len(maxf0s) != n:
+            raise ValueError("waves, minf0s and maxf0s must be lists of the same non-zero length")
+        for w, lo, hi in zip(waves, minf0s, maxf0s):
+            size = int(w.numel() if isinstance(w, torch.Tensor) else np.asarray(w).size)
+            if size < HARVEST_MIN_SAMPLES:
+                raise ValueError(f"a waveform of {size} samples: Harvest needs at least {HARVEST_MIN_SAMPLES}")
+            if not (np.isfinite(lo) and np.isfinite(hi) and 40.0 <= lo < hi <= 800.0):
+                raise ValueError(f"search range {lo} .. {hi} Hz: Harvest takes 40 <= minf0 < maxf0 <= 800")
+
+    def _layout(self, lens, minf0s, maxf0s):
+        """The batch's integers, formed once on the host in float64 / int64 (the kernels trust them): utt, range, chan_bf,
+        chan as include/crank_hip.h lays them out, and the totals."""
+        fs, r, fs_d = self.fs, self.r, self.fs_d
+        utt = np.zeros((len(lens), 12), np.int64)
+        rng = np.zeros((len(lens), 2))
+        bfs, chans = [], []
+        s0 = d0 = t0 = c0 = r0 = o0 = e0 = 0
+        for u, (n, lo, hi) in enumerate(zip(lens, minf0s, maxf0s)):
+            floor, ceil = 0.9 * float(lo), 1.1 * float(hi)
+            n_ch = 1 + int(np.log2(ceil / floor) * 40)
+            if n_ch > HARVEST_MAX_CHANNELS:
+                raise ValueError(f"{n_ch} channels: the kernels take {HARVEST_MAX_CHANNELS}")
+            bf = floor * 2.0 ** ((np.arange(n_ch) + 1.0) / 40)
+            nd, T1 = -(-n // r), int(1000.0 * n / fs) + 1
+            To = int(1000.0 * n / fs / self.shiftms) + 1
+            h = np.floor(2.0 * fs_d / bf + 0.5).astype(np.int64)
+            # a band-passed signal crosses zero about bf times a second in each direction; 3 bf and 16 spare
+            cap = np.minimum(nd, (3.0 * bf * nd / fs_d).astype(np.int64) + 16)
+            off = e0 + 4 * (np.cumsum(cap) - cap)
+            chans.append(np.stack([h, off, cap, np.full(n_ch, u, np.int64)], 1))
+            bfs.append(bf)
+            utt[u, :11] = (s0, n, d0, nd, t0, T1, c0, n_ch, r0, o0, To)
+            rng[u] = (floor, ceil)
+            s0, d0, t0, c0, r0, o0 = s0 + n, d0 + nd, t0 + T1, c0 + n_ch, r0 + n_ch * T1, o0 + To
+            e0 += 4 * int(cap.sum())
+        dev = self.device
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)  # noqa: E731
+        return dict(utt=up(utt), range=up(rng), chan_bf=up(np.concatenate(bfs)), chan=up(np.concatenate(chans)),
+                    host=utt, n=len(lens), S=s0, D=d0, F=t0, C=c0, R=r0, O=o0, E=e0)
+
+    def _batch(self, waves, minf0s, maxf0s):
+        self.check(waves, minf0s, maxf0s)
+        self.handle()
+        xs = [_f64(w, self.device).reshape(-1) for w in waves]
+        L = self._layout([int(x.numel()) for x in xs], minf0s, maxf0s)
+        L["x"] = torch.cat(xs).contiguous()
+        self.reserve(L["n"], L["S"], L["F"], L["C"], L["E"])
+        return L
+
+    @staticmethod
+    def _split(t, L, col):
+        """Rows of t per utterance: col 3 decimated samples, 5 the 1 ms frames, 10 the output frames."""
+        return list(t.split([int(v) for v in L["host"][:, col]]))
+
+    # -- device resources
+    def reserve(self, n_utts, total_samples, total_frames, total_channels, total_events):
+        """Workspace for a call of that size and the handle's event storage (kept and grown, never per call)."""
+        need = int(_lib.lib().crk_f0_workspace_bytes(n_utts, total_samples, total_frames, total_channels))
+        if need < 0:
+            raise ValueError("crk_f0_workspace_bytes: bad shape")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if total_events > self._events:
+            check(_lib.lib().crk_f0_reserve(self.handle(), int(total_events)), "crk_f0_reserve")
+            self._events = int(total_events)
+        return self._ws
+
+    @staticmethod
+    def _status(status):
+        if bool(status.any()):
+            raise RuntimeError("Harvest: an event stream overflowed its capacity (more than 3 zero crossings per period of "
+                               "a channel's centre frequency)")
+
+    # -- the estimator
+    def harvest_batch(self, waves, minf0s, maxf0s):
+        """F0 contours (float64, int(1000 n / fs / shiftms) + 1 frames, 0 = unvoiced) of a ragged batch."""
+        L = self._batch(waves, minf0s, maxf0s)
+        f0 = torch.empty(L["O"], dtype=torch.float64, device=self.device)
+        status = torch.empty(L["n"], dtype=torch.int32, device=self.device)
+        ws = self._ws
+        check(_lib.lib().crk_f0_harvest(self._h, L["x"].data_ptr(), L["utt"].data_ptr(), L["range"].data_ptr(),
+                                        L["chan_bf"].data_ptr(), L["chan"].data_ptr(), L["n"], L["S"], L["C"], L["F"],
+                                        L["E"], L["O"], f0.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        stream_ptr()), "crk_f0_harvest")
+        self._status(status)
+        return self._split(f0, L, 10)
+
+    def harvest(self, wave, minf0, maxf0):
+        return self.harvest_batch([wave], [minf0], [maxf0])[0]
+
+    # -- the stages alone (tests)
+    def decimate_batch(self, waves, minf0s, maxf0s):
+        """Per utterance the zero-phase low-passed, decimated, mean-free signal the band-pass filters run on."""
+        L = self._batch(waves, minf0s, maxf0s)
+        yd = torch.empty(L["D"], dtype=torch.float64, device=self.device)
+        ws = self._ws
+        check(_lib.lib().crk_f0_decimate(self._h, L["x"].data_ptr(), L["utt"].data_ptr(), L["n"], L["S"], yd.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), stream_ptr()), "crk_f0_decimate")
+        return self._split(yd, L, 3)
+
+    def raw_candidates_batch(self, waves, minf0s, maxf0s, decimated=None):
+        """Per utterance the (channels, 1 ms frames) raw candidate table; ``decimated``: the signals to filter instead of
+        this object's own decimation of ``waves``."""
+        yds = self.decimate_batch(waves, minf0s, maxf0s) if decimated is None else [_f64(y, self.device) for y in decimated]
+        L = self._batch(waves, minf0s, maxf0s)
+        if [int(y.numel()) for y in yds] != [int(v) for v in L["host"][:, 3]]:
+            raise ValueError("decimated signals must have ceil(samples / r) samples")
+        yd = torch.cat(yds).contiguous()
+        raw = torch.empty(L["R"], dtype=torch.float64, device=self.device)
+        status = torch.empty(L["n"], dtype=torch.int32, device=self.device)
+        ws = self._ws
+        check(_lib.lib().crk_f0_raw_candidates(self._h, yd.data_ptr(), L["utt"].data_ptr(), L["range"].data_ptr(),
+                                               L["chan_bf"].data_ptr(), L["chan"].data_ptr(), L["n"], L["C"], L["F"],
+                                               L["E"], raw.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               stream_ptr()), "crk_f0_raw_candidates")
+        self._status(status)
+        h = L["host"]
+        return [t.view(int(h[u, 7]), int(h[u, 5])) for u, t in enumerate(raw.split([int(v) for v in h[:, 7] * h[:, 5]]))]
+
+    def _tables(self, L, tables):
+        ts = [_f64(t, self.device) for t in tables]
+        for u, t in enumerate(ts):
+            if tuple(t.shape) != (int(L["host"][u, 5]), HARVEST_SLOTS):
+                raise ValueError(f"a candidate table must be (1 ms frames, {HARVEST_SLOTS}), got {tuple(t.shape)}")
+        return torch.cat(ts).contiguous()
+
+    def candidates_batch(self, waves, minf0s, maxf0s, raws):
+        """Per utterance the (1 ms frames, 112) candidate table of a raw table: run means, overlapped over +-3 frames."""
+        L = self._batch(waves, minf0s, maxf0s)
+        rs = [_f64(t, self.device) for t in raws]
+        for u, t in enumerate(rs):
+            if tuple(t.shape) != (int(L["host"][u, 7]), int(L["host"][u, 5])):
+                raise ValueError("a raw table must be (channels, 1 ms frames)")
+        raw = torch.cat([t.reshape(-1) for t in rs]).contiguous()
+        out = torch.empty(L["F"], HARVEST_SLOTS, dtype=torch.float64, device=self.device)
+        ws = self._ws
+        check(_lib.lib().crk_f0_candidates(self._h, raw.data_ptr(), L["utt"].data_ptr(), L["n"], L["F"], out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), stream_ptr()), "crk_f0_candidates")
+        return self._split(out, L, 5)
+
+    def refine_batch(self, waves, minf0s, maxf0s, cands):
+        """Per utterance (refined F0, score), each (1 ms frames, 112), of a candidate table on the undecimated waveform."""
+        L = self._batch(waves, minf0s, maxf0s)
+        c = self._tables(L, cands)
+        ref, sc = torch.empty_like(c), torch.empty_like(c)
+        check(_lib.lib().crk_f0_refine(self._h, L["x"].data_ptr(), c.data_ptr(), L["utt"].data_ptr(),
+                                       L["range"].data_ptr(), L["n"], L["F"], ref.data_ptr(), sc.data_ptr(), stream_ptr()),
+              "crk_f0_refine")
+        return list(zip(self._split(ref, L, 5), self._split(sc, L, 5)))
+
+    def contour_batch(self, waves, minf0s, maxf0s, refined, scores):
+        """Per utterance the 1 ms contour of the refined candidate and score tables."""
+        L = self._batch(waves, minf0s, maxf0s)
+        c, s = self._tables(L, refined), self._tables(L, scores)
+        f1 = torch.empty(L["F"], dtype=torch.float64, device=self.device)
+        ws = self._ws
+        check(_lib.lib().crk_f0_contour(self._h, c.data_ptr(), s.data_ptr(), L["utt"].data_ptr(), L["n"], L["F"],
+                                        f1.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "crk_f0_contour")
+        return self._split(f1, L, 5)
+
+
+def continuous_f0_batch(f0s, device="cuda", return_filled=False):
+    """The reference's ``convert_continuos_f0`` and feature.py:86-88 for each contour: (uv float32, cf0, lf0, lcf0), with
+    its quirk: the ends of the contour are overwritten with the first / last voiced value before lf0 = log(f0 + 1e-10) is
+    taken (``return_filled`` appends that contour).  A contour without a voiced frame raises ValueError (the reference:
+    IndexError)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("continuous_f0_batch runs in the HIP kernels: the device must be the GPU")
+    f0s = [_f64(f, dev).reshape(-1) for f in f0s]
+    lens = [int(f.numel()) for f in f0s]
+    if not lens or min(lens) < 1:
+        raise ValueError("an F0 contour needs at least 1 frame")
+    F = sum(lens)
+    f0 = torch.cat(f0s).contiguous()
+    foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
+    uv = torch.empty(F, dtype=torch.float32, device=dev)
+    filled, cf0, lf0, lcf0 = (torch.empty(F, dtype=torch.float64, device=dev) for _ in range(4))
+    status = torch.empty(len(lens), dtype=torch.int32, device=dev)
+    check(_lib.lib().crk_f0_continuous(f0.data_ptr(), foff.data_ptr(), len(lens), F, uv.data_ptr(), filled.data_ptr(),
+                                       cf0.data_ptr(), lf0.data_ptr(), lcf0.data_ptr(), status.data_ptr(), stream_ptr()),
+          "crk_f0_continuous")
+    bad = status.nonzero().reshape(-1).tolist()
+    if bad:
+        raise ValueError(f"utterance {bad[0]} has no voiced frame")
+    outs = [t.split(lens) for t in ((uv, cf0, lf0, lcf0, filled) if return_filled else (uv, cf0, lf0, lcf0))]
+    return [tuple(o[u] for o in outs) for u in range(len(lens))]
 
 
 def world2wav(f0, mcep, codeap, rmcep=None, wavf=None, fs=22050, fftl=1024, shiftms=10, alpha=0.455):

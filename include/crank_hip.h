@@ -553,6 +553,56 @@ int crk_wana_npow(void* wana, const double* sp, const long long* frame_offsets, 
 int crk_wana_frame_shapes(void* wana, const double* f0, const long long* frame_offsets, int n_utts, long long total_frames,
                           int* shapes, long long* draw_offsets, void* stream);
 
+/* ---- Harvest F0 estimation (csrc/f0_kernels.hip) ----
+ * pyworld.harvest as sprocket's FeatureExtractor.analyze calls it, in float64, for a ragged batch of utterances with a
+ * search range each.  The definition is tests/harvest_ref.py; parity with pyworld is unpinned.
+ *
+ * The caller forms the batch's layout on the host (crank_amd/world.py HarvestF0._layout) and passes DEVICE tables:
+ *   utt     int64 [n_utts][12]: sample offset, samples, decimated offset, decimated samples (ceil(samples / r)), 1 ms frame
+ *           offset, 1 ms frames (int(1000 samples / fs) + 1), channel offset, channels (<= 192), raw-table offset (cells),
+ *           output frame offset, output frames, 0
+ *   range   double [n_utts][2]: 0.9 minf0, 1.1 maxf0
+ *   chan_bf double [total_channels]: centre frequencies;  chan int64 [total_channels][4]: half filter length
+ *           round(2 fs_d / bf) <= 672, offset of the channel's 4 event streams (doubles), capacity of one stream, utterance
+ * total_events is the sum of 4 * capacity.  The kernels trust these tables.
+ *
+ * crk_f0_create: one handle per (fs, shiftms); cheby: HOST [8] = b[4], a[4] of the decimation low-pass (order-3 Chebyshev-I,
+ * 0.05 dB, 0.8 / r of Nyquist, r = clamp(round(fs / 8000), 1, 12)).  Allocates the twiddle table (synchronises).  NULL
+ * unless 8000 <= fs <= 48000.  crk_f0_reserve: the event streams' storage, kept and grown (allocates and synchronises
+ * only then).  The compute entries never allocate and never synchronise; total_events above the reservation, or a
+ * workspace below crk_f0_workspace_bytes, is CRK_ERR_ARG.  status: DEVICE int [n_utts], 1 where an event stream
+ * overflowed its capacity (its later events were dropped). */
+void* crk_f0_create(int fs, int shiftms, const double* cheby);
+void crk_f0_destroy(void* f0);
+int crk_f0_reserve(void* f0, long long total_events);
+long long crk_f0_workspace_bytes(int n_utts, long long total_samples, long long total_frames, long long total_channels);
+/* f0: [total_out] at shiftms, utterance u = its output frames */
+int crk_f0_harvest(void* f0h, const double* x, const long long* utt, const double* range, const double* chan_bf,
+                   const long long* chan, int n_utts, long long total_samples, long long total_channels,
+                   long long total_frames, long long total_events, long long total_out, double* f0, int* status,
+                   void* workspace, long long workspace_bytes, void* stream);
+/* the stages.  yd: decimated, mean-free signals at the decimated offsets */
+int crk_f0_decimate(void* f0h, const double* x, const long long* utt, int n_utts, long long total_samples, double* yd,
+                    void* workspace, long long workspace_bytes, void* stream);
+/* raw: per utterance a (channels, 1 ms frames) table at its raw-table offset; 0 marks an empty cell */
+int crk_f0_raw_candidates(void* f0h, const double* yd, const long long* utt, const double* range, const double* chan_bf,
+                          const long long* chan, int n_utts, long long total_channels, long long total_frames,
+                          long long total_events, double* raw, int* status, void* workspace, long long workspace_bytes,
+                          void* stream);
+/* cands: [total_frames][112]: 16 run means per frame, overlapped with the frames 1, 2, 3 before and after */
+int crk_f0_candidates(void* f0h, const double* raw, const long long* utt, int n_utts, long long total_frames, double* cands,
+                      void* workspace, long long workspace_bytes, void* stream);
+/* refined, scores: [total_frames][112]; 0 where the candidate is empty or rejected */
+int crk_f0_refine(void* f0h, const double* x, const double* cands, const long long* utt, const double* range, int n_utts,
+                  long long total_frames, double* refined, double* scores, void* stream);
+/* f0_1ms: [total_frames] */
+int crk_f0_contour(void* f0h, const double* refined, const double* scores, const long long* utt, int n_utts,
+                   long long total_frames, double* f0_1ms, void* workspace, long long workspace_bytes, void* stream);
+/* the reference's convert_continuos_f0 and lf0 / lcf0; frame_offsets: DEVICE int64 [n_utts + 1]; status [n_utts]: 1 for an
+ * utterance without a voiced frame (its outputs are not written) */
+int crk_f0_continuous(const double* f0, const long long* frame_offsets, int n_utts, long long total_frames, float* uv,
+                      double* f0_filled, double* cf0, double* lf0, double* lcf0, int* status, void* stream);
+
 /* ---- Griffin-Lim waveform synthesis for log-mel models (csrc/griffin_lim_kernels.hip) ----
  * Replaces the reference's mlfb2wav (crank/utils/utils.py:94-107, 210-269: logmelspc_to_linearspc, griffin_lim -> librosa.griffinlim
  * with momentum 0.99, centred reflect-padded STFT, periodic Hann window; called by BaseTrainer._save_decoded_mlfb,
