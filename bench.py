@@ -3,29 +3,35 @@
 (BASELINE.json configs[1]: vqvae trainer, VCC2020-shaped 80-dim mlfb, batch 64 x 500
 frames per GPU, 14 speakers, bf16 MFMA compute) on synthetic inputs resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            the headline figure and nothing else
+    python bench.py --gpus N --steps K --warmup W --full     + every side measurement and check described below
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL over xGMI)
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked to and prints its line.  `--full` adds,
+all after the timed region and the dump: the eagerly enqueued step, `roofline`, `stacks_alone`, `parity_mode`, `other_configs`,
+`logmel_use_raw`, `dp_path_world_of_one`, `parity_gates` and `cpu_baseline`; `--no-roofline`, `--no-extras` and
+`--no-cpu-baseline` leave parts of it out again (without `--full` there is nothing for them to leave out).
 
 Rank 0 prints ONE JSON line.  `value` = frames processed by all ranks / max-over-ranks
 wall time of exactly K steps (barrier + synchronize on both sides).  At N = 1 a step is
 `trainer.train_graphed`'s replay of the captured HIP graph of `trainer.train(batch)` (the
 product's `hip_graph` mode: the same kernels in the same order, one launch per step; field
-`launch`); the eagerly enqueued step is timed next to it (`eager_ms_per_step`; `--no-graph`
+`launch`); `--full` times the eagerly enqueued step next to it (`eager_ms_per_step`, null in a plain run; `--no-graph`
 makes it the headline).  N > 1 under RCCL replays the step as ONE HIP graph with its collectives captured
 (parallel.graph_collectives; CRANK_AMD_DP_GRAPH_COLLECTIVES=0 or the gloo backend: a chain of HIP graphs cut at every
 collective, the collectives issued from the host between the replays, GraphedStep.segments); every rank replays or, if
 one of them could not capture, all step eagerly.  Weak scaling: every rank trains on its own 64 utterances;
 gradients, VQ-EMA statistics and masked-mean normalisers are all-reduced (crank_amd/parallel.py).
 `--force-dist` runs that data-parallel code path in a world of ONE rank over RCCL (every collective issued, every
-graph segment replayed): the N = 1 line carries its time as `dp_path_world_of_one` - the per-step price of the
+graph segment replayed): the N = 1 line of a `--full` run carries its time as `dp_path_world_of_one` - the per-step price of the
 collectives' launches and the segment boundaries before any xGMI traffic.
 
-`roofline` is measured in a second pass of K identical steps with HIP events recorded
+`--full`: `roofline` is measured in a second pass of K identical steps with HIP events recorded
 around every conv-class kernel on its launch stream (the first pass, which defines
 `value`, runs without events so they cannot perturb it); it reports the kernel class
 with the largest summed time, every class against the bound that is its own (algorithmic
 FLOP / dense bf16 MFMA peak vs algorithmic bytes / HBM peak, whichever takes longer).
-N=1 only, after the timed region: `parity_mode` (the same step in the bf16x3 arithmetic
+`--full` at N=1 only, after the timed region: `parity_mode` (the same step in the bf16x3 arithmetic
 that meets the 1e-3 bar against the fp32 reference), `other_configs` (BASELINE configs[2],
 the lsgan step) and `cpu_baseline` (the CPU oracle under the same trainer class on bounded
 samples of the configs[0] and configs[1] shapes).
@@ -379,7 +385,7 @@ def dp_path_world_of_one(args, headline_ms):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--force-dist", "--steps", str(min(args.steps, 50)), "--warmup", "10",
-           "--batch", str(args.batch), "--no-roofline", "--no-extras", "--no-cpu-baseline"]
+           "--batch", str(args.batch), "--full", "--no-roofline", "--no-extras", "--no-cpu-baseline"]  # (--full: the eager step)
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ))
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -418,6 +424,15 @@ def dump_outputs(path, trainer, vals, limit=60 << 20):
     return {"dir": path, "arrays": len(out), "bytes": sum(a.nbytes for a in out.values()), "sampled": total > limit}
 
 
+def side_legs(args):
+    """What a run measures besides its headline: nothing unless `--full` asks for it, and then all that the `--no-*`
+    options do not leave out.  `eager`: the eagerly enqueued step next to the replayed one; `roofline`: the per-class event
+    pass, `stacks_alone` and `step_mfma_frac`; `extras`: the other precisions and configurations, the log-mel front end,
+    the data-parallel path in a world of one and the parity gates; `cpu_baseline`: the CPU oracle's step rates."""
+    return {"eager": args.full and not args.no_graph, "roofline": args.full and not args.no_roofline,
+            "extras": args.full and not args.no_extras, "cpu_baseline": args.full and not args.no_cpu_baseline}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -425,9 +440,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--trainer", default="vqvae", choices=["vqvae", "lsgan", "cyclegan", "stargan"])
     ap.add_argument("--batch", type=int, default=64, help="utterances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity-mode and configs[2] timings")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take every side measurement and check: the eager step, roofline, "
+                         "stacks alone, parity modes and gates, configs[2], log-mel, the forced data-parallel path, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's step rates")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-class event pass and stacks_alone")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the parity-mode and configs[2] timings, log-mel, the forced data-parallel path "
+                         "and the parity gates")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "bf16x3f", "bf16x3"],
                     help="arithmetic of the timed steps (default bf16, the headline; the others are what `parity_mode` reports)")
     ap.add_argument("--no-graph", action="store_true",
@@ -440,6 +460,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    legs = side_legs(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(respawn_under_torchrun(args.gpus))
@@ -524,7 +545,7 @@ def main():
     if vals is None:  # (--warmup 0)
         vals = last["vals"]
     dump = dump_outputs(args.dump_outputs, trainer, last["vals"]) if args.dump_outputs and rank == 0 else None
-    dt_eager = run(args.steps, replay=False) if graphed is not None else dt
+    dt_eager = dt if graphed is None else run(args.steps, replay=False) if legs["eager"] else None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if torch.distributed.get_backend() == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -550,7 +571,7 @@ def main():
         "launch": ("eager" if graphed is None else "hip graph replay (trainer.train_graphed)" if not dist_on else
                    "one hip graph, the RCCL collectives captured with the step" if len(graphed.segments) == 1 else
                    f"chain of {len(graphed.segments)} hip graphs with the host-issued collectives between them"),
-        "eager_ms_per_step": dt_eager / args.steps * 1e3,
+        "eager_ms_per_step": None if dt_eager is None else dt_eager / args.steps * 1e3,
         "world_size_seen": world,
         "dist_backend": torch.distributed.get_backend() if dist_on else None,
     }
@@ -559,7 +580,7 @@ def main():
     if dump is not None:
         out["dump_outputs"] = dump
 
-    if not args.no_roofline:
+    if legs["roofline"]:
         L = _lib.lib()
         # one stream for this pass: next to the classifier's update on its second stream (the timed step) a kernel's
         # begin-to-end time includes the time it shares compute units with that stream's kernels - the roofline prices
@@ -583,7 +604,7 @@ def main():
         if flop_per_frame:
             out["step_mfma_frac"] = (frames / dt) * flop_per_frame / (world * MFMA_BF16_PEAK_TFLOPS * 1e12)
 
-    if world == 1 and not args.no_extras and args.trainer == "vqvae":
+    if world == 1 and legs["extras"] and args.trainer == "vqvae":
         def timed(tr, k, w=3):
             for _ in range(w):
                 tr.train(batch)
@@ -650,7 +671,7 @@ def main():
                     "step_mfma_frac": B * T / tl * STEP_MFLOP["lsgan"] * 1e6 / (MFMA_BF16_PEAK_TFLOPS * 1e12),
                     "what": "configs[2]: VQ-VAE + residual D (dropout 0.25) + spkradv, GAN phase, "
                             f"{B} x {T} frames, 20 replayed steps"}
-            if not args.no_roofline:  # the same per-class event pass as the headline's, over 10 eager lsgan steps
+            if legs["roofline"]:  # the same per-class event pass as the headline's, over 10 eager lsgan steps
                 Lr = _lib.lib()
                 with config.override(overlap_c=0):
                     Lr.crk_prof_enable(1)
@@ -668,23 +689,23 @@ def main():
         except Exception as e:
             out["other_configs"] = {"error": repr(e)[:200]}
 
-    if rank == 0 and world == 1 and not args.no_extras and args.trainer == "vqvae":
+    if rank == 0 and world == 1 and legs["extras"] and args.trainer == "vqvae":
         try:  # north_star's "STFT / mel filterbank" kernel: off the benchmarked path (use_raw is false), timed by itself
             out["logmel_use_raw"] = logmel_alone(B, T, dev)
         except Exception as e:
             out["logmel_use_raw"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_extras and not args.force_dist and args.trainer == "vqvae":
+    if rank == 0 and world == 1 and legs["extras"] and not args.force_dist and args.trainer == "vqvae":
         out["dp_path_world_of_one"] = dp_path_world_of_one(args, out["ms_per_step"])
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and legs["extras"]:
         try:
             out["parity_gates"] = parity_gates(dev)
             g = out["parity_gates"].get(args.precision, {})
             out["mcd_vs_ref_dB"] = g.get("mcd_vs_ref_dB")  # the metric's "MCD vs ref" for the arithmetic that was timed
         except Exception as e:
             out["parity_gates"] = {"error": repr(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and legs["cpu_baseline"]:
         out["cpu_baseline"] = cpu_baseline(dict(trainer_type=args.trainer))
-        if args.trainer == "vqvae" and not args.no_extras and isinstance(out.get("other_configs", {}).get("lsgan"), dict):
+        if args.trainer == "vqvae" and legs["extras"] and isinstance(out.get("other_configs", {}).get("lsgan"), dict):
             try:  # configs[2] next to its own CPU number (bounded: ~8 s of host time)
                 torch.set_num_threads(min(16, os.cpu_count() or 1))
                 v3, s3 = _cpu_step_rate(dict(trainer_type="lsgan", n_steps_gan_start=0), 14, 64, 500, budget_s=6.0, max_steps=3)

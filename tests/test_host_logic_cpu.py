@@ -178,7 +178,7 @@ def test_lossvalues_resolve_lazily_and_behave_like_a_dict_of_floats():
 
 
 def test_committed_bench_line_follows_the_bench_contract():
-    """The newest profiles/round*_bench_line.json (what `python bench.py` printed on the MI355X box) carries every field
+    """The newest profiles/round*_bench_line.json (what `python bench.py --full` prints on the MI355X box) carries every field
     of the driver's contract, the metric of BASELINE.json's first clause, a roofline object whose fraction is
     achieved / peak, and a CPU baseline that says what was timed."""
     import glob
@@ -206,6 +206,26 @@ def test_committed_bench_line_follows_the_bench_contract():
     assert r["traffic"] is None or r["traffic"] > 0
     c = d["cpu_baseline"]
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == d["unit"] and c["sample"]
+
+
+def test_bench_takes_its_side_measurements_under_full_only():
+    """`bench.py` without `--full` measures its headline alone, whatever `--no-*` options come with it; `--full` turns every
+    side measurement on, and each `--no-*` option (`--no-graph` for the eager step, which is then the headline itself)
+    takes out its own and no other."""
+    import argparse
+
+    import bench
+
+    def legs(**over):
+        return bench.side_legs(argparse.Namespace(**dict(dict(full=False, no_graph=False, no_roofline=False, no_extras=False,
+                                                                no_cpu_baseline=False), **over)))
+
+    assert set(legs()) == {"eager", "roofline", "extras", "cpu_baseline"}
+    assert not any(legs().values())
+    assert not any(legs(no_roofline=True, no_extras=True, no_cpu_baseline=True, no_graph=True).values())
+    assert all(legs(full=True).values())
+    for flag, leg in (("no_graph", "eager"), ("no_roofline", "roofline"), ("no_extras", "extras"), ("no_cpu_baseline", "cpu_baseline")):
+        assert legs(full=True, **{flag: True}) == dict(legs(full=True), **{leg: False}), flag
 
 
 def test_vq_search_key_bounds_cover_what_seven_replaced_mantissa_bits_can_do():
