@@ -14,6 +14,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import check, ptr, stream_ptr
+from crank_amd._ragged import offsets
 
 
 def mcd_fastdtw(cv_mceps, cv_f0s, gt_mceps, gt_f0s, radius=1, return_paths=False, device="cuda"):
@@ -35,8 +36,7 @@ def mcd_fastdtw(cv_mceps, cv_f0s, gt_mceps, gt_f0s, radius=1, return_paths=False
     nx, ny = [a.shape[0] for a in cv], [a.shape[0] for a in gt]
     dev = torch.device(device)
     up = lambda arrs: torch.as_tensor(np.concatenate(arrs), device=dev)  # noqa: E731
-    off = lambda ns: torch.as_tensor(np.concatenate([[0], np.cumsum(ns)]).astype(np.int64), device=dev)  # noqa: E731
-    x, y, xo, yo = up(cv), up(gt), off(nx), off(ny)
+    x, y, xo, yo = up(cv), up(gt), offsets(nx, dev), offsets(ny, dev)
     L = _lib.lib()
     mx, my = max(nx), max(ny)
     nbytes = L.crk_mcd_scratch_bytes(P, mx, my, D, radius)

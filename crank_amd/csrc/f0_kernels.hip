@@ -25,12 +25,8 @@
 //  * f0_contour_kernel    one wave per utterance: sequential along frames, the lanes share every scan.
 //  * f0_subsample_kernel, f0_continuous_kernel.
 // No atomics anywhere; every sum has a fixed order, so two calls give the same bits and a batch equals its rows alone.
-#include "common.h"
 #include "../../include/crank_hip.h"
-#include "world_fft.h"
-#include <math.h>
-#include <stdint.h>
-#include <vector>
+#include "signal_common.h"
 
 #define F0_U 12
 #define F0_MAX_CH 192
@@ -44,8 +40,6 @@
 #define F0_SPAD 300
 enum { U_S0, U_N, U_D0, U_ND, U_T0, U_T1, U_C0, U_NCH, U_R0, U_O0, U_TO };
 
-long long crk_count_alloc_(void);
-
 struct F0Coef { double b[4], a[4]; };
 
 struct F0 {
@@ -56,15 +50,6 @@ struct F0 {
   double* events;
   long long events_len;
 };
-
-__device__ __forceinline__ int f0_find(const long long* utt, int n, int col, long long v) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (utt[(size_t)mid * F0_U + col] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // ---------------------------------------------------------------------------------------------------------- decimation
 __device__ __forceinline__ void f0_iir3_chunk(double* buf, int len, const F0Coef& cb, double* st) {
@@ -277,7 +262,7 @@ __global__ __launch_bounds__(F0_MAX_CH) void f0_raw_kernel(const double* __restr
 #pragma clang fp contract(off)
   __shared__ double col[F0_MAX_CH];
   const long long fg = blockIdx.x;
-  const int u = f0_find(utt, n_utts, U_T0, fg), c = threadIdx.x;
+  const int u = w_find(utt + U_T0, n_utts, fg, F0_U), c = threadIdx.x;
   const long long* d = utt + (size_t)u * F0_U;
   const long long i = fg - d[U_T0], T1 = d[U_T1];
   const int n_ch = (int)min((long long)F0_MAX_CH, d[U_NCH]);
@@ -321,7 +306,7 @@ __global__ __launch_bounds__(W_THREADS) void f0_official_kernel(const double* __
                                                                 double* __restrict__ official) {
   const long long fg = (long long)blockIdx.x * W_THREADS + threadIdx.x;
   if (fg >= F) return;
-  const int u = f0_find(utt, n_utts, U_T0, fg);
+  const int u = w_find(utt + U_T0, n_utts, fg, F0_U);
   const long long* d = utt + (size_t)u * F0_U;
   f0_runs(raw + d[U_R0] + (fg - d[U_T0]), d[U_T1], (int)min((long long)F0_MAX_CH, d[U_NCH]), official + fg * F0_NC);
 }
@@ -333,7 +318,7 @@ __global__ __launch_bounds__(W_THREADS) void f0_overlap_kernel(const double* __r
   if (g >= F * F0_NS) return;
   const long long fg = g / F0_NS;
   const int slot = (int)(g - fg * F0_NS), b = slot / F0_NC, j = slot - b * F0_NC;
-  const int u = f0_find(utt, n_utts, U_T0, fg);
+  const int u = w_find(utt + U_T0, n_utts, fg, F0_U);
   const long long t0 = utt[(size_t)u * F0_U + U_T0], T1 = utt[(size_t)u * F0_U + U_T1];
   const long long src = fg - t0 + (b == 0 ? 0 : (b <= 3 ? -b : b - 3));
   cands[g] = (src >= 0 && src < T1) ? official[(t0 + src) * F0_NC + j] : 0.0;
@@ -347,7 +332,7 @@ __global__ __launch_bounds__(64) void f0_refine_kernel(const double* __restrict_
                                                        double* __restrict__ scores) {
 #pragma clang fp contract(off)
   const long long fg = blockIdx.x;
-  const int u = f0_find(utt, n_utts, U_T0, fg), lane = threadIdx.x;
+  const int u = w_find(utt + U_T0, n_utts, fg, F0_U), lane = threadIdx.x;
   const long long* d = utt + (size_t)u * F0_U;
   const double* xs = x + d[U_S0];
   const long long n_s = d[U_N];
@@ -431,7 +416,7 @@ __global__ __launch_bounds__(W_THREADS) void f0_reliable_kernel(const double* __
   const long long fg = g / F0_NS;
   double f = cands[g], sc = scores[g];
   if (f != 0.0) {
-    const int u = f0_find(utt, n_utts, U_T0, fg);
+    const int u = w_find(utt + U_T0, n_utts, fg, F0_U);
     const long long i = fg - utt[(size_t)u * F0_U + U_T0], T1 = utt[(size_t)u * F0_U + U_T1];
     if (i >= 1 && i <= T1 - 2) {
       double e = 1.0e300;
@@ -629,7 +614,7 @@ __global__ __launch_bounds__(W_THREADS) void f0_subsample_kernel(const double* _
                                                                  long long total_out, double* __restrict__ f0) {
   const long long g = (long long)blockIdx.x * W_THREADS + threadIdx.x;
   if (g >= total_out) return;
-  const int u = f0_find(utt, n_utts, U_O0, g);
+  const int u = w_find(utt + U_O0, n_utts, g, F0_U);
   const long long* d = utt + (size_t)u * F0_U;
   f0[g] = f1[d[U_T0] + min((g - d[U_O0]) * shift, d[U_T1] - 1)];
 }
@@ -693,18 +678,9 @@ extern "C" void* crk_f0_create(int fs, int shiftms, const double* cheby) {
   h->r = (int)fmin(12.0, fmax(1.0, floor(fs / 8000.0 + 0.5)));
   h->fs_d = (double)fs / h->r;
   for (int i = 0; i < 4; ++i) { h->cb.b[i] = cheby[i]; h->cb.a[i] = cheby[4 + i]; }
-  std::vector<double> host(2 * F0_NTW);
-  for (int m = 0; m < F0_NTW; ++m) {
-    host[m] = cos(2.0 * M_PI * m / F0_NTW);
-    host[F0_NTW + m] = sin(2.0 * M_PI * m / F0_NTW);
-  }
-  if (hipMalloc(&h->tw, host.size() * sizeof(double)) != hipSuccess) {
-    delete h;
-    return nullptr;
-  }
-  crk_count_alloc_();
-  if (hipMemcpy(h->tw, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(h->tw);
+  WTables tb;
+  tb.add_twiddles(F0_NTW, F0_NTW);  // the full circle
+  if (!tb.upload(&h->tw)) {
     delete h;
     return nullptr;
   }
@@ -723,13 +699,7 @@ extern "C" int crk_f0_reserve(void* p, long long total_events) {
   F0* h = (F0*)p;
   if (!h || total_events < 1 || total_events > (1LL << 36)) return CRK_ERR_ARG;
   if (total_events <= h->events_len) return CRK_OK;
-  double* d = nullptr;
-  if (hipMalloc(&d, (size_t)total_events * sizeof(double)) != hipSuccess) return CRK_ERR_HIP;
-  crk_count_alloc_();
-  if (h->events) (void)hipFree(h->events);
-  h->events = d;
-  h->events_len = total_events;
-  return CRK_OK;
+  return w_grow_table(&h->events, &h->events_len, total_events, nullptr);  // the kernels fill it
 }
 
 struct F0Ws {
@@ -740,26 +710,24 @@ struct F0Ws {
 
 static F0Ws f0_ws(int n_utts, long long S, long long F, long long C, unsigned char* base) {
   F0Ws r;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += w_align(bytes); return p; };
-  const size_t D = sizeof(double);
-  r.tmp = (double*)take((size_t)(S + 2LL * F0_PAD * n_utts) * D);
-  r.yd = (double*)take((size_t)S * D);
-  r.official = (double*)take((size_t)F * F0_NC * D);
-  r.ta = (double*)take((size_t)F * F0_NS * D);
-  r.tb = (double*)take((size_t)F * F0_NS * D);
-  r.tc = (double*)take((size_t)F * F0_NS * D);
-  r.td = (double*)take((size_t)F * F0_NS * D);
-  r.te = (double*)take((size_t)F * F0_NS * D);
-  r.base = (double*)take((size_t)F * D);
-  r.step = (double*)take((size_t)F * D);
-  r.ext = (double*)take((size_t)F * D);
-  r.merged = (double*)take((size_t)F * D);
-  r.f1 = (double*)take((size_t)F * D);
-  r.pad = (double*)take((size_t)n_utts * 64 * F0_SPAD * D);
-  r.bl = (int*)take((size_t)(F + 2LL * n_utts) * sizeof(int));
-  r.counts = (int*)take((size_t)C * 4 * sizeof(int));
-  r.bytes = o;
+  WCarve c{base};
+  r.tmp = c.take<double>((size_t)(S + 2LL * F0_PAD * n_utts));
+  r.yd = c.take<double>((size_t)S);
+  r.official = c.take<double>((size_t)F * F0_NC);
+  r.ta = c.take<double>((size_t)F * F0_NS);
+  r.tb = c.take<double>((size_t)F * F0_NS);
+  r.tc = c.take<double>((size_t)F * F0_NS);
+  r.td = c.take<double>((size_t)F * F0_NS);
+  r.te = c.take<double>((size_t)F * F0_NS);
+  r.base = c.take<double>((size_t)F);
+  r.step = c.take<double>((size_t)F);
+  r.ext = c.take<double>((size_t)F);
+  r.merged = c.take<double>((size_t)F);
+  r.f1 = c.take<double>((size_t)F);
+  r.pad = c.take<double>((size_t)n_utts * 64 * F0_SPAD);
+  r.bl = c.take<int>((size_t)(F + 2LL * n_utts));
+  r.counts = c.take<int>((size_t)C * 4);
+  r.bytes = c.bytes;
   return r;
 }
 
@@ -780,9 +748,10 @@ extern "C" int crk_f0_decimate(void* p, const double* x, const long long* utt, i
                                double* yd, void* workspace, long long workspace_bytes, void* stream) {
   F0* h = (F0*)p;
   if (!h || !x || !utt || !yd || !workspace || n_utts < 1 || total_samples < 1) return CRK_ERR_ARG;
-  const size_t need = w_align((size_t)(total_samples + 2LL * F0_PAD * n_utts) * sizeof(double));
-  if (workspace_bytes < (long long)need) return CRK_ERR_ARG;
-  f0_decimate_kernel<<<dim3(n_utts), dim3(W_THREADS), 0, (hipStream_t)stream>>>(x, utt, h->r, h->cb, (double*)workspace, yd);
+  WCarve c{(unsigned char*)workspace};
+  double* tmp = c.take<double>((size_t)(total_samples + 2LL * F0_PAD * n_utts));
+  if (workspace_bytes < (long long)c.bytes) return CRK_ERR_ARG;
+  f0_decimate_kernel<<<dim3(n_utts), dim3(W_THREADS), 0, (hipStream_t)stream>>>(x, utt, h->r, h->cb, tmp, yd);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -808,17 +777,20 @@ extern "C" int crk_f0_raw_candidates(void* p, const double* yd, const long long*
   if (!h || !yd || !utt || !range || !chan_bf || !chan || !raw || !status || !workspace ||
       !f0_shape_ok(n_utts, 1, total_frames, total_channels))
     return CRK_ERR_ARG;
-  if (workspace_bytes < (long long)w_align((size_t)total_channels * 4 * sizeof(int))) return CRK_ERR_ARG;
+  WCarve c{(unsigned char*)workspace};
+  int* counts = c.take<int>((size_t)total_channels * 4);
+  if (workspace_bytes < (long long)c.bytes) return CRK_ERR_ARG;
   return f0_raw(h, yd, utt, range, chan_bf, chan, n_utts, total_channels, total_frames, total_events, raw, nullptr,
-                (int*)workspace, status, (hipStream_t)stream);
+                counts, status, (hipStream_t)stream);
 }
 
 extern "C" int crk_f0_candidates(void* p, const double* raw, const long long* utt, int n_utts, long long total_frames,
                                  double* cands, void* workspace, long long workspace_bytes, void* stream) {
   F0* h = (F0*)p;
   if (!h || !raw || !utt || !cands || !workspace || !f0_shape_ok(n_utts, 1, total_frames, 1)) return CRK_ERR_ARG;
-  if (workspace_bytes < (long long)w_align((size_t)total_frames * F0_NC * sizeof(double))) return CRK_ERR_ARG;
-  double* official = (double*)workspace;
+  WCarve c{(unsigned char*)workspace};
+  double* official = c.take<double>((size_t)total_frames * F0_NC);
+  if (workspace_bytes < (long long)c.bytes) return CRK_ERR_ARG;
   f0_official_kernel<<<dim3(f0_blocks(total_frames)), dim3(W_THREADS), 0, (hipStream_t)stream>>>(raw, utt, n_utts,
                                                                                                total_frames, official);
   CRK_CHECK_LAUNCH();

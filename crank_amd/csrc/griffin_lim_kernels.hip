@@ -5,7 +5,7 @@
 // librosa.griffinlim with momentum 0.99, centred reflect-padded STFT, periodic Hann window).  The oracle is the CPU
 // restatement tests/griffin_lim_ref.py; parity with librosa is unpinned.  Structure:
 //  * gl_linear_kernel: one workgroup per frame: 10^mlfb in LDS, then |sum_m 10^mlfb[m] P[k][m]| per bin, ascending m.
-//  * gl_frame_kernel<MODE>: one workgroup per frame, the 1024-point fp64 LDS FFT of world_fft.h.
+//  * gl_frame_kernel<MODE>: one workgroup per frame, the 1024-point fp64 LDS FFT of signal_common.h.
 //      GL_INIT    S * angles0 -> inverse FFT -> windowed frame.
 //      GL_ITER    gather the padded frame from the previous iteration's windowed frames (overlap-add in ascending frame
 //                 order, divided by the window-sum-square envelope, reflected at the two ends), window, FFT, read tprev and
@@ -16,19 +16,14 @@
 //  * gl_ola_kernel: one thread per output sample: the same overlap-add, envelope division, trim and the clip.
 // n_iter + 2 launches per call.  No atomics; a frame reads only its own utterance, so an utterance's bits do not depend on
 // the batch around it.
-#include "common.h"
 #include "../../include/crank_hip.h"
-#include "world_fft.h"
-#include <math.h>
-#include <vector>
+#include "signal_common.h"
 
 #define GL_MAX_MELS 256
 #define GL_CLIP_HI 0.999969482421875  // 1 - 2^-15: the reference's upper clip
 #define GL_TINY 2.2250738585072014e-308  // the smallest normal float64: below it the envelope does not divide
 #define GL_MOMENTUM 0.99
 #define GL_PHASE_EPS 1e-16
-
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 struct Gl {
   int fs, win, hop, n_mels;
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(W_THREADS) void gl_frame_kernel(GlArgs a) {
   const long long f = blockIdx.x;
   const int u = w_find(a.foff, a.n_utts, f);
   const long long F0 = a.foff[u], T = a.foff[u + 1] - F0, t = f - F0;
-  for (int m = tid; m < W_N / 2; m += W_THREADS) { tc[m] = a.twc[m]; ts[m] = a.tws[m]; }
+  w_stage_twiddles(tc, ts, a.twc, a.tws);
   double2 sp[3];  // the spectrum to invert at bins tid, tid + 256 and (thread 0) 512
 #pragma unroll
   for (int r = 0; r < 3; ++r) sp[r] = make_double2(0.0, 0.0);
@@ -195,35 +190,27 @@ extern "C" int crk_gl_create(int fs, int n_fft, int win_length, int hop, int n_m
   if (!pinv_basis || fs < 1) return CRK_ERR_ARG;
   if (n_fft != W_N || win_length < 1 || win_length > W_N || hop < 1 || hop > W_N || n_mels < 1 || n_mels > GL_MAX_MELS)
     return CRK_ERR_UNSUPPORTED;
-  std::vector<double> host;
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(cos(2.0 * M_PI * m / W_N));
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(sin(2.0 * M_PI * m / W_N));
   // the periodic Hann window of win_length, zero-padded symmetrically to W_N
-  std::vector<double> w(W_N, 0.0);
+  std::vector<double> w(W_N, 0.0), wsq(W_N), pt;
   const int lpad = (W_N - win_length) / 2;
   for (int i = 0; i < win_length; ++i) w[lpad + i] = 0.5 - 0.5 * cos(2.0 * M_PI * i / win_length);
-  host.insert(host.end(), w.begin(), w.end());
-  for (int i = 0; i < W_N; ++i) host.push_back(w[i] * w[i]);
+  for (int i = 0; i < W_N; ++i) wsq[i] = w[i] * w[i];
   for (int m = 0; m < n_mels; ++m)
-    for (int k = 0; k < W_K; ++k) host.push_back(pinv_basis[(size_t)k * n_mels + m]);
+    for (int k = 0; k < W_K; ++k) pt.push_back(pinv_basis[(size_t)k * n_mels + m]);
+  WTables tb;
+  const size_t o_tw = tb.add_twiddles(W_N, W_N / 2), o_w = tb.add(w), o_wsq = tb.add(wsq), o_pt = tb.add(pt);
   Gl* g = new Gl();
   g->fs = fs; g->win = win_length; g->hop = hop; g->n_mels = n_mels;
   g->coef = GL_MOMENTUM / (1.0 + GL_MOMENTUM);
-  if (hipMalloc(&g->tables, host.size() * sizeof(double)) != hipSuccess) {
+  if (!tb.upload(&g->tables)) {
     delete g;
     return CRK_ERR_HIP;
   }
-  crk_count_alloc_();
-  if (hipMemcpy(g->tables, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(g->tables);
-    delete g;
-    return CRK_ERR_HIP;
-  }
-  g->twc = g->tables;
+  g->twc = g->tables + o_tw;
   g->tws = g->twc + W_N / 2;
-  g->window = g->tws + W_N / 2;
-  g->wsq = g->window + W_N;
-  g->pt = g->wsq + W_N;
+  g->window = g->tables + o_w;
+  g->wsq = g->tables + o_wsq;
+  g->pt = g->tables + o_pt;
   *handle = g;
   return CRK_OK;
 }
@@ -242,12 +229,11 @@ struct GlWs {
 
 static GlWs gl_ws(long long F, unsigned char* base) {
   GlWs r;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += w_align(bytes); return p; };
-  r.fa = (double*)take((size_t)F * W_N * sizeof(double));
-  r.fb = (double*)take((size_t)F * W_N * sizeof(double));
-  r.R = (double2*)take((size_t)F * W_K * sizeof(double2));
-  r.bytes = o;
+  WCarve c{base};
+  r.fa = c.take<double>((size_t)F * W_N);
+  r.fb = c.take<double>((size_t)F * W_N);
+  r.R = c.take<double2>((size_t)F * W_K);
+  r.bytes = c.bytes;
   return r;
 }
 

@@ -11,18 +11,14 @@
 //    sum of the frames' randn draw counts (2 * half + 1 window draws, then 513).
 //  * wana_cheaptrick_kernel: one workgroup per frame.  Window with its three reductions, FFT, power, DC correction,
 //    the mirrored cumulative spectrum (summed by one thread in the restatement's order), the two band-edge reads per bin, log, FFT of the even log
-//    spectrum, lifter, FFT, exp: three 1024-point fp64 LDS FFTs (world_fft.h) per frame.  Writes sp and / or the
+//    spectrum, lifter, FFT, exp: three 1024-point fp64 LDS FFTs (signal_common.h) per frame.  Writes sp and / or the
 //    liftered cepstrum.  No atomics: a frame's result does not depend on the batch around it.
 //  * wana_mcep_kernel: one wave per frame: mcep = A c, A the (order + 1) x 513 freqt matrix folded over the even
 //    cepstrum (c0 / 2 included), made once per handle.  c is the liftered cepstrum of the last CheapTrick stage, which
 //    is irfft(log sp) up to the rounding of exp and log.
 //  * wana_power_kernel / wana_npow_kernel: per-frame power by one wave, then the utterance's mean in a fixed order.
-#include "common.h"
 #include "../../include/crank_hip.h"
-#include "world_fft.h"
-#include <math.h>
-#include <stdint.h>
-#include <vector>
+#include "signal_common.h"
 
 #define WA_MAX_ORDER1 128
 #define WA_MAX_TAPS 256
@@ -32,8 +28,6 @@
 #define WA_EPS 2.220446049250313e-16
 #define WA_NOISE 1e-12
 #define WA_Q1 (-0.15)
-
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 struct Wana {
   int fs, m1;
@@ -166,7 +160,7 @@ __global__ __launch_bounds__(W_THREADS) void wana_cheaptrick_kernel(WaFrame a) {
   const double fsd = (double)a.fs, cur = sh.cur;
   const int half = sh.half, n = 2 * half + 1;
 
-  for (int m = tid; m < W_N / 2; m += W_THREADS) { tc[m] = a.twc[m]; ts[m] = a.tws[m]; }
+  w_stage_twiddles(tc, ts, a.twc, a.tws);
   // the F0-adaptive window, unit energy
   double e = 0.0;
   for (int j = tid; j < n; j += W_THREADS) {
@@ -351,16 +345,9 @@ __global__ __launch_bounds__(W_THREADS) void wana_npow_kernel(const double* __re
 // matrix on c[0 .. N/2]: column k carries freqt(e_k) + freqt(e_{N-k}) for 0 < k < N/2 and freqt(e_0) / 2 for k = 0.
 static void wa_freqt_matrix(int m1, double alpha, std::vector<double>& at) {
   at.assign((size_t)m1 * W_K, 0.0);
-  const double b = 1.0 - alpha * alpha;
-  std::vector<double> g(m1 + 1), d(m1 + 1);
+  std::vector<double> g, d;
   for (int col = 0; col < W_N; ++col) {
-    std::fill(g.begin(), g.end(), 0.0);
-    for (int i = col; i >= 0; --i) {  // the input is zero above `col`: freqt's state is still zero there
-      d = g;
-      g[0] = (i == col ? 1.0 : 0.0) + alpha * d[0];
-      if (m1 > 1) g[1] = b * d[0] + alpha * d[1];
-      for (int m = 2; m < m1; ++m) g[m] = d[m - 1] + alpha * (d[m] - g[m - 1]);
-    }
+    w_freqt_unit(col, col, m1, alpha, g, d);  // the input is zero above `col`
     const int k = col <= W_N / 2 ? col : W_N - col;
     const double scale = col == 0 ? 0.5 : 1.0;
     for (int m = 0; m < m1; ++m) at[(size_t)m * W_K + k] += scale * g[m];
@@ -373,24 +360,17 @@ extern "C" void* crk_wana_create(int fs, int fftl, double shiftms, double alpha,
     return nullptr;
   Wana* w = new Wana();
   w->fs = fs; w->m1 = order1; w->shiftms = shiftms; w->alpha = alpha;
-  std::vector<double> host, at;
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(cos(2.0 * M_PI * m / W_N));
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(sin(2.0 * M_PI * m / W_N));
+  std::vector<double> at;
   wa_freqt_matrix(order1, alpha, at);
-  host.insert(host.end(), at.begin(), at.end());
-  if (hipMalloc(&w->tables, host.size() * sizeof(double)) != hipSuccess) {
+  WTables tb;
+  const size_t o_tw = tb.add_twiddles(W_N, W_N / 2), o_at = tb.add(at);
+  if (!tb.upload(&w->tables)) {
     delete w;
     return nullptr;
   }
-  crk_count_alloc_();
-  if (hipMemcpy(w->tables, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(w->tables);
-    delete w;
-    return nullptr;
-  }
-  w->twc = w->tables;
+  w->twc = w->tables + o_tw;
   w->tws = w->twc + W_N / 2;
-  w->at = w->tws + W_N / 2;
+  w->at = w->tables + o_at;
   return w;
 }
 
@@ -407,29 +387,9 @@ extern "C" int crk_wana_reserve(void* h, long long max_draws) {
   Wana* w = (Wana*)h;
   if (!w || max_draws < 1 || max_draws > (1LL << 31)) return CRK_ERR_ARG;
   if (max_draws <= w->noise_len) return CRK_OK;
-  std::vector<double> v(max_draws);
-  uint32_t x = 123456789u, y = 362436069u, z = 521288629u, ww = 88675123u;
-  for (long long i = 0; i < max_draws; ++i) {
-    uint32_t acc = 0;
-    for (int r = 0; r < 12; ++r) {
-      const uint32_t t = x ^ (x << 11);
-      x = y; y = z; z = ww;
-      ww = (ww ^ (ww >> 19)) ^ (t ^ (t >> 8));
-      acc += ww >> 4;
-    }
-    v[i] = acc / 268435456.0 - 6.0;
-  }
-  double* d = nullptr;
-  if (hipMalloc(&d, max_draws * sizeof(double)) != hipSuccess) return CRK_ERR_HIP;
-  crk_count_alloc_();
-  if (hipMemcpy(d, v.data(), max_draws * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return CRK_ERR_HIP;
-  }
-  if (w->noise) (void)hipFree(w->noise);
-  w->noise = d;
-  w->noise_len = max_draws;
-  return CRK_OK;
+  std::vector<double> v;
+  w_randn_table(max_draws, v);
+  return w_grow_table(&w->noise, &w->noise_len, max_draws, v.data());
 }
 
 struct WaWs {
@@ -439,12 +399,11 @@ struct WaWs {
 
 static WaWs wa_ws(long long F, unsigned char* base) {
   WaWs r;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += w_align(bytes); return p; };
-  r.doff = (long long*)take((size_t)F * sizeof(long long));
-  r.cep = (double*)take((size_t)F * W_K * sizeof(double));
-  r.p = (double*)take((size_t)F * sizeof(double));
-  r.bytes = o;
+  WCarve c{base};
+  r.doff = c.take<long long>((size_t)F);
+  r.cep = c.take<double>((size_t)F * W_K);
+  r.p = c.take<double>((size_t)F);
+  r.bytes = c.bytes;
   return r;
 }
 

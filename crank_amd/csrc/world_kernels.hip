@@ -15,21 +15,15 @@
 //    both inverse transforms in four 1024-point fp64 LDS FFTs (two real sequences per complex transform); writes the
 //    pulse's response.
 //  * world_ola_kernel: one thread per output sample sums the responses that cover it, in pulse order (no atomics).
-#include "common.h"
 #include "../../include/crank_hip.h"
-#include "world_fft.h"
-#include <math.h>
+#include "signal_common.h"
 #include <string.h>
-#include <algorithm>
-#include <vector>
 
 #define W_IRLEN 1024
 #define W_MAX_ORDER1 128
 #define W_CHUNK 2048
 #define W_SAFE 1e-12
 #define W_DEFAULT_F0 500.0
-
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 struct World {
   int fs, m1, bands, capacity;
@@ -281,7 +275,7 @@ __global__ __launch_bounds__(W_THREADS) void world_pulse_kernel(WPulse a) {
   const int T = (int)(a.foff[u + 1] - F0);
   double* out = a.resp + (size_t)blockIdx.x * W_N;
 
-  for (int m = tid; m < W_N / 2; m += W_THREADS) { tc[m] = a.twc[m]; ts[m] = a.tws[m]; }
+  w_stage_twiddles(tc, ts, a.twc, a.tws);
   // envelope and aperiodic ratio at t = s / fs (WORLD GetSpectralEnvelope / GetAperiodicRatio)
   const double q = (double)s / (double)a.fs / a.fp;
   const int lo = min(T - 1, (int)floor(q)), hi = min(T - 1, (int)ceil(q));
@@ -417,16 +411,9 @@ __global__ void world_ola_kernel(const long long* __restrict__ soff, const long 
 // freqt(., N/2, -alpha) too: g_m does not depend on the order)
 static void w_freqt_matrix(int m1, double alpha, std::vector<double>& at) {
   at.assign((size_t)m1 * W_IRLEN, 0.0);
-  const double a = -alpha, b = 1.0 - a * a;
-  std::vector<double> g(W_IRLEN + 1), d(W_IRLEN + 1);
+  std::vector<double> g, d;
   for (int col = 0; col < m1; ++col) {
-    std::fill(g.begin(), g.end(), 0.0);
-    for (int i = m1 - 1; i >= 0; --i) {
-      d = g;
-      g[0] = (i == col ? 1.0 : 0.0) + a * d[0];
-      g[1] = b * d[0] + a * d[1];
-      for (int m = 2; m <= W_IRLEN; ++m) g[m] = d[m - 1] + a * (d[m] - g[m - 1]);
-    }
+    w_freqt_unit(col, m1 - 1, W_IRLEN + 1, -alpha, g, d);
     for (int n = 0; n < W_IRLEN; ++n) at[(size_t)col * W_IRLEN + n] = g[n];
   }
 }
@@ -464,27 +451,17 @@ extern "C" void* crk_world_create(int fs, int fftl, double shiftms, double alpha
     dcw[i] /= dc;
     dcw[W_N - i - 1] = dcw[i];
   }
-  std::vector<double> host;
-  host.insert(host.end(), at.begin(), at.end());
-  host.insert(host.end(), wt.begin(), wt.end());
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(cos(2.0 * M_PI * m / W_N));
-  for (int m = 0; m < W_N / 2; ++m) host.push_back(sin(2.0 * M_PI * m / W_N));
-  host.insert(host.end(), dcw.begin(), dcw.end());
-  if (hipMalloc(&w->tables, host.size() * sizeof(double)) != hipSuccess) {
+  WTables tb;
+  const size_t o_at = tb.add(at), o_wt = tb.add(wt), o_tw = tb.add_twiddles(W_N, W_N / 2), o_dc = tb.add(dcw);
+  if (!tb.upload(&w->tables)) {
     delete w;
     return nullptr;
   }
-  crk_count_alloc_();
-  if (hipMemcpy(w->tables, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(w->tables);
-    delete w;
-    return nullptr;
-  }
-  w->at = w->tables;
-  w->wt = w->at + at.size();
-  w->twc = w->wt + wt.size();
+  w->at = w->tables + o_at;
+  w->wt = w->tables + o_wt;
+  w->twc = w->tables + o_tw;
   w->tws = w->twc + W_N / 2;
-  w->dcw = w->tws + W_N / 2;
+  w->dcw = w->tables + o_dc;
   return w;
 }
 
@@ -501,29 +478,9 @@ extern "C" int crk_world_reserve(void* h, long long max_samples) {
   World* w = (World*)h;
   if (!w || max_samples < 1 || max_samples > (1LL << 31)) return CRK_ERR_ARG;
   if (max_samples <= w->noise_len) return CRK_OK;
-  std::vector<double> v(max_samples);
-  uint32_t x = 123456789u, y = 362436069u, z = 521288629u, ww = 88675123u;
-  for (long long i = 0; i < max_samples; ++i) {
-    uint32_t acc = 0;
-    for (int r = 0; r < 12; ++r) {
-      const uint32_t t = x ^ (x << 11);
-      x = y; y = z; z = ww;
-      ww = (ww ^ (ww >> 19)) ^ (t ^ (t >> 8));
-      acc += ww >> 4;
-    }
-    v[i] = acc / 268435456.0 - 6.0;
-  }
-  double* d = nullptr;
-  if (hipMalloc(&d, max_samples * sizeof(double)) != hipSuccess) return CRK_ERR_HIP;
-  crk_count_alloc_();
-  if (hipMemcpy(d, v.data(), max_samples * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return CRK_ERR_HIP;
-  }
-  if (w->noise) (void)hipFree(w->noise);
-  w->noise = d;
-  w->noise_len = max_samples;
-  return CRK_OK;
+  std::vector<double> v;
+  w_randn_table(max_samples, v);
+  return w_grow_table(&w->noise, &w->noise_len, max_samples, v.data());
 }
 
 struct WWs {
@@ -534,18 +491,17 @@ struct WWs {
 
 static WWs w_ws(const World* w, int n_utts, long long F, long long S, unsigned char* base) {
   WWs r;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += w_align(bytes); return p; };
-  r.e = (double*)take((size_t)F * 2 * sizeof(double));
-  r.sp = (double*)take((size_t)F * W_K * sizeof(double));
-  r.ap = (double*)take((size_t)F * W_K * sizeof(double));
-  r.ppos = (int*)take((size_t)S * sizeof(int));
-  r.pshift = (double*)take((size_t)S * sizeof(double));
-  r.pvuv = (unsigned char*)take((size_t)S);
-  r.pcount = (long long*)take((size_t)n_utts * sizeof(long long));
-  r.poff = (long long*)take((size_t)(n_utts + 1) * sizeof(long long));
-  r.resp = (double*)take((size_t)w->capacity * W_N * sizeof(double));
-  r.bytes = o;
+  WCarve c{base};
+  r.e = c.take<double>((size_t)F * 2);
+  r.sp = c.take<double>((size_t)F * W_K);
+  r.ap = c.take<double>((size_t)F * W_K);
+  r.ppos = c.take<int>((size_t)S);
+  r.pshift = c.take<double>((size_t)S);
+  r.pvuv = c.take<unsigned char>((size_t)S);
+  r.pcount = c.take<long long>((size_t)n_utts);
+  r.poff = c.take<long long>((size_t)(n_utts + 1));
+  r.resp = c.take<double>((size_t)w->capacity * W_N);
+  r.bytes = c.bytes;
   return r;
 }
 
@@ -583,8 +539,10 @@ extern "C" int crk_world_frames(void* h, const double* mcep, const double* rmcep
   World* w = (World*)h;
   if (!w || !mcep || !cap || !sp || !ap || total_frames < 1 || !workspace) return CRK_ERR_ARG;
   if (order1 != w->m1 || bands != w->bands) return CRK_ERR_UNSUPPORTED;
-  if (workspace_bytes < (long long)w_align((size_t)total_frames * 2 * sizeof(double))) return CRK_ERR_ARG;
-  return w_frames(w, mcep, rmcep, cap, total_frames, (double*)workspace, sp, ap, (hipStream_t)stream);
+  WCarve c{(unsigned char*)workspace};
+  double* e = c.take<double>((size_t)total_frames * 2);
+  if (workspace_bytes < (long long)c.bytes) return CRK_ERR_ARG;
+  return w_frames(w, mcep, rmcep, cap, total_frames, e, sp, ap, (hipStream_t)stream);
 }
 
 extern "C" int crk_world_pulses(void* h, const double* f0, const long long* frame_offsets, const long long* sample_offsets,

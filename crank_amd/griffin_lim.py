@@ -27,6 +27,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import check, stream_ptr
+from crank_amd._ragged import Workspace, f64, offsets, release, require_gpu, size_of
 
 FFTL = 1024  # the only fftl the kernels implement (every recipe uses it)
 K = FFTL // 2 + 1
@@ -71,14 +72,10 @@ class GriffinLim:
         self.min_frames = FFTL // 2 // self.hop + 2  # the fewest frames with hop * (T - 1) > fftl / 2
         self._pinv = None
         self._handle = None
-        self._ws = None
+        self._workspace = Workspace(self.device)
 
     def __del__(self):
-        try:
-            if self._handle:
-                _lib.lib().crk_gl_destroy(self._handle)
-        except Exception:
-            pass
+        release(self, "_handle", "crk_gl_destroy")
 
     # -- host tables
     def pinv_basis(self):
@@ -102,8 +99,7 @@ class GriffinLim:
         return self._handle
 
     def _on_device(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("Griffin-Lim runs in the HIP kernels: the synthesizer's device must be the GPU")
+        require_gpu(self.device, "Griffin-Lim", "the synthesizer's device")
 
     def samples(self, frames):
         """Samples of an utterance of `frames` frames: librosa's istft length, hop * (frames - 1)."""
@@ -130,13 +126,8 @@ class GriffinLim:
             if not _finite(x):
                 raise ValueError(f"{what} holds non-finite values")
 
-    def _to(self, x, dtype=torch.float64):
-        if isinstance(x, torch.Tensor):
-            return x.detach().to(device=self.device, dtype=dtype)
-        return torch.as_tensor(np.asarray(x), device=self.device).to(dtype)
-
     def _offsets(self, lens):
-        return torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=self.device)
+        return offsets(lens, self.device)
 
     # -- device resources
     def workspace_bytes(self, n_utts, total_frames, total_samples):
@@ -145,13 +136,9 @@ class GriffinLim:
     def reserve(self, n_utts, total_frames, total_samples):
         """Workspace for a call of that size (kept and grown, never per call)."""
         need = self.workspace_bytes(n_utts, total_frames, total_samples)
-        if need < 0:
-            raise ValueError("crk_gl_workspace_bytes: bad shape")
-        self.handle()
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        if need >= 0:
+            self.handle()
+        return self._workspace.ensure(need, "crk_gl_workspace_bytes")
 
     def _cap(self):
         if self.workspace_cap is None:
@@ -182,7 +169,7 @@ class GriffinLim:
         self._check_matrices(mlfbs, self.n_mels, "a log-mel matrix", min_frames=False)
         self._on_device()
         lens = [int(_shape(m)[0]) for m in mlfbs]
-        x = torch.cat([self._to(m) for m in mlfbs]).contiguous()
+        x = torch.cat([f64(m, self.device) for m in mlfbs]).contiguous()
         S = torch.empty(sum(lens), K, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             check(_lib.lib().crk_gl_linear_spectrum(self.handle(), x.data_ptr(), sum(lens), int(bool(magnitude)),
@@ -219,8 +206,8 @@ class GriffinLim:
         ys = []
         for lo, hi in self._chunks(lens):
             ang = (self.initial_angles(lens[lo:hi], None if seed is None else int(seed) + lo) if angles is None
-                   else [self._to(a, torch.complex128) for a in angles[lo:hi]])
-            ys += self._run([self._to(s).abs() for s in spcs[lo:hi]], ang, int(n_iters), bool(clip))
+                   else [f64(a, self.device, torch.complex128) for a in angles[lo:hi]])
+            ys += self._run([f64(s, self.device).abs() for s in spcs[lo:hi]], ang, int(n_iters), bool(clip))
         return ys
 
     def _run(self, S, ang, n_iters, clip):
@@ -251,7 +238,7 @@ class GriffinLim:
         (1 + len // hop, 513) complex128."""
         if not isinstance(waves, (list, tuple)) or len(waves) < 1:
             raise ValueError("waves must be a non-empty list")
-        slens = [int(np.prod(_shape(w))) for w in waves]
+        slens = [size_of(w) for w in waves]
         for n in slens:
             if n <= FFTL // 2:
                 raise ValueError(f"a waveform of {n} samples: the reflect padding needs more than fftl / 2 = {FFTL // 2}")
@@ -260,7 +247,7 @@ class GriffinLim:
                 raise ValueError("a waveform holds non-finite values")
         self._on_device()
         lens = [1 + n // self.hop for n in slens]
-        x = torch.cat([self._to(w).reshape(-1) for w in waves]).contiguous()
+        x = torch.cat([f64(w, self.device).reshape(-1) for w in waves]).contiguous()
         foff, soff = self._offsets(lens), self._offsets(slens)
         spec = torch.empty(sum(lens), K, 2, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
@@ -277,7 +264,7 @@ class GriffinLim:
         slens = [self.samples(T) for T in lens]
         F, N = sum(lens), sum(slens)
         ws = self.reserve(len(lens), F, N)
-        X = torch.view_as_real(torch.cat([self._to(s, torch.complex128) for s in specs]).contiguous())
+        X = torch.view_as_real(torch.cat([f64(s, self.device, torch.complex128) for s in specs]).contiguous())
         foff, soff = self._offsets(lens), self._offsets(slens)
         y = torch.empty(N, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):

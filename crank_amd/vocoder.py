@@ -15,6 +15,7 @@ import torch
 
 from crank_amd import _lib, ops
 from crank_amd._lib import check, stream_ptr
+from crank_amd._ragged import Workspace, made, offsets, release
 
 MAX_AUX = 128
 MAX_SCALE = 16
@@ -190,7 +191,7 @@ class ParallelWaveGANVocoder:
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(0)
         self._handle = None
-        self._ws = None
+        self._workspace = Workspace(self.device)
 
     @classmethod
     def from_checkpoint(cls, checkpoint, config, stats=None, device="cuda"):
@@ -205,11 +206,9 @@ class ParallelWaveGANVocoder:
         if self._handle is None:
             p = self.params
             sc = (ctypes.c_int * len(self.scales))(*self.scales)
-            h = _lib.lib().crk_voc_create(p["layers"], p["stacks"], p["aux_channels"], p["aux_context_window"],
-                                          ctypes.addressof(sc), len(self.scales), self.block.data_ptr())
-            if not h:
-                raise RuntimeError("libcrank_hip: crk_voc_create failed (unsupported configuration or HIP error)")
-            self._handle = h
+            self._handle = made(_lib.lib().crk_voc_create(p["layers"], p["stacks"], p["aux_channels"],
+                                                          p["aux_context_window"], ctypes.addressof(sc), len(self.scales),
+                                                          self.block.data_ptr()), "crk_voc_create")
         return self._handle
 
     def workspace_bytes(self, n_utts, total_frames):
@@ -217,20 +216,10 @@ class ParallelWaveGANVocoder:
 
     def reserve(self, n_utts, total_frames):
         """Device workspace for a call of n_utts utterances / total_frames frames (kept and grown, never per call)."""
-        need = self.workspace_bytes(n_utts, total_frames)
-        if need < 0:
-            raise ValueError("crk_voc_workspace_bytes: bad shape")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._workspace.ensure(self.workspace_bytes(n_utts, total_frames), "crk_voc_workspace_bytes")
 
     def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().crk_voc_destroy(self._handle)
-        except Exception:
-            pass
+        release(self, "_handle", "crk_voc_destroy")
 
     def manual_seed(self, seed):
         self.generator.manual_seed(int(seed))
@@ -250,7 +239,7 @@ class ParallelWaveGANVocoder:
             if c.dim() != 2 or c.shape[1] != self.aux_channels or c.shape[0] < 1:
                 raise ValueError(f"c must be (frames >= 1, {self.aux_channels}), got {tuple(c.shape)}")
         lens = [int(c.shape[0]) for c in cs]
-        off = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=self.device)
+        off = offsets(lens, self.device)
         return torch.cat(cs).contiguous(), off, lens
 
     def upsample_batch(self, cs):

@@ -24,6 +24,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import check, stream_ptr
+from crank_amd._ragged import Workspace, f64, made, offsets, release, require_gpu, size_of
 
 FFTL = 1024  # the only fftl the kernels implement (every mcep recipe uses it)
 K = FFTL // 2 + 1
@@ -41,12 +42,6 @@ def y_length(frames, fs, shiftms):
     return int(frames * shiftms * fs / 1000)
 
 
-def _f64(x, device):
-    if isinstance(x, torch.Tensor):
-        return x.detach().to(device=device, dtype=torch.float64)
-    return torch.as_tensor(np.asarray(x, np.float64), device=device)
-
-
 class WorldSynthesizer:
     """sprocket's ``Synthesizer(fs, fftl, shiftms)`` with ``synthesis(f0, mcep, codeap, rmcep)``, run by the kernels.
     ``alpha`` is the all-pass constant of the mel-cepstrum (the reference passes it to ``synthesis``)."""
@@ -61,24 +56,17 @@ class WorldSynthesizer:
         self.device = torch.device(device)
         self.pulse_capacity = int(pulse_capacity)
         self._handles = {}  # order + 1 -> handle
-        self._ws = None
+        self._workspace = Workspace(self.device)
         self._reserved = {}  # order + 1 -> samples the handle's noise table covers
         self.last_pulse_count = None
 
     def __del__(self):
-        try:
-            for h in self._handles.values():
-                _lib.lib().crk_world_destroy(h)
-        except Exception:
-            pass
+        release(self, "_handles", "crk_world_destroy")
 
     def handle(self, order1):
         if order1 not in self._handles:
-            h = _lib.lib().crk_world_create(self.fs, self.fftl, self.shiftms, self.alpha, order1, self.bands,
-                                            self.pulse_capacity)
-            if not h:
-                raise RuntimeError("libcrank_hip: crk_world_create failed (unsupported configuration or HIP error)")
-            self._handles[order1] = h
+            self._handles[order1] = made(_lib.lib().crk_world_create(self.fs, self.fftl, self.shiftms, self.alpha, order1,
+                                                                     self.bands, self.pulse_capacity), "crk_world_create")
         return self._handles[order1]
 
     # -- inputs
@@ -106,10 +94,10 @@ class WorldSynthesizer:
         if len(rmceps) != n or (any(r is None for r in rmceps) and any(r is not None for r in rmceps)):
             raise ValueError("rmceps must be None or given for every utterance")
         dev = self.device
-        f0s = [_f64(f, dev).reshape(-1) for f in f0s]
-        mceps = [_f64(m, dev) for m in mceps]
-        codeaps = [_f64(c, dev) for c in codeaps]
-        rmceps = [None if r is None else _f64(r, dev) for r in rmceps]
+        f0s = [f64(f, dev).reshape(-1) for f in f0s]
+        mceps = [f64(m, dev) for m in mceps]
+        codeaps = [f64(c, dev) for c in codeaps]
+        rmceps = [None if r is None else f64(r, dev) for r in rmceps]
         for f, m, c, r in zip(f0s, mceps, codeaps, rmceps):
             self._check(f, m, c, r)
         order1 = mceps[0].shape[1]
@@ -120,16 +108,15 @@ class WorldSynthesizer:
         if min(ylens) < 1:
             raise ValueError("an utterance shorter than one output sample")
         self._on_device()
-        foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
-        soff = torch.tensor([0] + list(np.cumsum(ylens)), dtype=torch.int64, device=dev)
+        foff = offsets(lens, dev)
+        soff = offsets(ylens, dev)
         cat = lambda xs: torch.cat(xs).contiguous()  # noqa: E731
         rm = None if rmceps[0] is None else cat(rmceps)
         return dict(f0=cat(f0s), mcep=cat(mceps), cap=cat(codeaps), rmcep=rm, order1=order1, lens=lens, ylens=ylens,
                     foff=foff, soff=soff)
 
     def _on_device(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("WORLD synthesis runs in the HIP kernels: the synthesizer's device must be the GPU")
+        require_gpu(self.device, "WORLD synthesis", "the synthesizer's device")
 
     # -- device resources
     def workspace_bytes(self, n_utts, total_frames, total_samples, order1=40):
@@ -138,16 +125,12 @@ class WorldSynthesizer:
     def reserve(self, n_utts, total_frames, total_samples, max_samples, order1=40):
         """Workspace for a call of that size and the noise table for utterances of up to max_samples samples (kept
         and grown, never per call)."""
-        need = self.workspace_bytes(n_utts, total_frames, total_samples, order1)
-        if need < 0:
-            raise ValueError("crk_world_workspace_bytes: bad shape")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace.ensure(self.workspace_bytes(n_utts, total_frames, total_samples, order1),
+                                    "crk_world_workspace_bytes")
         if max_samples > self._reserved.get(order1, 0):
             check(_lib.lib().crk_world_reserve(self.handle(order1), int(max_samples)), "crk_world_reserve")
             self._reserved[order1] = int(max_samples)
-        return self._ws
+        return ws
 
     # -- synthesis
     def synthesis_batch(self, f0s, mceps, codeaps, rmceps=None):
@@ -175,7 +158,7 @@ class WorldSynthesizer:
     def frame_tables_batch(self, mceps, codeaps, rmceps=None):
         """Per utterance (sp, ap), each (frames, 513): the power-modified mc2sp and the decoded aperiodicity."""
         n = len(mceps)
-        mceps = [_f64(m, self.device) for m in mceps]
+        mceps = [f64(m, self.device) for m in mceps]
         f0s = [torch.zeros(m.shape[0], dtype=torch.float64, device=self.device) for m in mceps]
         b = self._batch(f0s, mceps, codeaps, rmceps)
         F = sum(b["lens"])
@@ -192,14 +175,14 @@ class WorldSynthesizer:
     def pulses_batch(self, f0s):
         """Per utterance (pulse samples, noise sizes, fractional shifts in seconds, vuv at each pulse) on the host."""
         dev = self.device
-        f0s = [_f64(f, dev).reshape(-1) for f in f0s]
+        f0s = [f64(f, dev).reshape(-1) for f in f0s]
         lens = [f.numel() for f in f0s]
         if min(lens) < 2:
             raise ValueError("WORLD synthesis needs at least 2 frames")
         ylens = [y_length(T, self.fs, self.shiftms) for T in lens]
         self._on_device()
-        foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
-        soff = torch.tensor([0] + list(np.cumsum(ylens)), dtype=torch.int64, device=dev)
+        foff = offsets(lens, dev)
+        soff = offsets(ylens, dev)
         S = sum(ylens)
         pos = torch.empty(S, dtype=torch.int32, device=dev)
         shift = torch.empty(S, dtype=torch.float64, device=dev)
@@ -228,7 +211,7 @@ class WorldSynthesizer:
         for d in outputs:
             if d.get("cap") is None:
                 raise ValueError("an mcep eval output without 'cap' (the batch has no coded aperiodicity)")
-        f0s = [_f64(d["f0"], self.device).reshape(-1) for d in outputs]
+        f0s = [f64(d["f0"], self.device).reshape(-1) for d in outputs]
         rm = [d.get("rmcep") for d in outputs]
         rm = None if all(r is None for r in rm) else rm
         ys = self.synthesis_batch(f0s, [d["feats"] for d in outputs], [d["cap"] for d in outputs], rm)
@@ -256,27 +239,20 @@ class WorldAnalyzer:
         self._handles = {}  # (order + 1, alpha) -> handle
         self._reserved = {}  # handle key -> randn draws its table covers
         self._taps = {}  # cutoff -> device taps
-        self._ws = None
+        self._workspace = Workspace(self.device)
         self._harvest = None
 
     def __del__(self):
-        try:
-            for h in self._handles.values():
-                _lib.lib().crk_wana_destroy(h)
-        except Exception:
-            pass
+        release(self, "_handles", "crk_wana_destroy")
 
     def _on_device(self):
-        if self.device.type != "cuda":
-            raise RuntimeError("WORLD analysis runs in the HIP kernels: the analyzer's device must be the GPU")
+        require_gpu(self.device, "WORLD analysis", "the analyzer's device")
 
     def handle(self, order1=1, alpha=0.0):
         key = (int(order1), float(alpha))
         if key not in self._handles:
-            h = _lib.lib().crk_wana_create(self.fs, self.fftl, self.shiftms, key[1], key[0])
-            if not h:
-                raise RuntimeError("libcrank_hip: crk_wana_create failed (unsupported configuration or HIP error)")
-            self._handles[key] = h
+            self._handles[key] = made(_lib.lib().crk_wana_create(self.fs, self.fftl, self.shiftms, key[1], key[0]),
+                                      "crk_wana_create")
         return self._handles[key]
 
     # -- inputs
@@ -284,8 +260,7 @@ class WorldAnalyzer:
         n = len(waves)
         if n < 1 or len(f0s) != n:
             raise ValueError("waves and f0s must be lists of the same non-zero length")
-        size = lambda a: int(a.numel() if isinstance(a, torch.Tensor) else np.asarray(a).size)  # noqa: E731
-        lens, slens = [size(f) for f in f0s], [size(w) for w in waves]
+        lens, slens = [size_of(f) for f in f0s], [size_of(w) for w in waves]
         shift = self.shiftms / 1000.0 * self.fs
         for T, S in zip(lens, slens):
             if T < 1:
@@ -297,15 +272,15 @@ class WorldAnalyzer:
                                  f"shift ({self.shiftms} ms) past the waveform's end ({S} samples)")
         self._on_device()
         dev = self.device
-        f0 = torch.cat([_f64(f, dev).reshape(-1) for f in f0s]).contiguous()
+        f0 = torch.cat([f64(f, dev).reshape(-1) for f in f0s]).contiguous()
         # the contours stay on the device; two flags come back
         flags = torch.stack([(~torch.isfinite(f0) | (f0 < 0)).any(), (f0 > self.fs / 4.0).any()]).tolist()
         if flags[0]:
             raise ValueError("F0 must be finite and not negative (0 marks an unvoiced frame)")
         if flags[1]:
             raise ValueError(f"F0 above fs / 4 = {self.fs / 4.0} Hz: the smoothing band would leave the spectrum")
-        foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
-        soff = torch.tensor([0] + list(np.cumsum(slens)), dtype=torch.int64, device=dev)
+        foff = offsets(lens, dev)
+        soff = offsets(slens, dev)
         return dict(f0=f0, lens=lens, slens=slens, foff=foff, soff=soff)
 
     def _waves(self, waves, dtype):
@@ -320,18 +295,14 @@ class WorldAnalyzer:
     def reserve(self, n_utts, total_frames, total_samples, max_frames, order1=1, alpha=0.0):
         """Workspace for a call of that size and the randn table for utterances of up to max_frames frames (kept and
         grown, never per call).  Returns (workspace, the draw count the table is asked to cover)."""
-        need = int(_lib.lib().crk_wana_workspace_bytes(n_utts, total_frames, total_samples))
-        if need < 0:
-            raise ValueError("crk_wana_workspace_bytes: bad shape")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace.ensure(int(_lib.lib().crk_wana_workspace_bytes(n_utts, total_frames, total_samples)),
+                                    "crk_wana_workspace_bytes")
         key = (int(order1), float(alpha))
         draws = int(max_frames) * DRAWS_PER_FRAME
         if draws > self._reserved.get(key, 0):
             check(_lib.lib().crk_wana_reserve(self.handle(*key), draws), "crk_wana_reserve")
             self._reserved[key] = draws
-        return self._ws, draws
+        return ws, draws
 
     # -- the stages
     def low_cut_batch(self, waves, cutoff=70):
@@ -340,7 +311,7 @@ class WorldAnalyzer:
 
         if len(waves) < 1:
             raise ValueError("waves must be a non-empty list")
-        slens = [int(w.numel() if isinstance(w, torch.Tensor) else np.asarray(w).size) for w in waves]
+        slens = [size_of(w) for w in waves]
         if min(slens) < 1:
             raise ValueError("an empty waveform")
         self._on_device()
@@ -348,7 +319,7 @@ class WorldAnalyzer:
             taps = firwin(LOWCUT_TAPS, cutoff / (self.fs // 2), pass_zero=False)
             self._taps[cutoff] = torch.as_tensor(taps, dtype=torch.float64, device=self.device)
         x = self._waves(waves, torch.float32)
-        soff = torch.tensor([0] + list(np.cumsum(slens)), dtype=torch.int64, device=self.device)
+        soff = offsets(slens, self.device)
         y = torch.empty(x.numel(), dtype=torch.float64, device=self.device)
         check(_lib.lib().crk_wana_lowcut(self.handle(), x.data_ptr(), self._taps[cutoff].data_ptr(), LOWCUT_TAPS,
                                          soff.data_ptr(), len(slens), x.numel(), y.data_ptr(), stream_ptr()),
@@ -395,14 +366,14 @@ class WorldAnalyzer:
     def npow_of_sp_batch(self, sps):
         """sprocket ``spc2npow`` of each (T, 513) envelope: list of (T,) in dB over the utterance's mean power."""
         self._on_device()
-        sps = [_f64(s, self.device) for s in sps]
+        sps = [f64(s, self.device) for s in sps]
         lens = [int(s.shape[0]) for s in sps]
         if not lens or min(lens) < 1 or any(s.dim() != 2 or s.shape[1] != K for s in sps):
             raise ValueError(f"spectral envelopes must be (frames >= 1, {K})")
         F = sum(lens)
         ws, _ = self.reserve(len(lens), F, 1, 1)
         sp = torch.cat(sps).contiguous()
-        foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=self.device)
+        foff = offsets(lens, self.device)
         out = torch.empty(F, dtype=torch.float64, device=self.device)
         check(_lib.lib().crk_wana_npow(self.handle(), sp.data_ptr(), foff.data_ptr(), len(lens), F, out.data_ptr(),
                                        ws.data_ptr(), ws.numel(), stream_ptr()), "crk_wana_npow")
@@ -421,12 +392,12 @@ class WorldAnalyzer:
         half, dc_limit, boundary, offset."""
         self._on_device()
         dev = self.device
-        f0s = [_f64(f, dev).reshape(-1) for f in f0s]
+        f0s = [f64(f, dev).reshape(-1) for f in f0s]
         lens = [int(f.numel()) for f in f0s]
         if not lens or min(lens) < 1:
             raise ValueError("an F0 contour needs at least 1 frame")
         F = sum(lens)
-        foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
+        foff = offsets(lens, dev)
         f0 = torch.cat(f0s).contiguous()
         shapes = torch.empty(F, 4, dtype=torch.int32, device=dev)
         off = torch.empty(F, dtype=torch.int64, device=dev)
@@ -458,7 +429,7 @@ class WorldAnalyzer:
         if self._harvest is None:
             self._harvest = HarvestF0(self.fs, int(self.shiftms), self.device)
         self._harvest.check(waves, minf0s, maxf0s)
-        xs = [_f64(w, self.device).reshape(-1) for w in waves] if low_cut is None else self.low_cut_batch(waves, low_cut)
+        xs = [f64(w, self.device).reshape(-1) for w in waves] if low_cut is None else self.low_cut_batch(waves, low_cut)
         f0s = self._harvest.harvest_batch(xs, minf0s, maxf0s)
         return f0s, self.cheaptrick_batch(xs, f0s)
 
@@ -482,27 +453,24 @@ class HarvestF0:
         self.r = int(min(12, max(1, np.floor(self.fs / 8000.0 + 0.5))))
         self.fs_d = self.fs / self.r
         self._h = None
-        self._ws = None
+        self._workspace = Workspace(self.device)
         self._events = 0
 
     def __del__(self):
-        try:
-            if self._h:
-                _lib.lib().crk_f0_destroy(self._h)
-        except Exception:
-            pass
+        release(self, "_h", "crk_f0_destroy")
+
+    @property
+    def _ws(self):
+        return self._workspace.buf
 
     def handle(self):
         if self._h is None:
-            if self.device.type != "cuda":
-                raise RuntimeError("Harvest runs in the HIP kernels: the device must be the GPU")
+            require_gpu(self.device, "Harvest")
             from scipy.signal import cheby1
 
             b, a = cheby1(3, 0.05, 0.8 / self.r)
             co = (ctypes.c_double * 8)(*[float(v) for v in list(b) + list(a)])
-            self._h = _lib.lib().crk_f0_create(self.fs, self.shiftms, co)
-            if not self._h:
-                raise RuntimeError("libcrank_hip: crk_f0_create failed (unsupported configuration or HIP error)")
+            self._h = made(_lib.lib().crk_f0_create(self.fs, self.shiftms, co), "crk_f0_create")
         return self._h
 
     # -- inputs
@@ -512,9 +480,8 @@ class HarvestF0:
         if n < 1 or len(minf0s) != n or len(maxf0s) != n:
             raise ValueError("waves, minf0s and maxf0s must be lists of the same non-zero length")
         for w, lo, hi in zip(waves, minf0s, maxf0s):
-            size = int(w.numel() if isinstance(w, torch.Tensor) else np.asarray(w).size)
-            if size < HARVEST_MIN_SAMPLES:
-                raise ValueError(f"a waveform of {size} samples: Harvest needs at least {HARVEST_MIN_SAMPLES}")
+            if size_of(w) < HARVEST_MIN_SAMPLES:
+                raise ValueError(f"a waveform of {size_of(w)} samples: Harvest needs at least {HARVEST_MIN_SAMPLES}")
             if not (np.isfinite(lo) and np.isfinite(hi) and 40.0 <= lo < hi <= 800.0):
                 raise ValueError(f"search range {lo} .. {hi} Hz: Harvest takes 40 <= minf0 < maxf0 <= 800")
 
@@ -552,7 +519,7 @@ class HarvestF0:
     def _batch(self, waves, minf0s, maxf0s):
         self.check(waves, minf0s, maxf0s)
         self.handle()
-        xs = [_f64(w, self.device).reshape(-1) for w in waves]
+        xs = [f64(w, self.device).reshape(-1) for w in waves]
         L = self._layout([int(x.numel()) for x in xs], minf0s, maxf0s)
         L["x"] = torch.cat(xs).contiguous()
         self.reserve(L["n"], L["S"], L["F"], L["C"], L["E"])
@@ -566,16 +533,12 @@ class HarvestF0:
     # -- device resources
     def reserve(self, n_utts, total_samples, total_frames, total_channels, total_events):
         """Workspace for a call of that size and the handle's event storage (kept and grown, never per call)."""
-        need = int(_lib.lib().crk_f0_workspace_bytes(n_utts, total_samples, total_frames, total_channels))
-        if need < 0:
-            raise ValueError("crk_f0_workspace_bytes: bad shape")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace.ensure(int(_lib.lib().crk_f0_workspace_bytes(n_utts, total_samples, total_frames,
+                                                                          total_channels)), "crk_f0_workspace_bytes")
         if total_events > self._events:
             check(_lib.lib().crk_f0_reserve(self.handle(), int(total_events)), "crk_f0_reserve")
             self._events = int(total_events)
-        return self._ws
+        return ws
 
     @staticmethod
     def _status(status):
@@ -613,7 +576,7 @@ class HarvestF0:
     def raw_candidates_batch(self, waves, minf0s, maxf0s, decimated=None):
         """Per utterance the (channels, 1 ms frames) raw candidate table; ``decimated``: the signals to filter instead of
         this object's own decimation of ``waves``."""
-        yds = self.decimate_batch(waves, minf0s, maxf0s) if decimated is None else [_f64(y, self.device) for y in decimated]
+        yds = self.decimate_batch(waves, minf0s, maxf0s) if decimated is None else [f64(y, self.device) for y in decimated]
         L = self._batch(waves, minf0s, maxf0s)
         if [int(y.numel()) for y in yds] != [int(v) for v in L["host"][:, 3]]:
             raise ValueError("decimated signals must have ceil(samples / r) samples")
@@ -630,7 +593,7 @@ class HarvestF0:
         return [t.view(int(h[u, 7]), int(h[u, 5])) for u, t in enumerate(raw.split([int(v) for v in h[:, 7] * h[:, 5]]))]
 
     def _tables(self, L, tables):
-        ts = [_f64(t, self.device) for t in tables]
+        ts = [f64(t, self.device) for t in tables]
         for u, t in enumerate(ts):
             if tuple(t.shape) != (int(L["host"][u, 5]), HARVEST_SLOTS):
                 raise ValueError(f"a candidate table must be (1 ms frames, {HARVEST_SLOTS}), got {tuple(t.shape)}")
@@ -639,7 +602,7 @@ class HarvestF0:
     def candidates_batch(self, waves, minf0s, maxf0s, raws):
         """Per utterance the (1 ms frames, 112) candidate table of a raw table: run means, overlapped over +-3 frames."""
         L = self._batch(waves, minf0s, maxf0s)
-        rs = [_f64(t, self.device) for t in raws]
+        rs = [f64(t, self.device) for t in raws]
         for u, t in enumerate(rs):
             if tuple(t.shape) != (int(L["host"][u, 7]), int(L["host"][u, 5])):
                 raise ValueError("a raw table must be (channels, 1 ms frames)")
@@ -677,15 +640,14 @@ def continuous_f0_batch(f0s, device="cuda", return_filled=False):
     taken (``return_filled`` appends that contour).  A contour without a voiced frame raises ValueError (the reference:
     IndexError)."""
     dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("continuous_f0_batch runs in the HIP kernels: the device must be the GPU")
-    f0s = [_f64(f, dev).reshape(-1) for f in f0s]
+    require_gpu(dev, "continuous_f0_batch")
+    f0s = [f64(f, dev).reshape(-1) for f in f0s]
     lens = [int(f.numel()) for f in f0s]
     if not lens or min(lens) < 1:
         raise ValueError("an F0 contour needs at least 1 frame")
     F = sum(lens)
     f0 = torch.cat(f0s).contiguous()
-    foff = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int64, device=dev)
+    foff = offsets(lens, dev)
     uv = torch.empty(F, dtype=torch.float32, device=dev)
     filled, cf0, lf0, lcf0 = (torch.empty(F, dtype=torch.float64, device=dev) for _ in range(4))
     status = torch.empty(len(lens), dtype=torch.int32, device=dev)

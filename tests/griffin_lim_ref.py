@@ -6,7 +6,7 @@ is restated from its published algorithm, and parity with librosa itself is unpi
 
 Every FFT goes through one hook, a transform object with ``rfft`` ((T, 1024) real -> (T, 513) complex) and ``irfft`` (the
 inverse, dropping the imaginary parts of bin 0 and bin 512).  Three are here: ``NumpyFFT``, ``TorchFFT`` and ``Radix2FFT``, a
-plain radix-2 decimation-in-time transform with table twiddles, the class of the kernels' world_fft.h.  The largest pairwise
+plain radix-2 decimation-in-time transform with table twiddles, the class of the kernels' signal_common.h.  The largest pairwise
 distance between the three results of one case is the restatement's own rounding spread; the GPU tests measure the kernels
 against a multiple of it.
 
