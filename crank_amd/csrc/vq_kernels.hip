@@ -2,8 +2,9 @@
 //   vq_forward   - nearest code (fp32 L2 search, first index wins ties), gather and
 //                  straight-through value, replaces Quantizer.vq + the one-hot GEMM
 //                  lookup of crank/net/module/vqvae2.py:306-313,333,338-347
-//   vq_ema_stats - per-code frame counts and feature sums (vqvae2.py:316-321)
-//   vq_ema_apply - EMA blend, Laplace smoothing, codebook refresh (vqvae2.py:316-330)
+//   vq_ema_*     - the codebook's EMA update for up to 4 quantizers per launch: per-code frame counts and feature
+//                  sums (vqvae2.py:316-321), then EMA blend, Laplace smoothing, codebook refresh (vqvae2.py:316-330);
+//                  one device body per piece of arithmetic, the per-quantizer entry points are the nq = 1 case
 //
 // The distance is evaluated with the reference's own fp32 expression
 //   dist = (sum_d W^2 - 2 * x.w) + sum_d x^2
@@ -1117,7 +1118,6 @@ static bool vq_use_f16(int kt) {
 // eight waves where the tile count splits evenly between two waves per frame group
 static void vq_mfma_launch(int nblk, int kt, size_t lds, hipStream_t s, const float* x, int ldx, const float* cb, int N, int K,
                            long long* idx, float* e, int lde, float* qx, int ldq, const VqFuse& fz) {
-  const int tp_env = 2;
   // algorithmic bytes of a quantizer call = N x (64 x 4 read + 8 index + 64 x 4 gathered code) = 520 B per frame
   conv_prof_bytes(7, 520.0 * N);
   conv_prof_begin(7, 2.0 * N * (double)K * 64.0, s);
@@ -1127,7 +1127,7 @@ static void vq_mfma_launch(int nblk, int kt, size_t lds, hipStream_t s, const fl
     conv_prof_end(7, s);
     return;
   }
-  if (tp_env == 2 && kt % 4 == 0)
+  if (kt % 4 == 0)
     hipLaunchKernelGGL(vq_forward_mfma_kernel<2>, dim3(nblk), dim3(512), lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz);
   else
     hipLaunchKernelGGL(vq_forward_mfma_kernel<1>, dim3(nblk), dim3(256), lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz);
@@ -1261,6 +1261,10 @@ extern "C" int crk_vq_forward(const float* x, int ldx, const float* codebook, in
 // reruns agree bit for bit).  No global atomics: workgroup (chunk, slice) owns a run of frames and
 // a slice of SW dims, accumulates an [SW][K] int64 table in LDS, and writes it to its own slot of
 // the scratch buffer; a second kernel adds the chunk slots up.
+//
+// Every piece of the update's arithmetic has ONE device body (vq_ema_partial_body, vq_ema_chunk_sum, ema_mix,
+// vq_ema_size_body, vq_ema_blend_step) and every kernel takes up to VQ_EMA_MAXQ quantizers; the per-quantizer entry
+// points are the same kernels with nq = 1.  So the fused and the per-quantizer paths agree bit for bit by construction.
 __device__ __forceinline__ void vq_ema_partial_body(const float* __restrict__ x, int ldx, const long long* __restrict__ idx,
                                                     int N, int D, int K, int SW, int frames_per_chunk,
                                                     unsigned long long* __restrict__ part_sums, int* __restrict__ part_counts,
@@ -1296,99 +1300,47 @@ __device__ __forceinline__ void vq_ema_partial_body(const float* __restrict__ x,
     for (int i = tid; i < K; i += 256) part_counts[(size_t)chunk * K + i] = cnt[i];
 }
 
-__global__ __launch_bounds__(256) void vq_ema_partial_kernel(const float* __restrict__ x, int ldx,
-                                                             const long long* __restrict__ idx, int N, int D, int K,
-                                                             int SW, int frames_per_chunk,
-                                                             unsigned long long* __restrict__ part_sums,
-                                                             int* __restrict__ part_counts) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char vq_smem[];
-  vq_ema_partial_body(x, ldx, idx, N, D, K, SW, frames_per_chunk, part_sums, part_counts, blockIdx.x, blockIdx.y, vq_smem);
-}
+// One quantizer of an EMA launch; a launch takes up to VQ_EMA_MAXQ of them (the quantizer calls of one generator forward).
+// An entry point fills the fields its kernels read.
+#define VQ_EMA_MAXQ 4
+struct EmaQ {
+  const float* x; const long long* idx; int ldx, N;             // partial: the call's frames and codes
+  int SW, fpc, chunks, slices;                                  // vq_ema_plan's tiling of the call
+  unsigned long long* part_sums; int* part_counts;              // the per-chunk tables in the call's scratch buffer
+  int D, K;
+  float keps;                         // (float)(K * eps), the product taken in double like the python scalar
+  int* counts; long long* sums;       // integer statistics (caller-owned; all-reduced between reduce and apply)
+  float* ema_size; float* ema_w; float* cb;
+};
+// python-float semantics of vqvae2.py:316-328: the scalars are rounded to fp32 when they meet an fp32 tensor
+struct EmaMP { EmaQ q[VQ_EMA_MAXQ]; int nq; float decay, omd, eps; };
+
 // the per-chunk tables of several quantizer calls in one launch (grid z = call)
-struct EmaPQ { const float* x; const long long* idx; unsigned long long* part_sums; int* part_counts; int ldx, N, D, K, SW, fpc, chunks, slices; };
-struct EmaPM { EmaPQ q[4]; int nq; };
-__global__ __launch_bounds__(256) void vq_ema_partial_multi_kernel(const EmaPM m) {
+__global__ __launch_bounds__(256) void vq_ema_partial_multi_kernel(const EmaMP m) {
   extern __shared__ __attribute__((aligned(16))) unsigned char vq_smem[];
-  EmaPQ e = m.q[0];  // (statically indexed copies: a dynamic index into the kernel argument would put it into scratch)
+  EmaQ e = m.q[0];  // (statically indexed copies: a dynamic index into the kernel argument would put it into scratch)
 #pragma unroll
-  for (int k = 1; k < 4; k++)
+  for (int k = 1; k < VQ_EMA_MAXQ; k++)
     if ((int)blockIdx.z == k) e = m.q[k];
   if ((int)blockIdx.x >= e.chunks || (int)blockIdx.y >= e.slices) return;
   vq_ema_partial_body(e.x, e.ldx, e.idx, e.N, e.D, e.K, e.SW, e.fpc, e.part_sums, e.part_counts, blockIdx.x, blockIdx.y, vq_smem);
 }
 
-__global__ __launch_bounds__(256) void vq_ema_reduce_kernel(const unsigned long long* __restrict__ part_sums,
-                                                            const int* __restrict__ part_counts, int chunks, int DK,
-                                                            int K, unsigned long long* __restrict__ sums,
-                                                            int* __restrict__ counts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < DK) {
-    unsigned long long a = 0ull;
-    int c = 0;
-    for (; c + 8 <= chunks; c += 8) {  // 8 independent loads in flight (integer sums: any order is exact)
-      unsigned long long t[8];
+// element i of the sum of `chunks` tables that lie `stride` elements apart: 8 independent loads in flight (one load per
+// iteration would be `chunks` dependent memory round trips; integer sums: any order is exact), then the tail
+template <typename T>
+__device__ __forceinline__ T vq_ema_chunk_sum(const T* __restrict__ part, int chunks, int stride, int i) {
+  T a = 0;
+  int c = 0;
+  for (; c + 8 <= chunks; c += 8) {
+    T t[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = part_sums[(size_t)(c + u) * DK + i];
+    for (int u = 0; u < 8; u++) t[u] = part[(size_t)(c + u) * stride + i];
 #pragma unroll
-      for (int u = 0; u < 8; u++) a += t[u];
-    }
-    for (; c < chunks; c++) a += part_sums[(size_t)c * DK + i];
-    sums[i] = a;
+    for (int u = 0; u < 8; u++) a += t[u];
   }
-  if (i < K) {  // same shape as above: one load per iteration would be `chunks` dependent memory round trips
-    int a = 0, c = 0;
-    for (; c + 8 <= chunks; c += 8) {
-      int t[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = part_counts[(size_t)(c + u) * K + i];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a += t[u];
-    }
-    for (; c < chunks; c++) a += part_counts[(size_t)c * K + i];
-    counts[i] = a;
-  }
-}
-
-static int vq_ema_plan(int N, int D, int K, int* SW, int* chunks, int* fpc) {
-  int sw = 16;
-  while (sw >= 4 && (size_t)sw * K * 8 + (size_t)K * 4 > 150 * 1024) sw >>= 1;
-  if (sw < 4) return CRK_ERR_UNSUPPORTED;
-  int c = (N + 127) / 128;
-  if (c > 64) c = 64;
-  if (c < 1) c = 1;
-  *SW = sw; *chunks = c; *fpc = (N + c - 1) / c;
-  return CRK_OK;
-}
-
-extern "C" long long crk_vq_ema_scratch_bytes(int N, int D, int K) {
-  int sw, c, fpc;
-  if (N < 0 || D <= 0 || K <= 0 || vq_ema_plan(N, D, K, &sw, &c, &fpc) != CRK_OK) return -1;
-  return (long long)c * ((long long)D * K * 8 + (long long)K * 4);
-}
-
-extern "C" int crk_vq_ema_stats(const float* x, int ldx, const long long* idx, int N, int D, int K, int* counts,
-                                long long* sums, void* scratch, void* stream) {
-  if (!x || !idx || !counts || !sums || !scratch || (D & 3) || (ldx & 3)) return CRK_ERR_ARG;
-  int sw, chunks, fpc;
-  if (vq_ema_plan(N, D, K, &sw, &chunks, &fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vq_ema_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            152 * 1024) != hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
-  }
-  unsigned long long* part_sums = reinterpret_cast<unsigned long long*>(scratch);
-  int* part_counts = reinterpret_cast<int*>(part_sums + (size_t)chunks * D * K);
-  const size_t lds = (size_t)sw * K * 8 + (size_t)K * 4;
-  hipLaunchKernelGGL(vq_ema_partial_kernel, dim3(chunks, (D + sw - 1) / sw), dim3(256), lds, s, x, ldx, idx, N, D, K,
-                     sw, fpc, part_sums, part_counts);
-  const int DK = D * K;
-  hipLaunchKernelGGL(vq_ema_reduce_kernel, dim3((DK + 255) / 256), dim3(256), 0, s, part_sums, part_counts, chunks, DK,
-                     K, reinterpret_cast<unsigned long long*>(sums), counts);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
+  for (; c < chunks; c++) a += part[(size_t)c * stride + i];
+  return a;
 }
 
 // decay * a + (1 - decay) * b with ONE fixed rounding sequence (the compiler's choice of which product to fuse
@@ -1397,104 +1349,16 @@ __device__ __forceinline__ float ema_mix(float decay, float a, float omd, float 
   return __fmaf_rn(decay, a, __fmul_rn(omd, b));
 }
 
-// ---- EMA apply: cluster sizes in one workgroup (K <= 4096), then the D x K blend ----
-__global__ __launch_bounds__(1024) void vq_ema_size_kernel(const int* __restrict__ counts, float* __restrict__ ema_size,
-                                                           int K, float decay, float omd, float eps, float keps) {
+// Cluster sizes of one quantizer in one 1024-thread workgroup (K <= 4096): the EMA of the counts, their total through
+// a fixed tree, Laplace smoothing.  count(k) is code k's frame count.
+template <typename F>
+__device__ __forceinline__ void vq_ema_size_body(const EmaQ& e, float decay, float omd, float eps, F count) {
   __shared__ float red[1024];
   __shared__ float sz[4096];
-  const int tid = threadIdx.x;
-  float part = 0.f;
-  for (int k = tid; k < K; k += 1024) {
-    const float v = ema_mix(decay, ema_size[k], omd, (float)counts[k]);
-    sz[k] = v;
-    part += v;
-  }
-  red[tid] = part;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const float n = red[0];
-  const float den = n + keps;
-  for (int k = tid; k < K; k += 1024) ema_size[k] = (sz[k] + eps) / den * n;
-}
-
-// one thread per (k, d): reads ema_w / sums along k (their fast axis), writes the codebook
-// through an LDS transpose so both sides are coalesced
-__global__ __launch_bounds__(256) void vq_ema_blend_kernel(const long long* __restrict__ sums,
-                                                           const float* __restrict__ ema_size,
-                                                           float* __restrict__ ema_w, float* __restrict__ cb, int D,
-                                                           int K, float decay, float omd) {
-  __shared__ float tile[16][17];
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const int k0 = blockIdx.x * 16, d0 = blockIdx.y * 16;
-  const int k = k0 + tx, d = d0 + ty;
-  if (k < K && d < D) {
-    const int i = d * K + k;
-    const float es = (float)sums[i] * VQ_FIX_INV;
-    const float w = ema_mix(decay, ema_w[i], omd, es);
-    ema_w[i] = w;
-    tile[ty][tx] = w / ema_size[k];
-  }
-  __syncthreads();
-  const int kk = k0 + ty, dd = d0 + tx;
-  if (kk < K && dd < D) cb[(size_t)kk * D + dd] = tile[tx][ty];
-}
-
-// ---- every quantizer of a generator forward at once (one reduce launch, one apply launch) ----
-#define VQ_EMA_MAXQ 4
-struct EmaQ {
-  const unsigned long long* part_sums; const int* part_counts;  // reduce: per-chunk tables (crk_vq_ema_partial)
-  int chunks, D, K;
-  float keps;                         // (float)(K * eps), the product taken in double like the python scalar
-  int* counts; long long* sums;       // integer statistics (caller-owned; all-reduced between reduce and apply)
-  float* ema_size; float* ema_w; float* cb;
-};
-struct EmaMP { EmaQ q[VQ_EMA_MAXQ]; int nq; float decay, omd, eps; };
-
-__global__ __launch_bounds__(256) void vq_ema_reduce_multi_kernel(const EmaMP m) {
-  const EmaQ& e = m.q[blockIdx.y];
-  const int DK = e.D * e.K, K = e.K, chunks = e.chunks;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < DK) {
-    unsigned long long a = 0ull;
-    int c = 0;
-    for (; c + 8 <= chunks; c += 8) {
-      unsigned long long t[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = e.part_sums[(size_t)(c + u) * DK + i];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a += t[u];
-    }
-    for (; c < chunks; c++) a += e.part_sums[(size_t)c * DK + i];
-    reinterpret_cast<unsigned long long*>(e.sums)[i] = a;
-  }
-  if (i < K) {
-    int a = 0, c = 0;
-    for (; c + 8 <= chunks; c += 8) {
-      int t[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = e.part_counts[(size_t)(c + u) * K + i];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a += t[u];
-    }
-    for (; c < chunks; c++) a += e.part_counts[(size_t)c * K + i];
-    e.counts[i] = a;
-  }
-}
-
-// cluster sizes of every quantizer (one workgroup each), then every quantizer's blend: two launches per forward.
-// (Sizes and blend in ONE launch needs a "last workgroup writes the sizes" step; the device-scope fences that takes
-// cost more on this multi-XCD part than the second launch.)
-__global__ __launch_bounds__(1024) void vq_ema_size_multi_kernel(const EmaMP m) {
-  __shared__ float red[1024];
-  __shared__ float sz[4096];
-  const EmaQ& e = m.q[blockIdx.x];
   const int tid = threadIdx.x, K = e.K;
   float part = 0.f;
   for (int k = tid; k < K; k += 1024) {
-    const float v = ema_mix(m.decay, e.ema_size[k], m.omd, (float)e.counts[k]);
+    const float v = ema_mix(decay, e.ema_size[k], omd, (float)count(k));
     sz[k] = v;
     part += v;
   }
@@ -1506,9 +1370,35 @@ __global__ __launch_bounds__(1024) void vq_ema_size_multi_kernel(const EmaMP m) 
   }
   const float n = red[0];
   const float den = n + e.keps;
-  for (int k = tid; k < K; k += 1024) e.ema_size[k] = (sz[k] + m.eps) / den * n;
+  for (int k = tid; k < K; k += 1024) e.ema_size[k] = (sz[k] + eps) / den * n;
 }
 
+// element i = d * K + k of the blend: the new ema_w (stored) and from it the code's component (returned)
+__device__ __forceinline__ float vq_ema_blend_step(const EmaQ& e, int i, float decay, float omd, float size) {
+  const float es = (float)e.sums[i] * VQ_FIX_INV;
+  const float w = ema_mix(decay, e.ema_w[i], omd, es);
+  e.ema_w[i] = w;
+  return w / size;
+}
+
+__global__ __launch_bounds__(256) void vq_ema_reduce_multi_kernel(const EmaMP m) {
+  const EmaQ& e = m.q[blockIdx.y];
+  const int DK = e.D * e.K, K = e.K;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < DK) reinterpret_cast<unsigned long long*>(e.sums)[i] = vq_ema_chunk_sum(e.part_sums, e.chunks, DK, i);
+  if (i < K) e.counts[i] = vq_ema_chunk_sum(e.part_counts, e.chunks, K, i);
+}
+
+// cluster sizes of every quantizer (one workgroup each), then every quantizer's blend: two launches per forward.
+// (Sizes and blend in ONE launch needs a "last workgroup writes the sizes" step; the device-scope fences that takes
+// cost more on this multi-XCD part than the second launch.)
+__global__ __launch_bounds__(1024) void vq_ema_size_multi_kernel(const EmaMP m) {
+  const EmaQ& e = m.q[blockIdx.x];
+  vq_ema_size_body(e, m.decay, m.omd, m.eps, [&](int k) { return e.counts[k]; });
+}
+
+// one thread per (k, d): reads ema_w / sums along k (their fast axis), writes the codebook
+// through an LDS transpose so both sides are coalesced
 __global__ __launch_bounds__(256) void vq_ema_blend_multi_kernel(const EmaMP m) {
   __shared__ float tile[16][17];
   const EmaQ& e = m.q[blockIdx.z];
@@ -1517,21 +1407,15 @@ __global__ __launch_bounds__(256) void vq_ema_blend_multi_kernel(const EmaMP m) 
   const int k0 = blockIdx.x * 16, d0 = blockIdx.y * 16;
   if (k0 >= K || d0 >= D) return;  // the grid spans the largest quantizer
   const int k = k0 + tx, d = d0 + ty;
-  if (k < K && d < D) {
-    const int i = d * K + k;
-    const float es = (float)e.sums[i] * VQ_FIX_INV;
-    const float w = ema_mix(m.decay, e.ema_w[i], m.omd, es);
-    e.ema_w[i] = w;
-    tile[ty][tx] = w / e.ema_size[k];
-  }
+  if (k < K && d < D) tile[ty][tx] = vq_ema_blend_step(e, d * K + k, m.decay, m.omd, e.ema_size[k]);
   __syncthreads();
   const int kk = k0 + ty, dd = d0 + tx;
   if (kk < K && dd < D) e.cb[(size_t)kk * D + dd] = tile[tx][ty];
 }
 
 // The blend AND the codebook's image for the split-f16 search in one launch (D = 64, K <= 512): a workgroup owns a 32-code
-// tile of one quantizer - it blends the tile's ema_w rows (the arithmetic of vq_ema_blend_multi_kernel, element for element),
-// writes the tile's new code vectors and derives the tile's part of the image from them exactly as vq_image_kernel does from
+// tile of one quantizer - it blends the tile's ema_w rows (vq_ema_blend_step, as vq_ema_blend_multi_kernel does), writes
+// the tile's new code vectors and derives the tile's part of the image from them exactly as vq_image_kernel does from
 // the codebook it would read back (vq_code_stats / vq_plane_piece: the same bits).  The generator's next forward finds its
 // images current instead of spending a launch on them (two per training step).
 __global__ __launch_bounds__(256) void vq_ema_blend_image_multi_kernel(const EmaMP m, const VqImgM im) {
@@ -1547,15 +1431,7 @@ __global__ __launch_bounds__(256) void vq_ema_blend_image_multi_kernel(const Ema
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const int d = (tid >> 5) + 8 * j;
-      float v = 0.f;
-      if (k < K) {
-        const int i = d * K + k;
-        const float es = (float)e.sums[i] * VQ_FIX_INV;
-        const float w = ema_mix(m.decay, e.ema_w[i], m.omd, es);
-        e.ema_w[i] = w;
-        v = w / size;
-      }
-      wimg[(size_t)kl * VQH_WS + d] = v;
+      wimg[(size_t)kl * VQH_WS + d] = k < K ? vq_ema_blend_step(e, d * K + k, m.decay, m.omd, size) : 0.f;
     }
   }
   __syncthreads();
@@ -1582,49 +1458,81 @@ __global__ __launch_bounds__(256) void vq_ema_blend_image_multi_kernel(const Ema
   }
 }
 
-// per-chunk tables only (the first half of crk_vq_ema_stats); scratch: crk_vq_ema_scratch_bytes(N, D, K)
-extern "C" int crk_vq_ema_partial(const float* x, int ldx, const long long* idx, int N, int D, int K, void* scratch,
-                                  void* stream) {
-  if (!x || !idx || !scratch || (D & 3) || (ldx & 3)) return CRK_ERR_ARG;
-  int sw, chunks, fpc;
-  if (vq_ema_plan(N, D, K, &sw, &chunks, &fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vq_ema_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            152 * 1024) != hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
+// crk_vq_ema_reduce_multi and the cluster-size half of crk_vq_ema_apply_multi in ONE launch (single process: nothing is
+// all-reduced between them): the last workgroup of a quantizer's row sums the per-chunk counts itself (integers: the same
+// counts the other workgroups would write) and hands them to vq_ema_size_body as it stores them.
+__global__ __launch_bounds__(1024) void vq_ema_reduce_size_multi_kernel(const EmaMP m, int nblk) {
+  EmaQ e = m.q[0];  // (statically indexed copies, as in vq_ema_partial_multi_kernel)
+#pragma unroll
+  for (int k = 1; k < VQ_EMA_MAXQ; k++)
+    if ((int)blockIdx.y == k) e = m.q[k];
+  if ((int)blockIdx.x < nblk) {
+    const int DK = e.D * e.K, i = blockIdx.x * 1024 + threadIdx.x;
+    if (i < DK) reinterpret_cast<unsigned long long*>(e.sums)[i] = vq_ema_chunk_sum(e.part_sums, e.chunks, DK, i);
+    return;
   }
-  unsigned long long* part_sums = reinterpret_cast<unsigned long long*>(scratch);
-  int* part_counts = reinterpret_cast<int*>(part_sums + (size_t)chunks * D * K);
-  const size_t lds = (size_t)sw * K * 8 + (size_t)K * 4;
-  hipLaunchKernelGGL(vq_ema_partial_kernel, dim3(chunks, (D + sw - 1) / sw), dim3(256), lds, (hipStream_t)stream, x, ldx, idx,
-                     N, D, K, sw, fpc, part_sums, part_counts);
-  CRK_CHECK_LAUNCH();
+  vq_ema_size_body(e, m.decay, m.omd, m.eps, [&](int k) { return e.counts[k] = vq_ema_chunk_sum(e.part_counts, e.chunks, e.K, k); });
+}
+
+// ---- host side: the chunk plan, one builder for the launch record, the entry points ----
+static size_t vq_ema_partial_lds(int sw, int K) { return (size_t)sw * K * 8 + (size_t)K * 4; }
+
+static int vq_ema_plan(int N, int D, int K, int* SW, int* chunks, int* fpc) {
+  int sw = 16;
+  while (sw >= 4 && vq_ema_partial_lds(sw, K) > 150 * 1024) sw >>= 1;
+  if (sw < 4) return CRK_ERR_UNSUPPORTED;
+  int c = (N + 127) / 128;
+  if (c > 64) c = 64;
+  if (c < 1) c = 1;
+  *SW = sw; *chunks = c; *fpc = (N + c - 1) / c;
   return CRK_OK;
 }
 
-// crk_vq_ema_partial for up to 4 quantizer calls in one launch (the calls of one generator forward)
+extern "C" long long crk_vq_ema_scratch_bytes(int N, int D, int K) {
+  int sw, c, fpc;
+  if (N < 0 || D <= 0 || K <= 0 || vq_ema_plan(N, D, K, &sw, &c, &fpc) != CRK_OK) return -1;
+  return (long long)c * ((long long)D * K * 8 + (long long)K * 4);
+}
+
+static EmaMP vq_ema_record(int nq, double decay, double eps) {
+  EmaMP m{};
+  m.nq = nq; m.decay = (float)decay; m.omd = (float)(1.0 - decay); m.eps = (float)eps;
+  return m;
+}
+// One quantizer of the record.  vq_ema_q_call: an (N, D, K) call's tiling and its tables in `scratch`
+// (crk_vq_ema_scratch_bytes(N, D, K) bytes), CRK_ERR_UNSUPPORTED where K has no plan; vq_ema_q_state: the statistics and
+// the EMA state they update (NULL: the launch does not touch it).
+static int vq_ema_q_call(EmaQ& e, const void* scratch, int N, int D, int K) {
+  if (vq_ema_plan(N, D, K, &e.SW, &e.chunks, &e.fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
+  e.N = N; e.D = D; e.K = K; e.slices = (D + e.SW - 1) / e.SW;
+  e.part_sums = reinterpret_cast<unsigned long long*>(const_cast<void*>(scratch));
+  e.part_counts = reinterpret_cast<int*>(e.part_sums + (size_t)e.chunks * D * K);
+  return CRK_OK;
+}
+static void vq_ema_q_state(EmaQ& e, int D, int K, double eps, const int* counts, const long long* sums, float* ema_size,
+                           float* ema_w, float* cb) {
+  e.D = D; e.K = K; e.keps = (float)(K * eps);
+  e.counts = const_cast<int*>(counts); e.sums = const_cast<long long*>(sums);
+  e.ema_size = ema_size; e.ema_w = ema_w; e.cb = cb;
+}
+// the largest f(quantizer) of a record: the grids span the largest quantizer of the call
+template <typename F>
+static int vq_ema_max(const EmaMP& m, F f) {
+  int v = 0;
+  for (int q = 0; q < m.nq; q++) v = f(m.q[q]) > v ? f(m.q[q]) : v;
+  return v;
+}
+
+// per-chunk tables of up to 4 quantizer calls in one launch (the calls of one generator forward); scratch[q]:
+// crk_vq_ema_scratch_bytes(N[q], D[q], K[q]) bytes
 extern "C" int crk_vq_ema_partial_multi(int nq, const float* const* x, const int* ldx, const long long* const* idx, const int* N,
                                         const int* D, const int* K, void* const* scratch, void* stream) {
   if (nq < 1 || nq > 4 || !x || !ldx || !idx || !N || !D || !K || !scratch) return CRK_ERR_ARG;
-  EmaPM m{};
-  m.nq = nq;
-  int gx = 0, gy = 0;
-  size_t lds = 0;
+  EmaMP m = vq_ema_record(nq, 0.0, 0.0);
   for (int q = 0; q < nq; q++) {
     if (!x[q] || !idx[q] || !scratch[q] || (D[q] & 3) || (ldx[q] & 3)) return CRK_ERR_ARG;
-    int sw, chunks, fpc;
-    if (vq_ema_plan(N[q], D[q], K[q], &sw, &chunks, &fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
-    EmaPQ& e = m.q[q];
-    e.x = x[q]; e.idx = idx[q]; e.ldx = ldx[q]; e.N = N[q]; e.D = D[q]; e.K = K[q]; e.SW = sw; e.fpc = fpc; e.chunks = chunks;
-    e.slices = (D[q] + sw - 1) / sw;
-    e.part_sums = reinterpret_cast<unsigned long long*>(scratch[q]);
-    e.part_counts = reinterpret_cast<int*>(e.part_sums + (size_t)chunks * D[q] * K[q]);
-    if (chunks > gx) gx = chunks;
-    if (e.slices > gy) gy = e.slices;
-    const size_t need = (size_t)sw * K[q] * 8 + (size_t)K[q] * 4;
-    if (need > lds) lds = need;
+    if (vq_ema_q_call(m.q[q], scratch[q], N[q], D[q], K[q]) != CRK_OK) return CRK_ERR_UNSUPPORTED;
+    m.q[q].x = x[q]; m.q[q].idx = idx[q]; m.q[q].ldx = ldx[q];
   }
   static bool attr_set = false;
   if (!attr_set) {
@@ -1632,84 +1540,9 @@ extern "C" int crk_vq_ema_partial_multi(int nq, const float* const* x, const int
       return CRK_ERR_HIP;
     attr_set = true;
   }
-  hipLaunchKernelGGL(vq_ema_partial_multi_kernel, dim3(gx, gy, nq), dim3(256), lds, (hipStream_t)stream, m);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
-}
-
-// crk_vq_ema_reduce_multi and the cluster-size half of crk_vq_ema_apply_multi in ONE launch (single process: nothing is
-// all-reduced between them): the last workgroup of a quantizer's row sums the per-chunk counts itself (integers: the same
-// counts the other workgroups write) and runs vq_ema_size_multi_kernel's arithmetic on them, value for value.
-__global__ __launch_bounds__(1024) void vq_ema_reduce_size_multi_kernel(const EmaMP m, int nblk) {
-  __shared__ float red[1024];
-  __shared__ float sz[4096];
-  EmaQ e = m.q[0];
-#pragma unroll
-  for (int k = 1; k < VQ_EMA_MAXQ; k++)
-    if ((int)blockIdx.y == k) e = m.q[k];
-  const int DK = e.D * e.K, K = e.K, chunks = e.chunks, tid = threadIdx.x;
-  if ((int)blockIdx.x < nblk) {
-    const int i = blockIdx.x * 1024 + tid;
-    if (i < DK) {
-      unsigned long long a = 0ull;
-      int c = 0;
-      for (; c + 8 <= chunks; c += 8) {
-        unsigned long long t[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) t[u] = e.part_sums[(size_t)(c + u) * DK + i];
-#pragma unroll
-        for (int u = 0; u < 8; u++) a += t[u];
-      }
-      for (; c < chunks; c++) a += e.part_sums[(size_t)c * DK + i];
-      reinterpret_cast<unsigned long long*>(e.sums)[i] = a;
-    }
-    return;
-  }
-  float part = 0.f;
-  for (int k = tid; k < K; k += 1024) {
-    int a = 0, c = 0;
-    for (; c + 8 <= chunks; c += 8) {
-      int t[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = e.part_counts[(size_t)(c + u) * K + k];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a += t[u];
-    }
-    for (; c < chunks; c++) a += e.part_counts[(size_t)c * K + k];
-    e.counts[k] = a;
-    const float v = ema_mix(m.decay, e.ema_size[k], m.omd, (float)a);
-    sz[k] = v;
-    part += v;
-  }
-  red[tid] = part;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if (tid < o) red[tid] += red[tid + o];
-    __syncthreads();
-  }
-  const float n = red[0];
-  const float den = n + e.keps;
-  for (int k = tid; k < K; k += 1024) e.ema_size[k] = (sz[k] + m.eps) / den * n;
-}
-extern "C" int crk_vq_ema_reduce_size_multi(int nq, const void* const* scratch, const int* N, const int* D, const int* K,
-                                            int* const* counts, long long* const* sums, float* const* ema_size, double decay,
-                                            double eps, void* stream) {
-  if (nq < 1 || nq > VQ_EMA_MAXQ || !scratch || !N || !D || !K || !counts || !sums || !ema_size) return CRK_ERR_ARG;
-  EmaMP m{};
-  m.nq = nq; m.decay = (float)decay; m.omd = (float)(1.0 - decay); m.eps = (float)eps;
-  int maxdk = 0;
-  for (int q = 0; q < nq; q++) {
-    int sw, chunks, fpc;
-    if (K[q] > 4096 || vq_ema_plan(N[q], D[q], K[q], &sw, &chunks, &fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
-    EmaQ& e = m.q[q];
-    e.part_sums = reinterpret_cast<const unsigned long long*>(scratch[q]);
-    e.part_counts = reinterpret_cast<const int*>(e.part_sums + (size_t)chunks * D[q] * K[q]);
-    e.chunks = chunks; e.D = D[q]; e.K = K[q]; e.counts = counts[q]; e.sums = sums[q];
-    e.ema_size = ema_size[q]; e.keps = (float)(K[q] * eps);
-    if (D[q] * K[q] > maxdk) maxdk = D[q] * K[q];
-  }
-  const int nblk = (maxdk + 1023) / 1024;
-  hipLaunchKernelGGL(vq_ema_reduce_size_multi_kernel, dim3(nblk + 1, nq), dim3(1024), 0, (hipStream_t)stream, m, nblk);
+  const dim3 grid(vq_ema_max(m, [](const EmaQ& e) { return e.chunks; }), vq_ema_max(m, [](const EmaQ& e) { return e.slices; }), nq);
+  const size_t lds = vq_ema_max(m, [](const EmaQ& e) { return (int)vq_ema_partial_lds(e.SW, e.K); });
+  hipLaunchKernelGGL(vq_ema_partial_multi_kernel, grid, dim3(256), lds, (hipStream_t)stream, m);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -1718,41 +1551,50 @@ extern "C" int crk_vq_ema_reduce_size_multi(int nq, const void* const* scratch, 
 extern "C" int crk_vq_ema_reduce_multi(int nq, const void* const* scratch, const int* N, const int* D, const int* K,
                                        int* const* counts, long long* const* sums, void* stream) {
   if (nq < 1 || nq > VQ_EMA_MAXQ || !scratch || !N || !D || !K || !counts || !sums) return CRK_ERR_ARG;
-  EmaMP m{};
-  m.nq = nq;
-  int maxdk = 0;
+  EmaMP m = vq_ema_record(nq, 0.0, 0.0);
   for (int q = 0; q < nq; q++) {
-    int sw, chunks, fpc;
-    if (vq_ema_plan(N[q], D[q], K[q], &sw, &chunks, &fpc) != CRK_OK) return CRK_ERR_UNSUPPORTED;
-    EmaQ& e = m.q[q];
-    e.part_sums = reinterpret_cast<const unsigned long long*>(scratch[q]);
-    e.part_counts = reinterpret_cast<const int*>(e.part_sums + (size_t)chunks * D[q] * K[q]);
-    e.chunks = chunks; e.D = D[q]; e.K = K[q]; e.counts = counts[q]; e.sums = sums[q];
-    if (D[q] * K[q] > maxdk) maxdk = D[q] * K[q];
+    if (vq_ema_q_call(m.q[q], scratch[q], N[q], D[q], K[q]) != CRK_OK) return CRK_ERR_UNSUPPORTED;
+    vq_ema_q_state(m.q[q], D[q], K[q], 0.0, counts[q], sums[q], nullptr, nullptr, nullptr);
   }
+  const int maxdk = vq_ema_max(m, [](const EmaQ& e) { return e.D * e.K; });
   hipLaunchKernelGGL(vq_ema_reduce_multi_kernel, dim3((maxdk + 255) / 256, nq), dim3(256), 0, (hipStream_t)stream, m);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
 
-// crk_vq_ema_apply for every quantizer: one size launch, one blend launch
+// crk_vq_ema_reduce_multi and the cluster-size launch of crk_vq_ema_apply_multi in one (vq_ema_reduce_size_multi_kernel)
+extern "C" int crk_vq_ema_reduce_size_multi(int nq, const void* const* scratch, const int* N, const int* D, const int* K,
+                                            int* const* counts, long long* const* sums, float* const* ema_size, double decay,
+                                            double eps, void* stream) {
+  if (nq < 1 || nq > VQ_EMA_MAXQ || !scratch || !N || !D || !K || !counts || !sums || !ema_size) return CRK_ERR_ARG;
+  EmaMP m = vq_ema_record(nq, decay, eps);
+  for (int q = 0; q < nq; q++) {
+    if (K[q] > 4096 || vq_ema_q_call(m.q[q], scratch[q], N[q], D[q], K[q]) != CRK_OK) return CRK_ERR_UNSUPPORTED;
+    vq_ema_q_state(m.q[q], D[q], K[q], eps, counts[q], sums[q], ema_size[q], nullptr, nullptr);
+  }
+  const int nblk = (vq_ema_max(m, [](const EmaQ& e) { return e.D * e.K; }) + 1023) / 1024;
+  hipLaunchKernelGGL(vq_ema_reduce_size_multi_kernel, dim3(nblk + 1, nq), dim3(1024), 0, (hipStream_t)stream, m, nblk);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+static dim3 vq_ema_blend_grid(const EmaMP& m) {
+  return dim3((vq_ema_max(m, [](const EmaQ& e) { return e.K; }) + 15) / 16, (vq_ema_max(m, [](const EmaQ& e) { return e.D; }) + 15) / 16, m.nq);
+}
+
+// vqvae2.py:316-330 for every quantizer: EMA blend, Laplace smoothing (stored back), codebook refresh; one size launch, one
+// blend launch.  ema_w is (D,K), codebook (K,D), like the reference buffers.
 extern "C" int crk_vq_ema_apply_multi(int nq, const int* const* counts, const long long* const* sums,
                                       float* const* ema_size, float* const* ema_w, float* const* codebook, const int* D,
                                       const int* K, double decay, double eps, void* stream) {
   if (nq < 1 || nq > VQ_EMA_MAXQ || !counts || !sums || !ema_size || !ema_w || !codebook || !D || !K) return CRK_ERR_ARG;
-  EmaMP m{};
-  m.nq = nq; m.decay = (float)decay; m.omd = (float)(1.0 - decay); m.eps = (float)eps;
-  int maxk = 0, maxd = 0;
+  EmaMP m = vq_ema_record(nq, decay, eps);
   for (int q = 0; q < nq; q++) {
     if (K[q] > 4096) return CRK_ERR_ARG;
-    EmaQ& e = m.q[q];
-    e.D = D[q]; e.K = K[q]; e.counts = const_cast<int*>(counts[q]); e.sums = const_cast<long long*>(sums[q]);
-    e.ema_size = ema_size[q]; e.ema_w = ema_w[q]; e.cb = codebook[q]; e.keps = (float)(K[q] * eps);
-    if (K[q] > maxk) maxk = K[q];
-    if (D[q] > maxd) maxd = D[q];
+    vq_ema_q_state(m.q[q], D[q], K[q], eps, counts[q], sums[q], ema_size[q], ema_w[q], codebook[q]);
   }
   hipLaunchKernelGGL(vq_ema_size_multi_kernel, dim3(nq), dim3(1024), 0, (hipStream_t)stream, m);
-  hipLaunchKernelGGL(vq_ema_blend_multi_kernel, dim3((maxk + 15) / 16, (maxd + 15) / 16, nq), dim3(256), 0, (hipStream_t)stream, m);
+  hipLaunchKernelGGL(vq_ema_blend_multi_kernel, vq_ema_blend_grid(m), dim3(256), 0, (hipStream_t)stream, m);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -1761,17 +1603,9 @@ extern "C" int crk_vq_ema_apply_multi(int nq, const int* const* counts, const lo
 extern "C" int crk_vq_ema_blend_multi(int nq, const long long* const* sums, float* const* ema_size, float* const* ema_w,
                                       float* const* codebook, const int* D, const int* K, double decay, void* stream) {
   if (nq < 1 || nq > VQ_EMA_MAXQ || !sums || !ema_size || !ema_w || !codebook || !D || !K) return CRK_ERR_ARG;
-  EmaMP m{};
-  m.nq = nq; m.decay = (float)decay; m.omd = (float)(1.0 - decay);
-  int maxk = 0, maxd = 0;
-  for (int q = 0; q < nq; q++) {
-    EmaQ& e = m.q[q];
-    e.D = D[q]; e.K = K[q]; e.sums = const_cast<long long*>(sums[q]);
-    e.ema_size = ema_size[q]; e.ema_w = ema_w[q]; e.cb = codebook[q];
-    if (K[q] > maxk) maxk = K[q];
-    if (D[q] > maxd) maxd = D[q];
-  }
-  hipLaunchKernelGGL(vq_ema_blend_multi_kernel, dim3((maxk + 15) / 16, (maxd + 15) / 16, nq), dim3(256), 0, (hipStream_t)stream, m);
+  EmaMP m = vq_ema_record(nq, decay, 0.0);
+  for (int q = 0; q < nq; q++) vq_ema_q_state(m.q[q], D[q], K[q], 0.0, nullptr, sums[q], ema_size[q], ema_w[q], codebook[q]);
+  hipLaunchKernelGGL(vq_ema_blend_multi_kernel, vq_ema_blend_grid(m), dim3(256), 0, (hipStream_t)stream, m);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -1782,35 +1616,36 @@ extern "C" int crk_vq_ema_blend_image_multi(int nq, const long long* const* sums
                                             float* const* codebook, const int* D, const int* K, double decay, void* const* images,
                                             void* stream) {
   if (nq < 1 || nq > 4 || nq > VQ_EMA_MAXQ || !sums || !ema_size || !ema_w || !codebook || !D || !K || !images) return CRK_ERR_ARG;
-  EmaMP m{};
+  EmaMP m = vq_ema_record(nq, decay, 0.0);
   VqImgM im{};
-  m.nq = nq; m.decay = (float)decay; m.omd = (float)(1.0 - decay);
-  int ktmax = 0;
   for (int q = 0; q < nq; q++) {
     if (!sums[q] || !ema_size[q] || !ema_w[q] || !codebook[q] || !images[q] || K[q] <= 0) return CRK_ERR_ARG;
     if (D[q] != 64 || K[q] > 512) return CRK_ERR_UNSUPPORTED;
-    EmaQ& e = m.q[q];
-    e.D = D[q]; e.K = K[q]; e.sums = const_cast<long long*>(sums[q]);
-    e.ema_size = ema_size[q]; e.ema_w = ema_w[q]; e.cb = codebook[q];
+    vq_ema_q_state(m.q[q], D[q], K[q], 0.0, nullptr, sums[q], ema_size[q], ema_w[q], codebook[q]);
     im.q[q].cb = codebook[q]; im.q[q].img = (unsigned char*)images[q]; im.q[q].K = K[q];
-    const int kt = ((K[q] + 63) / 64) * 2;
-    if (kt > ktmax) ktmax = kt;
   }
+  const int ktmax = vq_ema_max(m, [](const EmaQ& e) { return ((e.K + 63) / 64) * 2; });
   hipLaunchKernelGGL(vq_ema_blend_image_multi_kernel, dim3(ktmax, nq), dim3(256), 0, (hipStream_t)stream, m, im);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
 
+// ---- the per-quantizer entry points: their own argument checks, then the launches above with nq = 1 ----
+extern "C" int crk_vq_ema_partial(const float* x, int ldx, const long long* idx, int N, int D, int K, void* scratch,
+                                  void* stream) {
+  if (!x || !idx || !scratch || (D & 3) || (ldx & 3)) return CRK_ERR_ARG;
+  return crk_vq_ema_partial_multi(1, &x, &ldx, &idx, &N, &D, &K, &scratch, stream);
+}
+
+extern "C" int crk_vq_ema_stats(const float* x, int ldx, const long long* idx, int N, int D, int K, int* counts,
+                                long long* sums, void* scratch, void* stream) {
+  if (!x || !idx || !counts || !sums || !scratch || (D & 3) || (ldx & 3)) return CRK_ERR_ARG;
+  const int rc = crk_vq_ema_partial_multi(1, &x, &ldx, &idx, &N, &D, &K, &scratch, stream);
+  return rc != CRK_OK ? rc : crk_vq_ema_reduce_multi(1, &scratch, &N, &D, &K, &counts, &sums, stream);
+}
+
 extern "C" int crk_vq_ema_apply(const int* counts, const long long* sums, float* ema_size, float* ema_w,
                                 float* codebook, int D, int K, double decay, double eps, void* stream) {
   if (!counts || !sums || !ema_size || !ema_w || !codebook || K > 4096) return CRK_ERR_ARG;
-  // python-float semantics of vqvae2.py:316-328: scalars are rounded to fp32 when
-  // they meet an fp32 tensor
-  const float decay_f = (float)decay, omd_f = (float)(1.0 - decay), eps_f = (float)eps, keps_f = (float)(K * eps);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(vq_ema_size_kernel, dim3(1), dim3(1024), 0, s, counts, ema_size, K, decay_f, omd_f, eps_f, keps_f);
-  hipLaunchKernelGGL(vq_ema_blend_kernel, dim3((K + 15) / 16, (D + 15) / 16), dim3(256), 0, s, sums, ema_size, ema_w,
-                     codebook, D, K, decay_f, omd_f);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
+  return crk_vq_ema_apply_multi(1, &counts, &sums, &ema_size, &ema_w, &codebook, &D, &K, decay, eps, stream);
 }

@@ -560,6 +560,14 @@ def vq_commit_apply(x, codebook, mask, qx_out=None, add=None, alias=False, image
     return head + r[5:] if alias else head  # (e, qx, idx, commit[, x + add][, x_alias, qx_alias])
 
 
+def _ema_scratch(who, device, N, D, K):
+    """The buffer for the per-chunk tables of one (N, D, K) quantizer call."""
+    nbytes = _lib.lib().crk_vq_ema_scratch_bytes(N, D, K)
+    if nbytes < 0:
+        raise ValueError(f"{who}: unsupported codebook size K={K}")
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
 def vq_ema_stats(x, idx, counts, sums):
     """Integer EMA statistics of one quantizer call into caller-owned buffers: counts (K) int32, sums (D*K)
     int64 2^-28 fixed point (crk_vq_ema_stats overwrites both)."""
@@ -567,10 +575,7 @@ def vq_ema_stats(x, idx, counts, sums):
     xk, ldx = _rows(x)
     K, D = counts.numel(), sums.numel() // counts.numel()
     N = idx.numel()
-    nbytes = L.crk_vq_ema_scratch_bytes(N, D, K)
-    if nbytes < 0:
-        raise ValueError(f"vq_ema_stats: unsupported codebook size K={K}")
-    scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    scratch = _ema_scratch("vq_ema_stats", x.device, N, D, K)
     check(L.crk_vq_ema_stats(ptr(xk), ldx, ptr(idx), N, D, K, ptr(counts), ptr(sums), ptr(scratch), stream_ptr()),
           "crk_vq_ema_stats")
 
@@ -581,10 +586,7 @@ def vq_ema_partial(x, idx, D, K):
     L = _lib.lib()
     xk, ldx = _rows(x)
     N = idx.numel()
-    nbytes = L.crk_vq_ema_scratch_bytes(N, D, K)
-    if nbytes < 0:
-        raise ValueError(f"vq_ema_partial: unsupported codebook size K={K}")
-    scratch = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    scratch = _ema_scratch("vq_ema_partial", x.device, N, D, K)
     check(L.crk_vq_ema_partial(ptr(xk), ldx, ptr(idx), N, D, K, ptr(scratch), stream_ptr()), "crk_vq_ema_partial")
     return scratch, N
 
@@ -602,12 +604,7 @@ def vq_ema_partial_multi(xs, idxs, Ds, Ks):
     L = _lib.lib()
     rows = [_rows(x) for x in xs]
     Ns = [i.numel() for i in idxs]
-    scr = []
-    for x, N, D, K in zip(xs, Ns, Ds, Ks):
-        nbytes = L.crk_vq_ema_scratch_bytes(N, D, K)
-        if nbytes < 0:
-            raise ValueError(f"vq_ema_partial: unsupported codebook size K={K}")
-        scr.append(torch.empty(nbytes, device=x.device, dtype=torch.uint8))
+    scr = [_ema_scratch("vq_ema_partial", x.device, N, D, K) for x, N, D, K in zip(xs, Ns, Ds, Ks)]
     check(L.crk_vq_ema_partial_multi(len(xs), _parr([r[0] for r in rows]), _iarr([r[1] for r in rows]), _parr(idxs), _iarr(Ns),
                                      _iarr(Ds), _iarr(Ks), _parr(scr), stream_ptr()), "crk_vq_ema_partial_multi")
     return list(zip(scr, Ns))

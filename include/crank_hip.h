@@ -153,7 +153,8 @@ int crk_vq_image_build_multi(int nq, const float* const* codebooks, const int* K
 /* vqvae2.py:316-321: counts[K] (int32) and sums[D][K] (int64, 2^-28 fixed point: integer
  * sums are exact and order independent).  `scratch` holds per-chunk partial tables
  * (crk_vq_ema_scratch_bytes; -1: unsupported K).  Under data parallelism all-reduce counts
- * and sums between stats and apply. */
+ * and sums between stats and apply.  crk_vq_ema_stats, crk_vq_ema_partial and crk_vq_ema_apply are the nq = 1 case
+ * of the *_multi entry points below (after their own argument checks): the same kernels, so the same bits. */
 long long crk_vq_ema_scratch_bytes(int N, int D, int K);
 int crk_vq_ema_stats(const float* x, int ldx, const long long* idx, int N, int D, int K, int* counts, long long* sums,
                      void* scratch, void* stream);
@@ -163,9 +164,9 @@ int crk_vq_ema_apply(const int* counts, const long long* sums, float* ema_size, 
                      int K, double decay, double eps, void* stream);
 /* The same update for every quantizer of a generator forward (vqvae2.py:171-190 calls the quantizers one after the
  * other; nothing reads a codebook between them) with fewer launches than four per quantizer:
- * crk_vq_ema_partial per quantizer (per-chunk tables into scratch[q]), ONE crk_vq_ema_reduce_multi (tables ->
- * counts[q], sums[q]; all-reduce them here under data parallelism), ONE crk_vq_ema_apply_multi (a size launch and a
- * blend launch for all quantizers).  nq <= 4. */
+ * crk_vq_ema_partial per quantizer or ONE crk_vq_ema_partial_multi (per-chunk tables into scratch[q]), ONE
+ * crk_vq_ema_reduce_multi (tables -> counts[q], sums[q]; all-reduce them here under data parallelism), ONE
+ * crk_vq_ema_apply_multi (a size launch and a blend launch for all quantizers).  nq <= 4. */
 int crk_vq_ema_partial(const float* x, int ldx, const long long* idx, int N, int D, int K, void* scratch, void* stream);
 int crk_vq_ema_reduce_multi(int nq, const void* const* scratch, const int* N, const int* D, const int* K,
                             int* const* counts, long long* const* sums, void* stream);
@@ -174,7 +175,7 @@ int crk_vq_ema_apply_multi(int nq, const int* const* counts, const long long* co
                            double eps, void* stream);
 /* Fewer launches for the same update in a single process (nothing is all-reduced between the steps): the per-chunk tables
  * of all quantizer calls of a forward in one launch (crk_vq_ema_partial_multi, <= 4 calls), tables -> counts / sums AND the
- * cluster-size update (the first half of crk_vq_ema_apply_multi, same arithmetic) in one launch
+ * cluster-size update (the first half of crk_vq_ema_apply_multi: the same device function) in one launch
  * (crk_vq_ema_reduce_size_multi), then the blend (crk_vq_ema_blend_multi): 3 launches per generator forward instead of 5. */
 int crk_vq_ema_partial_multi(int nq, const float* const* x, const int* ldx, const long long* const* idx, const int* N,
                              const int* D, const int* K, void* const* scratch, void* stream);

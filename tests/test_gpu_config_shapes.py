@@ -2,6 +2,8 @@
 quantizers off (D, K) = (64, 512) - the frame-per-lane search kernel with its codebook in LDS chunks, the composed path
 behind the fused search, the per-quantizer EMA - and generator stacks at the channel counts, kernel sizes, conditioning
 widths and lengths of the other configurations."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -216,6 +218,123 @@ def test_vq_ema_at_other_shapes_against_the_oracle(D, K):
         cbg = st[2].cpu().numpy()
         np.testing.assert_allclose(cbg, cb.numpy(), rtol=1e-4, atol=1e-5 * np.abs(cb.numpy()).max())
         assert np.abs(cbg[K - K // 5:]).max() > 1e3  # dead codes: ema_w over a smoothed size of ~1e-5
+
+
+# (D, K, N): 9 chunks (one unrolled group of 8 and a tail of 1) | 2 chunks, K no multiple of 16 | one frame, 8 dim slices |
+# the 64-chunk cap, a padded last image tile | slice width 4, four codes per lane in the size kernel
+EMA_EXACT_SHAPES = [(64, 512, 1100), (32, 100, 129), (128, 1024, 1), (64, 500, 8200), (32, 4096, 300)]
+EMA_DECAY, EMA_EPS = 0.99, 1e-5
+
+
+def _ema_mix_exact(decay, a, omd, b):
+    """ema_mix of vq_kernels.hip on fp32 arrays: fl32(omd * b), then decay * a + t with ONE rounding (a fused
+    multiply-add).  Formed in float64, where the product is exact, and rounded to fp32: that differs from the single
+    rounding only where the float64 sum lies exactly on an fp32 midpoint.  Returns (values, number of such elements)."""
+    t = omd * b
+    assert t.dtype == np.float32
+    v = np.float64(decay) * a.astype(np.float64) + t.astype(np.float64)
+    return v.astype(np.float32), int(np.count_nonzero((v.view(np.uint64) & np.uint64(0x1FFFFFFF)) == np.uint64(0x10000000)))
+
+
+@functools.lru_cache(maxsize=None)
+def _ema_exact_case(D, K, N):
+    """Inputs of three EMA updates in a row (drawn as in test_vq_ema_at_other_shapes_against_the_oracle, the last fifth
+    of the codes dead) and what the kernels must leave after each, restated on the CPU in the kernels' rounding order:
+    [(x, idx, counts, sums, ema_size, ema_w, codebook)], the initial (ema_size, ema_w), and the midpoint count."""
+    f32 = np.float32
+    rs = np.random.RandomState(1000 + D + K + N)
+    size = np.where(np.arange(K) < K - K // 5, rs.uniform(1, 30, K), 0.0).astype(f32)
+    ema_w = rs.standard_normal((D, K)).astype(f32)
+    init, steps, mid = (size, ema_w), [], 0
+    decay, omd, eps, keps = f32(EMA_DECAY), f32(1.0 - EMA_DECAY), f32(EMA_EPS), f32(K * EMA_EPS)
+    for it in range(3):
+        x = (rs.standard_normal((N, D)) * (1.0 + it)).astype(f32)
+        idx = rs.randint(0, K - K // 5, N).astype(np.int64)
+        counts = np.bincount(idx, minlength=K).astype(np.int32)
+        sums = np.zeros((D, K), np.int64)
+        np.add.at(sums.T, idx, np.rint(x.astype(np.float64) * 2.0 ** 28).astype(np.int64))
+        # cluster sizes: 1024 lanes add their codes k = lane, lane + 1024, ... in turn, a tree adds the lanes
+        v, m = _ema_mix_exact(decay, size, omd, counts.astype(f32))
+        mid += m
+        lanes = np.zeros(-(-K // 1024) * 1024, f32)
+        lanes[:K] = v
+        red = np.zeros(1024, f32)
+        for row in lanes.reshape(-1, 1024):
+            red = red + row
+        o = 512
+        while o > 0:
+            red[:o] = red[:o] + red[o:2 * o]
+            o >>= 1
+        n = red[0]
+        den = n + keps
+        size = (v + eps) / den * n
+        # blend
+        es = sums.astype(f32) * f32(2.0 ** -28)
+        ema_w, m = _ema_mix_exact(decay, ema_w, omd, es)
+        mid += m
+        cb = np.ascontiguousarray((ema_w / size[None, :]).T)
+        assert size.dtype == ema_w.dtype == cb.dtype == f32
+        for a in (x, idx, counts, sums, size, ema_w, cb):
+            a.setflags(write=False)
+        steps.append((x, idx, counts, sums, size, ema_w, cb))
+    return steps, init, mid
+
+
+@pytest.mark.parametrize("shapes", [[s] for s in EMA_EXACT_SHAPES] + [EMA_EXACT_SHAPES[:4]],
+                         ids=lambda ss: "+".join("x".join(map(str, s)) for s in ss))
+def test_vq_ema_every_entry_point_equals_an_exact_cpu_restatement(shapes):
+    """Every EMA entry point against a NumPy restatement of the kernels' arithmetic in their rounding order, bit for
+    bit - counts, fixed-point sums, ema_size, ema_w and codebook after each of three updates in a row: (A) stats + apply,
+    (B) partial + reduce_multi + apply_multi, (C) partial_multi + reduce_size_multi + blend_multi, (D, for D = 64 and
+    K <= 512) the same with the blend that leaves the search image current, which must equal vq_image_build of the new
+    codebook; then four shapes in one nq = 4 call through (B) and (C).  The oracle tests pin this arithmetic to 2e-5
+    only, and the batched-equals-single tests compare one kernel with itself; this is the exact anchor."""
+    from crank_amd import ops
+
+    def dev(a):  # (a copy: the shared reference arrays are read-only)
+        return torch.tensor(a, device="cuda")
+
+    cases = [_ema_exact_case(*s) for s in shapes]
+    assert sum(c[2] for c in cases) == 0  # no element on an fp32 midpoint: the restatement is exact for these inputs
+    Ds, Ks = [s[0] for s in shapes], [s[1] for s in shapes]
+    single = len(shapes) == 1
+    paths = ["B", "C"] + (["A"] if single else []) + (["D"] if single and Ds[0] == 64 and Ks[0] <= 512 else [])
+    for path in paths:
+        size = [dev(c[1][0]) for c in cases]
+        ema_w = [dev(c[1][1]) for c in cases]
+        cb = [torch.zeros(K, D, device="cuda") for D, K in zip(Ds, Ks)]
+        for it in range(3):
+            xs = [dev(c[0][it][0]) for c in cases]
+            idxs = [dev(c[0][it][1]) for c in cases]
+            counts = [torch.empty(K, device="cuda", dtype=torch.int32) for K in Ks]
+            sums = [torch.empty(D * K, device="cuda", dtype=torch.int64) for D, K in zip(Ds, Ks)]
+            img = None
+            if path == "A":
+                ops.vq_ema_stats(xs[0], idxs[0], counts[0], sums[0])
+                ops.vq_ema_apply(counts[0], sums[0], size[0], ema_w[0], cb[0], EMA_DECAY, EMA_EPS)
+            elif path == "B":
+                parts = [ops.vq_ema_partial(x, i, D, K) for x, i, D, K in zip(xs, idxs, Ds, Ks)]
+                ops.vq_ema_reduce_multi([p[0] for p in parts], [p[1] for p in parts], Ds, Ks, counts, sums)
+                ops.vq_ema_apply_multi(counts, sums, size, ema_w, cb, Ds, Ks, EMA_DECAY, EMA_EPS)
+            else:
+                parts = ops.vq_ema_partial_multi(xs, idxs, Ds, Ks)
+                ops.vq_ema_reduce_size_multi([p[0] for p in parts], [p[1] for p in parts], Ds, Ks, counts, sums, size,
+                                             EMA_DECAY, EMA_EPS)
+                if path == "D":
+                    img = [torch.full((ops.vq_image_bytes(Ks[0], 64),), 0x5A, device="cuda", dtype=torch.uint8)]
+                assert ops.vq_ema_blend_multi(sums, size, ema_w, cb, Ds, Ks, EMA_DECAY, images=img) is (path == "D")
+            if img is not None:
+                built = [torch.full_like(img[0], 0xA5)]
+                ops.vq_image_build(cb, built)
+                assert torch.equal(img[0], built[0]), (path, it)
+            torch.cuda.synchronize()
+            for q, c in enumerate(cases):
+                _, _, r_counts, r_sums, r_size, r_w, r_cb = c[0][it]
+                got = (counts[q], sums[q].view(Ds[q], Ks[q]), size[q], ema_w[q], cb[q])
+                for name, g, r in zip(("counts", "sums", "ema_size", "ema_w", "codebook"), got, (r_counts, r_sums, r_size, r_w, r_cb)):
+                    g = g.cpu().numpy()
+                    # (bytes, so that neither a NaN nor the sign of a zero can hide)
+                    assert g.tobytes() == r.tobytes(), (path, shapes[q], it, name, int(np.count_nonzero(g != r)), g[g != r][:4], r[g != r][:4])
 
 
 def test_generator_ema_of_quantizers_of_different_shapes_equals_each_alone():
