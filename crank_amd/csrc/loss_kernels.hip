@@ -7,6 +7,7 @@
 // All reductions are two-stage (per-workgroup partials, then one finishing block) so
 // results are deterministic; there are no host synchronisations.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -20,15 +21,20 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// Finishing step of the two-stage reductions: ONE workgroup sums the partials in a fixed order.  (A "last workgroup
-// finishes" scheme was measured and dropped: a device-scope fence per workgroup costs an L2 write-back on this
-// multi-XCD part - 1024 of them turned a 12 us kernel into a 34 us one, a finishing launch costs ~4 us.)
-__device__ __forceinline__ void mean_from_partials(const float* part, int nblocks, float* out, float* sh) {
-  float s = 0.f, c = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { s += part[2 * i]; c += part[2 * i + 1]; }
-  s = block_sum_256(s, sh);
-  c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) { out[0] = s / c; out[1] = c; }  // 0/0 -> NaN like torch's mean of an empty tensor
+// Finishing step of the two-stage reductions: ONE workgroup sums the partials in a fixed order - a thread-strided loop over
+// the n workgroups' records (`stride` floats apart, the first NC floats of each summed), then block_sum_256 per column.
+// (A "last workgroup finishes" scheme was measured and dropped: a device-scope fence per workgroup costs an L2 write-back
+// on this multi-XCD part - 1024 of them turned a 12 us kernel into a 34 us one, a finishing launch costs ~4 us.)
+template <int NC>
+__device__ __forceinline__ void sum_partials(const float* part, int stride, int n, float (&s)[NC], float* sh) {
+#pragma unroll
+  for (int j = 0; j < NC; j++) s[j] = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+#pragma unroll
+    for (int j = 0; j < NC; j++) s[j] += part[stride * i + j];
+  }
+#pragma unroll
+  for (int j = 0; j < NC; j++) s[j] = block_sum_256(s[j], sh);
 }
 
 // ------------------------------------------------------------------------------
@@ -40,126 +46,146 @@ __device__ __forceinline__ void mean_from_partials(const float* part, int nblock
 #define LOSS_MAX_BLOCKS 1024
 #define LOSS_MAX_RES 4                                  // STFT resolutions of one fused launch
 
-__global__ __launch_bounds__(256) void masked_loss_partial(const float* __restrict__ x, int ldx,
-                                                           const float* __restrict__ y, int ldy, float yconst,
-                                                           const unsigned char* __restrict__ mask, long N, int D,
-                                                           int mode, float* __restrict__ part) {
-  __shared__ float sh[4];
-  float s = 0.f, c = 0.f;
-  const long total = N * D;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long n = i / D;
-    const int d = (int)(i - n * D);
-    if (mask && !mask[n]) continue;
-    const float yv = y ? y[n * ldy + d] : yconst;
-    const float df = x[n * ldx + d] - yv;
-    s += mode == 0 ? fabsf(df) : df * df;
-    c += 1.f;
-  }
-  s = block_sum_256(s, sh);
-  c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s; part[2 * blockIdx.x + 1] = c; }
-}
-
-// four consecutive channels per thread (16-byte loads): D, the row strides and the pointers are multiples of 4 floats,
-// y is a tensor.  MODE 0 / 1: partials {sum, count}; 2: {sum |d|, sum d^2, count} (masked_loss_both_partial's).
-template <int MODE>
-__global__ __launch_bounds__(256) void masked_loss_partial4(const float* __restrict__ x, int ldx,
-                                                            const float* __restrict__ y, int ldy,
-                                                            const unsigned char* __restrict__ mask, long N, int D4,
-                                                            float* __restrict__ part) {
-  __shared__ float sh[4];
-  float s1 = 0.f, s2 = 0.f, c = 0.f;
-  const long total = N * D4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long n = i / D4;
-    const int d = (int)(i - n * D4) * 4;
-    if (mask && !mask[n]) continue;
-    const float4 xv = *reinterpret_cast<const float4*>(x + n * ldx + d);
-    const float4 yv = *reinterpret_cast<const float4*>(y + n * ldy + d);
-    const float df[4] = {xv.x - yv.x, xv.y - yv.y, xv.z - yv.z, xv.w - yv.w};
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      if (MODE != 1) s1 += fabsf(df[j]);
-      if (MODE != 0) s2 += df[j] * df[j];
-    }
-    c += 4.f;
-  }
-  if (MODE != 1) s1 = block_sum_256(s1, sh);
-  if (MODE != 0) s2 = block_sum_256(s2, sh);
-  c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) {
-    if (MODE == 2) { part[3 * blockIdx.x] = s1; part[3 * blockIdx.x + 1] = s2; part[3 * blockIdx.x + 2] = c; }
-    else { part[2 * blockIdx.x] = MODE == 0 ? s1 : s2; part[2 * blockIdx.x + 1] = c; }
-  }
+static int loss_blocks(long total) {
+  long b = (total + 255) / 256;
+  if (b > LOSS_MAX_BLOCKS) b = LOSS_MAX_BLOCKS;
+  if (b < 1) b = 1;
+  return (int)b;
 }
 __device__ __host__ inline bool loss_vec4_ok(const void* a, const void* b, const void* c, int D, int l0, int l1, int l2) {
   return !((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) && !((D | l0 | l1 | l2) & 3);
 }
 
+// x - y of V consecutive channels: V = 4 with 16-byte loads (D, the row strides and the pointers are multiples of 4
+// floats, y is a tensor), V = 1 with y == nullptr meaning the constant target
+template <int V>
+__device__ __forceinline__ void loss_diff(const float* x, const float* y, float yconst, float (&df)[V]) {
+  if constexpr (V == 4) {
+    const float4 xv = *reinterpret_cast<const float4*>(x);
+    const float4 yv = *reinterpret_cast<const float4*>(y);
+    df[0] = xv.x - yv.x; df[1] = xv.y - yv.y; df[2] = xv.z - yv.z; df[3] = xv.w - yv.w;
+  } else {
+    df[0] = x[0] - (y ? y[0] : yconst);
+  }
+}
+
+// THE masked element loop: items first, first + step, ... of the N * DV items (V consecutive channels of a frame each)
+// add to s1 = sum |x-y| (MODE 0 and 2), s2 = sum (x-y)^2 (MODE 1 and 2) and the element count c.
+// The rounding of s2 is pinned, and only to keep the bits of earlier builds: the first channel of a 16-byte item joins
+// the sum through one fused multiply-add, every other element (and every element of the scalar path) as a rounded square
+// and an addition.  Nothing else argues for the asymmetry.  It is what every copy of this loop compiled to while
+// contraction was the compiler's to choose (it fused the one product the vectoriser left alone); written down, the
+// MSE-only, both-sums and fused reconstruction kernels agree bit for bit by construction.
+template <int V, int MODE>
+__device__ __forceinline__ void masked_sums(const float* __restrict__ x, int ldx, const float* __restrict__ y, int ldy,
+                                            float yconst, const unsigned char* __restrict__ mask, long N, int DV, long first,
+                                            long step, float& s1, float& s2, float& c) {
+#pragma clang fp contract(off)
+  const long total = N * DV;
+  for (long i = first; i < total; i += step) {
+    const long n = i / DV;
+    const int d = (int)(i - n * DV) * V;
+    if (mask && !mask[n]) continue;
+    float df[V];
+    loss_diff<V>(x + n * ldx + d, y ? y + n * ldy + d : nullptr, yconst, df);
+#pragma unroll
+    for (int j = 0; j < V; j++) {
+      if (MODE != 1) s1 += fabsf(df[j]);
+      if (MODE != 0) s2 = (V == 4 && j == 0) ? __builtin_fmaf(df[j], df[j], s2) : s2 + df[j] * df[j];
+    }
+    c += (float)V;
+  }
+}
+// the workgroup's record of such sums: {sum, count} (MODE 0 / 1) or {sum |d|, sum d^2, count} (MODE 2)
+template <int MODE>
+__device__ __forceinline__ void masked_sums_store(float s1, float s2, float c, float* rec, float* sh) {
+  if (MODE != 1) s1 = block_sum_256(s1, sh);
+  if (MODE != 0) s2 = block_sum_256(s2, sh);
+  c = block_sum_256(c, sh);
+  if (threadIdx.x == 0) {
+    if (MODE == 2) { rec[0] = s1; rec[1] = s2; rec[2] = c; }
+    else { rec[0] = MODE == 0 ? s1 : s2; rec[1] = c; }
+  }
+}
+
+template <int V, int MODE>
+__global__ __launch_bounds__(256) void masked_loss_partial(const float* __restrict__ x, int ldx,
+                                                           const float* __restrict__ y, int ldy, float yconst,
+                                                           const unsigned char* __restrict__ mask, long N, int DV,
+                                                           float* __restrict__ part) {
+  __shared__ float sh[4];
+  float s1 = 0.f, s2 = 0.f, c = 0.f;
+  masked_sums<V, MODE>(x, ldx, y, ldy, yconst, mask, N, DV, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256, s1, s2,
+                       c);
+  masked_sums_store<MODE>(s1, s2, c, part + (MODE == 2 ? 3 : 2) * blockIdx.x, sh);
+}
+
+// {mean, count} from {sum, count} records (0/0 -> NaN like torch's mean of an empty tensor); cross entropy finishes here too
 __global__ __launch_bounds__(256) void masked_loss_final(const float* __restrict__ part, int nblocks,
                                                          float* __restrict__ out) {
   __shared__ float sh[4];
-  mean_from_partials(part, nblocks, out, sh);
+  float s[2];
+  sum_partials<2>(part, 2, nblocks, s, sh);
+  if (threadIdx.x == 0) { out[0] = s[0] / s[1]; out[1] = s[1]; }
 }
 
-// L1 and MSE of the same pair in one pass (the trainers ask for both on the decoded features): partials {sum|d|, sum d^2,
-// count}; out4 = {L1 mean, count, MSE mean, count}, each half what the single-mode entry points write.  Same loop and
-// reduction order as the single-mode kernels: identical values.
-__global__ __launch_bounds__(256) void masked_loss_both_partial(const float* __restrict__ x, int ldx,
-                                                                const float* __restrict__ y, int ldy,
-                                                                const unsigned char* __restrict__ mask, long N, int D,
-                                                                float* __restrict__ part) {
-  __shared__ float sh[4];
-  float s1 = 0.f, s2 = 0.f, c = 0.f;
-  const long total = N * D;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long n = i / D;
-    const int d = (int)(i - n * D);
-    if (mask && !mask[n]) continue;
-    const float df = x[n * ldx + d] - y[n * ldy + d];
-    s1 += fabsf(df);
-    s2 += df * df;
-    c += 1.f;
-  }
-  s1 = block_sum_256(s1, sh);
-  s2 = block_sum_256(s2, sh);
-  c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) { part[3 * blockIdx.x] = s1; part[3 * blockIdx.x + 1] = s2; part[3 * blockIdx.x + 2] = c; }
+// L1 and MSE of the same pair in one pass (the trainers ask for both on the decoded features): out4 = {L1 mean, count,
+// MSE mean, count} from the sums of {sum|d|, sum d^2, count} records, each half what the single-mode entry points write.
+__device__ __forceinline__ void both_means(const float (&s)[3], float* out4) {
+  out4[0] = s[0] / s[2]; out4[1] = s[2]; out4[2] = s[1] / s[2]; out4[3] = s[2];
 }
 __global__ __launch_bounds__(256) void masked_loss_both_final(const float* __restrict__ part, int nblocks,
                                                               float* __restrict__ out) {
   __shared__ float sh[4];
-  float s1 = 0.f, s2 = 0.f, c = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { s1 += part[3 * i]; s2 += part[3 * i + 1]; c += part[3 * i + 2]; }
-  s1 = block_sum_256(s1, sh);
-  s2 = block_sum_256(s2, sh);
-  c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) { out[0] = s1 / c; out[1] = c; out[2] = s2 / c; out[3] = c; }
+  float s[3];
+  sum_partials<3>(part, 3, nblocks, s, sh);
+  if (threadIdx.x == 0) both_means(s, out);
 }
+
+// the partial launch of mode 0 / 1 / 2 on the 16-byte path where the operands allow it; returns its workgroups
+static int masked_partial_launch(const float* x, int ldx, const float* y, int ldy, float yconst, const unsigned char* mask,
+                                 long N, int D, int mode, float* part, hipStream_t s) {
+  const bool v4 = y && loss_vec4_ok(x, y, nullptr, D, ldx, ldy, 0);
+  const int DV = v4 ? D / 4 : D, nb = loss_blocks(N * DV);
+#define ML_LAUNCH(V, M) hipLaunchKernelGGL((masked_loss_partial<V, M>), dim3(nb), dim3(256), 0, s, x, ldx, y, ldy, yconst, mask, N, DV, part)
+  if (v4) { if (mode == 0) ML_LAUNCH(4, 0); else if (mode == 1) ML_LAUNCH(4, 1); else ML_LAUNCH(4, 2); }
+  else { if (mode == 0) ML_LAUNCH(1, 0); else if (mode == 1) ML_LAUNCH(1, 1); else ML_LAUNCH(1, 2); }
+#undef ML_LAUNCH
+  return nb;
+}
+
 extern "C" int crk_masked_loss_both_fwd(const float* x, int ldx, const float* y, int ldy, const unsigned char* mask,
                                         long long N, int D, float* out4, float* scratch, void* stream) {
   if (!x || !y || !out4 || !scratch || N < 0 || D <= 0) return CRK_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  long b = (N * D + 255) / 256;
-  const int nb = (int)(b > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : (b < 1 ? 1 : b));
-  if (loss_vec4_ok(x, y, nullptr, D, ldx, ldy, 0)) {
-    long b4 = (N * (D / 4) + 255) / 256;
-    const int nb4 = (int)(b4 > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : (b4 < 1 ? 1 : b4));
-    hipLaunchKernelGGL(masked_loss_partial4<2>, dim3(nb4), dim3(256), 0, s, x, ldx, y, ldy, mask, (long)N, D / 4, scratch);
-    hipLaunchKernelGGL(masked_loss_both_final, dim3(1), dim3(256), 0, s, scratch, nb4, out4);
-    CRK_CHECK_LAUNCH();
-    return CRK_OK;
-  }
-  hipLaunchKernelGGL(masked_loss_both_partial, dim3(nb), dim3(256), 0, s, x, ldx, y, ldy, mask, (long)N, D, scratch);
+  const int nb = masked_partial_launch(x, ldx, y, ldy, 0.f, mask, (long)N, D, 2, scratch, s);
   hipLaunchKernelGGL(masked_loss_both_final, dim3(1), dim3(256), 0, s, scratch, nb, out4);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
 
+extern "C" int crk_masked_loss_fwd(const float* x, int ldx, const float* y, int ldy, float yconst,
+                                   const unsigned char* mask, long long N, int D, int mode, float* out2,
+                                   float* scratch, void* stream) {
+  if (!x || !out2 || !scratch || N < 0 || D <= 0) return CRK_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = masked_partial_launch(x, ldx, y, ldy, yconst, mask, (long)N, D, mode == 0 ? 0 : 1, scratch, s);
+  hipLaunchKernelGGL(masked_loss_final, dim3(1), dim3(256), 0, s, scratch, nb, out2);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+// d |d| / dx and d d^2 / dx of one element, times the upstream gradient over the count
+__device__ __forceinline__ float l1_grad(float df, float g) { return df > 0.f ? g : (df < 0.f ? -g : 0.f); }
+__device__ __forceinline__ float mse_grad(float df, float g) { return 2.f * df * g; }
+
+// dx = add * add_scale + d loss / dx (add optional), dy = -d loss / dx; V = 4: four consecutive channels of a frame per
+// thread (16-byte accesses: D, the row strides and the pointers are multiples of 4 floats, y is a tensor, only dx is
+// wanted).  Per-element arithmetic is the same in both: identical values.
+template <int V>
 __global__ __launch_bounds__(256) void masked_loss_bwd(const float* __restrict__ x, int ldx,
                                                        const float* __restrict__ y, int ldy, float yconst,
-                                                       const unsigned char* __restrict__ mask, long N, int D,
+                                                       const unsigned char* __restrict__ mask, long N, int DV,
                                                        int mode, const float* __restrict__ stat,
                                                        const float* __restrict__ gout, float* __restrict__ dx,
                                                        int lddx, float* __restrict__ dy, int lddy,
@@ -167,51 +193,30 @@ __global__ __launch_bounds__(256) void masked_loss_bwd(const float* __restrict__
                                                        const float* __restrict__ add_scale) {
   const float g = gout[0] / stat[1];
   const float as = add_scale ? add_scale[0] : 1.f;
-  const long total = N * D;
+  const long total = N * DV;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long n = i / D;
-    const int d = (int)(i - n * D);
-    float r = 0.f;
-    if (!mask || mask[n]) {
-      const float yv = y ? y[n * ldy + d] : yconst;
-      const float df = x[n * ldx + d] - yv;
-      r = mode == 0 ? (df > 0.f ? g : (df < 0.f ? -g : 0.f)) : 2.f * df * g;
-    }
-    if (dx) dx[n * lddx + d] = add ? add[n * ldadd + d] * as + r : r;
-    if (dy) dy[n * lddy + d] = -r;
-  }
-}
-
-// the same, four consecutive channels of a frame per thread (16-byte accesses): D, the row strides and the pointers are
-// multiples of 4 floats, y is a tensor, only dx is wanted.  Per-element arithmetic unchanged: identical values.
-__global__ __launch_bounds__(256) void masked_loss_bwd4(const float* __restrict__ x, int ldx,
-                                                        const float* __restrict__ y, int ldy,
-                                                        const unsigned char* __restrict__ mask, long N, int D4,
-                                                        int mode, const float* __restrict__ stat,
-                                                        const float* __restrict__ gout, float* __restrict__ dx,
-                                                        int lddx, const float* __restrict__ add, int ldadd,
-                                                        const float* __restrict__ add_scale) {
-  const float g = gout[0] / stat[1];
-  const float as = add_scale ? add_scale[0] : 1.f;
-  const long total = N * D4;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long n = i / D4;
-    const int d = (int)(i - n * D4) * 4;
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!mask || mask[n]) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + n * ldx + d);
-      const float4 yv = *reinterpret_cast<const float4*>(y + n * ldy + d);
-      const float df[4] = {xv.x - yv.x, xv.y - yv.y, xv.z - yv.z, xv.w - yv.w};
-      float rr[4];
+    const long n = i / DV;
+    const int d = (int)(i - n * DV) * V;
+    float r[V];
 #pragma unroll
-      for (int j = 0; j < 4; j++) rr[j] = mode == 0 ? (df[j] > 0.f ? g : (df[j] < 0.f ? -g : 0.f)) : 2.f * df[j] * g;
-      r = make_float4(rr[0], rr[1], rr[2], rr[3]);
+    for (int j = 0; j < V; j++) r[j] = 0.f;
+    if (!mask || mask[n]) {
+      float df[V];
+      loss_diff<V>(x + n * ldx + d, y ? y + n * ldy + d : nullptr, yconst, df);
+#pragma unroll
+      for (int j = 0; j < V; j++) r[j] = mode == 0 ? l1_grad(df[j], g) : mse_grad(df[j], g);
     }
-    if (add) {
-      const float4 a = *reinterpret_cast<const float4*>(add + n * ldadd + d);
-      r = make_float4(a.x * as + r.x, a.y * as + r.y, a.z * as + r.z, a.w * as + r.w);
+    if constexpr (V == 4) {
+      float4 o = make_float4(r[0], r[1], r[2], r[3]);
+      if (add) {
+        const float4 a = *reinterpret_cast<const float4*>(add + n * ldadd + d);
+        o = make_float4(a.x * as + o.x, a.y * as + o.y, a.z * as + o.z, a.w * as + o.w);
+      }
+      *reinterpret_cast<float4*>(dx + n * lddx + d) = o;
+    } else {
+      if (dx) dx[n * lddx + d] = add ? add[n * ldadd + d] * as + r[0] : r[0];
+      if (dy) dy[n * lddy + d] = -r[0];
     }
-    *reinterpret_cast<float4*>(dx + n * lddx + d) = r;
   }
 }
 
@@ -237,11 +242,10 @@ __global__ __launch_bounds__(256) void masked_loss_join4(const float* __restrict
     const int d = (int)(i - n * D4) * 4;
     float r[4] = {0.f, 0.f, 0.f, 0.f};
     if (!mask || mask[n]) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + n * ldx + d);
-      const float4 yv = *reinterpret_cast<const float4*>(y + n * ldy + d);
-      const float df[4] = {xv.x - yv.x, xv.y - yv.y, xv.z - yv.z, xv.w - yv.w};
+      float df[4];
+      loss_diff<4>(x + n * ldx + d, y + n * ldy + d, 0.f, df);
 #pragma unroll
-      for (int j = 0; j < 4; j++) r[j] = 2.f * df[j] * g;
+      for (int j = 0; j < 4; j++) r[j] = mse_grad(df[j], g);
     }
     if (a1 || a2) {
       float4 s = *reinterpret_cast<const float4*>((a1 ? a1 + n * ld1 : a2 + n * ld2) + d);
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(256) void masked_loss_join4(const float* __restrict
         const float4 b = *reinterpret_cast<const float4*>(a2 + n * ld2 + d);
         s = make_float4(s.x + b.x, s.y + b.y, s.z + b.z, s.w + b.w);
       }
-      // (masked_loss_bwd4 forms fma(s, scale, r) with its scale at 1: one rounding, of s + r)
+      // (masked_loss_bwd<4> forms fma(s, scale, r) with its scale at 1: one rounding, of s + r)
       r[0] = s.x + r[0]; r[1] = s.y + r[1]; r[2] = s.z + r[2]; r[3] = s.w + r[3];
     }
     if (dsum) *reinterpret_cast<float4*>(dsum + n * ldsum + d) = make_float4(r[0], r[1], r[2], r[3]);
@@ -261,49 +265,18 @@ __global__ __launch_bounds__(256) void masked_loss_join4(const float* __restrict
   }
 }
 
-static int loss_blocks(long total) {
-  long b = (total + 255) / 256;
-  if (b > LOSS_MAX_BLOCKS) b = LOSS_MAX_BLOCKS;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-extern "C" int crk_masked_loss_fwd(const float* x, int ldx, const float* y, int ldy, float yconst,
-                                   const unsigned char* mask, long long N, int D, int mode, float* out2,
-                                   float* scratch, void* stream) {
-  if (!x || !out2 || !scratch || N < 0 || D <= 0) return CRK_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (y && loss_vec4_ok(x, y, nullptr, D, ldx, ldy, 0)) {
-    const int nb4 = loss_blocks(N * (D / 4));
-    if (mode == 0) hipLaunchKernelGGL(masked_loss_partial4<0>, dim3(nb4), dim3(256), 0, s, x, ldx, y, ldy, mask, (long)N, D / 4, scratch);
-    else hipLaunchKernelGGL(masked_loss_partial4<1>, dim3(nb4), dim3(256), 0, s, x, ldx, y, ldy, mask, (long)N, D / 4, scratch);
-    hipLaunchKernelGGL(masked_loss_final, dim3(1), dim3(256), 0, s, scratch, nb4, out2);
-    CRK_CHECK_LAUNCH();
-    return CRK_OK;
-  }
-  const int nb = loss_blocks(N * D);
-  hipLaunchKernelGGL(masked_loss_partial, dim3(nb), dim3(256), 0, s, x, ldx, y, ldy, yconst, mask, (long)N, D, mode, scratch);
-  hipLaunchKernelGGL(masked_loss_final, dim3(1), dim3(256), 0, s, scratch, nb, out2);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
-}
-
 extern "C" int crk_masked_loss_bwd_acc(const float* x, int ldx, const float* y, int ldy, float yconst,
                                        const unsigned char* mask, long long N, int D, int mode, const float* stat2,
                                        const float* gout, float* dx, int lddx, float* dy, int lddy, const float* add,
                                        int ldadd, const float* add_scale, void* stream) {
   if (!x || !stat2 || !gout) return CRK_ERR_ARG;
   const bool al16 = !((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)dx) | ((uintptr_t)add)) & 15);
-  if (y && dx && !dy && al16 && !((D | ldx | ldy | lddx | (add ? ldadd : 0)) & 3)) {
-    const int nb4 = loss_blocks(N * (D / 4));
-    hipLaunchKernelGGL(masked_loss_bwd4, dim3(nb4), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, mask, (long)N, D / 4, mode,
-                       stat2, gout, dx, lddx, add, ldadd, add_scale);
-    CRK_CHECK_LAUNCH();
-    return CRK_OK;
-  }
-  const int nb = loss_blocks(N * D);
-  hipLaunchKernelGGL(masked_loss_bwd, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, yconst, mask, (long)N,
-                     D, mode, stat2, gout, dx, lddx, dy, lddy, add, ldadd, add_scale);
+  if (y && dx && !dy && al16 && !((D | ldx | ldy | lddx | (add ? ldadd : 0)) & 3))
+    hipLaunchKernelGGL(masked_loss_bwd<4>, dim3(loss_blocks(N * (D / 4))), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy,
+                       yconst, mask, (long)N, D / 4, mode, stat2, gout, dx, lddx, dy, lddy, add, ldadd, add_scale);
+  else
+    hipLaunchKernelGGL(masked_loss_bwd<1>, dim3(loss_blocks(N * D)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, yconst,
+                       mask, (long)N, D, mode, stat2, gout, dx, lddx, dy, lddy, add, ldadd, add_scale);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -477,21 +450,55 @@ __device__ __forceinline__ int reflect_idx(int s, int T) {
   return s;
 }
 
+// One (frame, bin) point of the loss, from the powers re^2 + im^2 of x and y: the magnitude with its clamp, the point's
+// loss term, and k with d term / d (re, im) of x = k * (re, im) for an upstream gradient g (valid where the power of x is
+// above the clamp: the gradient is 0 below it).  olr = 1 - logratio, lr = logratio.
+__device__ __forceinline__ float stft_mag(float pw) { return sqrtf(fmaxf(pw, 1e-7f)); }
+__device__ __forceinline__ float stft_point_loss(float mx, float my, float olr, float lr) {
+  float v = olr * fabsf(mx - my);
+  if (lr != 0.f) v += lr * fabsf(logf(mx) - logf(my));
+  return v;
+}
+__device__ __forceinline__ float stft_point_coef(float mx, float my, float olr, float lr, float g) {
+  const float dm = mx - my;
+  float c = olr * (dm > 0.f ? 1.f : (dm < 0.f ? -1.f : 0.f));
+  if (lr != 0.f) {
+    const float dl = logf(mx) - logf(my);
+    c += lr * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f)) / mx;
+  }
+  return g * c / mx;
+}
+
+// LDS twiddles of one resolution: cos [n_bins][W], sin [n_bins][W], times the window; TILE: W is a tile of p.win or more
+// taps, zero from tap p.win on (otherwise W == p.win)
+template <bool TILE>
+__device__ __forceinline__ void stft_fill_twiddles(const StftP& p, int W, float* tw) {
+  const int nb = p.n_bins;
+  const int lpad = (p.n_fft - p.win) / 2;
+  for (int i = threadIdx.x; i < nb * W; i += 256) {
+    const int f = i / W, j = i - f * W;
+    float c = 0.f, s = 0.f;
+    if (!TILE || j < p.win) {
+      // exact phase reduction: angle = 2*pi*((f*(j+lpad)) mod n_fft)/n_fft
+      const int ph = (int)(((long)f * (j + lpad)) % p.n_fft);
+      const float a = 6.283185307179586476925f * (float)ph / (float)p.n_fft;
+      c = cosf(a) * p.window[j];
+      s = sinf(a) * p.window[j];
+    }
+    tw[i] = c;
+    tw[nb * W + i] = s;
+  }
+  __syncthreads();
+}
+
+// Windows above 64 taps: one thread per (signal, frame, bin), the gradient with win atomics per point.
 template <bool BWD>
 __global__ __launch_bounds__(256) void stft_loss_kernel(const StftP p) {
   extern __shared__ float tw[];  // cos [n_bins][win], sin [n_bins][win]
   __shared__ float sh[4];
   const int nb = p.n_bins, W = p.win;
   const int lpad = (p.n_fft - W) / 2;
-  for (int i = threadIdx.x; i < nb * W; i += 256) {
-    const int f = i / W, j = i - f * W;
-    // exact phase reduction: angle = 2*pi*((f*(j+lpad)) mod n_fft)/n_fft
-    const int ph = (int)(((long)f * (j + lpad)) % p.n_fft);
-    const float a = 6.283185307179586476925f * (float)ph / (float)p.n_fft;
-    tw[i] = cosf(a) * p.window[j];
-    tw[nb * W + i] = sinf(a) * p.window[j];
-  }
-  __syncthreads();
+  stft_fill_twiddles<false>(p, W, tw);
   const long total = (long)p.B * p.D * p.n_frames * nb;
   float s = 0.f;
   const float g = BWD ? p.gout[0] * p.scale : 0.f;
@@ -514,33 +521,23 @@ __global__ __launch_bounds__(256) void stft_loss_kernel(const StftP p) {
       ry += yv * cw[j]; iy -= yv * sw[j];
     }
     const float px = rx * rx + ix * ix, py = ry * ry + iy * iy;
-    const float mx = sqrtf(fmaxf(px, 1e-7f)), my = sqrtf(fmaxf(py, 1e-7f));
+    const float mx = stft_mag(px), my = stft_mag(py);
     if (!BWD) {
-      float v = (1.f - p.logratio) * fabsf(mx - my);
-      if (p.logratio != 0.f) v += p.logratio * fabsf(logf(mx) - logf(my));
-      s += v;
-    } else {
-      if (px > 1e-7f) {
-        const float dm = mx - my;
-        float c = (1.f - p.logratio) * (dm > 0.f ? 1.f : (dm < 0.f ? -1.f : 0.f));
-        if (p.logratio != 0.f) {
-          const float dl = logf(mx) - logf(my);
-          c += p.logratio * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f)) / mx;
-        }
-        const float k = g * c / mx;  // d loss / d (re,im) = k * (re, im)
-        if (k != 0.f) {
-          for (int j = 0; j < W; j++) {
-            const int t = reflect_idx(s0 + j, p.T);
-            const long n = (long)b * p.T + t;
-            atomicAdd(p.dx + n * p.lddx + d, k * (rx * cw[j] - ix * sw[j]));
-          }
+      s += stft_point_loss(mx, my, 1.f - p.logratio, p.logratio);
+    } else if (px > 1e-7f) {
+      const float k = stft_point_coef(mx, my, 1.f - p.logratio, p.logratio, g);
+      if (k != 0.f) {
+        for (int j = 0; j < W; j++) {
+          const int t = reflect_idx(s0 + j, p.T);
+          const long n = (long)b * p.T + t;
+          atomicAdd(p.dx + n * p.lddx + d, k * (rx * cw[j] - ix * sw[j]));
         }
       }
     }
   }
   if (!BWD) {
     s = block_sum_256(s, sh);
-    if (threadIdx.x == 0) { p.part[2 * blockIdx.x] = s; p.part[2 * blockIdx.x + 1] = 0.f; }
+    if (threadIdx.x == 0) p.part[2 * blockIdx.x] = s;
   }
 }
 
@@ -559,19 +556,7 @@ template <int W, int MODE>
 __device__ __forceinline__ float stft_frame_body(const StftP& p, int bid, int nblk, float* tw, float* sh) {
   const int nb = p.n_bins;
   const int lpad = (p.n_fft - p.win) / 2;
-  for (int i = threadIdx.x; i < nb * W; i += 256) {
-    const int f = i / W, j = i - f * W;
-    float c = 0.f, s = 0.f;
-    if (j < p.win) {
-      const int ph = (int)(((long)f * (j + lpad)) % p.n_fft);
-      const float a = 6.283185307179586476925f * (float)ph / (float)p.n_fft;
-      c = cosf(a) * p.window[j];
-      s = sinf(a) * p.window[j];
-    }
-    tw[i] = c;
-    tw[nb * W + i] = s;
-  }
-  __syncthreads();
+  stft_fill_twiddles<true>(p, W, tw);
   // a (batch, frame, feature dim) item is shared by STFT_BG lanes, each taking every STFT_BG-th
   // bin: 8x the parallelism of one thread per item (B * n_frames * D is only ~20 k items); lane =
   // bin group * 8 + item, so the partial window gradients meet through three xor shuffles
@@ -610,20 +595,13 @@ __device__ __forceinline__ float stft_frame_body(const StftP& p, int bid, int nb
         ry += ys[j] * c; iy -= ys[j] * s;
       }
       const float px = rx * rx + ix * ix, py = ry * ry + iy * iy;
-      const float mx = sqrtf(fmaxf(px, 1e-7f)), my = sqrtf(fmaxf(py, 1e-7f));
+      const float mx = stft_mag(px), my = stft_mag(py);
       if (FWD) {
-        float v = (1.f - p.logratio) * fabsf(mx - my);
-        if (p.logratio != 0.f) v += p.logratio * fabsf(logf(mx) - logf(my));
+        const float v = stft_point_loss(mx, my, 1.f - p.logratio, p.logratio);
         if (on) lsum += v;
       }
       if (BWD && px > 1e-7f) {
-        const float dm = mx - my;
-        float c = (1.f - p.logratio) * (dm > 0.f ? 1.f : (dm < 0.f ? -1.f : 0.f));
-        if (p.logratio != 0.f) {
-          const float dl = logf(mx) - logf(my);
-          c += p.logratio * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f)) / mx;
-        }
-        const float k = g * c / mx;
+        const float k = stft_point_coef(mx, my, 1.f - p.logratio, p.logratio, g);
         const float kr = k * rx, ki = k * ix;
 #pragma unroll
         for (int j = 0; j < W; j++) gr[j] += kr * cw[j] - ki * sw[j];
@@ -645,22 +623,16 @@ __device__ __forceinline__ float stft_frame_body(const StftP& p, int bid, int nb
   return lsum;
 }
 
-template <int W, bool BWD>
-__global__ __launch_bounds__(256) void stft_frame_kernel(const StftP p) {
-  extern __shared__ float tw[];  // cos [n_bins][W], sin [n_bins][W] (zero beyond win)
-  __shared__ float sh[4];
-  const float lsum = stft_frame_body<W, BWD ? 1 : 0>(p, blockIdx.x, gridDim.x, tw, sh);
-  if (!BWD && threadIdx.x == 0) { p.part[2 * blockIdx.x] = lsum; p.part[2 * blockIdx.x + 1] = 0.f; }
-}
-
 // Every resolution of the multi-resolution loss in ONE launch per direction: workgroups [bstart[r], bstart[r+1]) work on
-// resolution r; the forward's last workgroup sums each resolution's partials and writes the loss.
+// resolution r; a finishing launch sums each resolution's partials and writes the loss.  A single resolution
+// (crk_stft_loss_fwd / _bwd) is the same launch with nres = 1, the caller's weight and its accumulate flag.
 struct StftMP {
   StftP r[LOSS_MAX_RES];
   int nres;
   int bstart[LOSS_MAX_RES + 1];
   float inv_count[LOSS_MAX_RES];
   float weight;
+  int accumulate;             // out[0] += the loss instead of out[0] = the loss
   float* out;
 };
 
@@ -681,45 +653,82 @@ __global__ __launch_bounds__(256, 2) void stft_multi_kernel(const StftMP m) {
   if (MODE != 1 && threadIdx.x == 0) p.part[2 * bid] = lsum;
 }
 
-// one workgroup: every resolution's partials -> the loss (same arithmetic as one stft_final per resolution, accumulating)
+// one resolution's share of the loss from its n workgroups' partials, `stride` floats apart
+__device__ __forceinline__ float stft_res_loss(const float* part, int stride, int n, float inv_count, float weight, float* sh) {
+  float s[1];
+  sum_partials<1>(part, stride, n, s, sh);
+  return s[0] * inv_count * weight;
+}
+// one workgroup: every resolution's partials -> the loss
 __global__ __launch_bounds__(256) void stft_multi_final(const StftMP m) {
   __shared__ float sh[4];
   float total = 0.f;
   for (int q = 0; q < m.nres; q++) {
-    float s = 0.f;
-    const int nq = m.bstart[q + 1] - m.bstart[q];
-    for (int i = threadIdx.x; i < nq; i += 256) s += m.r[q].part[2 * i];
-    s = block_sum_256(s, sh);
-    const float v = s * m.inv_count[q] * m.weight;
+    const float v = stft_res_loss(m.r[q].part, 2, m.bstart[q + 1] - m.bstart[q], m.inv_count[q], m.weight, sh);
     total = q ? total + v : v;
   }
-  if (threadIdx.x == 0) m.out[0] = total;
+  if (threadIdx.x == 0) m.out[0] = m.accumulate ? m.out[0] + total : total;
 }
 
-template <bool BWD>
-static bool launch_stft_frames(const StftP& p, int* nblocks, hipStream_t s) {
-  if (p.win > 64) return false;
-  const int W = p.win <= 16 ? 16 : (p.win <= 32 ? 32 : 64);
-  const size_t lds = (size_t)2 * p.n_bins * W * sizeof(float);
-  if (lds > 60 * 1024) return false;
-  const int nb = loss_blocks((long)p.B * p.n_frames * p.D * STFT_BG);
-  *nblocks = nb;
-  if (W == 16) hipLaunchKernelGGL((stft_frame_kernel<16, BWD>), dim3(nb), dim3(256), lds, s, p);
-  else if (W == 32) hipLaunchKernelGGL((stft_frame_kernel<32, BWD>), dim3(nb), dim3(256), lds, s, p);
-  else hipLaunchKernelGGL((stft_frame_kernel<64, BWD>), dim3(nb), dim3(256), lds, s, p);
-  return true;
+// the window tile (taps held in registers) of a window of up to 64 taps, and a call of f with it as a compile-time constant
+static int rc_tile(int win) { return win <= 16 ? 16 : (win <= 32 ? 32 : 64); }
+template <class F>
+static void with_tile(int W, F&& f) {
+  if (W == 16) f(std::integral_constant<int, 16>());
+  else if (W == 32) f(std::integral_constant<int, 32>());
+  else f(std::integral_constant<int, 64>());
 }
 
-__global__ __launch_bounds__(256) void stft_final(const float* __restrict__ part, int nblocks, float inv_count,
-                                                  float weight, float* __restrict__ out, int accumulate) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblocks; i += 256) s += part[2 * i];
-  s = block_sum_256(s, sh);
-  if (threadIdx.x == 0) {
-    const float v = s * inv_count * weight;
-    out[0] = accumulate ? out[0] + v : v;
+// the geometry of one resolution (everything but part and the backward fields); returns its (signal, frame, bin) count
+static long stft_fill(StftP& p, const float* x, int ldx, const float* y, int ldy, int B, int T, int D, int n_fft, int hop,
+                      int win, const float* window, float logratio) {
+  p.x = x; p.y = y; p.ldx = ldx; p.ldy = ldy; p.B = B; p.T = T; p.D = D;
+  p.n_fft = n_fft; p.hop = hop; p.win = win;
+  p.n_frames = 1 + T / hop;  // center=True: (T + 2*(n_fft/2) - n_fft)/hop + 1
+  p.n_bins = n_fft / 2 + 1;
+  p.logratio = logratio; p.window = window;
+  return (long)B * D * p.n_frames * p.n_bins;
+}
+
+// m.r[..] filled, every window of 64 taps or fewer: the grid, the launch and (forward modes) the finishing launch
+template <int MODE>
+static int stft_multi_launch(StftMP& m, hipStream_t s) {
+  size_t lds = 0;
+  int wmax = 16;
+  m.bstart[0] = 0;
+  for (int r = 0; r < m.nres; r++) {
+    const StftP& p = m.r[r];
+    const int W = rc_tile(p.win);
+    wmax = std::max(wmax, W);
+    lds = std::max(lds, (size_t)2 * p.n_bins * W * sizeof(float));
+    m.bstart[r + 1] = m.bstart[r] + loss_blocks((long)p.B * p.n_frames * p.D * STFT_BG);
   }
+  if (lds > 60 * 1024) return CRK_ERR_UNSUPPORTED;
+  with_tile(wmax, [&](auto w) {
+    hipLaunchKernelGGL((stft_multi_kernel<MODE, decltype(w)::value>), dim3(m.bstart[m.nres]), dim3(256), lds, s, m);
+  });
+  if (MODE != 1) hipLaunchKernelGGL(stft_multi_final, dim3(1), dim3(256), 0, s, m);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+// One resolution, p filled: stft_multi_kernel with nres = 1 for windows of 64 taps or fewer whose tile's twiddles fit in
+// LDS, stft_loss_kernel otherwise; MODE 0 finishes out1[0] (+)= loss * weight, MODE 1 adds the gradient to p.dx.
+template <int MODE>
+static int stft_single_launch(const StftP& p, long total, float weight, int accumulate, float* out1, hipStream_t s) {
+  StftMP m{};
+  m.nres = 1; m.r[0] = p; m.inv_count[0] = 1.0f / (float)total; m.weight = weight; m.accumulate = accumulate; m.out = out1;
+  if (p.win <= 64) {
+    const int rc = stft_multi_launch<MODE>(m, s);
+    if (rc != CRK_ERR_UNSUPPORTED) return rc;
+  }
+  const size_t lds = (size_t)2 * p.n_bins * p.win * sizeof(float);
+  if (lds > 60 * 1024) return CRK_ERR_UNSUPPORTED;
+  m.bstart[1] = loss_blocks(total);
+  hipLaunchKernelGGL(stft_loss_kernel<MODE == 1>, dim3(m.bstart[1]), dim3(256), lds, s, p);
+  if (MODE == 0) hipLaunchKernelGGL(stft_multi_final, dim3(1), dim3(256), 0, s, m);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
 }
 
 // one resolution; the caller loops over resolutions with weight = 1/n_resolutions.
@@ -728,22 +737,9 @@ extern "C" int crk_stft_loss_fwd(const float* x, int ldx, const float* y, int ld
                                  int accumulate, float* out1, float* scratch, void* stream) {
   if (!x || !y || !window || !out1 || !scratch || win_length > n_fft || n_fft / 2 >= T) return CRK_ERR_ARG;
   StftP p{};
-  p.x = x; p.y = y; p.ldx = ldx; p.ldy = ldy; p.B = B; p.T = T; p.D = D;
-  p.n_fft = n_fft; p.hop = hop_length; p.win = win_length;
-  p.n_frames = 1 + T / hop_length;  // center=True: (T + 2*(n_fft/2) - n_fft)/hop + 1
-  p.n_bins = n_fft / 2 + 1;
-  p.logratio = logratio; p.window = window; p.part = scratch;
-  const long total = (long)B * D * p.n_frames * p.n_bins;
-  int nb = loss_blocks(total);
-  hipStream_t s = (hipStream_t)stream;
-  if (!launch_stft_frames<false>(p, &nb, s)) {
-    const size_t lds = (size_t)2 * p.n_bins * win_length * sizeof(float);
-    if (lds > 60 * 1024) return CRK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(stft_loss_kernel<false>, dim3(nb), dim3(256), lds, s, p);
-  }
-  hipLaunchKernelGGL(stft_final, dim3(1), dim3(256), 0, s, scratch, nb, 1.0f / (float)total, weight, out1, accumulate);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
+  const long total = stft_fill(p, x, ldx, y, ldy, B, T, D, n_fft, hop_length, win_length, window, logratio);
+  p.part = scratch;
+  return stft_single_launch<0>(p, total, weight, accumulate, out1, (hipStream_t)stream);
 }
 
 // dx must be zero-initialised by the caller before the first resolution.
@@ -752,54 +748,28 @@ extern "C" int crk_stft_loss_bwd(const float* x, int ldx, const float* y, int ld
                                  const float* gout, float* dx, int lddx, void* stream) {
   if (!x || !y || !window || !gout || !dx || win_length > n_fft) return CRK_ERR_ARG;
   StftP p{};
-  p.x = x; p.y = y; p.ldx = ldx; p.ldy = ldy; p.B = B; p.T = T; p.D = D;
-  p.n_fft = n_fft; p.hop = hop_length; p.win = win_length;
-  p.n_frames = 1 + T / hop_length;
-  p.n_bins = n_fft / 2 + 1;
-  p.logratio = logratio; p.window = window;
-  const long total = (long)B * D * p.n_frames * p.n_bins;
+  const long total = stft_fill(p, x, ldx, y, ldy, B, T, D, n_fft, hop_length, win_length, window, logratio);
   p.gout = gout; p.scale = weight / (float)total; p.dx = dx; p.lddx = lddx;
-  int nb = loss_blocks(total);
-  if (!launch_stft_frames<true>(p, &nb, (hipStream_t)stream)) {
-    const size_t lds = (size_t)2 * p.n_bins * win_length * sizeof(float);
-    if (lds > 60 * 1024) return CRK_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(stft_loss_kernel<true>, dim3(nb), dim3(256), lds, (hipStream_t)stream, p);
-  }
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
+  return stft_single_launch<1>(p, total, weight, 0, nullptr, (hipStream_t)stream);
 }
 
-static int stft_fill(StftP& p, const float* x, int ldx, const float* y, int ldy, int B, int T, int D, int n_fft, int hop,
-                     int win, const float* window, float logratio) {
-  if (!window || win > n_fft || n_fft / 2 >= T || win > 64) return CRK_ERR_UNSUPPORTED;
-  p.x = x; p.y = y; p.ldx = ldx; p.ldy = ldy; p.B = B; p.T = T; p.D = D;
-  p.n_fft = n_fft; p.hop = hop; p.win = win;
-  p.n_frames = 1 + T / hop;
-  p.n_bins = n_fft / 2 + 1;
-  p.logratio = logratio; p.window = window;
-  return CRK_OK;
-}
-
+// the three crk_stft_loss_multi_* entry points behind their argument checks; MODE as stft_frame_body's, with the
+// pointers its mode does not use NULL
 template <int MODE>
-static int stft_multi_launch(StftMP& m, hipStream_t s) {
-  size_t lds = 0;
-  int wmax = 16;
-  m.bstart[0] = 0;
-  for (int r = 0; r < m.nres; r++) {
-    const StftP& p = m.r[r];
-    const int W = p.win <= 16 ? 16 : (p.win <= 32 ? 32 : 64);
-    if (W > wmax) wmax = W;
-    const size_t l = (size_t)2 * p.n_bins * W * sizeof(float);
-    if (l > lds) lds = l;
-    m.bstart[r + 1] = m.bstart[r] + loss_blocks((long)p.B * p.n_frames * p.D * STFT_BG);
+static int stft_multi_run(const float* x, int ldx, const float* y, int ldy, int B, int T, int D, int nres, const int* n_fft,
+                          const int* hop_length, const int* win_length, const float* const* windows, float logratio,
+                          const float* gout, float* out1, float* dx, int lddx, float* scratch, void* stream) {
+  if (nres > LOSS_MAX_RES) return CRK_ERR_UNSUPPORTED;
+  StftMP m{};
+  m.nres = nres; m.weight = 1.0f / (float)nres; m.out = out1;
+  for (int r = 0; r < nres; r++) {
+    StftP& p = m.r[r];
+    if (!windows[r] || win_length[r] > n_fft[r] || n_fft[r] / 2 >= T || win_length[r] > 64) return CRK_ERR_UNSUPPORTED;
+    const long total = stft_fill(p, x, ldx, y, ldy, B, T, D, n_fft[r], hop_length[r], win_length[r], windows[r], logratio);
+    if (MODE != 1) { p.part = scratch + (size_t)r * 2 * LOSS_MAX_BLOCKS; m.inv_count[r] = 1.0f / (float)total; }
+    if (MODE != 0) { p.gout = gout; p.scale = m.weight / (float)total; p.dx = dx; p.lddx = lddx; }
   }
-  if (lds > 60 * 1024) return CRK_ERR_UNSUPPORTED;
-  if (wmax == 16) hipLaunchKernelGGL((stft_multi_kernel<MODE, 16>), dim3(m.bstart[m.nres]), dim3(256), lds, s, m);
-  else if (wmax == 32) hipLaunchKernelGGL((stft_multi_kernel<MODE, 32>), dim3(m.bstart[m.nres]), dim3(256), lds, s, m);
-  else hipLaunchKernelGGL((stft_multi_kernel<MODE, 64>), dim3(m.bstart[m.nres]), dim3(256), lds, s, m);
-  if (MODE != 1) hipLaunchKernelGGL(stft_multi_final, dim3(1), dim3(256), 0, s, m);
-  CRK_CHECK_LAUNCH();
-  return CRK_OK;
+  return stft_multi_launch<MODE>(m, (hipStream_t)stream);
 }
 
 // All resolutions at once (every win_length <= 64, at most LOSS_MAX_RES of them); CRK_ERR_UNSUPPORTED otherwise: the
@@ -809,16 +779,8 @@ extern "C" int crk_stft_loss_multi_fwd(const float* x, int ldx, const float* y, 
                                        const float* const* windows, float logratio, float* out1, float* scratch,
                                        void* stream) {
   if (!x || !y || !out1 || !scratch || !n_fft || !hop_length || !win_length || !windows || nres < 1) return CRK_ERR_ARG;
-  if (nres > LOSS_MAX_RES) return CRK_ERR_UNSUPPORTED;
-  StftMP m{};
-  m.nres = nres; m.weight = 1.0f / (float)nres; m.out = out1;
-  for (int r = 0; r < nres; r++) {
-    const int rc = stft_fill(m.r[r], x, ldx, y, ldy, B, T, D, n_fft[r], hop_length[r], win_length[r], windows[r], logratio);
-    if (rc != CRK_OK) return rc;
-    m.r[r].part = scratch + (size_t)r * 2 * LOSS_MAX_BLOCKS;
-    m.inv_count[r] = 1.0f / (float)((long)B * D * m.r[r].n_frames * m.r[r].n_bins);
-  }
-  return stft_multi_launch<0>(m, (hipStream_t)stream);
+  return stft_multi_run<0>(x, ldx, y, ldy, B, T, D, nres, n_fft, hop_length, win_length, windows, logratio, nullptr, out1,
+                           nullptr, 0, scratch, stream);
 }
 
 // Loss AND its gradient in one pass (the forward of a loss that is going to be differentiated): out1[0] as above,
@@ -829,18 +791,8 @@ extern "C" int crk_stft_loss_multi_fwd_grad(const float* x, int ldx, const float
                                             const float* const* windows, float logratio, float* out1, float* dx_unit,
                                             int lddx, float* scratch, void* stream) {
   if (!x || !y || !out1 || !dx_unit || !scratch || !n_fft || !hop_length || !win_length || !windows || nres < 1) return CRK_ERR_ARG;
-  if (nres > LOSS_MAX_RES) return CRK_ERR_UNSUPPORTED;
-  StftMP m{};
-  m.nres = nres; m.weight = 1.0f / (float)nres; m.out = out1;
-  for (int r = 0; r < nres; r++) {
-    const int rc = stft_fill(m.r[r], x, ldx, y, ldy, B, T, D, n_fft[r], hop_length[r], win_length[r], windows[r], logratio);
-    if (rc != CRK_OK) return rc;
-    const long total = (long)B * D * m.r[r].n_frames * m.r[r].n_bins;
-    m.r[r].part = scratch + (size_t)r * 2 * LOSS_MAX_BLOCKS;
-    m.inv_count[r] = 1.0f / (float)total;
-    m.r[r].scale = (1.0f / (float)nres) / (float)total; m.r[r].dx = dx_unit; m.r[r].lddx = lddx;
-  }
-  return stft_multi_launch<2>(m, (hipStream_t)stream);
+  return stft_multi_run<2>(x, ldx, y, ldy, B, T, D, nres, n_fft, hop_length, win_length, windows, logratio, nullptr, out1,
+                           dx_unit, lddx, scratch, stream);
 }
 
 // dx must be zero-initialised by the caller (or hold a gradient this one is to be added to).
@@ -849,16 +801,8 @@ extern "C" int crk_stft_loss_multi_bwd(const float* x, int ldx, const float* y, 
                                        const float* const* windows, float logratio, const float* gout, float* dx,
                                        int lddx, void* stream) {
   if (!x || !y || !gout || !dx || !n_fft || !hop_length || !win_length || !windows || nres < 1) return CRK_ERR_ARG;
-  if (nres > LOSS_MAX_RES) return CRK_ERR_UNSUPPORTED;
-  StftMP m{};
-  m.nres = nres;
-  for (int r = 0; r < nres; r++) {
-    const int rc = stft_fill(m.r[r], x, ldx, y, ldy, B, T, D, n_fft[r], hop_length[r], win_length[r], windows[r], logratio);
-    if (rc != CRK_OK) return rc;
-    const long total = (long)B * D * m.r[r].n_frames * m.r[r].n_bins;
-    m.r[r].gout = gout; m.r[r].scale = (1.0f / (float)nres) / (float)total; m.r[r].dx = dx; m.r[r].lddx = lddx;
-  }
-  return stft_multi_launch<1>(m, (hipStream_t)stream);
+  return stft_multi_run<1>(x, ldx, y, ldy, B, T, D, nres, n_fft, hop_length, win_length, windows, logratio, gout, nullptr, dx,
+                           lddx, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------
@@ -881,18 +825,7 @@ extern "C" int crk_stft_loss_multi_bwd(const float* x, int ldx, const float* y, 
 #define RC_SPAN_EXTRA 3
 #define RC_NW 4  // waves per workgroup: the bins of a frame are dealt to them (8 - half the run of FMAs per wave - measured
                  // slower at the step's shape, 35 against 32 us: twice the redundant window loads)
-__device__ __forceinline__ float block_sum_nw(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int tid = threadIdx.x;
-  __syncthreads();
-  if ((tid & 63) == 0) sh[tid >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-#pragma unroll
-  for (int w = 1; w < RC_NW; w++) t += sh[w];
-  return t;
-}
+static_assert(RC_NW == 4, "the recon kernels reduce with block_sum_256: 256 threads, four waves");
 struct ReconRes {
   const float* tw;   // [n_bins][2][W]
   float* gc;         // compact gradient or nullptr
@@ -980,16 +913,11 @@ __device__ __forceinline__ void recon_stft_body(const ReconP& p, const ReconRes&
 #pragma unroll
       for (int j = 0; j < W; j++) { re += xy[j] * cs[j]; im += xy[j] * ns[j]; }
       const rc_f2 pw = re * re + im * im;
-      const float mx = sqrtf(fmaxf(pw.x, 1e-7f)), my = sqrtf(fmaxf(pw.y, 1e-7f));
-      float v = olr * fabsf(mx - my);
-      float dl = 0.f;
-      if (lr != 0.f) { dl = logf(mx) - logf(my); v += lr * fabsf(dl); }
+      const float mx = stft_mag(pw.x), my = stft_mag(pw.y);
+      const float v = stft_point_loss(mx, my, olr, lr);
       if (on) lsum += v;
       if (GRAD) {
-        const float dm = mx - my;
-        float c = olr * (dm > 0.f ? 1.f : (dm < 0.f ? -1.f : 0.f));
-        if (lr != 0.f) c += lr * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f)) / mx;
-        const float k = pw.x > 1e-7f ? r.scale * c / mx : 0.f;  // d loss / d (re, im) = k * (re, im)
+        const float k = pw.x > 1e-7f ? stft_point_coef(mx, my, olr, lr, r.scale) : 0.f;
         const float kr = k * re.x, ki = k * im.x;
 #pragma unroll
         for (int j = 0; j < W; j += 2) gr[j / 2] += (rc_f2){cs[j], cs[j + 1]} * kr + (rc_f2){ns[j], ns[j + 1]} * ki;
@@ -1020,7 +948,7 @@ __device__ __forceinline__ void recon_stft_body(const ReconP& p, const ReconRes&
       }
     }
   }
-  lsum = block_sum_nw(lsum, sh);
+  lsum = block_sum_256(lsum, sh);
   if (tid == 0) p.part[ri * LOSS_MAX_BLOCKS + bid] = lsum;
 }
 
@@ -1029,40 +957,13 @@ __global__ __launch_bounds__(RC_NW * 64) void recon_fwd_kernel(const ReconP p) {
   extern __shared__ float lds[];
   __shared__ float sh[RC_NW];
   const int bx = blockIdx.x;
-  if (bx >= p.el_blk0) {  // |x-y| and (x-y)^2 over the masked frames (the loops of masked_loss_partial4<2> / _both_partial)
+  if (bx >= p.el_blk0) {  // |x-y| and (x-y)^2 over the masked frames: workgroup bid of crk_masked_loss_both_fwd's el_nblk
     const int bid = bx - p.el_blk0;
+    const long first = (long)bid * (RC_NW * 64) + threadIdx.x, step = (long)p.el_nblk * (RC_NW * 64);
     float s1 = 0.f, s2 = 0.f, c = 0.f;
-    if (p.el_vec4) {
-      const int D4 = p.D / 4;
-      const long total = (long)p.B * p.T * D4;
-      for (long i = (long)bid * (RC_NW * 64) + threadIdx.x; i < total; i += (long)p.el_nblk * (RC_NW * 64)) {
-        const long n = i / D4;
-        const int d = (int)(i - n * D4) * 4;
-        if (p.mask && !p.mask[n]) continue;
-        const float4 xv = *reinterpret_cast<const float4*>(p.x + n * p.ldx + d);
-        const float4 yv = *reinterpret_cast<const float4*>(p.y + n * p.ldy + d);
-        const float df[4] = {xv.x - yv.x, xv.y - yv.y, xv.z - yv.z, xv.w - yv.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) { s1 += fabsf(df[j]); s2 += df[j] * df[j]; }
-        c += 4.f;
-      }
-    } else {
-      const long total = (long)p.B * p.T * p.D;
-      for (long i = (long)bid * (RC_NW * 64) + threadIdx.x; i < total; i += (long)p.el_nblk * (RC_NW * 64)) {
-        const long n = i / p.D;
-        const int d = (int)(i - n * p.D);
-        if (p.mask && !p.mask[n]) continue;
-        const float df = p.x[n * p.ldx + d] - p.y[n * p.ldy + d];
-        s1 += fabsf(df); s2 += df * df; c += 1.f;
-      }
-    }
-    s1 = block_sum_nw(s1, sh);
-    s2 = block_sum_nw(s2, sh);
-    c = block_sum_nw(c, sh);
-    if (threadIdx.x == 0) {
-      float* q = p.part + LOSS_MAX_RES * LOSS_MAX_BLOCKS + 3 * bid;
-      q[0] = s1; q[1] = s2; q[2] = c;
-    }
+    if (p.el_vec4) masked_sums<4, 2>(p.x, p.ldx, p.y, p.ldy, 0.f, p.mask, (long)p.B * p.T, p.D / 4, first, step, s1, s2, c);
+    else masked_sums<1, 2>(p.x, p.ldx, p.y, p.ldy, 0.f, p.mask, (long)p.B * p.T, p.D, first, step, s1, s2, c);
+    masked_sums_store<2>(s1, s2, c, p.part + LOSS_MAX_RES * LOSS_MAX_BLOCKS + 3 * bid, sh);
     return;
   }
   // (statically indexed copies: a dynamic index into the kernel argument would move the whole struct to scratch)
@@ -1077,29 +978,22 @@ __global__ __launch_bounds__(RC_NW * 64) void recon_fwd_kernel(const ReconP p) {
   else recon_stft_body<64, GRAD>(p, r, ri, bid, lds, sh);
 }
 
+// crk_masked_loss_both_fwd's finish on the element workgroups' records, then the STFT loss as stft_multi_final forms it
 __global__ __launch_bounds__(256) void recon_final_kernel(const ReconP p) {
   __shared__ float sh[4];
-  float s1 = 0.f, s2 = 0.f, c = 0.f;
-  const float* q = p.part + LOSS_MAX_RES * LOSS_MAX_BLOCKS;
-  for (int i = threadIdx.x; i < p.el_nblk; i += 256) { s1 += q[3 * i]; s2 += q[3 * i + 1]; c += q[3 * i + 2]; }
-  s1 = block_sum_256(s1, sh);
-  s2 = block_sum_256(s2, sh);
-  c = block_sum_256(c, sh);
+  float e[3];
+  sum_partials<3>(p.part + LOSS_MAX_RES * LOSS_MAX_BLOCKS, 3, p.el_nblk, e, sh);
   float total = 0.f;
 #pragma unroll
   for (int k = 0; k < LOSS_MAX_RES; k++) {
     if (k < p.nres) {  // (uniform)
-      float s = 0.f;
-      for (int i = threadIdx.x; i < p.r[k].nblk; i += 256) s += p.part[k * LOSS_MAX_BLOCKS + i];
-      s = block_sum_256(s, sh);
-      const float v = s * p.r[k].inv_count * p.weight;
+      const float v = stft_res_loss(p.part + k * LOSS_MAX_BLOCKS, 1, p.r[k].nblk, p.r[k].inv_count, p.weight, sh);
       total = k ? total + v : v;
     }
   }
-  if (threadIdx.x == 0) { p.out[0] = s1 / c; p.out[1] = c; p.out[2] = s2 / c; p.out[3] = c; p.out[4] = total; }
+  if (threadIdx.x == 0) { both_means(e, p.out); p.out[4] = total; }
 }
 
-static int rc_tile(int win) { return win <= 16 ? 16 : (win <= 32 ? 32 : 64); }
 // the geometry the fused path takes; everything else goes through crk_masked_loss_both_fwd + crk_stft_loss_multi_*
 static bool recon_res_ok(int T, int n_fft, int hop, int win) {
   if (win < 1 || win > 64 || win > n_fft || n_fft / 2 >= T || hop < win + RC_SPAN_EXTRA) return false;
@@ -1126,6 +1020,13 @@ extern "C" long long crk_recon_grad_floats(int B, int T, int D, int nres, const 
   long long n = 0;
   for (int r = 0; r < nres; r++) n += (long long)B * (1 + T / hop_length[r]) * (win_length[r] + RC_SPAN_EXTRA) * D;
   return n;
+}
+
+template <int WMAX, bool GRAD>
+static void recon_fwd_launch(const ReconP& p, int blk, size_t lds, hipStream_t s) {
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)recon_fwd_kernel<WMAX, GRAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((recon_fwd_kernel<WMAX, GRAD>), dim3(blk), dim3(RC_NW * 64), lds, s, p);
 }
 
 // out5 = {L1 mean, count, MSE mean, count, STFT loss}; grad (crk_recon_grad_floats floats, or NULL when nothing will be
@@ -1158,31 +1059,18 @@ extern "C" int crk_recon_loss_fwd(const float* x, int ldx, const float* y, int l
     q.blk0 = blk; blk += q.nblk;
     q.gc = g;
     if (g) g += (size_t)B * q.nf * (q.win + RC_SPAN_EXTRA) * D;
-    if (q.W > wmax) wmax = q.W;
-    const size_t need = (size_t)RC_NW * q.W * 64 * sizeof(float);
-    if (need > lds) lds = need;
+    wmax = std::max(wmax, q.W);
+    lds = std::max(lds, (size_t)RC_NW * q.W * 64 * sizeof(float));
   }
   p.el_blk0 = blk;
   p.el_vec4 = loss_vec4_ok(x, y, nullptr, D, ldx, ldy, 0) ? 1 : 0;
-  {
-    const long el = p.el_vec4 ? (long)B * T * (D / 4) : (long)B * T * D;
-    const long nb = (el + RC_NW * 64 - 1) / (RC_NW * 64);
-    p.el_nblk = (int)(nb > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : (nb < 1 ? 1 : nb));
-  }
+  p.el_nblk = loss_blocks((long)B * T * (p.el_vec4 ? D / 4 : D));  // (RC_NW * 64 = 256 items per workgroup)
   blk += p.el_nblk;
   hipStream_t s = (hipStream_t)stream;
-#define RC_LAUNCH(WM, GR)                                                                                           \
-  do {                                                                                                               \
-    if (lds > 48 * 1024)                                                                                             \
-      (void)hipFuncSetAttribute((const void*)recon_fwd_kernel<WM, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((recon_fwd_kernel<WM, GR>), dim3(blk), dim3(RC_NW * 64), lds, s, p);                                 \
-  } while (0)
-  if (grad) {
-    if (wmax == 16) RC_LAUNCH(16, true); else if (wmax == 32) RC_LAUNCH(32, true); else RC_LAUNCH(64, true);
-  } else {
-    if (wmax == 16) RC_LAUNCH(16, false); else if (wmax == 32) RC_LAUNCH(32, false); else RC_LAUNCH(64, false);
-  }
-#undef RC_LAUNCH
+  with_tile(wmax, [&](auto w) {
+    if (grad) recon_fwd_launch<decltype(w)::value, true>(p, blk, lds, s);
+    else recon_fwd_launch<decltype(w)::value, false>(p, blk, lds, s);
+  });
   hipLaunchKernelGGL(recon_final_kernel, dim3(1), dim3(256), 0, s, p);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
@@ -1198,6 +1086,8 @@ struct ReconBP {
   ReconBRes r[LOSS_MAX_RES];
 };
 // dx = g3 * (gathered STFT gradient) + g1 * d L1 + g2 * d MSE, V consecutive feature dims per thread
+// (its own expressions, not l1_grad / mse_grad: v += 2 d g2 contracts to one fma here, and the kernel keeps the
+// instruction order it was measured with)
 template <int V>
 __global__ __launch_bounds__(256) void recon_bwd_kernel(const ReconBP p) {
   const float g1 = p.g1 ? p.g1[0] / p.stat[1] : 0.f;

@@ -688,6 +688,55 @@ def _as2d(t):
     return k, 1, k.numel(), 1
 
 
+def _mask_bytes(mask, N):
+    """A frame mask as N contiguous bytes (None stays None)."""
+    if mask is None:
+        return None
+    mk = mask.reshape(-1).contiguous()
+    mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
+    assert mk.numel() == N, (mk.numel(), N)
+    return mk
+
+
+def _res_arrays(resolutions):
+    """The (n_fft, hop_length, win_length) int arrays of a resolution list."""
+    return [_iarr([r[i] for r in resolutions]) for i in range(3)]
+
+
+def _masked_bwd_acc(xk, yk, mk, geom, out4, grads, dx=None, scale=None):
+    """dx * scale + the L1 / MSE gradients of out4 = {L1 mean, count, MSE mean, count} for the upstream gradients
+    grads = (g1, g2) that are not None, one crk_masked_loss_bwd_acc launch each.  Returns (dx, scale), scale None once a
+    launch has applied it."""
+    N, Dm, ldx, ldy = geom
+    for mode, g in enumerate(grads):
+        if g is None:
+            continue
+        nxt = torch.empty(N, Dm, device=xk.device, dtype=torch.float32)
+        gg = g.contiguous().reshape(1)
+        check(_lib.lib().crk_masked_loss_bwd_acc(ptr(xk), ldx, ptr(yk), ldy, 0.0, ptr(mk), N, Dm, mode,
+                                                 ptr(out4[2 * mode: 2 * mode + 2]), ptr(gg), ptr(nxt), Dm, None, 0, ptr(dx), Dm,
+                                                 ptr(scale), stream_ptr()), "crk_masked_loss_bwd_acc")
+        dx, scale = nxt, None
+    return dx, scale
+
+
+def _stft_multi_fwd(xk, ldx, yk, ldy, resolutions, windows, logratio, out1, unit):
+    """Every resolution in one launch: the loss into out1, and with unit (zeros, B x T x D) its gradient for an upstream
+    gradient of 1 in the same pass over the DFTs."""
+    L = _lib.lib()
+    B, T, Dm = xk.shape
+    ia = _res_arrays(resolutions)
+    scr = _loss_scratch(xk.device)
+    if unit is not None:
+        check(L.crk_stft_loss_multi_fwd_grad(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(resolutions), ia[0], ia[1], ia[2],
+                                             _parr(windows), float(logratio), ptr(out1), ptr(unit), Dm, ptr(scr), stream_ptr()),
+              "crk_stft_loss_multi_fwd_grad")
+    else:
+        check(L.crk_stft_loss_multi_fwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(resolutions), ia[0], ia[1], ia[2],
+                                        _parr(windows), float(logratio), ptr(out1), ptr(scr), stream_ptr()),
+              "crk_stft_loss_multi_fwd")
+
+
 class _MaskedLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, mask, mode, yconst):
@@ -698,11 +747,7 @@ class _MaskedLossFn(torch.autograd.Function):
             assert (Ny, Dy) == (N, Dm), (x.shape, y.shape)
         else:
             yk, ldy = None, 0
-        mk = None
-        if mask is not None:
-            mk = mask.reshape(-1).contiguous()
-            mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
-            assert mk.numel() == N, (mk.numel(), N)
+        mk = _mask_bytes(mask, N)
         out = _scalars(2, x.device)
         check(L.crk_masked_loss_fwd(ptr(xk), ldx, ptr(yk), ldy, float(yconst), ptr(mk), N, Dm, mode, ptr(out),
                                     ptr(_loss_scratch(x.device)), stream_ptr()), "crk_masked_loss_fwd")
@@ -738,11 +783,7 @@ class _MaskedBothFn(torch.autograd.Function):
         xk, ldx, N, Dm = _as2d(x)
         yk, ldy, Ny, Dy = _as2d(y)
         assert (Ny, Dy) == (N, Dm), (x.shape, y.shape)
-        mk = None
-        if mask is not None:
-            mk = mask.reshape(-1).contiguous()
-            mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
-            assert mk.numel() == N, (mk.numel(), N)
+        mk = _mask_bytes(mask, N)
         out = _scalars(4, x.device)
         check(L.crk_masked_loss_both_fwd(ptr(xk), ldx, ptr(yk), ldy, ptr(mk), N, Dm, ptr(out), ptr(_loss_scratch(x.device)),
                                          stream_ptr()), "crk_masked_loss_both_fwd")
@@ -755,22 +796,11 @@ class _MaskedBothFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g1, g2):
-        L = _lib.lib()
         xk, yk, mk, out = ctx.saved_tensors
-        N, Dm, ldx, ldy = ctx.geom
         mk = mk if ctx.has_m else None
         if not ctx.needs_input_grad[0] or (g1 is None and g2 is None):
             return None, None, None
-        dx = None
-        for mode, g in ((0, g1), (1, g2)):
-            if g is None:
-                continue
-            nxt = torch.empty(N, Dm, device=xk.device, dtype=torch.float32)
-            gg = g.contiguous().reshape(1)
-            check(L.crk_masked_loss_bwd_acc(ptr(xk), ldx, ptr(yk), ldy, 0.0, ptr(mk), N, Dm, mode, ptr(out[2 * mode: 2 * mode + 2]),
-                                            ptr(gg), ptr(nxt), Dm, None, 0, ptr(dx), Dm, None, stream_ptr()),
-                  "crk_masked_loss_bwd_acc")
-            dx = nxt
+        dx, _ = _masked_bwd_acc(xk, yk, mk, ctx.geom, out, (g1, g2))
         return dx.view(ctx.xshape), None, None
 
 
@@ -825,19 +855,11 @@ class _STFTLossFn(torch.autograd.Function):
         w = 1.0 / len(resolutions)
         ctx.multi = len(resolutions) <= 4 and all(win <= 64 for _, _, win in resolutions)
         ctx.unit = None
-        if ctx.multi and ctx.needs_input_grad[0] and not cfg.stft_two_pass:
-            # the loss will be differentiated: loss and gradient (for an upstream gradient of 1) in ONE pass over the DFTs
-            ctx.unit = torch.zeros(B, T, Dm, device=x.device, dtype=torch.float32)
-            check(L.crk_stft_loss_multi_fwd_grad(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(resolutions),
-                                                 _iarr([r[0] for r in resolutions]), _iarr([r[1] for r in resolutions]),
-                                                 _iarr([r[2] for r in resolutions]), _parr(windows), float(logratio), ptr(out),
-                                                 ptr(ctx.unit), Dm, ptr(_loss_scratch(x.device)), stream_ptr()),
-                  "crk_stft_loss_multi_fwd_grad")
-        elif ctx.multi:  # every resolution in one launch
-            check(L.crk_stft_loss_multi_fwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(resolutions),
-                                            _iarr([r[0] for r in resolutions]), _iarr([r[1] for r in resolutions]),
-                                            _iarr([r[2] for r in resolutions]), _parr(windows), float(logratio), ptr(out),
-                                            ptr(_loss_scratch(x.device)), stream_ptr()), "crk_stft_loss_multi_fwd")
+        if ctx.multi:  # every resolution in one launch
+            if ctx.needs_input_grad[0] and not cfg.stft_two_pass:
+                # the loss will be differentiated: loss and gradient (for an upstream gradient of 1) in ONE pass over the DFTs
+                ctx.unit = torch.zeros(B, T, Dm, device=x.device, dtype=torch.float32)
+            _stft_multi_fwd(xk, ldx, yk, ldy, resolutions, windows, logratio, out, ctx.unit)
         else:
             for i, ((n_fft, hop, win), wt) in enumerate(zip(resolutions, windows)):
                 check(L.crk_stft_loss_fwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, n_fft, hop, win, ptr(wt), float(logratio), w,
@@ -860,8 +882,8 @@ class _STFTLossFn(torch.autograd.Function):
         g = g.contiguous().reshape(1)
         w = 1.0 / len(ctx.res)
         if ctx.multi:
-            check(L.crk_stft_loss_multi_bwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(ctx.res), _iarr([r[0] for r in ctx.res]),
-                                            _iarr([r[1] for r in ctx.res]), _iarr([r[2] for r in ctx.res]), _parr(windows),
+            ia = _res_arrays(ctx.res)
+            check(L.crk_stft_loss_multi_bwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, len(ctx.res), ia[0], ia[1], ia[2], _parr(windows),
                                             ctx.logratio, ptr(g), ptr(dx), Dm, stream_ptr()), "crk_stft_loss_multi_bwd")
             return dx, None, None, None, None
         for (n_fft, hop, win), wt in zip(ctx.res, windows):
@@ -892,7 +914,7 @@ def _stft_tables(resolutions, windows):
 
 
 def recon_supported(T, resolutions):
-    ia = [_iarr([r[i] for r in resolutions]) for i in range(3)]
+    ia = _res_arrays(resolutions)
     return bool(_lib.lib().crk_recon_supported(int(T), len(resolutions), ia[0], ia[1], ia[2]))
 
 
@@ -910,15 +932,11 @@ class _ReconFn(torch.autograd.Function):
         yk, ldy = _rows(y)
         B, T, Dm = xk.shape
         N = B * T
-        mk = None
-        if mask is not None:
-            mk = mask.reshape(-1).contiguous()
-            mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.to(torch.uint8)
-            assert mk.numel() == N, (mk.numel(), N)
+        mk = _mask_bytes(mask, N)
         out = _scalars(5, x.device)
         scr = _loss_scratch(x.device)
         nres = len(resolutions)
-        ia = [_iarr([r[i] for r in resolutions]) for i in range(3)]
+        ia = _res_arrays(resolutions)
         ctx.fused = recon_supported(T, resolutions) and not cfg.recon_dense
         ctx.geom = (N, Dm, ldx, ldy)
         ctx.has_m = mk is not None
@@ -936,13 +954,7 @@ class _ReconFn(torch.autograd.Function):
         check(L.crk_masked_loss_both_fwd(ptr(xk), ldx, ptr(yk), ldy, ptr(mk), N, Dm, ptr(out), ptr(scr), stream_ptr()),
               "crk_masked_loss_both_fwd")
         unit = torch.zeros(B, T, Dm, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        if unit is not None:
-            check(L.crk_stft_loss_multi_fwd_grad(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, nres, ia[0], ia[1], ia[2], _parr(windows),
-                                                 float(logratio), ptr(out[4:]), ptr(unit), Dm, ptr(scr), stream_ptr()),
-                  "crk_stft_loss_multi_fwd_grad")
-        else:
-            check(L.crk_stft_loss_multi_fwd(ptr(xk), ldx, ptr(yk), ldy, B, T, Dm, nres, ia[0], ia[1], ia[2], _parr(windows),
-                                            float(logratio), ptr(out[4:]), ptr(scr), stream_ptr()), "crk_stft_loss_multi_fwd")
+        _stft_multi_fwd(xk, ldx, yk, ldy, resolutions, windows, logratio, out[4:], unit)
         ctx.unit = unit
         ctx.save_for_backward(xk, yk, mk if mk is not None else out, out)
         return out[0], out[2], out[4]
@@ -960,7 +972,7 @@ class _ReconFn(torch.autograd.Function):
             return None, None, None, None, None, None
         if ctx.fused:
             B, T = xk.shape[0], xk.shape[1]
-            ia = [_iarr([r[i] for r in ctx.res]) for i in range(3)]
+            ia = _res_arrays(ctx.res)
             gs = [None if g is None else g.contiguous().reshape(1) for g in (g1, g2, g3)]
             dx = torch.empty(N, Dm, device=xk.device, dtype=torch.float32)
             check(L.crk_recon_loss_bwd(ptr(xk), ldx, ptr(yk), ldy, ptr(mk), B, T, Dm, len(ctx.res), ia[0], ia[1], ia[2],
@@ -968,15 +980,7 @@ class _ReconFn(torch.autograd.Function):
                   "crk_recon_loss_bwd")
             return dx.view(ctx.xshape), None, None, None, None, None
         dx, scale = (unit, g3.contiguous().reshape(1)) if g3 is not None else (None, None)
-        for mode, g in ((0, g1), (1, g2)):
-            if g is None:
-                continue
-            nxt = torch.empty(N, Dm, device=xk.device, dtype=torch.float32)
-            gg = g.contiguous().reshape(1)
-            check(L.crk_masked_loss_bwd_acc(ptr(xk), ldx, ptr(yk), ldy, 0.0, ptr(mk), N, Dm, mode, ptr(out[2 * mode: 2 * mode + 2]),
-                                            ptr(gg), ptr(nxt), Dm, None, 0, ptr(dx), Dm, ptr(scale), stream_ptr()),
-                  "crk_masked_loss_bwd_acc")
-            dx, scale = nxt, None
+        dx, scale = _masked_bwd_acc(xk, yk, mk, ctx.geom, out, (g1, g2), dx, scale)
         if scale is not None:  # only the STFT term is differentiated
             dx = dx.mul_(scale)
         return dx.view(ctx.xshape), None, None, None, None, None

@@ -83,7 +83,7 @@ def ml_bwd(x, y, mask, mode, stat, g, yconst=0.0, add=None, add_scale=None, want
 
 
 def bwd4_taken(x, y, dx, add, want_dy):
-    """crk_masked_loss_bwd_acc's choice of masked_loss_bwd4: y a tensor, dx wanted, dy not, 16-byte pointers, D and the
+    """crk_masked_loss_bwd_acc's choice of masked_loss_bwd<4>: y a tensor, dx wanted, dy not, 16-byte pointers, D and the
     row strides multiples of 4."""
     ts = [t for t in (x, y, dx, add) if t is not None]
     return y is not None and not want_dy and vec4_ok(x.shape[1], *ts)
@@ -172,7 +172,7 @@ def test_masked_losses_vs_float64(name, mask_kind):
 
 def test_masked_loss_paths_agree_on_the_same_values():
     """One (64 x 500 x 80) pair through the 16-byte kernels and, copied to row stride 83, through the scalar ones: the
-    same count, means within 1e-6, and the backward kernels (bwd4 against the scalar one; the scalar one again with dy
+    same count, means within 1e-6, and the backward kernels (masked_loss_bwd<4> against <1>; the scalar one again with dy
     wanted) bit for bit, with and without add / add_scale."""
     gen = torch.Generator().manual_seed(11)
     N, D = 32000, 80
@@ -395,7 +395,7 @@ def test_recon_loss_at_the_benchmark_size(res, monkeypatch):
 
 @pytest.mark.parametrize("sliced", [False, True])
 def test_recon_fused_l1_mse_equal_masked_loss_both_bitwise(sliced):
-    """The fused kernel's L1 / MSE run the loops of masked_loss_partial4<2> / masked_loss_both_partial: the same four
+    """The fused kernel's L1 / MSE run masked_sums, the loop of masked_loss_partial<4, 2> / <1, 2>: the same four
     values as crk_masked_loss_both_fwd on the same pair, bit for bit, on the 16-byte path and (row stride 83) the scalar
     one."""
     from crank_amd.ops import _iarr, _parr, _stft_tables
@@ -437,7 +437,7 @@ def test_stft_losses_at_the_benchmark_size():
     res = crit.loss_func.resolutions
     assert res == [(64, 64, 16), (128, 128, 32)] and all(w <= 64 for _, _, w in res)
     direct = STFTLoss(fft_size=128, win_size=80, hop_size=32)
-    assert direct.resolutions == [(128, 32, 80)]  # win > 64: no frame kernel; 2 * 65 * 80 twiddles fit in 60 KB of LDS
+    assert direct.resolutions == [(128, 32, 80)]  # win > 64: not stft_multi_kernel; 2 * 65 * 80 twiddles fit in 60 KB of LDS
     assert B * D * (1 + T // 32) * 65 > LOSS_MAX_BLOCKS * 256
     for lossf, r, rtol_v in ((crit, res, 3e-5), (direct, direct.resolutions, 5e-5)):
         leaf = xh.cuda().requires_grad_(True)
@@ -449,6 +449,76 @@ def test_stft_losses_at_the_benchmark_size():
         g, gr = leaf.grad.cpu().numpy(), xr.grad.numpy()
         np.testing.assert_allclose(v.item(), ref.item(), rtol=rtol_v)
         np.testing.assert_allclose(g, gr, rtol=2e-3, atol=5e-5 * np.abs(gr).max())
+
+
+THREE_TILES = [(16, 5, 9), (32, 10, 20), (128, 70, 40)]  # (n_fft, hop, win) as torch.stft receives them
+STFT_PATHS = {
+    # name: (resolutions, passes)
+    "three-tiles-one-pass": (THREE_TILES, 1),
+    "three-tiles-two-pass": (THREE_TILES, 2),
+    "five-resolutions": (THREE_TILES + [(16, 16, 16), (64, 19, 33)], 1),
+    "mixed": ([(16, 5, 9), (128, 32, 80)], 1),
+}
+
+
+def _tile(win):
+    return 16 if win <= 16 else 32 if win <= 32 else 64
+
+
+@pytest.mark.parametrize("logratio", [0.0, 0.3])
+@pytest.mark.parametrize("path", list(STFT_PATHS))
+def test_stft_loss_paths_outside_the_step(path, logratio, monkeypatch):
+    """The STFT-loss paths the training step never takes, at 2 x 130 x 3 against torch.stft in float64 (the bars of
+    test_stft_losses_at_the_benchmark_size).  "three tiles": windows shorter than their 16-, 32- and 64-tap tiles in one
+    launch (the 64-tap instantiation's dispatch), overlapping frames, both reflect edges, item counts that are no
+    multiple of 8 and six workgroups for the first resolution - loss and gradient in one pass, and as two passes
+    (cfg.stft_two_pass: the loss-only and the gradient-only modes), the two against each other at the fused-against-dense
+    bars.  "five resolutions": more than LOSS_MAX_RES, so crk_stft_loss_fwd / _bwd run per resolution and accumulate.
+    "mixed": a window above 64 taps sends the whole list there; the 9-tap resolution takes stft_multi_kernel with nres = 1, the
+    80-tap one stft_loss_kernel, accumulated onto the first."""
+    from crank_amd import config
+    from crank_amd.net.module.loss import MultiSizeSTFTLoss
+    from tests.test_gpu_ops import _torch_recon
+
+    B, T, D = 2, 130, 3
+    res, passes = STFT_PATHS[path]
+    items = [B * (1 + T // hop) * D for _, hop, _ in res]
+    multi = len(res) <= 4 and all(win <= 64 for _, _, win in res)  # _STFTLossFn's choice of the one-launch kernels
+    if path.startswith("three-tiles"):
+        assert multi and [_tile(w) for _, _, w in res] == [16, 32, 64] and all(w < _tile(w) for _, _, w in res)
+        assert items == [162, 84, 12] and all(i % 8 for i in items) and blocks(items[0] * 8) == 6
+        assert all(hop < win for _, hop, win in res[:2])  # overlapping frames: more than two atomics per sample
+    elif path == "five-resolutions":
+        assert len(res) > 4 and all(win <= 64 for _, _, win in res)
+    else:
+        assert len(res) <= 4 and any(win > 64 for _, _, win in res) and any(win <= 64 for _, _, win in res)
+        assert not multi
+    assert all(n_fft // 2 < T and win <= n_fft for n_fft, _, win in res) and T % 2 == 0
+    gen = torch.Generator().manual_seed(31)
+    xh, yh = stft_pair(B, T, D, gen)
+    # MultiSizeSTFTLoss takes (fft, hop, win) lists in the reference's swapped order (quirk Q1)
+    crit = MultiSizeSTFTLoss(fft_sizes=[r[0] for r in res], win_sizes=[r[1] for r in res], hop_sizes=[r[2] for r in res],
+                             logratio=logratio)
+    assert crit.resolutions == res
+
+    def run(two_pass):
+        monkeypatch.setattr(config.cfg, "stft_two_pass", bool(two_pass))
+        leaf = xh.cuda().requires_grad_(True)
+        v = crit(leaf, yh.cuda())
+        (1.5 * v).backward()
+        return v.item(), leaf.grad.cpu().numpy()
+
+    xr = xh.clone().double().requires_grad_(True)
+    ref = _torch_recon(xr, yh, None, res, logratio)[2]
+    (1.5 * ref).backward()
+    gr = xr.grad.numpy()
+    v, g = run(passes == 2)
+    np.testing.assert_allclose(v, ref.item(), rtol=5e-5)
+    np.testing.assert_allclose(g, gr, rtol=2e-3, atol=5e-5 * np.abs(gr).max())
+    if passes == 2:
+        v1, g1 = run(False)
+        np.testing.assert_allclose(v1, v, rtol=2e-6)
+        np.testing.assert_allclose(g1, g, rtol=2e-3, atol=2e-6 * np.abs(gr).max())
 
 
 # ------------------------------------------------------------------ D. speaker embedding
