@@ -63,8 +63,9 @@ static int not_reserved(const char* what) {
 // host copies of the fused plain-conv chain tables (pstack_kernels.hip): [0] first/forward, [1] head forward / backward,
 // [2] head backward, [3] first backward; w: the weight-gradient table
 struct PsTables { PsLayer t[4][PS_MAXL]; int L[4]; PwLayer w[PS_MAXL]; int nw; int max_wa, max_wb, max_tiles; double wflops_per_frame; };
-// what a batch shape needs: scratch / partial-sum floats and the slot counts of the two weight-gradient regions
-struct ShapeNeed { long long need_s, need_p; int Gs, Gg, cpg; };
+// what a batch shape needs: scratch / partial-sum floats, the slot counts of the two weight-gradient regions, the 64-frame
+// chunks per group of the plain convs (cpg) and of the gated blocks (cpg_s), the latter's per-utterance segments per group
+struct ShapeNeed { long long need_s, need_p; int Gs, Gg, cpg, cpg_s, nseg; };
 // The kernels a net runs at a batch shape in one arithmetic (route_of).  It depends on the net, the shape, the arithmetic and
 // the process-wide switches only, never on a call's pointers, so a backward always reads the plane layout its forward wrote.
 // Every other path computes the same values, only slower.
@@ -75,7 +76,15 @@ struct Route {
   bool disc_split;  // discriminator, plain bf16: blocks and chain channel-split, gate planes in the lane-record layout
   bool usums;       // gated stack with conditioning, fused: an embedding behind the conditioning gets its gradient from the
                     // weight-gradient launch's per-utterance dG sums (crk_net_backward_embed), the chain computes no dc
+  unsigned char ps_fwd;      // fused plain chain: the forward's kernel (CHAIN_*)
+  unsigned char ps_fwd_x3f;  // ... of a bf16x3f forward, in the split-operand route: pstack2x_kernel, or pstack_kernel<PRECISE>
+  unsigned char ps_bwd[2];   // ... of the data-gradient chain: [0] down to dx, [1] stopped one layer early (PsP::tail, no dx)
+  bool fold_fwd;     // generator, plain bf16: first conv, blocks and head in one stack2_fwd_kernel launch (with gen_split, or on
+                     // row-layout planes where only the chain cannot split)
+  bool blocks_s2;    // fused gated stack, plain bf16, not folded: the blocks run stack2_fwd_kernel (else stack_fwd_kernel)
+  bool fold_bwd_fs;  // generator, plain bf16: the frame-split chain folds head and first conv in (its 8-wave window only)
 };
+enum { CHAIN_PS = 0, CHAIN_PS2 = 1, CHAIN_PS2X = 2 };  // pstack_kernel, pstack2_kernel, pstack2x_kernel
 // Everything batch shape (B, T) needs besides the growing buffers, made by crk_net_reserve: plane offsets are multiples of
 // N = B*T, partial-sum offsets of the slot counts Gs / Gg.
 struct Shape {
@@ -363,9 +372,16 @@ static int stack_aux_pad(const Net* n) { return n->d.aux_ch > 0 ? n->ents[n->idx
 //   gated : fp32 planes X | TA | SB | Z | SKIP | H1 (TA, SB, Z, H1: per-layer fallback only), then bf16:
 //           Xb Zb Tb Sg (block input, z, tanh, sigmoid; hi[L] lo[L], [N,64] each), Cb_hi Cb_lo ([N,aux_pad]), F_hi F_lo (first-conv input [N,kpF]),
 //           head_hi = S|H1 ([N,64] each), head_lo
+struct GatedF32 {  // float offsets of the gated stacks' fp32 planes: [N,64] each, block l's at + l * N * 64
+  long long x, ta, sb, z, skip, h1, saved_total;  // in `saved`
+  long long ds, dh1, dx, dg, scratch_total;       // in n->scratch: dX_l, l = 0..L (dX_L is never written: it is zero), then
+};                                                // dG_l [N,128] at dg + l * 2 * N * 64
+static GatedF32 gated_f32(const Net* n, long long N) {
+  const long long P = N * 64, LP = n->L * P;
+  return {0, LP, 2 * LP, 3 * LP, 4 * LP, 4 * LP + P, 4 * LP + 2 * P, 0, P, 2 * P, 3 * P + LP, 3 * P + 3 * LP};
+}
 static long long saved_f32_floats(const Net* n, long long N) {
-  if (n->d.kind == 2) return (long long)(n->L - 1) * N * n->d.conv_ch;
-  return (long long)(4 * n->L + 2) * N * 64;
+  return n->d.kind == 2 ? (long long)(n->L - 1) * N * n->d.conv_ch : gated_f32(n, N).saved_total;
 }
 static long long plain_planes_w(const Net* n) {  // sum of the operand-plane widths of a kind-2 net
   long long w = 0;
@@ -437,16 +453,22 @@ static ConvP base_conv(const Net* n, int B, int T) {
   p.ktaps = 1; p.dil = 1; p.off0 = 0;
   return p;
 }
-static void set_fw_weights(const Net* n, ConvP& p, const ConvEntry& e, const float* params) {
+// conv e of the per-layer kernels, in [N, e.cin] -> out; the caller adds taps, prologue and epilogue
+static ConvP conv_fw(const Net* n, int B, int T, const ConvEntry& e, const float* params, const float* in, int ldin, float* out, int ldo) {
+  ConvP p = base_conv(n, B, T);
   p.w_hi = n->whi + e.fw_off; p.w_lo = n->wlo + e.fw_off;
   p.cin = e.cin; p.cin_pad = e.fw_kp; p.cout = e.cout; p.cout_pad = e.fw_rows;
   p.bias = e.off_b >= 0 ? params + e.off_b : nullptr;
+  p.xa = in; p.lda = ldin; p.cinA = e.cin; p.y = out; p.ldy = ldo;
+  return p;
 }
-static void set_bw_weights(const Net* n, ConvP& p, const ConvEntry& e) {
-  // data gradient: "cin" = forward cout, "cout" = forward cin
+// ... and its data gradient, in [N, e.cout] -> out: "cin" = forward cout, "cout" = forward cin
+static ConvP conv_bw(const Net* n, int B, int T, const ConvEntry& e, const float* in, int ldin, float* out, int ldo) {
+  ConvP p = base_conv(n, B, T);
   p.w_hi = n->whi + e.bw_off; p.w_lo = n->wlo + e.bw_off;
   p.cin = e.cout; p.cin_pad = e.bw_kp; p.cout = e.cin; p.cout_pad = e.bw_rows;
-  p.bias = nullptr;
+  p.xa = in; p.lda = ldin; p.cinA = e.cout; p.y = out; p.ldy = ldo;
+  return p;
 }
 static int fwd_off0(const Net* n, int k, int dil) { return n->d.causal ? -(k - 1) * dil : -((k - 1) / 2) * dil; }
 
@@ -559,10 +581,14 @@ static PsP ps_base(const Net* n, int B, int T, const float* params) {
   p.B = B; p.T = T; p.slope = n->d.slope;
   return p;
 }
+// chain c of shape r (PsTables::t[c], p.L layers of it) on pstack_kernel: the plan fills the LDS carve-up
+static int pstack_go(const Shape* r, int c, PsP& p, bool precise, hipStream_t s) {
+  p.layers = r->d_ps + c * PS_MAXL;
+  RUN(pstack_plan(p, r->ps.t[c], precise));
+  return launch_pstack(p, precise, ps_flops(r->ps.t[c], p.L, (long long)p.B * p.T), s);
+}
 // can this kind-2 net / the first conv and head of this gated net run through the fused chains?
-static bool plain_chains_ok(const Net* n, int B, int T, bool precise) {
-  PsTables Tb;
-  ps_build(n, (long long)B * T, n->ents.data(), Tb);  // (relative partial offsets: the planners do not read them)
+static bool plain_chains_ok(const Net* n, int B, int T, bool precise, const PsTables& Tb) {
   const int nchains = n->d.kind == 2 ? 2 : 4;
   for (int c = 0; c < nchains; c++) {
     if (Tb.L[c] > PS_MAXL) return false;
@@ -606,282 +632,320 @@ static StackBP stack_bwd_shape(const Net* n, int B, int T) {
   return bp;
 }
 
-// The kernel path of net n at batch shape (B, T) in one arithmetic: the one place where the planners decide.  crk_net_reserve
-// keeps both arithmetics' routes in the shape's record; the compute entry points read them there.
+// The kernel path of net n at batch shape (B, T) in one arithmetic: the one place where the planners decide and the process
+// switches are read.  Every planner is asked with what the call will hand it (the planners read shapes, never pointers), so
+// the stored answer is the call's.  crk_net_reserve keeps both arithmetics' routes in the shape's record; the compute entry
+// points read them there and call a planner only to fill the LDS offsets of a launch whose kind is already chosen.
 static Route route_of(const Net* n, int B, int T, bool precise) {
-  Route r = {false, false, false, false, false};
+  Route r = {};
   const crk_net_desc& d = n->d;
   const CrkSwitches& sw = crk_sw();
   // forward, data-gradient chain and weight gradient run fused together or not at all (the fused kernels exchange bf16
   // planes the generic kernels do not produce).  CRK_NO_FUSE=1 selects the per-layer kernels (debugging / A-B timing).
   if (sw.no_fuse || n->L > PS_MAXL) return r;
-  if (d.kind == 2) { r.fused = plain_chains_ok(n, B, T, precise); return r; }
+  PsTables Tb;
+  ps_build(n, (long long)B * T, n->ents.data(), Tb);  // (relative partial offsets: the planners do not read them)
+  if (d.kind == 2) {
+    r.fused = plain_chains_ok(n, B, T, precise, Tb);
+    if (!r.fused || sw.ps_v != 2) return r;  // CRK_PS_V=1: the frame-split chains
+    PsP f = ps_base(n, B, T, nullptr);
+    f.cin = d.in_ch; f.L = Tb.L[0];
+    if (!precise && pstack2_plan(f, Tb.t[0]) == CRK_OK) r.ps_fwd = CHAIN_PS2;
+    if (precise && sw.s2x && pstack2x_plan(f, Tb.t[0]) == CRK_OK) r.ps_fwd_x3f = CHAIN_PS2X;
+    // the data-gradient chain; [1]: dx == nullptr and L >= 2, the chain is one layer shorter with tail = 1 and the planner is
+    // asked with that L
+    for (int tail = 0; tail < (Tb.L[1] >= 2 ? 2 : 1) && !precise; tail++) {
+      PsP b = ps_base(n, B, T, nullptr);
+      b.cin = d.out_ch; b.L = Tb.L[1] - tail; b.tail = tail;
+      if (pstack2_plan(b, Tb.t[1]) == CRK_OK) r.ps_bwd[tail] = CHAIN_PS2;
+    }
+    return r;
+  }
   int hl, hr, mo, max_dil;
   stack_halo(n, &hl, &hr, &mo, &max_dil);
   StackP sp = stack_fwd_shape(n, B, T);
   StackBP bp = stack_bwd_shape(n, B, T);
   r.fused = stack_fwd_plan(sp, precise) == CRK_OK && stack_bwd_plan(bp, precise) == CRK_OK &&
-            stack_wgrad_supported(d.kernel_size, max_dil, sp.aux_ch) && plain_chains_ok(n, B, T, precise);
+            stack_wgrad_supported(d.kernel_size, max_dil, sp.aux_ch) && plain_chains_ok(n, B, T, precise, Tb);
   r.usums = r.fused && d.aux_ch > 0;
-  if (!r.fused || precise || sw.sk_v != 2 || sw.skb_v != 2) return r;
-  if (d.kind == 0 && d.dropout == 0.f && d.in_ch % 8 == 0 && d.out_ch % 8 == 0) {
-    // Generator stacks in plain bf16: forward and data-gradient chain both run channel-split (stack2_kernels.hip,
-    // stack2b_kernels.hip), first conv and head folded in, and exchange the tanh / sigmoid planes in the lane-record layout.
+  if (!r.fused || precise) return r;
+  // plain bf16: the unfolded blocks on the channel-split kernel (stack2_kernels.hip); CRK_SK_V=1: the frame-split one
+  StackP u = stack_fwd_shape(n, B, T);
+  u.drop_p = d.dropout;
+  r.blocks_s2 = sw.sk_v != 1 && stack2_fwd_plan(u) == CRK_OK;
+  const bool split_sw = sw.sk_v == 2 && sw.skb_v == 2;
+  if (d.kind == 0 && sw.sk_v == 2 && d.dropout == 0.f) {
     StackP f = stack_fwd_shape(n, B, T);
     f.x_in = reinterpret_cast<const float*>(n);  // (any non-null value: folded, the plan sizes the first conv's input tile)
     f.in_ch = d.in_ch; f.kp_first = n->ents[n->idx_first].fw_kp;
     StackP fx = f;
     StackBP b = stack_bwd_shape(n, B, T);
-    r.gen_split = stack2_fwd_plan(f) == CRK_OK && stack2_bwd_plan(b) == CRK_OK;
+    // out_ch % 8 != 0 but % 4 == 0: the forward still folds, on row-layout planes; the backward stays frame-split and unfolded
+    r.fold_fwd = d.in_ch % 8 == 0 && d.out_ch % 4 == 0 && stack2_fwd_plan(f) == CRK_OK;
+    r.fold_bwd_fs = d.out_ch % 8 == 0 && stack_bwd_waves(false) == 8;
+    // Generator stacks in plain bf16: forward and data-gradient chain both run channel-split (stack2_kernels.hip,
+    // stack2b_kernels.hip), first conv and head folded in, and exchange the tanh / sigmoid planes in the lane-record layout.
+    r.gen_split = r.fold_fwd && split_sw && d.out_ch % 8 == 0 && stack2_bwd_plan(b) == CRK_OK;
     // bf16x3f (forward in split-operand arithmetic, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN; backward in plain bf16,
     // CRK_FLAG_FWD_PRECISE): the channel-split split-operand forward (stack2x_kernels.hip) leaves the hi planes in this route's
     // layout for this route's backward.  CRK_S2X=0: the round-4 pairing (frame-split stack_fwd_kernel<PRECISE>, frame-split
     // chain on row planes).
     r.x3f = r.gen_split && sw.s2x && stack2x_fwd_plan(fx) == CRK_OK;
   }
-  if (d.kind == 1 && d.aux_ch == 0 && sw.disc_split) {
+  if (d.kind == 1 && d.aux_ch == 0 && sw.disc_split && split_sw) {
     // The discriminator (no conditioning) in plain bf16, dropout or not: the forward's gated blocks (stack2_fwd_kernel, not
     // folded: first conv and head keep their own launches) and the data-gradient chain (stack2_bwd_kernel<.., FOLD = false>)
     // run channel-split.  CRK_DISC_SPLIT=0: the round-3 pairing (channel-split forward, frame-split chain, row-layout planes).
-    StackP f = stack_fwd_shape(n, B, T);
-    f.drop_p = d.dropout;
     StackBP b = stack_bwd_shape(n, B, T);
-    r.disc_split = stack2_fwd_plan(f) == CRK_OK && stack2_bwd_plan(b) == CRK_OK;
+    r.disc_split = r.blocks_s2 && stack2_bwd_plan(b) == CRK_OK;
   }
   return r;
-}
-
-static void tag_forward(Net* n, const float* saved, int B, int T, int flags, bool x3f) {
-  if (!saved || (flags & CRK_FLAG_NO_SAVE)) return;
-  for (int i = 0; i < n->fwd_tag_count; i++)
-    if (n->fwd_tags[i].saved == saved) { n->fwd_tags[i] = {saved, B, T, (unsigned char)((flags & CRK_FLAG_PRECISE) ? ((flags & CRK_FLAG_BWD_PLAIN) ? 2 : 1) : 0), x3f}; return; }
-  n->fwd_tags[n->fwd_tag_next] = {saved, B, T, (unsigned char)((flags & CRK_FLAG_PRECISE) ? ((flags & CRK_FLAG_BWD_PLAIN) ? 2 : 1) : 0), x3f};
-  n->fwd_tag_next = (n->fwd_tag_next + 1) % 32;
-  if (n->fwd_tag_count < 32) n->fwd_tag_count++;
-}
-// CRK_ERR_ARG when the backward's flags do not describe the forward that filled `saved` (an unknown workspace - evicted from
-// the ring, or written through another handle - passes: the caller's pairing is all there is then)
-static int check_forward_tag(const Net* n, const float* saved, int B, int T, int flags, bool expects_x3f) {
-  for (int i = 0; i < n->fwd_tag_count; i++) {
-    const Net::FwdTag& t = n->fwd_tags[i];
-    if (t.saved != saved) continue;
-    const int want = (flags & CRK_FLAG_PRECISE) ? 1 : ((flags & CRK_FLAG_FWD_PRECISE) ? 2 : 0);
-    if (t.B != B || t.T != T || t.mode != want || (want == 2 && t.x3f != expects_x3f)) {
-      fprintf(stderr, "[crank_hip] crk_net_backward: flags 0x%x (plane layout %d%s, B %d, T %d) do not match the forward that wrote this "
-                      "workspace (layout %d%s, B %d, T %d): CRK_FLAG_PRECISE pairs with CRK_FLAG_PRECISE, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN "
-                      "with CRK_FLAG_FWD_PRECISE, plain with plain\n", flags, want, expects_x3f ? " x3f" : "", B, T, t.mode, t.x3f ? " x3f" : "", t.B, t.T);
-      return CRK_ERR_ARG;
-    }
-    return CRK_OK;
-  }
-  return CRK_OK;
 }
 static const Shape* find_shape(const Net* n, int B, int T) {
   for (const Shape& r : n->shapes)
     if (r.B == B && r.T == T) return &r;
   return nullptr;
 }
+// the route the compute entry points read: the shape's record, or (a shape that is not reserved) what the record would hold
+static Route route_at(const Net* n, int B, int T, bool precise) {
+  const Shape* r = find_shape(n, B, T);
+  return r ? r->route[precise] : route_of(n, B, T, precise);
+}
+
+// What belongs to one call and not to its batch shape, read once at the top of the entry point.  in / out: x / y of a
+// forward, dy / dx of a backward.
+struct Call {
+  bool precise, keep, defer_wn;    // CRK_FLAG_PRECISE; no CRK_FLAG_NO_SAVE: a backward will read the planes; CRK_FLAG_DEFER_WNORM
+  bool want_dx, want_dc, want_w;   // backward: input, conditioning and parameter gradients are wanted
+  bool in16, out16, in4;           // base 16-byte aligned and row stride a multiple of 4 floats (no `out`: true); base 4-byte aligned
+  unsigned char mode;              // Net::FwdTag::mode: what a forward writes, what a backward expects to find
+  unsigned long long seed_val; const unsigned long long* seed_ptr;  // the dropout seed: a value, or (CRK_FLAG_SEED_ON_DEVICE)
+};                                                                  // the address of one in device memory
+static bool rows16(const float* p, int ld) { return ld % 4 == 0 && (((uintptr_t)p) & 15) == 0; }
+static Call call_facts(int flags, unsigned long long seed, bool forward, const float* in, int ldin, const float* out, int ldout,
+                       const float* dc, const float* grads) {
+  Call k;
+  k.precise = flags & CRK_FLAG_PRECISE; k.keep = !(flags & CRK_FLAG_NO_SAVE); k.defer_wn = flags & CRK_FLAG_DEFER_WNORM;
+  k.want_dx = out != nullptr; k.want_dc = dc != nullptr; k.want_w = !(flags & CRK_FLAG_NO_PARAM_GRAD) && grads;
+  k.in16 = rows16(in, ldin); k.out16 = !out || rows16(out, ldout); k.in4 = (((uintptr_t)in) & 3) == 0;
+  k.mode = k.precise ? ((forward && (flags & CRK_FLAG_BWD_PLAIN)) ? 2 : 1) : ((!forward && (flags & CRK_FLAG_FWD_PRECISE)) ? 2 : 0);
+  k.seed_ptr = (flags & CRK_FLAG_SEED_ON_DEVICE) ? reinterpret_cast<const unsigned long long*>((uintptr_t)seed) : nullptr;
+  k.seed_val = (flags & CRK_FLAG_SEED_ON_DEVICE) ? 0ull : seed;
+  return k;
+}
+
+static void tag_forward(Net* n, const float* saved, int B, int T, const Call& k, bool x3f) {
+  if (!saved || !k.keep) return;
+  const Net::FwdTag tag = {saved, B, T, k.mode, x3f};
+  for (int i = 0; i < n->fwd_tag_count; i++)
+    if (n->fwd_tags[i].saved == saved) { n->fwd_tags[i] = tag; return; }
+  n->fwd_tags[n->fwd_tag_next] = tag;
+  n->fwd_tag_next = (n->fwd_tag_next + 1) % 32;
+  if (n->fwd_tag_count < 32) n->fwd_tag_count++;
+}
+// CRK_ERR_ARG when the backward's flags do not describe the forward that filled `saved` (an unknown workspace - evicted from
+// the ring, or written through another handle - passes: the caller's pairing is all there is then)
+static int check_forward_tag(const Net* n, const float* saved, int B, int T, int flags, int want, bool expects_x3f) {
+  for (int i = 0; i < n->fwd_tag_count; i++) {
+    const Net::FwdTag& t = n->fwd_tags[i];
+    if (t.saved != saved) continue;
+    if (t.B == B && t.T == T && t.mode == want && (want != 2 || t.x3f == expects_x3f)) return CRK_OK;
+    fprintf(stderr, "[crank_hip] crk_net_backward: flags 0x%x (plane layout %d%s, B %d, T %d) do not match the forward that wrote this "
+                    "workspace (layout %d%s, B %d, T %d): CRK_FLAG_PRECISE pairs with CRK_FLAG_PRECISE, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN "
+                    "with CRK_FLAG_FWD_PRECISE, plain with plain\n", flags, want, expects_x3f ? " x3f" : "", B, T, t.mode, t.x3f ? " x3f" : "", t.B, t.T);
+    return CRK_ERR_ARG;
+  }
+  return CRK_OK;
+}
+
+// ---- forward: one function per route ----------------------------------------------------------------------------------
+struct FwdIo {  // the arguments of crk_net_forward
+  const float* params; const float* x; int ldx; const float* c; int ldc; float* y; int ldy; float* saved; int B, T; hipStream_t s;
+};
+enum { FWD_CHAIN, FWD_CHAIN_LAYERS, FWD_FOLDED, FWD_FUSED, FWD_LAYERS };
+// (route, call) -> the launch form of a forward, or the error the call returns
+static int fwd_form(const Net* n, const Route& rt, const Call& k, bool x3f, int* form) {
+  if (n->d.kind == 2) { *form = rt.fused ? FWD_CHAIN : FWD_CHAIN_LAYERS; return CRK_OK; }
+  // per call: the folded kernels read x and write y in 16-byte pieces
+  const bool io16 = k.in16 && k.out16;
+  if ((x3f || rt.gen_split) && !io16) {
+    // a channel-split route, whose backward reads the lane-record planes only the folded forward writes: the call fails
+    fprintf(stderr, "[crank_hip] crk_net_forward: x / y must be 16-byte aligned with row strides that are multiples of 4 floats\n");
+    return CRK_ERR_ARG;
+  }
+  if (x3f || (rt.fold_fwd && io16)) *form = FWD_FOLDED;
+  else if (rt.gen_split) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
+  // a generator on a non-split route with x or y only 4-byte aligned lands here: the unfolded fused path, no error
+  else *form = rt.fused ? FWD_FUSED : FWD_LAYERS;
+  return CRK_OK;
+}
+
+// plain chain, fused: the whole stack in one launch; every conv's input operand is kept as a bf16 plane
+static int fwd_chain(const Net* n, const Shape* r, const Call& k, const FwdIo& a) {
+  if (!a.saved && k.keep) return CRK_ERR_ARG;
+  const Route& rt = r->route[k.precise];
+  const PsTables& Tb = r->ps;
+  const long long N = (long long)a.B * a.T;
+  PsP p = ps_base(n, a.B, a.T, a.params);
+  p.x = a.x; p.ldx = a.ldx; p.cin = n->d.in_ch; p.y = a.y; p.ldy = a.ldy;
+  if (k.keep) {
+    p.save_hi = reinterpret_cast<uint16_t*>(a.saved + saved_f32_floats(n, N));
+    p.save_lo = p.save_hi + N * plain_planes_w(n);
+  }
+  p.layers = r->d_ps; p.L = Tb.L[0];
+  const double flops = ps_flops(Tb.t[0], Tb.L[0], N);
+  const int kern = k.mode == 2 ? rt.ps_fwd_x3f : rt.ps_fwd;
+  if (kern == CHAIN_PS2X) p.save_lo = nullptr;  // bf16x3f: split-operand forward, hi planes only
+  if (kern == CHAIN_PS2X) { RUN(pstack2x_plan(p, Tb.t[0])); return launch_pstack2x(p, flops, a.s); }
+  if (kern == CHAIN_PS2) { RUN(pstack2_plan(p, Tb.t[0])); return launch_pstack2(p, flops, a.s); }
+  return pstack_go(r, 0, p, k.precise, a.s);
+}
+static int fwd_chain_layers(const Net* n, const Call& k, const FwdIo& a) {
+  const crk_net_desc& d = n->d;
+  const int L = n->L;
+  const long long N = (long long)a.B * a.T;
+  if (L > 1 && !a.saved) return CRK_ERR_ARG;
+  const float* in = a.x; int ldin = a.ldx;
+  for (int i = 0; i < L; i++) {
+    const ConvEntry& e = n->ents[n->idx_plain[i]];
+    const int dil = n->meta[n->idx_plain[i]].dilation;
+    const bool last = i == L - 1;
+    ConvP p = conv_fw(n, a.B, a.T, e, a.params, in, ldin, last ? a.y : a.saved + (long long)i * N * d.conv_ch, last ? a.ldy : d.conv_ch);
+    p.act_in = (i == 0) ? ACT_NONE : ACT_LRELU;
+    p.ktaps = e.k; p.dil = dil; p.off0 = -((e.k - 1) / 2) * dil;
+    RUN(conv_go(p, MODE_PLAIN, k.precise, a.s));
+    in = p.y; ldin = p.ldy;
+  }
+  return CRK_OK;
+}
+// a gated forward's launch parameters, all but the stack's input and output.  lo: hi + lo planes (the unfolded kernels); else
+// the hi planes and the folded first conv's and head's
+static StackP stack_fwd_params(const Net* n, const Call& k, const FwdIo& a, bool lo) {
+  const long long N = (long long)a.B * a.T;
+  const GatedB16 gf = gated_b16(n, N);
+  uint16_t* b16 = reinterpret_cast<uint16_t*>(a.saved + saved_f32_floats(n, N));
+  StackP sp = stack_fwd_shape(n, a.B, a.T);
+  sp.c = a.c; sp.ldc = a.ldc; sp.params = a.params;
+  sp.skip = a.saved + gated_f32(n, N).skip;  // (unused by the folded kernel; a valid base for its dummy descriptors)
+  sp.whi = n->whi; sp.wlo = n->wlo; sp.layers = n->d_layers;
+  if (!k.keep) return sp;
+  sp.saved = a.saved;
+  sp.xb_hi = b16 + gf.xb_hi; sp.zb_hi = b16 + gf.zb_hi; sp.tb_hi = b16 + gf.tb_hi; sp.sg_hi = b16 + gf.sg_hi;
+  if (n->d.aux_ch > 0) sp.cb_hi = b16 + gf.cb_hi;
+  if (!lo) { sp.fin_hi = b16 + gf.f_hi; sp.head_hi = b16 + gf.head_hi; return sp; }
+  sp.xb_lo = b16 + gf.xb_lo; sp.zb_lo = b16 + gf.zb_lo; sp.tb_lo = b16 + gf.tb_lo; sp.sg_lo = b16 + gf.sg_lo;
+  if (n->d.aux_ch > 0) sp.cb_lo = b16 + gf.cb_lo;
+  return sp;
+}
+// generator stacks: first conv, gated blocks and head in ONE launch - plain bf16 (stack2_kernels.hip), or x3f: split-operand
+// arithmetic that saves the plain route's planes (stack2x_kernels.hip)
+static int fwd_folded(const Net* n, const Route& rt, const Call& k, const FwdIo& a, bool x3f) {
+  const crk_net_desc& d = n->d;
+  const ConvEntry& ef = n->ents[n->idx_first];
+  const ConvEntry& e1 = n->ents[n->idx_last1];
+  const ConvEntry& e2 = n->ents[n->idx_last2];
+  StackP sp = stack_fwd_params(n, k, a, false);
+  sp.x_in = a.x; sp.ldx_in = a.ldx; sp.in_ch = d.in_ch; sp.kp_first = ef.fw_kp;
+  sp.f_first = ef.fr_off; sp.b_first = ef.off_b;
+  sp.f_h1 = e1.fr_off; sp.b_h1 = e1.off_b; sp.f_h2 = e2.fr_off; sp.b_h2 = e2.off_b;
+  sp.y = a.y; sp.ldy = a.ldy; sp.out_ch = d.out_ch; sp.head_scale = (float)sqrt(1.0 / n->L);
+  // a channel-split route: the lane-record planes.  Not one (out_ch % 8 != 0 but % 4 == 0, or CRK_SKB_V=1): row-layout planes
+  if (x3f || rt.gen_split) sp.ts_stride = ts_plane_stride((long long)a.B * a.T);
+  if (x3f) { RUN(stack2x_fwd_plan(sp)); return launch_stack2x_fwd(sp, a.s); }
+  RUN(stack2_fwd_plan(sp));
+  return launch_stack2_fwd(sp, a.s);
+}
+// gated stack, fused and not folded: first conv, the blocks and the head, one launch each
+static int fwd_fused(const Net* n, const Shape* r, const Call& k, const FwdIo& a) {
+  const crk_net_desc& d = n->d;
+  const Route& rt = r->route[k.precise];
+  const long long N = (long long)a.B * a.T;
+  const GatedF32 lay = gated_f32(n, N);
+  const GatedB16 gf = gated_b16(n, N);
+  uint16_t* b16 = reinterpret_cast<uint16_t*>(a.saved + saved_f32_floats(n, N));
+  PsP f = ps_base(n, a.B, a.T, a.params);  // first conv (1x1; kind 1: + LeakyReLU) -> X_0, its input kept as a bf16 plane
+  f.x = a.x; f.ldx = a.ldx; f.cin = d.in_ch; f.y = a.saved + lay.x; f.ldy = 64; f.L = 1;
+  if (k.keep) { f.save_hi = b16 + gf.f_hi; f.save_lo = b16 + gf.f_lo; }
+  RUN(pstack_go(r, 0, f, k.precise, a.s));
+  StackP sp = stack_fwd_params(n, k, a, true);
+  sp.x0 = a.saved + lay.x;
+  if (d.dropout > 0.f) { sp.drop_p = d.dropout; sp.drop_seed = k.seed_val; sp.drop_seed_ptr = k.seed_ptr; }
+  if (rt.disc_split) sp.ts_stride = ts_plane_stride(N);  // (its data-gradient chain reads lane records)
+  if (rt.blocks_s2) { RUN(stack2_fwd_plan(sp)); RUN(launch_stack2_fwd(sp, a.s)); }
+  else {
+    if (sp.ts_stride) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
+    RUN(stack_fwd_plan(sp, k.precise));
+    RUN(launch_stack_fwd(sp, k.precise, a.s));
+  }
+  // head: act(skips * sqrt(1/L)) -> 1x1 -> act -> 1x1, one launch; both operands kept as bf16 planes
+  PsP p = ps_base(n, a.B, a.T, a.params);
+  p.x = a.saved + lay.skip; p.ldx = 64; p.cin = 64; p.in_scale = (float)sqrt(1.0 / n->L); p.in_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
+  p.y = a.y; p.ldy = a.ldy; p.L = 2;
+  if (k.keep) { p.save_hi = b16 + gf.head_hi; p.save_lo = b16 + gf.head_lo; }
+  return pstack_go(r, 1, p, k.precise, a.s);
+}
+static int fwd_layers(const Net* n, const Call& k, const FwdIo& a) {
+  const crk_net_desc& d = n->d;
+  const int L = n->L, head_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
+  const long long N = (long long)a.B * a.T, P = N * 64;
+  const GatedF32 lay = gated_f32(n, N);
+  float *X = a.saved + lay.x, *SKIP = a.saved + lay.skip, *H1 = a.saved + lay.h1;
+  ConvP f = conv_fw(n, a.B, a.T, n->ents[n->idx_first], a.params, a.x, a.ldx, X, 64);  // first conv (kind 1: + LeakyReLU)
+  f.act_out = d.kind == 1 ? ACT_LRELU : ACT_NONE;
+  RUN(conv_go(f, MODE_PLAIN, k.precise, a.s));
+  for (int l = 0; l < L; l++) {
+    const ConvEntry& ec = n->ents[n->idx_conv[l]];
+    const ConvEntry& eo = n->ents[n->idx_out[l]];
+    const ConvEntry& es = n->ents[n->idx_skip[l]];
+    const int dil = n->meta[n->idx_conv[l]].dilation;
+    ConvP p = conv_fw(n, a.B, a.T, ec, a.params, X + l * P, 64, (l < L - 1) ? X + (l + 1) * P : nullptr, 64);
+    p.ktaps = ec.k; p.dil = dil; p.off0 = fwd_off0(n, ec.k, dil);
+    if (d.dropout > 0.f) { p.drop_p = d.dropout; p.drop_seed = layer_seed(k.seed_val, l); p.drop_seed_ptr = k.seed_ptr; }
+    if (d.aux_ch > 0) {
+      const ConvEntry& ea = n->ents[n->idx_aux[l]];
+      p.xc = a.c; p.ldc = a.ldc; p.cinC = ea.cin; p.cinC_pad = ea.fw_kp;
+      p.wc_hi = n->whi + ea.fw_off; p.wc_lo = n->wlo + ea.fw_off;
+    }
+    p.w2_hi = n->whi + eo.fw_off; p.w2_lo = n->wlo + eo.fw_off;
+    p.bias2a = eo.off_b >= 0 ? a.params + eo.off_b : nullptr;
+    p.bias2b = es.off_b >= 0 ? a.params + es.off_b : nullptr;
+    p.skip = SKIP; p.skip_init = (l == 0);
+    p.sv_ta = a.saved + lay.ta + l * P; p.sv_sb = a.saved + lay.sb + l * P; p.sv_z = a.saved + lay.z + l * P;
+    RUN(conv_go(p, MODE_RESFWD, k.precise, a.s));
+  }
+  // head: act(skips * sqrt(1/L)) -> 1x1 -> act -> 1x1
+  ConvP h1 = conv_fw(n, a.B, a.T, n->ents[n->idx_last1], a.params, SKIP, 64, H1, 64);
+  h1.scaleA = (float)sqrt(1.0 / L); h1.act_in = head_act;
+  RUN(conv_go(h1, MODE_PLAIN, k.precise, a.s));
+  ConvP h2 = conv_fw(n, a.B, a.T, n->ents[n->idx_last2], a.params, H1, 64, a.y, a.ldy);
+  h2.act_in = head_act;
+  return conv_go(h2, MODE_PLAIN, k.precise, a.s);
+}
 extern "C" int crk_net_forward(void* h, const float* params, unsigned long long version, const float* x, int ldx,
                                const float* c, int ldc, float* y, int ldy, float* saved, int B, int T, int flags,
                                unsigned long long seed, void* stream) {
   Net* n = (Net*)h;
   if (!n || !params || !x || !y || B <= 0 || T <= 0) return CRK_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool precise = flags & CRK_FLAG_PRECISE;
-  // the call's dropout seed: a value, or (CRK_FLAG_SEED_ON_DEVICE) the address of one in device memory
-  const unsigned long long* seed_ptr = (flags & CRK_FLAG_SEED_ON_DEVICE) ? reinterpret_cast<const unsigned long long*>((uintptr_t)seed) : nullptr;
-  const unsigned long long seed_val = (flags & CRK_FLAG_SEED_ON_DEVICE) ? 0ull : seed;
-  const crk_net_desc& d = n->d;
+  const FwdIo a = {.params = params, .x = x, .ldx = ldx, .c = c, .ldc = ldc, .y = y, .ldy = ldy, .saved = saved, .B = B, .T = T,
+                   .s = (hipStream_t)stream};
+  const Call k = call_facts(flags, seed, true, x, ldx, y, ldy, nullptr, nullptr);
   const Shape* r = find_shape(n, B, T);
   if (!r) return not_reserved("crk_net_forward");
-  const Route& rt = r->route[precise];
+  const Route& rt = r->route[k.precise];
   // bf16x3f: split-operand arithmetic that saves the plain route's planes
-  const bool x3f = precise && (flags & CRK_FLAG_BWD_PLAIN) && r->route[0].x3f;
-  RUN(ensure_prepared(n, params, version, s));
-  tag_forward(n, saved, B, T, flags, x3f);
-  const long long N = (long long)B * T;
-  const PsTables& Tb = r->ps;
-  if (d.kind == 2 && rt.fused) {
-    // the whole stack in one launch; every conv's input operand is kept as a bf16 plane
-    if (!saved && !(flags & CRK_FLAG_NO_SAVE)) return CRK_ERR_ARG;
-    PsP p = ps_base(n, B, T, params);
-    p.x = x; p.ldx = ldx; p.cin = d.in_ch; p.y = y; p.ldy = ldy;
-    if (!(flags & CRK_FLAG_NO_SAVE)) {
-      p.save_hi = reinterpret_cast<uint16_t*>(saved + saved_f32_floats(n, N));
-      p.save_lo = p.save_hi + N * plain_planes_w(n);
-    }
-    p.layers = r->d_ps; p.L = Tb.L[0];
-    if (!precise && crk_sw().ps_v == 2) {  // channel-split chain (pstack2_kernels.hip); CRK_PS_V=1: the frame-split one
-      PsP q = p;
-      if (pstack2_plan(q, Tb.t[0]) == CRK_OK) return launch_pstack2(q, ps_flops(Tb.t[0], Tb.L[0], N), s);
-    }
-    if (precise && (flags & CRK_FLAG_BWD_PLAIN) && crk_sw().ps_v == 2) {  // bf16x3f: split-operand forward, hi planes only
-      PsP q = p;
-      q.save_lo = nullptr;
-      if (crk_sw().s2x && pstack2x_plan(q, Tb.t[0]) == CRK_OK) return launch_pstack2x(q, ps_flops(Tb.t[0], Tb.L[0], N), s);
-    }
-    RUN(pstack_plan(p, Tb.t[0], precise));
-    return launch_pstack(p, precise, ps_flops(Tb.t[0], Tb.L[0], N), s);
+  const bool x3f = k.mode == 2 && r->route[0].x3f;
+  RUN(ensure_prepared(n, params, version, a.s));
+  tag_forward(n, saved, B, T, k, x3f);
+  if (n->d.kind != 2 && (!saved || (n->d.aux_ch > 0 && !c))) return CRK_ERR_ARG;
+  int form;
+  RUN(fwd_form(n, rt, k, x3f, &form));
+  switch (form) {
+    case FWD_CHAIN: return fwd_chain(n, r, k, a);
+    case FWD_CHAIN_LAYERS: return fwd_chain_layers(n, k, a);
+    case FWD_FOLDED: return fwd_folded(n, rt, k, a, x3f);
+    case FWD_FUSED: return fwd_fused(n, r, k, a);
   }
-  if (d.kind == 2) {
-    const int L = n->L;
-    if (L > 1 && !saved) return CRK_ERR_ARG;
-    const float* in = x; int ldin = ldx;
-    for (int i = 0; i < L; i++) {
-      const ConvEntry& e = n->ents[n->idx_plain[i]];
-      const int dil = n->meta[n->idx_plain[i]].dilation;
-      ConvP p = base_conv(n, B, T);
-      set_fw_weights(n, p, e, params);
-      p.xa = in; p.lda = ldin; p.cinA = e.cin;
-      p.act_in = (i == 0) ? ACT_NONE : ACT_LRELU;
-      p.ktaps = e.k; p.dil = dil; p.off0 = -((e.k - 1) / 2) * dil;
-      if (i == L - 1) { p.y = y; p.ldy = ldy; }
-      else { p.y = saved + (long long)i * N * d.conv_ch; p.ldy = d.conv_ch; }
-      RUN(conv_go(p, MODE_PLAIN, precise, s));
-      in = p.y; ldin = p.ldy;
-    }
-    return CRK_OK;
-  }
-  if (!saved || (d.aux_ch > 0 && !c)) return CRK_ERR_ARG;
-  const int L = n->L;
-  const long long P = N * 64;
-  float* X = saved;                 // X[l], l < L
-  float* TA = saved + (long long)L * P;
-  float* SB = TA + (long long)L * P;
-  float* Z = SB + (long long)L * P;
-  float* SKIP = Z + (long long)L * P;
-  float* H1 = SKIP + P;
-  const int head_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
-  const bool fused = rt.fused;
-  uint16_t* b16 = reinterpret_cast<uint16_t*>(saved + saved_f32_floats(n, N));
-  const GatedB16 gf = gated_b16(n, N);
-  const bool keep = !(flags & CRK_FLAG_NO_SAVE);
-  // plain bf16, generator stacks: first conv, gated blocks and head in ONE launch (stack2_kernels.hip)
-  bool folded = false;
-  if ((fused && !precise && d.kind == 0) || x3f) {
-    const ConvEntry& ef = n->ents[n->idx_first];
-    const ConvEntry& e1 = n->ents[n->idx_last1];
-    const ConvEntry& e2 = n->ents[n->idx_last2];
-    StackP sp = stack_fwd_shape(n, B, T);
-    sp.c = c; sp.ldc = ldc;
-    sp.params = params;
-    if (keep) {
-      sp.saved = saved;
-      sp.xb_hi = b16 + gf.xb_hi; sp.zb_hi = b16 + gf.zb_hi; sp.tb_hi = b16 + gf.tb_hi; sp.sg_hi = b16 + gf.sg_hi;
-      if (d.aux_ch > 0) sp.cb_hi = b16 + gf.cb_hi;
-      sp.fin_hi = b16 + gf.f_hi; sp.head_hi = b16 + gf.head_hi;
-    }
-    sp.skip = SKIP;  // (unused by the folded kernel; a valid base for its dummy descriptors)
-    sp.whi = n->whi; sp.wlo = n->wlo; sp.layers = n->d_layers;
-    sp.x_in = x; sp.ldx_in = ldx; sp.in_ch = d.in_ch; sp.kp_first = ef.fw_kp;
-    sp.f_first = ef.fr_off; sp.b_first = ef.off_b;
-    sp.f_h1 = e1.fr_off; sp.b_h1 = e1.off_b; sp.f_h2 = e2.fr_off; sp.b_h2 = e2.off_b;
-    sp.y = y; sp.ldy = ldy; sp.out_ch = d.out_ch; sp.head_scale = (float)sqrt(1.0 / L);
-    // per call: the folded kernels read x and write y in 16-byte pieces; without that the stack takes the unfolded path, or
-    // (a channel-split route, whose backward reads the lane-record planes only this forward writes) the call fails
-    const bool shape_ok = (d.in_ch % 8 == 0) && (ldx % 4 == 0) && (d.out_ch % 4 == 0) && (ldy % 4 == 0) &&
-                          ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)y) & 15) == 0);
-    const bool split = x3f || rt.gen_split;
-    if (split && !shape_ok) {
-      fprintf(stderr, "[crank_hip] crk_net_forward: x / y must be 16-byte aligned with row strides that are multiples of 4 floats\n");
-      return CRK_ERR_ARG;
-    }
-    if (split) sp.ts_stride = ts_plane_stride(N);
-    if (x3f) {  // split-operand arithmetic, the plain path's planes
-      RUN(stack2x_fwd_plan(sp));
-      RUN(launch_stack2x_fwd(sp, s));
-      folded = true;
-    } else if (crk_sw().sk_v == 2 && shape_ok && d.dropout == 0.f && stack2_fwd_plan(sp) == CRK_OK) {
-      RUN(launch_stack2_fwd(sp, s));
-      folded = true;
-    } else if (split) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
-  }
-  if (folded) return CRK_OK;
-  if (fused) {  // first conv (1x1; kind 1: + LeakyReLU) -> X_0, its input kept as a bf16 plane
-    PsP p = ps_base(n, B, T, params);
-    p.x = x; p.ldx = ldx; p.cin = d.in_ch; p.y = X; p.ldy = 64;
-    if (keep) { p.save_hi = b16 + gf.f_hi; p.save_lo = b16 + gf.f_lo; }
-    p.layers = r->d_ps; p.L = 1;
-    RUN(pstack_plan(p, Tb.t[0], precise));
-    RUN(launch_pstack(p, precise, ps_flops(Tb.t[0], 1, N), s));
-  } else
-  {  // first conv (kind 1: followed by LeakyReLU)
-    const ConvEntry& e = n->ents[n->idx_first];
-    ConvP p = base_conv(n, B, T);
-    set_fw_weights(n, p, e, params);
-    p.xa = x; p.lda = ldx; p.cinA = e.cin;
-    p.y = X; p.ldy = 64; p.act_out = d.kind == 1 ? ACT_LRELU : ACT_NONE;
-    RUN(conv_go(p, MODE_PLAIN, precise, s));
-  }
-  if (fused) {
-    StackP sp = stack_fwd_shape(n, B, T);
-    sp.x0 = X; sp.c = c; sp.ldc = ldc;
-    sp.skip = SKIP; sp.params = params;
-    if (keep) {
-      sp.saved = saved;
-      sp.xb_hi = b16 + gf.xb_hi; sp.xb_lo = b16 + gf.xb_lo; sp.zb_hi = b16 + gf.zb_hi; sp.zb_lo = b16 + gf.zb_lo;
-      sp.tb_hi = b16 + gf.tb_hi; sp.tb_lo = b16 + gf.tb_lo; sp.sg_hi = b16 + gf.sg_hi; sp.sg_lo = b16 + gf.sg_lo;
-      if (d.aux_ch > 0) { sp.cb_hi = b16 + gf.cb_hi; sp.cb_lo = b16 + gf.cb_lo; }
-    }
-    sp.whi = n->whi; sp.wlo = n->wlo; sp.layers = n->d_layers;
-    if (d.dropout > 0.f) { sp.drop_p = d.dropout; sp.drop_seed = seed_val; sp.drop_seed_ptr = seed_ptr; }
-    // plain bf16: the channel-split kernel (stack2_kernels.hip); bf16x3 and CRK_SK_V=1: the frame-split one
-    if (rt.disc_split) sp.ts_stride = ts_plane_stride(N);  // (its data-gradient chain reads lane records)
-    if (!precise && crk_sw().sk_v != 1 && stack2_fwd_plan(sp) == CRK_OK) {
-      RUN(launch_stack2_fwd(sp, s));
-    } else {
-      if (sp.ts_stride) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
-      RUN(stack_fwd_plan(sp, precise));
-      RUN(launch_stack_fwd(sp, precise, s));
-    }
-  }
-  for (int l = 0; l < L && !fused; l++) {
-    const ConvEntry& ec = n->ents[n->idx_conv[l]];
-    const ConvEntry& eo = n->ents[n->idx_out[l]];
-    const ConvEntry& es = n->ents[n->idx_skip[l]];
-    const int dil = n->meta[n->idx_conv[l]].dilation;
-    ConvP p = base_conv(n, B, T);
-    set_fw_weights(n, p, ec, params);
-    p.xa = X + l * P; p.lda = 64; p.cinA = 64;
-    p.ktaps = ec.k; p.dil = dil; p.off0 = fwd_off0(n, ec.k, dil);
-    if (d.dropout > 0.f) { p.drop_p = d.dropout; p.drop_seed = layer_seed(seed_val, l); p.drop_seed_ptr = seed_ptr; }
-    if (d.aux_ch > 0) {
-      const ConvEntry& ea = n->ents[n->idx_aux[l]];
-      p.xc = c; p.ldc = ldc; p.cinC = ea.cin; p.cinC_pad = ea.fw_kp;
-      p.wc_hi = n->whi + ea.fw_off; p.wc_lo = n->wlo + ea.fw_off;
-    }
-    p.w2_hi = n->whi + eo.fw_off; p.w2_lo = n->wlo + eo.fw_off;
-    p.bias2a = eo.off_b >= 0 ? params + eo.off_b : nullptr;
-    p.bias2b = es.off_b >= 0 ? params + es.off_b : nullptr;
-    p.y = (l < L - 1) ? X + (l + 1) * P : nullptr; p.ldy = 64;
-    p.skip = SKIP; p.skip_init = (l == 0);
-    p.sv_ta = TA + l * P; p.sv_sb = SB + l * P; p.sv_z = Z + l * P;
-    RUN(conv_go(p, MODE_RESFWD, precise, s));
-  }
-  if (fused) {  // head: act(skips * sqrt(1/L)) -> 1x1 -> act -> 1x1, one launch; both operands kept as bf16 planes
-    PsP p = ps_base(n, B, T, params);
-    p.x = SKIP; p.ldx = 64; p.cin = 64; p.in_scale = (float)sqrt(1.0 / L); p.in_act = head_act;
-    p.y = y; p.ldy = ldy;
-    if (keep) { p.save_hi = b16 + gf.head_hi; p.save_lo = b16 + gf.head_lo; }
-    p.layers = r->d_ps + PS_MAXL; p.L = 2;
-    RUN(pstack_plan(p, Tb.t[1], precise));
-    RUN(launch_pstack(p, precise, ps_flops(Tb.t[1], 2, N), s));
-  } else
-  {  // head: act(skips * sqrt(1/L)) -> 1x1 -> act -> 1x1
-    const ConvEntry& e1 = n->ents[n->idx_last1];
-    ConvP p = base_conv(n, B, T);
-    set_fw_weights(n, p, e1, params);
-    p.xa = SKIP; p.lda = 64; p.cinA = 64; p.scaleA = (float)sqrt(1.0 / L); p.act_in = head_act;
-    p.y = H1; p.ldy = 64;
-    RUN(conv_go(p, MODE_PLAIN, precise, s));
-    const ConvEntry& e2 = n->ents[n->idx_last2];
-    ConvP q = base_conv(n, B, T);
-    set_fw_weights(n, q, e2, params);
-    q.xa = H1; q.lda = 64; q.cinA = 64; q.act_in = head_act;
-    q.y = y; q.ldy = ldy;
-    RUN(conv_go(q, MODE_PLAIN, precise, s));
-  }
-  return CRK_OK;
+  return fwd_layers(n, k, a);
 }
 
 // Weight-gradient groups of a net's "stack region" (the gated blocks' launch is one workgroup per (group, block); the
@@ -916,7 +980,7 @@ static long long usum_floats(const Net* n, int B, int T) {
   if (n->d.kind == 2 || n->d.aux_ch <= 0) return 0;
   return (long long)stack_groups(n, B, T) * usum_nseg(n, B, T) * n->L * 128;
 }
-static long long usum_off(const Net* n, long long N) { return N * 64 * (3LL * n->L + 3) + (gated_s16(n, N).total + 1) / 2; }
+static long long usum_off(const Net* n, long long N) { return gated_f32(n, N).scratch_total + (gated_s16(n, N).total + 1) / 2; }
 static ShapeNeed shape_need(const Net* n, int B, int T) {
   ShapeNeed q;
   const long long N = (long long)B * T;
@@ -928,7 +992,7 @@ static ShapeNeed shape_need(const Net* n, int B, int T) {
   // (+ head: dy and dH1 bf16 planes);  kind 2: per-layer fp32 gradients (fallback) + bf16 output-gradient planes
   q.need_s = n->d.kind == 2 ? (long long)n->L * N * cw + N * plain_gplanes_w(n)
                             : usum_off(n, N) + usum_floats(n, B, T);
-  q.Gs = stack_groups(n, B, T);
+  q.Gs = stack_groups(n, B, T); q.cpg_s = stack_cpg(n, B, T); q.nseg = usum_nseg(n, B, T);
   // generic convs: runs of 64-frame chunks, at most 32 groups: short runs = many workgroups hide the latency of the
   // table kernel's load -> MFMA chain, but every group is one more pass of the weight-norm backward over the
   // partial sums and one more set-up / partial-sum write-out (12 % + 21 % of a workgroup's life at 8 chunks per group).
@@ -1026,7 +1090,7 @@ long long crk_count_alloc_(void) { return ++g_net_allocs; }
 extern "C" int crk_debug_net_paths(void* h, int B, int T) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return -1;
-  const Route r = route_of(n, B, T, false);
+  const Route r = route_at(n, B, T, false);
   return (int)r.gen_split | (int)r.x3f << 1 | (int)r.disc_split << 2 | (int)(n->d.kind == 2 && r.fused) << 3;
 }
 
@@ -1045,12 +1109,22 @@ static void wgrad_slots(const Net* n, const Shape* r, int ei, WgradP& w) {
   w.partial = n->partials + a.pt_off;
   w.bias_partial = a.off_b >= 0 ? n->partials + a.pb_off : nullptr;
   w.ngroups = a.pt_groups;
-  w.cpg = stack ? stack_cpg(n, r->B, r->T) : r->q.cpg;
+  w.cpg = stack ? r->q.cpg_s : r->q.cpg;
 }
 // queue one weight-gradient problem; launched with the rest of the stack's by wgrad_flush
 static int wgrad_go(Net* n, WgradP& w, bool precise) {
   w.ca_pad = pad32(w.ca); w.cx_pad = pad32(w.cx); w.cc_pad = w.has_aux ? pad32(w.cc) : 0;
   return wgrad_expand(w, precise, n->jobs);
+}
+// ... of conv entry ei: dY = a1 [N, cout], the conv's input = act_in(sx * x) [N, cin]
+static int wgrad_conv(Net* n, const Shape* r, int ei, const float* a1, int lda1, const float* x, int ldx, int act_in, float sx, bool precise) {
+  const ConvEntry& e = n->ents[ei];
+  WgradP w = base_wgrad(n, r->B, r->T);
+  w.a1 = a1; w.lda1 = lda1; w.ca1 = e.cout; w.ca = e.cout;
+  w.x = x; w.ldx = ldx; w.cx = e.cin; w.sx = sx; w.act_in = act_in;
+  w.ktaps = e.k; w.dil = n->meta[ei].dilation; w.off0 = -((e.k - 1) / 2) * w.dil;  // (plain convs: never causal)
+  wgrad_slots(n, r, ei, w);
+  return wgrad_go(n, w, precise);
 }
 static int wgrad_flush(Net* n, int B, int T, bool precise, hipStream_t s) {
   if (n->jobs.empty()) return CRK_OK;
@@ -1097,17 +1171,310 @@ static int flush_pending_plain_wgrad(Net* n, hipStream_t s) {
 // dx_scale multiplies the returned input gradient (gradient reversal: -lambda).
 // the embedding table behind the conditioning columns [c0, c0 + E) (crk_net_backward_embed)
 struct CondEmbed { const long long* idx; long long run; int c0, E, n_rows; float* dtable; };
-static int net_backward_impl(void* h, const float* params, unsigned long long version, float* grads, const float* x,
-                             int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
-                             float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
-                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream,
-                             const CondEmbed* ce = nullptr);
+// ---- backward: one function per route; the entry point finishes the weight gradients of all of them ----------------------
+struct BwdIo {  // the arguments of crk_net_backward*
+  const float* params; float* grads; const float* x; int ldx; const float* c; int ldc; const float* dy; int lddy;
+  float* dx; int lddx; float dx_scale; float* dc; int lddc; const float* saved; int B, T;
+  const float* dy_num; const float* dy_den; const CondEmbed* ce; hipStream_t s;
+};
+enum { BWD_CHAIN, BWD_CHAIN_LAYERS, BWD_FOLDED_SPLIT, BWD_FOLDED, BWD_FUSED_SPLIT, BWD_FUSED, BWD_LAYERS };
+// (route, call) -> the launch form of a backward, or the error the call returns.  planes_precise: the forward left hi + lo
+// row planes (FWD_PRECISE flags where the forward was not the x3f one, or bf16x3): the channel-split chains, which read gate
+// planes in the lane-record layout only the plain-plane forwards write, are both off
+static int bwd_form(const Net* n, const Route& rt, const Call& k, bool planes_precise, int* form) {
+  if (n->d.kind == 2) { *form = rt.fused ? BWD_CHAIN : BWD_CHAIN_LAYERS; return CRK_OK; }
+  if (!rt.fused) { *form = BWD_LAYERS; return CRK_OK; }
+  // per call: the folds write dx in 16-byte pieces
+  const bool ok_x = k.out16 && (!k.want_dx || n->d.in_ch % 4 == 0);
+  if (rt.gen_split && !planes_precise) {
+    // the channel-split fold also takes a dy whose rows are only 4-byte aligned: a column slice of a wider gradient
+    if (!k.in4 || !ok_x) {
+      // the forward wrote the gate planes for the channel-split chain: nothing else can read them
+      fprintf(stderr, "[crank_hip] crk_net_backward: dy / dx must be 16-byte aligned with row strides that are multiples of 4 floats\n");
+      return CRK_ERR_ARG;
+    }
+    *form = BWD_FOLDED_SPLIT;
+  } else if (rt.disc_split && !planes_precise) *form = BWD_FUSED_SPLIT;  // the discriminator: the same chain without the folds
+  // the frame-split fold reads dy in 16-byte pieces
+  else *form = (rt.fold_bwd_fs && k.in16 && ok_x) ? BWD_FOLDED : BWD_FUSED;
+  return CRK_OK;
+}
+
+// plain chain, fused: the data-gradient chain in one launch (output-gradient planes kept), then all weight gradients in one
+static int bwd_chain(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
+  if (!a.saved) return CRK_ERR_ARG;
+  const crk_net_desc& d = n->d;
+  const PsTables& Tb = r->ps;
+  const long long N = (long long)a.B * a.T;
+  const long long cw = d.conv_ch > d.out_ch ? d.conv_ch : d.out_ch;
+  const uint16_t* f16 = reinterpret_cast<const uint16_t*>(a.saved + saved_f32_floats(n, N));
+  uint16_t* g16 = reinterpret_cast<uint16_t*>(n->scratch + (long long)n->L * N * cw);
+  PsP p = ps_base(n, a.B, a.T, a.params);
+  p.x = a.dy; p.ldx = a.lddy; p.cin = d.out_ch; p.y = a.dx; p.ldy = a.lddx; p.out_scale = a.dx_scale;
+  p.in_num = a.dy_num; p.in_den = a.dy_den;
+  p.save_hi = g16; p.save_lo = g16 + N * plain_gplanes_w(n); p.mask_hi = f16;
+  p.layers = r->d_ps + PS_MAXL; p.L = Tb.L[1];
+  // per call: nobody wants the input gradient (the classifier's input is data, the adversarial net's is detached in its own
+  // update): the chain stops at the output-gradient plane of the first conv - its weight gradient needs that - and the
+  // transposed first conv, the widest layer of the chain, is not computed (dx == nullptr and L >= 2: tail = 1)
+  if (!k.want_dx && p.L >= 2) { p.L -= 1; p.tail = 1; }
+  if (r->route[k.precise].ps_bwd[p.tail] == CHAIN_PS2) {
+    RUN(pstack2_plan(p, Tb.t[1]));
+    RUN(launch_pstack2(p, ps_flops(Tb.t[1], p.L, N), a.s));
+  } else RUN(pstack_go(r, 1, p, k.precise, a.s));
+  if (k.want_w) RUN(launch_plain_wgrad(r, plain_wgrad_params(n, r, g16, f16), k.precise, a.s));
+  return CRK_OK;
+}
+static int bwd_chain_layers(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
+  const crk_net_desc& d = n->d;
+  const long long N = (long long)a.B * a.T;
+  const long long cw = d.conv_ch > d.out_ch ? d.conv_ch : d.out_ch;
+  const float* dcur = a.dy; int ldcur = a.lddy;
+  for (int i = n->L - 1; i >= 0; i--) {
+    const int ei = n->idx_plain[i];
+    const ConvEntry& e = n->ents[ei];
+    const int dil = n->meta[ei].dilation;
+    const float* in = (i == 0) ? a.x : a.saved + (long long)(i - 1) * N * d.conv_ch;
+    const int ldin = (i == 0) ? a.ldx : d.conv_ch;
+    if (k.want_w) RUN(wgrad_conv(n, r, ei, dcur, ldcur, in, ldin, (i == 0) ? ACT_NONE : ACT_LRELU, 1.f, k.precise));
+    if (i == 0 && !k.want_dx) break;
+    float* out = i > 0 ? n->scratch + (long long)i * N * cw : a.dx;  // dH_{i-1}, kept for its weight gradient
+    ConvP p = conv_bw(n, a.B, a.T, e, dcur, ldcur, out, i > 0 ? d.conv_ch : a.lddx);
+    p.ktaps = e.k; p.dil = dil; p.off0 = -(-((e.k - 1) / 2) * dil) - (e.k - 1) * dil;
+    if (i > 0) { p.dmask = in; p.ldm = ldin; p.dmask_act = ACT_LRELU; }
+    else p.out_scale = a.dx_scale;
+    RUN(conv_go(p, MODE_PLAIN, k.precise, a.s));
+    dcur = out; ldcur = d.conv_ch;
+  }
+  return CRK_OK;
+}
+
+// the bf16 planes of a fused gated backward: the forward's in `saved`, this backward's in scratch
+struct GatedPlanes { const uint16_t* f16; uint16_t* s16; GatedB16 gf; GatedS16 gs; };
+static GatedPlanes gated_planes(const Net* n, const float* saved, long long N) {
+  return {reinterpret_cast<const uint16_t*>(saved + saved_f32_floats(n, N)),
+          reinterpret_cast<uint16_t*>(n->scratch + gated_f32(n, N).scratch_total), gated_b16(n, N), gated_s16(n, N)};
+}
+// the data-gradient chain's launch parameters, planned for the frame-split kernel (the channel-split plan goes on top)
+static int stack_bwd_params(const Net* n, const Call& k, const BwdIo& a, StackBP& bp) {
+  const crk_net_desc& d = n->d;
+  const long long N = (long long)a.B * a.T;
+  const GatedF32 lay = gated_f32(n, N);
+  const GatedPlanes q = gated_planes(n, a.saved, N);
+  bp = stack_bwd_shape(n, a.B, a.T);
+  bp.dS = n->scratch + lay.ds; bp.saved = a.saved; bp.dX0 = n->scratch + lay.dx;
+  bp.tb_hi = q.f16 + q.gf.tb_hi; bp.tb_lo = q.f16 + q.gf.tb_lo; bp.sg_hi = q.f16 + q.gf.sg_hi; bp.sg_lo = q.f16 + q.gf.sg_lo;
+  bp.gb_hi = q.s16 + q.gs.gb_hi; bp.gb_lo = q.s16 + q.gs.gb_lo; bp.dxb_hi = q.s16 + q.gs.dxb_hi; bp.dxb_lo = q.s16 + q.gs.dxb_lo;
+  bp.dsb_hi = q.s16 + q.gs.dsb_hi; bp.dsb_lo = q.s16 + q.gs.dsb_lo;
+  bp.dc = (k.want_dc && d.aux_ch > 0) ? a.dc : nullptr; bp.lddc = a.lddc;
+  bp.whi = n->whi; bp.wlo = n->wlo; bp.layers = n->d_blayers;
+  if (d.dropout > 0.f) { bp.drop_p = d.dropout; bp.drop_seed = k.seed_val; bp.drop_seed_ptr = k.seed_ptr; }
+  bp.mask_l0 = d.kind == 1; bp.slope = d.slope;
+  return stack_bwd_plan(bp, k.precise);
+}
+// the chain's launch (split: the channel-split kernel, stack2b_kernels.hip), then the weight gradients of every block in one
+// launch over (utterance group, block) and, for crk_net_backward_embed, the table gradient from its per-utterance dG sums
+static int stack_bwd_go(const Net* n, const Shape* r, const Call& k, const BwdIo& a, StackBP& bp, bool split) {
+  const long long N = (long long)a.B * a.T;
+  if (split) { bp.ts_stride = ts_plane_stride(N); RUN(stack2_bwd_plan(bp)); }  // (the route promised the plan)
+  // the planes the weight gradient reads after this chain as 4-frame records (StackBP::rec): the channel-split chain only
+  bp.rec = (split && N % 4 == 0) ? 1 : 0;
+  if (split) RUN(launch_stack2_bwd(bp, a.s));
+  else RUN(launch_stack_bwd(bp, k.precise, a.s));
+  if (!k.want_w) return CRK_OK;
+  const crk_net_desc& d = n->d;
+  const GatedPlanes q = gated_planes(n, a.saved, N);
+  StackWP wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.xb_hi = q.f16 + q.gf.xb_hi; wp.xb_lo = q.f16 + q.gf.xb_lo; wp.zb_hi = q.f16 + q.gf.zb_hi; wp.zb_lo = q.f16 + q.gf.zb_lo;
+  wp.aux_pad = stack_aux_pad(n);
+  if (d.aux_ch > 0) { wp.cb_hi = q.f16 + q.gf.cb_hi; wp.cb_lo = q.f16 + q.gf.cb_lo; }
+  wp.gb_hi = bp.gb_hi; wp.gb_lo = bp.gb_lo; wp.dxb_hi = bp.dxb_hi; wp.dxb_lo = bp.dxb_lo;
+  wp.dsb_hi = bp.dsb_hi; wp.dsb_lo = bp.dsb_lo;
+  wp.layers = r->d_wlayers; wp.partials = n->partials;
+  wp.B = a.B; wp.T = a.T; wp.L = n->L; wp.ktaps = d.kernel_size; wp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
+  wp.cpg = r->q.cpg_s; wp.G = r->q.Gs;
+  wp.rec_g = bp.rec;
+  if (a.ce) { wp.usums = n->scratch + usum_off(n, N); wp.nseg = r->q.nseg; }
+  RUN(launch_stack_wgrad(wp, k.precise, a.s));
+  if (!a.ce) return CRK_OK;
+  CondEmbedP ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.usums = wp.usums; ep.nseg = wp.nseg; ep.cpg = wp.cpg;
+  ep.whi = n->whi; ep.wlo = k.precise ? n->wlo : nullptr; ep.layers = n->d_blayers;
+  ep.idx = a.ce->idx; ep.run = a.ce->run;
+  ep.B = a.B; ep.T = a.T; ep.L = n->L; ep.c0 = a.ce->c0; ep.E = a.ce->E; ep.n_rows = a.ce->n_rows; ep.dtable = a.ce->dtable;
+  return launch_cond_embed_bwd(ep, a.s);
+}
+// weight gradients of first conv + head from the planes
+static int gated_plain_wgrad(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
+  if (!k.want_w) return CRK_OK;
+  const GatedPlanes q = gated_planes(n, a.saved, (long long)a.B * a.T);
+  const PwP wp = plain_wgrad_params(n, r, q.s16, q.f16);
+  // CRK_FLAG_DEFER_WNORM on a non-precise fused gated backward: parked in pw_shape, not launched - it goes with the
+  // weight-norm backward, one launch for all stacks of the model
+  if (k.defer_wn && !k.precise) { n->pw_shape = r; n->pw_params = wp; return CRK_OK; }
+  return launch_plain_wgrad(r, wp, k.precise, a.s);
+}
+// generator stacks, plain bf16: the head's and the first conv's data gradients run inside the chain's launch - the
+// channel-split chain (split), or the frame-split one at its 8-wave window
+static int bwd_folded(Net* n, const Shape* r, const Call& k, const BwdIo& a, bool split) {
+  const crk_net_desc& d = n->d;
+  const GatedPlanes q = gated_planes(n, a.saved, (long long)a.B * a.T);
+  const ConvEntry& ef = n->ents[n->idx_first];
+  const ConvEntry& e1 = n->ents[n->idx_last1];
+  const ConvEntry& e2 = n->ents[n->idx_last2];
+  StackBP bp;
+  RUN(stack_bwd_params(n, k, a, bp));
+  if (!split && bp.nw != 8) return CRK_ERR_UNSUPPORTED;  // (the route promised the window)
+  bp.dy = a.dy; bp.lddy = a.lddy; bp.out_ch = d.out_ch; bp.kp_y = e2.bw_kp;
+  bp.w_h2 = e2.bw_off; bp.w_h1 = e1.bw_off; bp.w_first = ef.bw_off;
+  bp.hmask_hi = q.f16 + q.gf.head_hi; bp.hb_hi = q.s16 + q.gs.hb_hi; bp.head_scale = (float)sqrt(1.0 / n->L);
+  bp.dx = a.dx; bp.lddx = a.lddx; bp.in_ch = d.in_ch; bp.in_rows = ef.bw_rows; bp.dx_scale = a.dx_scale;
+  bp.f_h2 = e2.bfr_off; bp.f_h1 = e1.bfr_off; bp.f_first = ef.bfr_off;
+  RUN(stack_bwd_go(n, r, k, a, bp, split));
+  return gated_plain_wgrad(n, r, k, a);
+}
+// gated stack, fused and not folded: head, chain (split: the discriminator's channel-split one) and first conv, one launch each
+static int bwd_fused(Net* n, const Shape* r, const Call& k, const BwdIo& a, bool split) {
+  const long long N = (long long)a.B * a.T;
+  const GatedF32 lay = gated_f32(n, N);
+  const GatedPlanes q = gated_planes(n, a.saved, N);
+  PsP h = ps_base(n, a.B, a.T, a.params);  // head backward: dy -> dH1 -> dS in one launch; dy and dH1 kept as bf16 planes
+  h.x = a.dy; h.ldx = a.lddy; h.cin = n->d.out_ch; h.y = n->scratch + lay.ds; h.ldy = 64; h.out_scale = (float)sqrt(1.0 / n->L);
+  h.save_hi = q.s16 + q.gs.hb_hi; h.save_lo = q.s16 + q.gs.hb_lo;
+  h.mask_hi = q.f16 + q.gf.head_hi; h.L = 2;
+  RUN(pstack_go(r, 2, h, k.precise, a.s));
+  StackBP bp;
+  RUN(stack_bwd_params(n, k, a, bp));
+  if (!bp.dS) return CRK_ERR_ARG;
+  RUN(stack_bwd_go(n, r, k, a, bp, split));
+  if (k.want_dx) {  // first conv: dx through one transposed 1x1
+    PsP p = ps_base(n, a.B, a.T, a.params);
+    p.x = n->scratch + lay.dx; p.ldx = 64; p.cin = 64; p.y = a.dx; p.ldy = a.lddx; p.out_scale = a.dx_scale; p.L = 1;
+    RUN(pstack_go(r, 3, p, k.precise, a.s));
+  }
+  return gated_plain_wgrad(n, r, k, a);
+}
+static int bwd_layers(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
+  const crk_net_desc& d = n->d;
+  const int L = n->L;
+  const long long N = (long long)a.B * a.T, P = N * 64;
+  const GatedF32 lay = gated_f32(n, N);
+  const float *X = a.saved + lay.x, *SKIP = a.saved + lay.skip, *H1 = a.saved + lay.h1;
+  float *dS = n->scratch + lay.ds, *dH1 = n->scratch + lay.dh1;
+  const int head_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
+  const float sL = (float)sqrt(1.0 / L), rs = 0.70710678118654752440f;
+  // head: dy -> dH1 -> dS, each conv's weight gradient in front of its data gradient
+  if (k.want_w) RUN(wgrad_conv(n, r, n->idx_last2, a.dy, a.lddy, H1, 64, head_act, 1.f, k.precise));
+  ConvP h2 = conv_bw(n, a.B, a.T, n->ents[n->idx_last2], a.dy, a.lddy, dH1, 64);
+  h2.dmask = H1; h2.ldm = 64; h2.dmask_act = head_act;
+  RUN(conv_go(h2, MODE_PLAIN, k.precise, a.s));
+  if (k.want_w) RUN(wgrad_conv(n, r, n->idx_last1, dH1, 64, SKIP, 64, head_act, sL, k.precise));
+  ConvP h1 = conv_bw(n, a.B, a.T, n->ents[n->idx_last1], dH1, 64, dS, 64);
+  h1.dmask = SKIP; h1.ldm = 64; h1.dmask_act = head_act; h1.out_scale = sL;
+  RUN(conv_go(h1, MODE_PLAIN, k.precise, a.s));
+  const float* dxo = nullptr;  // gradient wrt the block output; the last block's x output is unused
+  for (int l = L - 1; l >= 0; l--) {
+    const ConvEntry& ec = n->ents[n->idx_conv[l]];
+    const ConvEntry& eo = n->ents[n->idx_out[l]];
+    const int dil = n->meta[n->idx_conv[l]].dilation;
+    const int off0 = fwd_off0(n, ec.k, dil);
+    float* dG = n->scratch + lay.dg + (long long)l * 2 * P;
+    {  // gate backward: dz = [dxo*sqrt(.5) | dS] . [Wo;Ws]^T ; dG = gate'(dz)
+      ConvP p = base_conv(n, a.B, a.T);
+      p.w_hi = n->whi + eo.bw_off; p.w_lo = n->wlo + eo.bw_off;
+      p.cin = 128; p.cin_pad = 128; p.cout = 64; p.cout_pad = 64;
+      p.xa = dxo; p.lda = 64; p.cinA = 64; p.scaleA = rs;
+      p.xb = dS; p.ldb = 64; p.cinB = 64;
+      p.ta = a.saved + lay.ta + l * P; p.sb = a.saved + lay.sb + l * P;
+      p.y = dG; p.ldy = 128;
+      RUN(conv_go(p, MODE_BWDA, k.precise, a.s));
+    }
+    if (k.want_w) {
+      WgradP w = base_wgrad(n, a.B, a.T);  // dilated conv (+ aux as an extra table entry)
+      w.a1 = dG; w.lda1 = 128; w.ca1 = 128; w.ca = 128;
+      w.x = X + l * P; w.ldx = 64; w.cx = 64;
+      if (d.dropout > 0.f) { w.drop_p = d.dropout; w.drop_seed = layer_seed(k.seed_val, l); w.drop_seed_ptr = k.seed_ptr; }
+      w.ktaps = ec.k; w.dil = dil; w.off0 = off0;
+      wgrad_slots(n, r, n->idx_conv[l], w);
+      if (d.aux_ch > 0) {
+        const ConvEntry& ea = n->ents[n->idx_aux[l]];
+        w.has_aux = 1; w.xc = a.c; w.ldc = a.ldc; w.cc = ea.cin; w.partial_aux = n->partials + r->abs[n->idx_aux[l]].pt_off;
+      }
+      RUN(wgrad_go(n, w, k.precise));
+      WgradP v = base_wgrad(n, a.B, a.T);  // 1x1 out | skip on z
+      v.a1 = dxo; v.lda1 = 64; v.ca1 = 64; v.a2 = dS; v.lda2 = 64; v.ca2 = 64; v.ca = 128;
+      v.x = a.saved + lay.z + l * P; v.ldx = 64; v.cx = 64;
+      wgrad_slots(n, r, n->idx_out[l], v);
+      RUN(wgrad_go(n, v, k.precise));
+    }
+    if (k.want_dc && d.aux_ch > 0) {  // conditioning gradient, accumulated over layers
+      const ConvEntry& ea = n->ents[n->idx_aux[l]];
+      ConvP p = conv_bw(n, a.B, a.T, ea, dG, 128, a.dc, a.lddc);
+      p.accumulate = (l != L - 1);
+      RUN(conv_go(p, MODE_PLAIN, k.precise, a.s));
+    }
+    {  // dX_l = dxo*sqrt(.5) + convT(dG)   (kind 1, l == 0: times LeakyReLU'(X_0))
+      float* out = n->scratch + lay.dx + (long long)l * P;
+      ConvP p = conv_bw(n, a.B, a.T, ec, dG, 128, out, 64);
+      p.ktaps = ec.k; p.dil = dil; p.off0 = -off0 - (ec.k - 1) * dil;
+      // conv input was dropout(x): the conv path goes through the regenerated keep mask
+      if (d.dropout > 0.f) { p.epi_drop_p = d.dropout; p.epi_drop_seed = layer_seed(k.seed_val, l); p.drop_seed_ptr = k.seed_ptr; }
+      if (dxo) { p.res = dxo; p.ldr = 64; p.res_scale = rs; }
+      if (l == 0 && d.kind == 1) { p.dmask = X; p.ldm = 64; p.dmask_act = ACT_LRELU; }
+      RUN(conv_go(p, MODE_PLAIN, k.precise, a.s));
+      dxo = out;
+    }
+  }
+  // first conv
+  if (k.want_w) RUN(wgrad_conv(n, r, n->idx_first, dxo, 64, a.x, a.ldx, ACT_NONE, 1.f, k.precise));
+  if (!k.want_dx) return CRK_OK;
+  ConvP p = conv_bw(n, a.B, a.T, n->ents[n->idx_first], dxo, 64, a.dx, a.lddx);
+  p.out_scale = a.dx_scale;
+  return conv_go(p, MODE_PLAIN, k.precise, a.s);
+}
+static int net_backward_impl(void* h, unsigned long long version, int flags, unsigned long long seed, const BwdIo& a) {
+  Net* n = (Net*)h;
+  if (!n || !a.params || !a.x || !a.dy || a.B <= 0 || a.T <= 0) return CRK_ERR_ARG;
+  const Shape* r = find_shape(n, a.B, a.T);
+  if (!r) return not_reserved("crk_net_backward");
+  const Call k = call_facts(flags, seed, false, a.dy, a.lddy, a.dx, a.lddx, a.dc, a.grads);
+  const Route& rt = r->route[k.precise];
+  if (a.ce && !rt.usums) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_embed)
+  if (a.dy_num && !(n->d.kind == 2 && rt.fused)) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_scaled)
+  // CRK_FLAG_FWD_PRECISE: how the forward laid its planes out - unless that forward was the channel-split split-operand one
+  // (generator stacks of the bf16x3f mode), which writes the plain route's planes
+  const bool expects_x3f = k.mode == 2 && r->route[0].x3f;
+  const bool planes_precise = k.precise || (k.mode == 2 && !expects_x3f);
+  RUN(check_forward_tag(n, a.saved, a.B, a.T, flags, k.mode, expects_x3f));
+  RUN(flush_pending_wnorm(n, a.s));  // a second backward of this net reuses the partial-sum buffer and the gradient planes
+  RUN(ensure_prepared(n, a.params, version, a.s));
+  n->jobs.clear();
+  if (n->d.kind != 2 && !a.saved) return CRK_ERR_ARG;
+  int form;
+  RUN(bwd_form(n, rt, k, planes_precise, &form));
+  switch (form) {
+    case BWD_CHAIN: RUN(bwd_chain(n, r, k, a)); break;
+    case BWD_CHAIN_LAYERS: RUN(bwd_chain_layers(n, r, k, a)); break;
+    case BWD_FOLDED_SPLIT: case BWD_FOLDED: RUN(bwd_folded(n, r, k, a, form == BWD_FOLDED_SPLIT)); break;
+    case BWD_FUSED_SPLIT: case BWD_FUSED: RUN(bwd_fused(n, r, k, a, form == BWD_FUSED_SPLIT)); break;
+    default: RUN(bwd_layers(n, r, k, a));
+  }
+  if (k.want_w) {  // every route: the per-layer kernels' queued problems, then partial sums -> dg / dv / dbias
+    RUN(wgrad_flush(n, a.B, a.T, k.precise, a.s));
+    RUN(finish_wnorm(n, r, a.params, a.grads, k.defer_wn, a.s));
+  }
+  return CRK_OK;
+}
 extern "C" int crk_net_backward(void* h, const float* params, unsigned long long version, float* grads, const float* x,
                                 int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
                                 float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
                                 unsigned long long seed, void* stream) {
-  return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, dc, lddc, saved, B, T, flags,
-                           seed, nullptr, nullptr, stream);
+  const BwdIo a = {.params = params, .grads = grads, .x = x, .ldx = ldx, .c = c, .ldc = ldc, .dy = dy, .lddy = lddy, .dx = dx, .lddx = lddx,
+                   .dx_scale = dx_scale, .dc = dc, .lddc = lddc, .saved = saved, .B = B, .T = T, .dy_num = nullptr, .dy_den = nullptr, .ce = nullptr,
+                   .s = (hipStream_t)stream};
+  return net_backward_impl(h, version, flags, seed, a);
 }
 // crk_net_backward of dy * (dy_num[0] / dy_den[1]), the factor read on the device by the chain's first kernel: the backward
 // of a mean cross entropy on the net's output (dy = softmax - onehot, dy_num = upstream gradient, dy_den = {loss, count} as
@@ -1118,16 +1485,17 @@ extern "C" int crk_net_backward_scaled(void* h, const float* params, unsigned lo
                                        float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
                                        unsigned long long seed, const float* dy_num, const float* dy_den, void* stream) {
   if (!h || !dy_num || !dy_den) return CRK_ERR_ARG;
-  return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, dc, lddc, saved, B, T, flags,
-                           seed, dy_num, dy_den, stream);
+  const BwdIo a = {.params = params, .grads = grads, .x = x, .ldx = ldx, .c = c, .ldc = ldc, .dy = dy, .lddy = lddy, .dx = dx, .lddx = lddx,
+                   .dx_scale = dx_scale, .dc = dc, .lddc = lddc, .saved = saved, .B = B, .T = T, .dy_num = dy_num, .dy_den = dy_den, .ce = nullptr,
+                   .s = (hipStream_t)stream};
+  return net_backward_impl(h, version, flags, seed, a);
 }
 // 1: crk_net_backward_embed serves this net at this shape in the arithmetic of `flags` (a gated stack with conditioning on
 // the fused kernels); 0: it returns CRK_ERR_UNSUPPORTED - take dc from crk_net_backward and reduce it (crk_embed_bwd_run).
 extern "C" int crk_net_embed_grad_supported(void* h, int B, int T, int flags) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return 0;
-  const Shape* r = find_shape(n, B, T);
-  return (r ? r->route[(flags & CRK_FLAG_PRECISE) ? 1 : 0] : route_of(n, B, T, flags & CRK_FLAG_PRECISE)).usums ? 1 : 0;
+  return route_at(n, B, T, flags & CRK_FLAG_PRECISE).usums ? 1 : 0;  // (a shape that is not reserved: from route_of)
 }
 // crk_net_backward for a conditioning input c = [.. | table[idx[u * run]] | ..] whose columns [c0, c0 + E) are one row of an
 // embedding table per utterance (run == T: every frame of utterance u carries the label idx[u * run]) and whose other
@@ -1145,355 +1513,11 @@ extern "C" int crk_net_backward_embed(void* h, const float* params, unsigned lon
       (flags & CRK_FLAG_NO_PARAM_GRAD))
     return CRK_ERR_ARG;
   const CondEmbed ce = {idx, run, c0, E, n_rows, dtable};
-  return net_backward_impl(h, params, version, grads, x, ldx, c, ldc, dy, lddy, dx, lddx, dx_scale, nullptr, 0, saved, B, T, flags,
-                           seed, nullptr, nullptr, stream, &ce);
+  const BwdIo a = {.params = params, .grads = grads, .x = x, .ldx = ldx, .c = c, .ldc = ldc, .dy = dy, .lddy = lddy, .dx = dx, .lddx = lddx,
+                   .dx_scale = dx_scale, .dc = nullptr, .lddc = 0, .saved = saved, .B = B, .T = T, .dy_num = nullptr, .dy_den = nullptr, .ce = &ce,
+                   .s = (hipStream_t)stream};
+  return net_backward_impl(h, version, flags, seed, a);
 }
-static int net_backward_impl(void* h, const float* params, unsigned long long version, float* grads, const float* x,
-                             int ldx, const float* c, int ldc, const float* dy, int lddy, float* dx, int lddx,
-                             float dx_scale, float* dc, int lddc, const float* saved, int B, int T, int flags,
-                             unsigned long long seed, const float* dy_num, const float* dy_den, void* stream,
-                             const CondEmbed* ce) {
-  Net* n = (Net*)h;
-  if (!n || !params || !x || !dy || B <= 0 || T <= 0) return CRK_ERR_ARG;
-  const Shape* r = find_shape(n, B, T);
-  if (!r) return not_reserved("crk_net_backward");
-  hipStream_t s = (hipStream_t)stream;
-  const bool precise = flags & CRK_FLAG_PRECISE;
-  const Route& rt = r->route[precise];
-  if (ce && !rt.usums) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_embed)
-  if (dy_num && !(n->d.kind == 2 && rt.fused)) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_scaled)
-  // CRK_FLAG_FWD_PRECISE: how the forward laid its planes out - unless that forward was the channel-split split-operand one
-  // (generator stacks of the bf16x3f mode), which writes the plain route's planes
-  const bool expects_x3f = !precise && (flags & CRK_FLAG_FWD_PRECISE) && r->route[0].x3f;
-  const bool planes_precise = precise || ((flags & CRK_FLAG_FWD_PRECISE) && !expects_x3f);
-  // the channel-split chains read gate planes in the lane-record layout, which only the plain-plane forwards write
-  const bool gen_split = rt.gen_split && !planes_precise, disc_split = rt.disc_split && !planes_precise;
-  RUN(check_forward_tag(n, saved, B, T, flags, expects_x3f));
-  const bool want_w = !(flags & CRK_FLAG_NO_PARAM_GRAD) && grads;
-  const bool defer_wn = flags & CRK_FLAG_DEFER_WNORM;
-  const unsigned long long* seed_ptr = (flags & CRK_FLAG_SEED_ON_DEVICE) ? reinterpret_cast<const unsigned long long*>((uintptr_t)seed) : nullptr;
-  const unsigned long long seed_val = (flags & CRK_FLAG_SEED_ON_DEVICE) ? 0ull : seed;
-  const crk_net_desc& d = n->d;
-  RUN(flush_pending_wnorm(n, s));  // a second backward of this net reuses the partial-sum buffer and the gradient planes
-  RUN(ensure_prepared(n, params, version, s));
-  const long long N = (long long)B * T;
-  float* PT = n->partials;
-  n->jobs.clear();
-  const PsTables& Tb = r->ps;
-
-  if (d.kind == 2 && rt.fused) {
-    // data-gradient chain in one launch (output-gradient planes kept), then all weight gradients in one
-    if (!saved) return CRK_ERR_ARG;
-    const long long cw = d.conv_ch > d.out_ch ? d.conv_ch : d.out_ch;
-    const uint16_t* f16 = reinterpret_cast<const uint16_t*>(saved + saved_f32_floats(n, N));
-    uint16_t* g16 = reinterpret_cast<uint16_t*>(n->scratch + (long long)n->L * N * cw);
-    PsP p = ps_base(n, B, T, params);
-    p.x = dy; p.ldx = lddy; p.cin = d.out_ch; p.y = dx; p.ldy = lddx; p.out_scale = dx_scale;
-    p.in_num = dy_num; p.in_den = dy_den;
-    p.save_hi = g16; p.save_lo = g16 + N * plain_gplanes_w(n);
-    p.mask_hi = f16;
-    p.layers = r->d_ps + PS_MAXL; p.L = Tb.L[1];
-    // per call: nobody wants the input gradient (the classifier's input is data, the adversarial net's is detached in its own
-    // update): the chain stops at the output-gradient plane of the first conv - its weight gradient needs that - and the
-    // transposed first conv, the widest layer of the chain, is not computed
-    if (!dx && p.L >= 2) { p.L -= 1; p.tail = 1; }
-    bool done = false;
-    if (!precise && crk_sw().ps_v == 2) {
-      PsP q = p;
-      if (pstack2_plan(q, Tb.t[1]) == CRK_OK) { RUN(launch_pstack2(q, ps_flops(Tb.t[1], p.L, N), s)); done = true; }
-    }
-    if (!done) {
-      RUN(pstack_plan(p, Tb.t[1], precise));
-      RUN(launch_pstack(p, precise, ps_flops(Tb.t[1], p.L, N), s));
-    }
-    if (want_w) {
-      RUN(launch_plain_wgrad(r, plain_wgrad_params(n, r, g16, f16), precise, s));
-      RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
-    }
-    return CRK_OK;
-  }
-  if (d.kind == 2) {
-    const int L = n->L;
-    const long long cw = d.conv_ch > d.out_ch ? d.conv_ch : d.out_ch;
-    const float* dcur = dy; int ldcur = lddy;
-    for (int i = L - 1; i >= 0; i--) {
-      const int ei = n->idx_plain[i];
-      const ConvEntry& e = n->ents[ei];
-      const int dil = n->meta[ei].dilation;
-      const float* in = (i == 0) ? x : saved + (long long)(i - 1) * N * d.conv_ch;
-      const int ldin = (i == 0) ? ldx : d.conv_ch;
-      if (want_w) {
-        WgradP w = base_wgrad(n, B, T);
-        w.a1 = dcur; w.lda1 = ldcur; w.ca1 = e.cout; w.ca = e.cout;
-        w.x = in; w.ldx = ldin; w.cx = e.cin; w.act_in = (i == 0) ? ACT_NONE : ACT_LRELU;
-        w.ktaps = e.k; w.dil = dil; w.off0 = -((e.k - 1) / 2) * dil;
-        wgrad_slots(n, r, ei, w);
-        RUN(wgrad_go(n, w, precise));
-      }
-      if (i > 0 || dx) {
-        ConvP p = base_conv(n, B, T);
-        set_bw_weights(n, p, e);
-        p.xa = dcur; p.lda = ldcur; p.cinA = e.cout;
-        p.ktaps = e.k; p.dil = dil; p.off0 = -(-((e.k - 1) / 2) * dil) - (e.k - 1) * dil;
-        if (i > 0) {
-          float* out = n->scratch + (long long)i * N * cw;  // dH_{i-1}, kept for its weight gradient
-          p.y = out; p.ldy = d.conv_ch;
-          p.dmask = in; p.ldm = ldin; p.dmask_act = ACT_LRELU;
-          RUN(conv_go(p, MODE_PLAIN, precise, s));
-          dcur = out; ldcur = d.conv_ch;
-        } else {
-          p.y = dx; p.ldy = lddx; p.out_scale = dx_scale;
-          RUN(conv_go(p, MODE_PLAIN, precise, s));
-        }
-      }
-    }
-    if (want_w) {
-      RUN(wgrad_flush(n, B, T, precise, s));
-      RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
-    }
-    return CRK_OK;
-  }
-
-  if (!saved) return CRK_ERR_ARG;
-  const int L = n->L;
-  const long long P = N * 64;
-  const float* X = saved;
-  const float* TA = saved + (long long)L * P;
-  const float* SB = TA + (long long)L * P;
-  const float* Z = SB + (long long)L * P;
-  const float* SKIP = Z + (long long)L * P;
-  const float* H1 = SKIP + P;
-  float* dS = n->scratch;
-  float* dH1 = dS + P;
-  float* dXall = dH1 + P;                    // dX_l at dXall + l*P, l = 0..L (dX_L is never written: it is zero)
-  float* dGall = dXall + (long long)(L + 1) * P;  // dG_l [N,128] at dGall + l*2P
-  const int head_act = d.kind == 1 ? ACT_LRELU : ACT_RELU;
-  const float sL = (float)sqrt(1.0 / L);
-  const float rs = 0.70710678118654752440f;
-
-  const bool fused = rt.fused;
-  const uint16_t* f16 = reinterpret_cast<const uint16_t*>(saved + saved_f32_floats(n, N));
-  uint16_t* s16 = reinterpret_cast<uint16_t*>(n->scratch + N * 64 * (3LL * L + 3));
-  const GatedB16 gf = gated_b16(n, N);
-  const GatedS16 gs = gated_s16(n, N);
-  // plain bf16, generator stacks: the head's and the first conv's data gradients run inside the chain's launch
-  bool bfold = false;
-  if (fused && !precise && d.kind == 0 && d.dropout == 0.f) {
-    // per call: the folds read dy and write dx in 16-byte pieces (the channel-split chain also takes a dy whose rows are
-    // only 4-byte aligned: a column slice of a wider gradient)
-    const bool ok_y = (d.out_ch % 8 == 0) && (gen_split || ((lddy % 4 == 0) && ((((uintptr_t)dy) & 15) == 0))) && ((((uintptr_t)dy) & 3) == 0);
-    const bool ok_x = !dx || ((d.in_ch % 4 == 0) && (lddx % 4 == 0) && ((((uintptr_t)dx) & 15) == 0));
-    bfold = crk_sw().sk_v == 2 && ok_y && ok_x && (stack_bwd_waves(precise) == 8 || gen_split);
-  }
-  if (fused && !bfold) {  // head backward: dy -> dH1 -> dS in one launch; dy and dH1 kept as bf16 planes
-    PsP p = ps_base(n, B, T, params);
-    p.x = dy; p.ldx = lddy; p.cin = d.out_ch; p.y = dS; p.ldy = 64; p.out_scale = sL;
-    p.save_hi = s16 + gs.hb_hi; p.save_lo = s16 + gs.hb_lo;
-    p.mask_hi = f16 + gf.head_hi;
-    p.layers = r->d_ps + 2 * PS_MAXL; p.L = 2;
-    RUN(pstack_plan(p, Tb.t[2], precise));
-    RUN(launch_pstack(p, precise, ps_flops(Tb.t[2], 2, N), s));
-  } else if (!fused)
-  {  // head
-    const ConvEntry& e2 = n->ents[n->idx_last2];
-    if (want_w) {
-      WgradP w = base_wgrad(n, B, T);
-      w.a1 = dy; w.lda1 = lddy; w.ca1 = e2.cout; w.ca = e2.cout;
-      w.x = H1; w.ldx = 64; w.cx = 64; w.act_in = head_act;
-      wgrad_slots(n, r, n->idx_last2, w);
-      RUN(wgrad_go(n, w, precise));
-    }
-    ConvP p = base_conv(n, B, T);
-    set_bw_weights(n, p, e2);
-    p.xa = dy; p.lda = lddy; p.cinA = e2.cout;
-    p.y = dH1; p.ldy = 64; p.dmask = H1; p.ldm = 64; p.dmask_act = head_act;
-    RUN(conv_go(p, MODE_PLAIN, precise, s));
-    const ConvEntry& e1 = n->ents[n->idx_last1];
-    if (want_w) {
-      WgradP w = base_wgrad(n, B, T);
-      w.a1 = dH1; w.lda1 = 64; w.ca1 = 64; w.ca = 64;
-      w.x = SKIP; w.ldx = 64; w.cx = 64; w.sx = sL; w.act_in = head_act;
-      wgrad_slots(n, r, n->idx_last1, w);
-      RUN(wgrad_go(n, w, precise));
-    }
-    ConvP q = base_conv(n, B, T);
-    set_bw_weights(n, q, e1);
-    q.xa = dH1; q.lda = 64; q.cinA = 64;
-    q.y = dS; q.ldy = 64; q.dmask = SKIP; q.ldm = 64; q.dmask_act = head_act; q.out_scale = sL;
-    RUN(conv_go(q, MODE_PLAIN, precise, s));
-  }
-  const float* dxo = nullptr;  // gradient wrt the block output; the last block's x output is unused
-  if (fused) {
-    StackBP bp = stack_bwd_shape(n, B, T);
-    bp.dS = dS; bp.saved = saved; bp.dX0 = dXall;
-    bp.tb_hi = f16 + gf.tb_hi; bp.tb_lo = f16 + gf.tb_lo; bp.sg_hi = f16 + gf.sg_hi; bp.sg_lo = f16 + gf.sg_lo;
-    bp.gb_hi = s16 + gs.gb_hi; bp.gb_lo = s16 + gs.gb_lo;
-    bp.dxb_hi = s16 + gs.dxb_hi; bp.dxb_lo = s16 + gs.dxb_lo;
-    bp.dsb_hi = s16 + gs.dsb_hi; bp.dsb_lo = s16 + gs.dsb_lo;
-    bp.dc = (dc && d.aux_ch > 0) ? dc : nullptr; bp.lddc = lddc;
-    bp.whi = n->whi; bp.wlo = n->wlo; bp.layers = n->d_blayers;
-    if (d.dropout > 0.f) { bp.drop_p = d.dropout; bp.drop_seed = seed_val; bp.drop_seed_ptr = seed_ptr; }
-    bp.mask_l0 = d.kind == 1; bp.slope = d.slope;
-    RUN(stack_bwd_plan(bp, precise));
-    bool split = false;  // the channel-split chain (stack2b_kernels.hip): folded generator stacks, plain bf16
-    if (bfold && (bp.nw == 8 || gen_split)) {
-      const ConvEntry& ef = n->ents[n->idx_first];
-      const ConvEntry& e1 = n->ents[n->idx_last1];
-      const ConvEntry& e2 = n->ents[n->idx_last2];
-      bp.dy = dy; bp.lddy = lddy; bp.out_ch = d.out_ch; bp.kp_y = e2.bw_kp;
-      bp.w_h2 = e2.bw_off; bp.w_h1 = e1.bw_off; bp.w_first = ef.bw_off;
-      bp.hmask_hi = f16 + gf.head_hi; bp.hb_hi = s16 + gs.hb_hi; bp.head_scale = sL;
-      bp.dx = dx; bp.lddx = lddx; bp.in_ch = d.in_ch; bp.in_rows = ef.bw_rows; bp.dx_scale = dx_scale;
-      // CRK_SKB_V=1: the frame-split chain (A/B timing, the bitwise test); see route_of
-      bp.f_h2 = e2.bfr_off; bp.f_h1 = e1.bfr_off; bp.f_first = ef.bfr_off;
-      if (gen_split) {
-        StackBP q = bp;
-        q.ts_stride = ts_plane_stride(N);
-        if (stack2_bwd_plan(q) == CRK_OK) { bp = q; split = true; }
-      }
-    } else
-      bfold = false;
-    if (!split && disc_split) {  // the discriminator: the same chain without the folds
-      StackBP q = bp;
-      q.ts_stride = ts_plane_stride(N);
-      q.dy = nullptr;
-      if (stack2_bwd_plan(q) != CRK_OK) return CRK_ERR_UNSUPPORTED;  // (the route promised the plan)
-      bp = q; split = true;
-    }
-    if (!split && gen_split) {
-      // the forward wrote the gate planes for the channel-split chain: nothing else can read them
-      fprintf(stderr, "[crank_hip] crk_net_backward: dy / dx must be 16-byte aligned with row strides that are multiples of 4 floats\n");
-      return CRK_ERR_ARG;
-    }
-    if (!bfold && !bp.dS) return CRK_ERR_ARG;
-    // the planes the weight gradient reads after this chain as 4-frame records (StackBP::rec): the channel-split chain only
-    bp.rec = (split && N % 4 == 0) ? 1 : 0;
-    if (split) RUN(launch_stack2_bwd(bp, s));
-    else RUN(launch_stack_bwd(bp, precise, s));
-    if (want_w) {  // weight gradients of every block: one launch over (utterance group, block)
-      StackWP wp;
-      memset(&wp, 0, sizeof(wp));
-      wp.xb_hi = f16 + gf.xb_hi; wp.xb_lo = f16 + gf.xb_lo; wp.zb_hi = f16 + gf.zb_hi; wp.zb_lo = f16 + gf.zb_lo;
-      wp.aux_pad = stack_aux_pad(n);
-      if (d.aux_ch > 0) { wp.cb_hi = f16 + gf.cb_hi; wp.cb_lo = f16 + gf.cb_lo; }
-      wp.gb_hi = bp.gb_hi; wp.gb_lo = bp.gb_lo; wp.dxb_hi = bp.dxb_hi; wp.dxb_lo = bp.dxb_lo;
-      wp.dsb_hi = bp.dsb_hi; wp.dsb_lo = bp.dsb_lo;
-      wp.layers = r->d_wlayers; wp.partials = PT;
-      wp.B = B; wp.T = T; wp.L = L; wp.ktaps = d.kernel_size; wp.aux_ch = d.aux_ch > 0 ? d.aux_ch : 0;
-      wp.cpg = stack_cpg(n, B, T); wp.G = r->q.Gs;
-      wp.rec_g = bp.rec;
-      if (ce) { wp.usums = n->scratch + usum_off(n, N); wp.nseg = usum_nseg(n, B, T); }
-      RUN(launch_stack_wgrad(wp, precise, s));
-      if (ce) {
-        CondEmbedP ep;
-        memset(&ep, 0, sizeof(ep));
-        ep.usums = wp.usums; ep.nseg = wp.nseg; ep.cpg = wp.cpg;
-        ep.whi = n->whi; ep.wlo = precise ? n->wlo : nullptr; ep.layers = n->d_blayers;
-        ep.idx = ce->idx; ep.run = ce->run;
-        ep.B = B; ep.T = T; ep.L = L; ep.c0 = ce->c0; ep.E = ce->E; ep.n_rows = ce->n_rows; ep.dtable = ce->dtable;
-        RUN(launch_cond_embed_bwd(ep, s));
-      }
-    }
-    dxo = dXall;
-  }
-  for (int l = L - 1; l >= 0 && !fused; l--) {
-    const ConvEntry& ec = n->ents[n->idx_conv[l]];
-    const ConvEntry& eo = n->ents[n->idx_out[l]];
-    const int dil = n->meta[n->idx_conv[l]].dilation;
-    const int off0 = fwd_off0(n, ec.k, dil);
-    float* dG = dGall + (long long)l * 2 * P;
-    {  // gate backward: dz = [dxo*sqrt(.5) | dS] . [Wo;Ws]^T ; dG = gate'(dz)
-      ConvP p = base_conv(n, B, T);
-      p.w_hi = n->whi + eo.bw_off; p.w_lo = n->wlo + eo.bw_off;
-      p.cin = 128; p.cin_pad = 128; p.cout = 64; p.cout_pad = 64;
-      p.xa = dxo; p.lda = 64; p.cinA = 64; p.scaleA = rs;
-      p.xb = dS; p.ldb = 64; p.cinB = 64;
-      p.ta = TA + l * P; p.sb = SB + l * P;
-      p.y = dG; p.ldy = 128;
-      RUN(conv_go(p, MODE_BWDA, precise, s));
-    }
-    if (want_w) {
-      WgradP w = base_wgrad(n, B, T);  // dilated conv (+ aux as an extra table entry)
-      w.a1 = dG; w.lda1 = 128; w.ca1 = 128; w.ca = 128;
-      w.x = X + l * P; w.ldx = 64; w.cx = 64;
-      if (d.dropout > 0.f) { w.drop_p = d.dropout; w.drop_seed = layer_seed(seed_val, l); w.drop_seed_ptr = seed_ptr; }
-      w.ktaps = ec.k; w.dil = dil; w.off0 = off0;
-      wgrad_slots(n, r, n->idx_conv[l], w);
-      if (d.aux_ch > 0) {
-        const ConvEntry& ea = n->ents[n->idx_aux[l]];
-        w.has_aux = 1; w.xc = c; w.ldc = ldc; w.cc = ea.cin; w.partial_aux = PT + r->abs[n->idx_aux[l]].pt_off;
-      }
-      RUN(wgrad_go(n, w, precise));
-      WgradP v = base_wgrad(n, B, T);  // 1x1 out | skip on z
-      v.a1 = dxo; v.lda1 = 64; v.ca1 = 64; v.a2 = dS; v.lda2 = 64; v.ca2 = 64; v.ca = 128;
-      v.x = Z + l * P; v.ldx = 64; v.cx = 64;
-      wgrad_slots(n, r, n->idx_out[l], v);
-      RUN(wgrad_go(n, v, precise));
-    }
-    if (dc && d.aux_ch > 0) {  // conditioning gradient, accumulated over layers
-      const ConvEntry& ea = n->ents[n->idx_aux[l]];
-      ConvP p = base_conv(n, B, T);
-      set_bw_weights(n, p, ea);
-      p.xa = dG; p.lda = 128; p.cinA = 128;
-      p.y = dc; p.ldy = lddc; p.accumulate = (l != L - 1);
-      RUN(conv_go(p, MODE_PLAIN, precise, s));
-    }
-    {  // dX_l = dxo*sqrt(.5) + convT(dG)   (kind 1, l == 0: times LeakyReLU'(X_0))
-      float* out = dXall + (long long)l * P;
-      ConvP p = base_conv(n, B, T);
-      set_bw_weights(n, p, ec);
-      p.xa = dG; p.lda = 128; p.cinA = 128;
-      p.ktaps = ec.k; p.dil = dil; p.off0 = -off0 - (ec.k - 1) * dil;
-      p.y = out; p.ldy = 64;
-      // conv input was dropout(x): the conv path goes through the regenerated keep mask
-      if (d.dropout > 0.f) { p.epi_drop_p = d.dropout; p.epi_drop_seed = layer_seed(seed_val, l); p.drop_seed_ptr = seed_ptr; }
-      if (dxo) { p.res = dxo; p.ldr = 64; p.res_scale = rs; }
-      if (l == 0 && d.kind == 1) { p.dmask = X; p.ldm = 64; p.dmask_act = ACT_LRELU; }
-      RUN(conv_go(p, MODE_PLAIN, precise, s));
-      dxo = out;
-    }
-  }
-  if (fused) {  // first conv: dx through one transposed 1x1; weight gradients of first conv + head from the planes
-    if (dx && !bfold) {
-      PsP p = ps_base(n, B, T, params);
-      p.x = dxo; p.ldx = 64; p.cin = 64; p.y = dx; p.ldy = lddx; p.out_scale = dx_scale;
-      p.layers = r->d_ps + 3 * PS_MAXL; p.L = 1;
-      RUN(pstack_plan(p, Tb.t[3], precise));
-      RUN(launch_pstack(p, precise, ps_flops(Tb.t[3], 1, N), s));
-    }
-    if (want_w) {
-      const PwP wp = plain_wgrad_params(n, r, s16, f16);
-      if (defer_wn && !precise) {  // with the weight-norm backward: one launch for all stacks of the model
-        n->pw_shape = r; n->pw_params = wp;
-      } else {
-        RUN(launch_plain_wgrad(r, wp, precise, s));
-      }
-    }
-  } else
-  {  // first conv
-    const ConvEntry& e = n->ents[n->idx_first];
-    if (want_w) {
-      WgradP w = base_wgrad(n, B, T);
-      w.a1 = dxo; w.lda1 = 64; w.ca1 = 64; w.ca = 64;
-      w.x = x; w.ldx = ldx; w.cx = e.cin;
-      wgrad_slots(n, r, n->idx_first, w);
-      RUN(wgrad_go(n, w, precise));
-    }
-    if (dx) {
-      ConvP p = base_conv(n, B, T);
-      set_bw_weights(n, p, e);
-      p.xa = dxo; p.lda = 64; p.cinA = 64;
-      p.y = dx; p.ldy = lddx; p.out_scale = dx_scale;
-      RUN(conv_go(p, MODE_PLAIN, precise, s));
-    }
-  }
-  if (want_w) {
-    RUN(wgrad_flush(n, B, T, precise, s));
-    RUN(finish_wnorm(n, r, params, grads, defer_wn, s));
-  }
-  return CRK_OK;
-}
-
 
 __global__ void seed_next_kernel(unsigned long long* state, unsigned long long* out) {
   // splitmix64 of a Weyl sequence: distinct, well-mixed seeds; the per-layer / per-element hashing is dropout_scale's

@@ -746,3 +746,272 @@ def test_the_fast_kernel_generations_are_what_runs_at_the_benchmark_shape():
                     assert paths & 1 and paths & 2, (name, B, T, paths, "generator stack: plain / bf16x3f forward not channel-split")
             seen[kind] += 1
     assert seen[0] == 4 and seen[1] >= 1 and seen[2] >= 2, seen  # four generator stacks, D, C and SPKRADV
+
+
+# ---- each route launches the kernels its record names ---------------------------------------------------------------
+# The library's own launch recorder (crk_prof_enable / crk_prof_report: classes 0 conv_tile_kernel, 1 gated forward,
+# 2 gated data-gradient chain, 3 table weight gradient, 4 plain chains, 5 gated weight gradient, 6 plain-conv weight
+# gradient) around ONE forward and then ONE backward of small nets, one case per launch form of crk_net_forward /
+# crk_net_backward.  B = 2, T = 96, two gated blocks or three plain convs: the routes depend on the net and the flags, not on
+# the size - but for gen_x3f, whose 192-row window the cost model plans only where it saves a round of workgroups over the
+# 128-row one (129 utterances of 180 frames: 129 workgroups, one round of three tiles, against 258, two rounds of two).
+# What the recorder cannot tell apart: the three chain kernels of a kind-2 net (pstack_kernel, pstack2_kernel,
+# pstack2x_kernel are all class 4, with the same FLOPs and bytes), so the rows of chain, chain_x3f and their CRK_PS_V=1
+# runs are equal and Route::ps_fwd / ps_fwd_x3f / ps_bwd are pinned by no test, only by the benchmark's step time.
+_ROUTE_BASE = dict(kernel_size=5, layers=2, stacks=1, res_ch=64, gate_ch=128, skip_ch=64, aux_ch=0, conv_ch=64, causal=0,
+                   use_bias=1, slope=0.2, dropout=0.0)
+_ROUTE_NETS = {
+    "gen": dict(kind=0, in_ch=16, out_ch=8),
+    "gen_out4": dict(kind=0, in_ch=16, out_ch=4),  # out_ch % 8 != 0: no channel-split route, the forward still folds
+    "gen_in12": dict(kind=0, in_ch=12, out_ch=8),  # in_ch % 8 != 0: nothing folds forward, the frame-split chain folds
+    "gen_drop": dict(kind=0, in_ch=16, out_ch=8, dropout=0.1),
+    "disc": dict(kind=1, in_ch=16, out_ch=1),
+    "disc_drop": dict(kind=1, in_ch=16, out_ch=1, dropout=0.1),
+    "disc_cond": dict(kind=1, in_ch=16, out_ch=1, aux_ch=8),  # conditioning: the discriminator's split route is off
+    "chain": dict(kind=2, in_ch=16, out_ch=6, conv_ch=32, kernel_size=3, layers=3),
+}
+_PRECISE, _DEFER_WNORM, _FWD_PRECISE, _BWD_PLAIN = 1, 8, 32, 64
+_ROUTE_CASES = {  # name: (net, forward flags, backward flags, options)
+    "gen_split": ("gen", 0, 0, {}),
+    "gen_precise": ("gen", _PRECISE, _PRECISE, {}),
+    # bf16x3f: the folded split-operand forward, then the channel-split fold on the lane-record planes it wrote
+    "gen_x3f": ("gen", _PRECISE | _BWD_PLAIN, _FWD_PRECISE, {"B": 129, "T": 180}),
+    # (B = 2: the split-operand kernel's 192-row window is not planned, the forward is frame-split and the backward reads row planes)
+    "gen_x3f_window_not_planned": ("gen", _PRECISE | _BWD_PLAIN, _FWD_PRECISE, {}),
+    "gen_split_dy_column_slice": ("gen", 0, 0, {"dy_off": 1}),  # 4-byte aligned rows: the channel-split fold takes them
+    "gen_out4": ("gen_out4", 0, 0, {}),
+    "gen_out4_x_misaligned": ("gen_out4", 0, 0, {"x_off": 1}),  # not a split route: unfolded, no error
+    "gen_in12": ("gen_in12", 0, 0, {}),
+    "gen_in12_dy_column_slice": ("gen_in12", 0, 0, {"dy_off": 1}),  # the frame-split fold needs 16-byte dy: unfolded, no error
+    # the plain-conv weight gradient is parked, not launched: it goes with crk_nets_wnorm_bwd ("flush")
+    "gen_split_defer_wnorm": ("gen", 0, _DEFER_WNORM, {"flush": True}),
+    "gen_dropout": ("gen_drop", 0, 0, {}),
+    "disc": ("disc", 0, 0, {}),
+    "disc_dropout": ("disc_drop", 0, 0, {}),
+    "disc_conditioned": ("disc_cond", 0, 0, {}),
+    "chain": ("chain", 0, 0, {}),
+    "chain_no_dx": ("chain", 0, 0, {"no_dx": True}),
+    "chain_x3f": ("chain", _PRECISE | _BWD_PLAIN, _FWD_PRECISE, {}),
+}
+_ROUTE_SWITCHED = {  # process switch: the cases run under it, in one fresh child process (the switches are read once)
+    "CRK_NO_FUSE=1": ["gen_split", "disc", "chain"],
+    "CRK_SK_V=1": ["gen_split", "gen_dropout", "disc"],
+    "CRK_PS_V=1": ["chain", "chain_no_dx", "chain_x3f"],
+}
+# {case: {"paths": crk_debug_net_paths, "fwd" / "bwd" / "flush": {class: [launches, FLOPs, bytes]}}} (classes without a launch
+# are absent; "flush": the crk_nets_wnorm_bwd call behind a backward that deferred to it), recorded from the library before the compute entry points were split into one function per route
+_ROUTE_EXPECT = {
+    "chain": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 2359296, 72192], "6": [1, 1990656, 73728]}},
+    "chain@CRK_NO_FUSE=1": {"paths": 0,
+        "fwd": {"0": [3, 1990656, 0]},
+        "bwd": {"0": [3, 1990656, 0], "3": [1, 1990656, 0]}},
+    "chain@CRK_PS_V=1": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 2359296, 72192], "6": [1, 1990656, 73728]}},
+    "chain_no_dx": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 1769472, 59904], "6": [1, 1990656, 73728]}},
+    "chain_no_dx@CRK_PS_V=1": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 1769472, 59904], "6": [1, 1990656, 73728]}},
+    "chain_x3f": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 2359296, 72192], "6": [1, 1990656, 73728]}},
+    "chain_x3f@CRK_PS_V=1": {"paths": 8,
+        "fwd": {"4": [1, 1990656, 47616]},
+        "bwd": {"4": [1, 2359296, 72192], "6": [1, 1990656, 73728]}},
+    "disc": {"paths": 4,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 1990656, 166656]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 191232], "5": [1, 37748736, 294912], "6": [1, 1990656, 147456]}},
+    "disc@CRK_NO_FUSE=1": {"paths": 0,
+        "fwd": {"0": [5, 39739392, 0]},
+        "bwd": {"0": [7, 39739392, 0], "3": [1, 39739392, 0]}},
+    "disc@CRK_SK_V=1": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 1990656, 166656]},
+        "bwd": {"2": [1, 37748736, 417792], "4": [2, 2359296, 191232], "5": [1, 37748736, 294912], "6": [1, 1990656, 147456]}},
+    "disc_conditioned": {"paths": 0,
+        "fwd": {"1": [1, 38535168, 325632], "4": [2, 1990656, 166656]},
+        "bwd": {"2": [1, 37748736, 417792], "4": [2, 2359296, 191232], "5": [1, 38535168, 344064], "6": [1, 1990656, 147456]}},
+    "disc_dropout": {"paths": 4,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 1990656, 166656]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 191232], "5": [1, 37748736, 294912], "6": [1, 1990656, 147456]}},
+    "gen_dropout": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 172032]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 196608], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_dropout@CRK_SK_V=1": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 172032]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 196608], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_in12": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 168960]},
+        "bwd": {"2": [1, 37748736, 368640], "5": [1, 37748736, 294912], "6": [1, 2064384, 147456]}},
+    "gen_in12_dy_column_slice": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 168960]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2260992, 193536], "5": [1, 37748736, 294912], "6": [1, 2064384, 147456]}},
+    "gen_out4": {"paths": 0,
+        "fwd": {"1": [1, 39813120, 294912]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 193536], "5": [1, 37748736, 294912], "6": [1, 2064384, 147456]}},
+    "gen_out4_x_misaligned": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2064384, 168960]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 193536], "5": [1, 37748736, 294912], "6": [1, 2064384, 147456]}},
+    "gen_precise": {"paths": 1,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 172032]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 196608], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_split": {"paths": 1,
+        "fwd": {"1": [1, 39911424, 294912]},
+        "bwd": {"2": [1, 37748736, 368640], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_split@CRK_NO_FUSE=1": {"paths": 0,
+        "fwd": {"0": [5, 39911424, 0]},
+        "bwd": {"0": [7, 39911424, 0], "3": [1, 39911424, 0]}},
+    "gen_split@CRK_SK_V=1": {"paths": 0,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 172032]},
+        "bwd": {"2": [1, 37748736, 368640], "4": [2, 2359296, 196608], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_split_defer_wnorm": {"paths": 1,
+        "fwd": {"1": [1, 39911424, 294912]},
+        "bwd": {"2": [1, 37748736, 368640], "5": [1, 37748736, 294912]},
+        "flush": {"6": [1, 2162688, 147456]}},
+    "gen_split_dy_column_slice": {"paths": 1,
+        "fwd": {"1": [1, 39911424, 294912]},
+        "bwd": {"2": [1, 37748736, 368640], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+    "gen_x3f": {"paths": 3,
+        "fwd": {"1": [1, 4826787840, 35665920]},
+        "bwd": {"2": [1, 4565237760, 44582400], "5": [1, 4565237760, 35665920], "6": [1, 261550080, 17832960]}},
+    "gen_x3f_window_not_planned": {"paths": 1,
+        "fwd": {"1": [1, 37748736, 294912], "4": [2, 2162688, 172032]},
+        "bwd": {"2": [1, 37748736, 368640], "5": [1, 37748736, 294912], "6": [1, 2162688, 147456]}},
+}
+
+
+def _route_run(names, cases=None):
+    """{name: {"paths", "rc": [forward, backward(, flush)], "fwd", "bwd"(, "flush")}} of the cases `names` (of _ROUTE_CASES), in this process."""
+    import ctypes
+
+    from crank_amd import _lib, ops
+    from crank_amd._lib import ptr, stream_ptr
+
+    L = _lib.lib()
+
+    def report():
+        out = {}
+        for cls in range(7):
+            cnt, ms, fl, by = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+            assert L.crk_prof_report(cls, ctypes.byref(cnt), ctypes.byref(ms), ctypes.byref(fl)) == 0
+            assert L.crk_prof_report_bytes(cls, ctypes.byref(by)) == 0
+            if cnt.value:
+                out[str(cls)] = [cnt.value, fl.value, by.value]
+        return out
+
+    def rows(N, width, off, seed):  # [N, width] fp32 rows that start `off` floats into their (wider) buffer
+        buf = torch.randn(N * (width + off) + off, generator=torch.Generator().manual_seed(seed)).cuda()
+        return buf, buf[off:], width + off
+
+    res = {}
+    for name in names:
+        net_name, f_fwd, f_bwd, opt = (cases or _ROUTE_CASES)[name]
+        d = dict(_ROUTE_BASE, **_ROUTE_NETS[net_name])
+        B, T = opt.get("B", 2), opt.get("T", 96)
+        N = B * T
+        net = ops.HipNet(**d)
+        g = torch.Generator().manual_seed(7)
+        params = (0.1 * torch.randn(net.n_params, generator=g)).abs().add_(0.05).cuda()
+        grads = torch.zeros_like(params)
+        xb, x, ldx = rows(N, d["in_ch"], opt.get("x_off", 0), 1)
+        dyb, dy, lddy = rows(N, d["out_ch"], opt.get("dy_off", 0), 2)
+        dxb, dx, lddx = rows(N, d["in_ch"], opt.get("dx_off", 0), 3)
+        c = torch.randn(N, d["aux_ch"], generator=g).cuda() if d["aux_ch"] else None
+        y = torch.empty(N, d["out_ch"], device="cuda")
+        assert L.crk_net_reserve(net.handle, B, T) == 0
+        saved = torch.empty(L.crk_net_saved_bytes(net.handle, B, T) // 4 + 1, device="cuda")
+        L.crk_prof_enable(1)
+        rc_f = L.crk_net_forward(net.handle, ptr(params), 1, ptr(x), ldx, ptr(c), d["aux_ch"], ptr(y), d["out_ch"], ptr(saved), B, T,
+                                 f_fwd, 1234, stream_ptr())
+        fwd = report()
+        L.crk_prof_enable(1)
+        rc_b = 0
+        if rc_f == 0:
+            rc_b = L.crk_net_backward(net.handle, ptr(params), 1, ptr(grads), ptr(x), ldx, ptr(c), d["aux_ch"], ptr(dy), lddy,
+                                      None if opt.get("no_dx") else ptr(dx), lddx, 1.0, None, 0, ptr(saved), B, T, f_bwd, 1234,
+                                      stream_ptr())
+        bwd = report()
+        res[name] = {"paths": L.crk_debug_net_paths(net.handle, B, T), "rc": [rc_f, rc_b], "fwd": fwd, "bwd": bwd}
+        if opt.get("flush"):  # the launches a CRK_FLAG_DEFER_WNORM backward left to the call over all nets of the model
+            L.crk_prof_enable(1)
+            res[name]["rc"].append(L.crk_nets_wnorm_bwd(1, (ctypes.c_void_p * 1)(net.handle), stream_ptr()))
+            res[name]["flush"] = report()
+        L.crk_prof_enable(0)
+        torch.cuda.synchronize()
+        del xb, dyb, dxb
+    return res
+
+
+def _route_check(key, name, got):
+    exp = _ROUTE_EXPECT[key]
+    print(key, got)
+    assert not any(got["rc"]), (key, got)
+    assert got["paths"] == exp["paths"], (key, got["paths"], exp["paths"])
+    for phase in ("fwd", "bwd", "flush"):
+        assert (phase in got) == (phase in exp), (key, phase)
+        if phase not in got:
+            continue
+        for cls in map(str, range(7)):
+            assert got[phase].get(cls) == exp[phase].get(cls), (key, phase, cls, got[phase].get(cls), exp[phase].get(cls))
+    # the bits crk_debug_net_paths reports are what ran
+    count = lambda phase, cls: got[phase].get(str(cls), [0])[0]  # noqa: E731
+    net_name, f_fwd, f_bwd, opt = _ROUTE_CASES[name]
+    kind, paths = _ROUTE_NETS[net_name]["kind"], got["paths"]
+    if kind == 0 and paths & 1 and f_fwd == 0:  # channel-split generator: everything folded into one launch per direction
+        assert (count("fwd", 1), count("fwd", 4), count("fwd", 0)) == (1, 0, 0), (key, got)
+        assert [count("bwd", cls) for cls in (2, 5, 4, 0, 3)] == [1, 1, 0, 0, 0], (key, got)
+        assert count("bwd", 6) == (0 if f_bwd & _DEFER_WNORM else 1), (key, got)
+    if kind == 0 and paths & 2 and f_fwd == _PRECISE | _BWD_PLAIN:  # bf16x3f: the folded split-operand forward and the plain
+        assert (count("fwd", 1), count("fwd", 4), count("fwd", 0)) == (1, 0, 0), (key, got)  # route's channel-split fold
+        assert [count("bwd", cls) for cls in (2, 5, 6, 4, 0, 3)] == [1, 1, 1, 0, 0, 0], (key, got)
+    if f_bwd & _DEFER_WNORM:  # parked by the backward, launched by the flush
+        assert (count("bwd", 6), count("flush", 6)) == (0, 1), (key, got)
+    if kind == 1 and paths & 4:  # channel-split discriminator: first conv and head keep their launches
+        assert (count("fwd", 1), count("fwd", 4), count("fwd", 0)) == (1, 2, 0), (key, got)
+        assert [count("bwd", cls) for cls in (2, 5, 6, 4, 0, 3)] == [1, 1, 1, 2, 0, 0], (key, got)
+    if kind == 2:
+        fused = 1 if paths & 8 else 0
+        assert (count("fwd", 4), count("fwd", 0) > 0) == (fused, not fused), (key, got)
+        assert (count("bwd", 4), count("bwd", 6), count("bwd", 3)) == (fused, fused, 1 - fused), (key, got)
+
+
+@pytest.mark.parametrize("name", list(_ROUTE_CASES) + list(_ROUTE_SWITCHED))
+def test_each_route_launches_the_kernels_its_record_names(name):
+    """crk_debug_net_paths reports the shape's route record; this pins what a call LAUNCHES on every route - launch counts
+    per kernel class exactly, their summed FLOPs and bytes equal to the recorded values - so a route whose call quietly took
+    an older kernel, an extra launch or another fold fails here and not only as a timing.  The table was recorded from the
+    library in which both entry points still decided per call."""
+    if name in _ROUTE_CASES:
+        _route_check(name, name, _route_run([name])[name])
+        return
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from tests.helpers import REPO
+
+    var, val = name.split("=")
+    code = ("import sys, json; sys.path.insert(0, %r); from tests.test_gpu_nets import _route_run; "
+            "print('ROUTES ' + json.dumps(_route_run(%r)))" % (REPO, _ROUTE_SWITCHED[name]))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{var: val}), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("ROUTES ")][-1][7:])
+    for case in _ROUTE_SWITCHED[name]:
+        _route_check(case + "@" + name, case, got[case])
+
+
+def test_split_routes_refuse_rows_that_are_not_16_byte_aligned(capfd):
+    """A channel-split route's backward reads the lane-record planes only the folded forward writes, and both folds move x / y /
+    dx in 16-byte pieces: rows that are only 4-byte aligned are CRK_ERR_ARG there, in both directions, before anything runs
+    (the same call on a net without a split route takes the unfolded path: gen_out4_x_misaligned above)."""
+    cases = {"_x_misaligned": ("gen", 0, 0, {"x_off": 1}), "_dx_misaligned": ("gen", 0, 0, {"dx_off": 1})}
+    got = _route_run(list(cases), cases)
+    err = capfd.readouterr().err
+    assert got["_x_misaligned"]["paths"] & 1 and got["_x_misaligned"]["rc"] == [1, 0] and got["_x_misaligned"]["fwd"] == {}
+    assert "crk_net_forward: x / y must be 16-byte aligned with row strides that are multiples of 4 floats" in err
+    assert got["_dx_misaligned"]["rc"] == [0, 1] and got["_dx_misaligned"]["bwd"].get("2") is None
+    assert "crk_net_backward: dy / dx must be 16-byte aligned with row strides that are multiples of 4 floats" in err
