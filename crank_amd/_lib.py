@@ -106,6 +106,9 @@ SIGNATURES = {
     "crk_embed_bwd_run": (I, [P, I, I, I, P, LL, LL, I, P, P, P]),
     "crk_logmel_fwd": (I, [P, I, I, I, I, I, I, I, P, P, I, F, P, P, P, I, I, P]),
     "crk_scaler_apply": (I, [P, I, P, I, LL, I, P, P, I, P]),
+    "crk_scaler_workspace_bytes": (LL, [I, I]),
+    "crk_scaler_moments": (I, [P, I, I, I, LL, P, P, I, P, LL, P]),
+    "crk_scaler_merge": (I, [P, LL, I, I, P, P, P, P, I, P, P, P, P]),
     "crk_collate_batch": (I, [ctypes.POINTER(CollateDesc), P, I, I, P, P, P, P, P, P, P, P, P]),
     "crk_decode_f0": (I, [P, P, I, I, P, P, D, D, I, P, P, P, P, P, P]),
     "crk_mcd_scratch_bytes": (LL, [I, I, I, I, I]),

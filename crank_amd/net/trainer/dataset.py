@@ -85,7 +85,8 @@ def scaler_apply(x, mean, scale, inverse=False):
 class BaseDataset:
     """``BaseDataset(conf, scp, scaler, phase)`` of the reference; ``reader(h5f, ext) -> ndarray``
     replaces its HDF5 access.  ``assemble(indices)`` returns the collated batch dict on the device;
-    ``dataset[idx]`` returns the corresponding single sample (tensors without the batch axis)."""
+    ``dataset[idx]`` returns the corresponding single sample (tensors without the batch axis).  A reader that returns
+    tensors on the dataset's device (crank_amd.feature.FeatureStore) is packed with torch.cat, without a host round trip."""
 
     def __init__(self, conf, scp, scaler, phase="train", reader=None, device="cuda"):
         if conf.get("spec_augment"):
@@ -110,7 +111,12 @@ class BaseDataset:
         for f in self.h5list:
             f = Path(f)
             for k in cols:
-                a = np.asarray(reader(str(f), ext=k), dtype=np.float32)
+                a = reader(str(f), ext=k)
+                if self._resident(a):  # a feature store's tensor: packed below where it lies
+                    a = a.to(torch.float32)
+                    cols[k].append(a[:, None] if a.ndim == 1 else a)
+                    continue
+                a = np.asarray(a, dtype=np.float32)
                 cols[k].append(a[:, None] if a.ndim == 1 else a)
             lens.append(cols[self.in_type][-1].shape[0])
             self.flbl.append(str(Path(f.parent.stem) / f.stem))  # dataset.py:80-82
@@ -122,17 +128,31 @@ class BaseDataset:
         self.utt_spk = torch.as_tensor(np.asarray(spk, dtype=np.int32), device=dev)
         self.packed = {}
         for k, parts in cols.items():
-            raw = torch.as_tensor(np.ascontiguousarray(np.concatenate(parts)), device=dev)
+            if isinstance(parts[0], torch.Tensor):
+                raw = torch.cat(parts).contiguous()
+            else:
+                raw = torch.as_tensor(np.ascontiguousarray(np.concatenate(parts)), device=dev)
             if k == "lcf0":
                 self.lcf0_raw = raw.reshape(-1).contiguous()
             self.packed[k] = scaler_apply(raw, *self.stats.feat[k]) if k in self.stats.feat else raw
         self.drop_0th = "mcep" in types and not conf.get("use_mcep_0th", False)
         self.use_raw = bool(conf.get("use_raw"))
         if self.use_raw:  # waveforms, packed sample after sample (dataset.py:42-43)
-            waves = [np.asarray(reader(str(f), ext="raw"), dtype=np.float32).reshape(-1) for f in self.h5list]
-            self.raw = torch.as_tensor(np.ascontiguousarray(np.concatenate(waves)), device=dev)
-            self.raw_start = torch.as_tensor(np.concatenate([[0], np.cumsum([w.size for w in waves])]).astype(np.int64), device=dev)
+            waves = [reader(str(f), ext="raw") for f in self.h5list]
+            if all(self._resident(w) for w in waves):
+                waves = [w.to(torch.float32).reshape(-1) for w in waves]
+                self.raw = torch.cat(waves).contiguous()
+            else:
+                waves = [np.asarray(w, dtype=np.float32).reshape(-1) for w in waves]
+                self.raw = torch.as_tensor(np.ascontiguousarray(np.concatenate(waves)), device=dev)
+            sizes = [int(w.numel()) if isinstance(w, torch.Tensor) else w.size for w in waves]
+            self.raw_start = torch.as_tensor(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64), device=dev)
             self.fftl, self.hop = int(conf["feature"]["fftl"]), int(conf["feature"]["hop_size"])
+
+    def _resident(self, a):
+        """A tensor that already lies on this dataset's device."""
+        dev = self.device
+        return isinstance(a, torch.Tensor) and a.device.type == dev.type and (dev.index is None or a.device.index == dev.index)
 
     def __len__(self):
         return len(self.h5list)

@@ -358,6 +358,44 @@ int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples, int T, in
 int crk_scaler_apply(const float* x, int ldx, float* y, int ldy, long long N, int D, const double* mean,
                      const double* scale, int inverse, void* stream);
 
+/* ---- fitting the scalers (recipe stage 2, crank/bin/extract_statistics.py) ----------------
+ * What sklearn's StandardScaler.partial_fit, called once per utterance in file order, leaves in
+ * mean_ / var_ / n_samples_seen_, over a packed block x[F_total, ld] (fp32) of which columns
+ * [col0, col0 + D) are fitted.  Two launches: the moments of every utterance alone, then the
+ * sequential merge of each group's utterances.  Everything is float64.
+ *
+ * The workspace carries the moments from the first entry to the second.  Layout (every part starts
+ * at a multiple of 256 bytes, in this order; tiles = (D + 63) / 64):
+ *   int status[U * tiles]   0 fine, 1 a non-finite value in that utterance, 2 bad device offsets
+ *   long long n[U]          frames of the utterance
+ *   double sum[U * D]       sum x
+ *   double m2[U * D]        sum (x - T)^2 - (sum (x - T))^2 / n  with T = sum / n
+ * crk_scaler_workspace_bytes returns its size, -1 for U < 1 or D < 1.
+ *
+ * Neither compute entry allocates or synchronises; both can be captured into a graph.  Both take
+ * the offsets twice: the device copy the kernel reads and a host copy that is checked before
+ * anything is launched.  CRK_ERR_ARG, with nothing launched: a workspace shorter than
+ * crk_scaler_workspace_bytes(U, D), U < 1, D < 1, ld < col0 + D, an empty utterance
+ * (utt_start[u + 1] <= utt_start[u]), offsets outside [0, F_total], an empty group, a group member
+ * outside [0, U). */
+long long crk_scaler_workspace_bytes(int U, int D);
+/* One workgroup per utterance and tile of 64 columns; 16-byte loads when ld, col0 and D are
+ * multiples of 4 and x is 16-byte aligned, scalar loads otherwise, in the same summation order:
+ * the result depends on the utterance's values, its length and D alone, never on the load width,
+ * the other utterances or the call. */
+int crk_scaler_moments(const float* x, int ld, int col0, int D, long long F_total, const long long* utt_start,
+                       const long long* utt_start_host, int U, void* workspace, long long workspace_bytes,
+                       void* stream);
+/* Groups as a CSR pair: group g merges utterances group_utts[group_start[g] .. group_start[g + 1]) in
+ * that order, one thread per (group, column), by sklearn's update:
+ *   last_sum = mean * count;  mean' = (last_sum + sum) / (count + n);  r = count / n;
+ *   m2' = var * count + m2 + r / (count + n) * (last_sum / r - sum)^2   (the first utterance: m2' = m2);
+ *   var' = m2' / (count + n).
+ * mean, var: [G, D] doubles; count: [G] (all device memory). */
+int crk_scaler_merge(const void* workspace, long long workspace_bytes, int U, int D, const long long* group_start,
+                     const int* group_utts, const long long* group_start_host, const int* group_utts_host, int G,
+                     double* mean, double* var, long long* count, void* stream);
+
 #define CRK_COLLATE_MAX_STREAMS 8
 /* one continuous feature of the batch dict: columns [col0, col0 + ncols) of the packed
  * rows src[F_total, ld] -> dst (B, T, ncols), tail-padded with 0.0 */
