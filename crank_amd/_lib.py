@@ -39,6 +39,14 @@ class CollateDesc(ctypes.Structure):
     ]
 
 
+ADAM_MAX_BLOCKS = 4
+
+
+class AdamBlock(ctypes.Structure):
+    _fields_ = [("params", c_void_p), ("grads", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("n", c_longlong), ("lr_dev", c_void_p), ("step_dev", c_void_p)]
+
+
 P, I, LL, ULL, F, D = c_void_p, c_int, c_longlong, c_ulonglong, c_float, c_double
 
 SIGNATURES = {
@@ -52,9 +60,11 @@ SIGNATURES = {
     "crk_net_scratch_bytes": (LL, [P, I, I]),
     "crk_debug_alloc_count": (LL, []),
     "crk_debug_net_paths": (I, [P, I, I]),
+    "crk_debug_net_partials": (LL, [P, I, I, P, LL, P]),
     "crk_seed_next": (I, [P, P, P]),
     "crk_nets_wnorm_bwd": (I, [I, P, P]),
     "crk_nets_prepare": (I, [I, P, P, ULL, P, P]),
+    "crk_nets_prepare_models": (I, [I, P, P, P, I, P, P]),
     "crk_net_forward": (I, [P, P, ULL, P, I, P, I, P, I, P, I, I, I, ULL, P]),
     "crk_net_backward": (I, [P, P, ULL, P, P, I, P, I, P, I, P, I, F, P, I, P, I, I, I, ULL, P]),
     "crk_net_backward_scaled": (I, [P, P, ULL, P, P, I, P, I, P, I, P, I, F, P, I, P, I, I, I, ULL, P, P, P]),
@@ -96,6 +106,7 @@ SIGNATURES = {
     "crk_stft_loss_fwd": (I, [P, I, P, I, I, I, I, I, I, I, P, F, F, I, P, P, P]),
     "crk_stft_loss_bwd": (I, [P, I, P, I, I, I, I, I, I, I, P, F, F, P, P, I, P]),
     "crk_adam_step": (I, [P, P, P, P, LL, P, P, F, F, F, I, P]),
+    "crk_adam_step_multi": (I, [I, ctypes.POINTER(AdamBlock), F, F, F, I, P]),
     "crk_radam_step": (I, [P, P, P, P, LL, P, P, D, D, D, I, P]),
     "crk_lamb_step": (I, [P, P, P, P, P, P, I, P, I, P, P, P, P, D, D, D, I, P]),
     "crk_lamb_tile": (I, []),

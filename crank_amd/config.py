@@ -9,8 +9,11 @@ before the import.  The kernels' own A/B switches (`CRK_*`, read once per proces
     precision               CRANK_AMD_PRECISION                  bf16      arithmetic of the conv stacks: bf16 | bf16x3f | bf16x3
     lib_path                CRANK_AMD_LIB                        (in-tree) another build of libcrank_hip.so (instrumented builds)
     default_yaml            CRANK_DEFAULT_YAML                   (in-tree) recipe defaults (`utils.load_yaml`)
-    overlap_c               CRANK_AMD_OVERLAP_C                  1         speaker classifier's update on a second stream: 0 in line,
-                                                                           1 forked at the start of the step, 2 forked after G's update
+    overlap_c               CRANK_AMD_OVERLAP_C                  3         speaker classifier's update: 0 in line, 1 on a second stream
+                                                                           forked at the start of the step, 2 forked after G's
+                                                                           update, 3 in line and sharing its weight-gradient,
+                                                                           weight-norm, Adam and preparation launches with the
+                                                                           speaker-adversarial net's update
     separate_ce             CRANK_AMD_SEPARATE_CE                0         cross entropy and the net's backward as separate launches
     separate_commit         CRANK_AMD_SEPARATE_COMMIT            0         commitment loss outside the quantizer's launch
     recon_dense             CRANK_AMD_RECON_DENSE                0         L1 / MSE / STFT losses of the decoded features unfused
@@ -40,7 +43,7 @@ def _read():
         precision=_get("CRANK_AMD_PRECISION", "bf16"),
         lib_path=_get("CRANK_AMD_LIB") or None,
         default_yaml=_get("CRANK_DEFAULT_YAML") or None,
-        overlap_c=int(_get("CRANK_AMD_OVERLAP_C", "1") or 0),
+        overlap_c=int(_get("CRANK_AMD_OVERLAP_C", "3") or 0),
         separate_ce=_flag("CRANK_AMD_SEPARATE_CE", False),
         separate_commit=_flag("CRANK_AMD_SEPARATE_COMMIT", False),
         recon_dense=_flag("CRANK_AMD_RECON_DENSE", False),

@@ -189,8 +189,10 @@ struct PwP {
   float* partials;
   int B, T, cpg, G;       // 64-frame chunks per group, number of groups
 };
-struct PwMP { PwP q[CRK_MAX_NETS_PW]; int first[CRK_MAX_NETS_PW + 1]; int n; };  // several nets' tables in one launch
-int launch_pstack_wgrad_multi(const PwMP& m, int total_layers, int max_G, int max_wa, int max_wb, int max_tiles, double flops,
+// several nets' tables in one launch: net r owns workgroups [first[r], first[r + 1]), its q[r].G groups of conv 0, then of
+// conv 1, ... - the nets may differ in depth, taps and group count
+struct PwMP { PwP q[CRK_MAX_NETS_PW]; int first[CRK_MAX_NETS_PW + 1]; int n; };
+int launch_pstack_wgrad_multi(const PwMP& m, int total_blocks, int max_wa, int max_wb, int max_tiles, double flops,
                               double bytes, hipStream_t s);  // max_tiles: most (tap, cin band, cout band) tiles of any conv
 int pstack_wgrad_supported(int ca, int cb, int wa, int wb, int k, int dil);
 int launch_pstack_wgrad(const PwP& p, int nlayers, int max_wa, int max_wb, bool precise, double flops, hipStream_t s, int max_tiles = 0);
@@ -312,9 +314,11 @@ struct NetRef {
   uint16_t *whi, *wlo;
   int n_ents, first;  // entries of this net; index of its first workgroup column in the launch
 };
-struct NetRefs { NetRef r[CRK_MAX_NETS]; int n; float* bump; };  // bump: an Adam step count advanced by the prep launch
+#define CRK_MAX_BUMPS 4
+// bump[0 .. n_bump): Adam step counts advanced by the prep launch (one per model whose nets it prepares)
+struct NetRefs { NetRef r[CRK_MAX_NETS]; int n; float* bump[CRK_MAX_BUMPS]; int n_bump; };
 int launch_weight_prep_multi(const NetRefs& R, int total_entries, int nmax, hipStream_t s);  // nmax: largest cin * k
-int launch_step_bump(float* step, hipStream_t s);
+int launch_step_bump(float* const* steps, int n, hipStream_t s);
 int launch_wnorm_bwd_multi(const NetRefs& R, int total_entries, hipStream_t s);
 int launch_weight_prep(const ConvEntry* d_entries, int n_entries, int nmax, const float* params, uint16_t* wprep_hi,
                        uint16_t* wprep_lo, float* norms, hipStream_t s);

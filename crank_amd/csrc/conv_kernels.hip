@@ -811,12 +811,24 @@ __global__ __launch_bounds__(256) void weight_prep_multi_kernel(const NetRefs R)
   extern __shared__ unsigned wp_ws[];
   const NetRef& q = R.r[net_of_block(R, blockIdx.x)];
   const ConvEntry e = q.ents[blockIdx.x - q.first];
-  if (R.bump && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) R.bump[0] += 1.f;
+  if (blockIdx.x == 0 && blockIdx.y == 0) {
+#pragma unroll
+    for (int i = 0; i < CRK_MAX_BUMPS; i++)
+      if (i < R.n_bump && (int)threadIdx.x == i) R.bump[i][0] += 1.f;
+  }
   weight_prep_band<BAND>(e, blockIdx.y, q.params, q.whi, q.wlo, q.norms, wp_ws);
 }
-__global__ void step_bump_kernel(float* step) { step[0] += 1.f; }
-int launch_step_bump(float* step, hipStream_t s) {
-  hipLaunchKernelGGL(step_bump_kernel, dim3(1), dim3(1), 0, s, step);
+struct StepBumps { float* p[CRK_MAX_BUMPS]; };
+__global__ void step_bump_kernel(const StepBumps b) {
+#pragma unroll
+  for (int i = 0; i < CRK_MAX_BUMPS; i++)
+    if ((int)threadIdx.x == i) b.p[i][0] += 1.f;
+}
+int launch_step_bump(float* const* steps, int n, hipStream_t s) {
+  if (n < 1 || n > CRK_MAX_BUMPS) return CRK_ERR_ARG;
+  StepBumps b;
+  for (int i = 0; i < CRK_MAX_BUMPS; i++) b.p[i] = steps[i < n ? i : 0];
+  hipLaunchKernelGGL(step_bump_kernel, dim3(1), dim3(n), 0, s, b);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }

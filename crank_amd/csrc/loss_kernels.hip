@@ -1242,6 +1242,59 @@ extern "C" int crk_adam_step(float* params, float* grads, float* exp_avg, float*
   return CRK_OK;
 }
 
+// ... over several blocks (the models whose updates of a step are adjacent and independent) in ONE launch: workgroup x
+// belongs to the block whose range holds it and walks that block exactly as adam_kernel walks it alone - each block with
+// its own lr and step count, the same arithmetic per element
+#define CRK_ADAM_MAX_BLOCKS 4
+struct crk_adam_block {  // (the C ABI's record, include/crank_hip.h)
+  float *params, *grads, *exp_avg, *exp_avg_sq;
+  long long n;
+  const float* lr_dev;
+  float* step_dev;
+};
+struct AdamBlocks { crk_adam_block b[CRK_ADAM_MAX_BLOCKS]; int first[CRK_ADAM_MAX_BLOCKS + 1]; int n; };
+template <bool CLEAR>
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamBlocks A, float beta1, float beta2, float eps) {
+  int r = 0;
+  while (r + 1 < A.n && (int)blockIdx.x >= A.first[r + 1]) r++;
+  const crk_adam_block& q = A.b[r];
+  const AdamCoef c = adam_coef(q.lr_dev, q.step_dev, beta1, beta2, eps);
+  const long nb = A.first[r + 1] - A.first[r], n = (long)q.n;
+  for (long i = (long)((int)blockIdx.x - A.first[r]) * 256 + threadIdx.x; i < n; i += nb * 256)
+    adam_elem<CLEAR>(q.params, q.grads, q.exp_avg, q.exp_avg_sq, i, c);
+}
+struct AdamBumps { float* p[CRK_ADAM_MAX_BLOCKS]; };
+__global__ void adam_bump_multi_kernel(const AdamBumps b) {
+#pragma unroll
+  for (int i = 0; i < CRK_ADAM_MAX_BLOCKS; i++)
+    if ((int)threadIdx.x == i) b.p[i][0] += 1.f;
+}
+extern "C" int crk_adam_step_multi(int n_blocks, const crk_adam_block* blocks, float beta1, float beta2, float eps,
+                                   int clear_grads, void* stream) {
+  if (n_blocks < 1 || n_blocks > CRK_ADAM_MAX_BLOCKS || !blocks) return CRK_ERR_ARG;
+  AdamBlocks A{};
+  AdamBumps B;
+  int total = 0;
+  for (int i = 0; i < n_blocks; i++) {
+    const crk_adam_block& q = blocks[i];
+    if (!q.params || !q.grads || !q.exp_avg || !q.exp_avg_sq || !q.lr_dev || !q.step_dev || q.n < 0) return CRK_ERR_ARG;
+    for (int j = 0; j < i; j++) if (blocks[j].step_dev == q.step_dev) return CRK_ERR_ARG;  // (it would advance twice)
+    long b = ((long)q.n + 255) / 256;
+    if (b > 2048) b = 2048;
+    if (b < 1) b = 1;
+    A.b[i] = q; A.first[i] = total;
+    total += (int)b;
+  }
+  A.first[n_blocks] = total; A.n = n_blocks;
+  for (int i = 0; i < CRK_ADAM_MAX_BLOCKS; i++) B.p[i] = blocks[i < n_blocks ? i : 0].step_dev;
+  hipStream_t s = (hipStream_t)stream;
+  if (clear_grads & 1) hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(total), dim3(256), 0, s, A, beta1, beta2, eps);
+  else hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(total), dim3(256), 0, s, A, beta1, beta2, eps);
+  if (!(clear_grads & 2)) hipLaunchKernelGGL(adam_bump_multi_kernel, dim3(1), dim3(n_blocks), 0, s, B);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
 // ------------------------------------------------------------------------------
 // RAdam (crank/net/trainer/utils.py:44-45: torch_optimizer.RAdam(lr), a third-party package absent from the reference
 // tree; restated from Liu et al., "On the Variance of the Adaptive Learning Rate and Beyond", Alg. 2, in the form that

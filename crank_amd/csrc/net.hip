@@ -1094,6 +1094,17 @@ extern "C" int crk_debug_net_paths(void* h, int B, int T) {
   return (int)r.gen_split | (int)r.x3f << 1 | (int)r.disc_split << 2 | (int)(n->d.kind == 2 && r.fused) << 3;
 }
 
+// The weight-gradient partial sums of shape (B, T) as the last backward left them (tests compare launch forms on them):
+// returns their count and copies the first min(count, cap) floats to `out` (device memory); -1: the shape is not reserved.
+extern "C" long long crk_debug_net_partials(void* h, int B, int T, float* out, long long cap, void* stream) {
+  Net* n = (Net*)h;
+  const Shape* r = n ? find_shape(n, B, T) : nullptr;
+  if (!r || !n->partials || cap < 0 || (cap > 0 && !out)) return -1;
+  const long long cnt = r->q.need_p < cap ? r->q.need_p : cap;
+  if (cnt > 0 && hipMemcpyAsync(out, n->partials, sizeof(float) * cnt, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return -1;
+  return r->q.need_p;
+}
+
 static WgradP base_wgrad(const Net* n, int B, int T) {
   WgradP w;
   memset(&w, 0, sizeof(w));
@@ -1222,8 +1233,12 @@ static int bwd_chain(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
     RUN(pstack2_plan(p, Tb.t[1]));
     RUN(launch_pstack2(p, ps_flops(Tb.t[1], p.L, N), a.s));
   } else RUN(pstack_go(r, 1, p, k.precise, a.s));
-  if (k.want_w) RUN(launch_plain_wgrad(r, plain_wgrad_params(n, r, g16, f16), k.precise, a.s));
-  return CRK_OK;
+  if (!k.want_w) return CRK_OK;
+  const PwP wp = plain_wgrad_params(n, r, g16, f16);
+  // CRK_FLAG_DEFER_WNORM, plain bf16: parked like the plain convs around a gated stack (gated_plain_wgrad) - the group call
+  // runs it in one launch with the other nets' (the speaker nets of a step: two updates, one set of launches)
+  if (k.defer_wn && !k.precise) { n->pw_shape = r; n->pw_params = wp; return CRK_OK; }
+  return launch_plain_wgrad(r, wp, k.precise, a.s);
 }
 static int bwd_chain_layers(Net* n, const Shape* r, const Call& k, const BwdIo& a) {
   const crk_net_desc& d = n->d;
@@ -1537,32 +1552,38 @@ extern "C" int crk_seed_next(unsigned long long* state, unsigned long long* out,
 // The deferred weight-norm backward of every net that has one pending (crk_net_backward with CRK_FLAG_DEFER_WNORM),
 // in ONE launch.  Nets without pending work are skipped.
 static int flush_plain_wgrads(int n_nets, void* const* nets, hipStream_t s) {
-  {  // the deferred weight gradients of the plain convs (first conv + head of every stack), one launch
-    PwMP M; memset(&M, 0, sizeof(M));
-    int layers = 0, max_G = 0, max_wa = 0, max_wb = 0, max_tiles = 0;
-    double flops = 0.0, bytes = 0.0;
-    for (int i = 0; i < n_nets; i++) {
-      Net* n = (Net*)nets[i];
-      if (!n) return CRK_ERR_ARG;
-      const Shape* r = n->pw_shape;
-      if (!r) continue;
-      if (M.n == CRK_MAX_NETS_PW) { RUN(flush_pending_plain_wgrad(n, s)); continue; }
-      const PsTables& Tb = r->ps;
-      M.q[M.n] = n->pw_params;
-      M.first[M.n] = layers;
-      layers += Tb.nw;
-      if (n->pw_params.G > max_G) max_G = n->pw_params.G;
-      if (Tb.max_wa > max_wa) max_wa = Tb.max_wa;
-      if (Tb.max_wb > max_wb) max_wb = Tb.max_wb;
-      if (Tb.max_tiles > max_tiles) max_tiles = Tb.max_tiles;
-      flops += Tb.wflops_per_frame * r->B * r->T;
-      bytes += 2.0 * (Tb.max_wa + Tb.max_wb) * (double)r->B * r->T * Tb.nw;
-      M.n++;
-      n->pw_shape = nullptr;
-    }
-    M.first[M.n] = layers;
-    if (M.n > 0) RUN(launch_pstack_wgrad_multi(M, layers, max_G, max_wa, max_wb, max_tiles, flops, bytes, s));
+  // the deferred weight gradients of the plain convs (first conv + head of every stack; every conv of a plain net), one
+  // launch: the nets' (layer, group) workgroups side by side, each net with its own depth, taps and group count
+  PwMP M; memset(&M, 0, sizeof(M));
+  int blocks = 0, max_wa = 0, max_wb = 0, max_tiles = 0, pending = 0;
+  double flops = 0.0, bytes = 0.0;
+  Net* only = nullptr;
+  for (int i = 0; i < n_nets; i++) {
+    Net* n = (Net*)nets[i];
+    if (!n) return CRK_ERR_ARG;
+    if (n->pw_shape) { pending++; only = n; }
   }
+  // a plain net on its own keeps the single-net launch (the instantiation for its tile count)
+  if (pending == 1 && only->d.kind == 2) return flush_pending_plain_wgrad(only, s);
+  for (int i = 0; i < n_nets; i++) {
+    Net* n = (Net*)nets[i];
+    const Shape* r = n->pw_shape;
+    if (!r) continue;
+    if (M.n == CRK_MAX_NETS_PW) { RUN(flush_pending_plain_wgrad(n, s)); continue; }
+    const PsTables& Tb = r->ps;
+    M.q[M.n] = n->pw_params;
+    M.first[M.n] = blocks;
+    blocks += Tb.nw * n->pw_params.G;
+    if (Tb.max_wa > max_wa) max_wa = Tb.max_wa;
+    if (Tb.max_wb > max_wb) max_wb = Tb.max_wb;
+    if (Tb.max_tiles > max_tiles) max_tiles = Tb.max_tiles;
+    flops += Tb.wflops_per_frame * r->B * r->T;
+    bytes += 2.0 * (Tb.max_wa + Tb.max_wb) * (double)r->B * r->T * Tb.nw;
+    M.n++;
+    n->pw_shape = nullptr;
+  }
+  M.first[M.n] = blocks;
+  if (M.n > 0) RUN(launch_pstack_wgrad_multi(M, blocks, max_wa, max_wb, max_tiles, flops, bytes, s));
   return CRK_OK;
 }
 extern "C" int crk_nets_wnorm_bwd(int n_nets, void* const* nets, void* stream) {
@@ -1591,26 +1612,38 @@ extern "C" int crk_nets_wnorm_bwd(int n_nets, void* const* nets, void* stream) {
 
 // Weight preparation (weight-norm fold + bf16 operand planes) of every net whose parameters changed, in ONE launch;
 // what crk_net_forward / crk_net_backward would do one net at a time on their first call after an optimizer step.
-// params[i]: the parameter block of nets[i]; version: as for crk_net_forward.
-extern "C" int crk_nets_prepare(int n_nets, void* const* nets, const float* const* params, unsigned long long version,
-                                float* bump_step, void* stream) {
-  if (n_nets < 0 || (n_nets > 0 && (!nets || !params))) return CRK_ERR_ARG;
+// params[i] / versions[i]: the parameter block of nets[i] and its version, as for crk_net_forward (the nets of several
+// models: each model counts its own); bump_steps: the Adam step counts of those models.
+extern "C" int crk_nets_prepare_models(int n_nets, void* const* nets, const float* const* params,
+                                       const unsigned long long* versions, int n_bumps, float* const* bump_steps,
+                                       void* stream) {
+  if (n_nets < 0 || (n_nets > 0 && (!nets || !params || !versions))) return CRK_ERR_ARG;
+  if (n_bumps < 0 || n_bumps > CRK_MAX_BUMPS || (n_bumps > 0 && !bump_steps)) return CRK_ERR_ARG;
+  for (int i = 0; i < n_bumps; i++) if (!bump_steps[i]) return CRK_ERR_ARG;
+  for (int i = 0; i < n_nets; i++) if (!nets[i] || !params[i]) return CRK_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   NetRefs R; memset(&R, 0, sizeof(R));
   int total = 0, nmax = 1;
   for (int i = 0; i < n_nets; i++) {
     Net* n = (Net*)nets[i];
-    if (!n || !params[i]) return CRK_ERR_ARG;
-    if (n->prepared_version == version && n->prepared_params == params[i]) continue;
+    if (n->prepared_version == versions[i] && n->prepared_params == params[i]) continue;
     if (net_nmax(n) > nmax) nmax = net_nmax(n);
-    if (R.n == CRK_MAX_NETS) { RUN(ensure_prepared(n, params[i], version, s)); continue; }
+    if (R.n == CRK_MAX_NETS) { RUN(ensure_prepared(n, params[i], versions[i], s)); continue; }
     NetRef& q = R.r[R.n++];
     q.ents = n->d_ents; q.n_ents = (int)n->ents.size(); q.first = total;
     q.params = params[i]; q.whi = n->whi; q.wlo = n->wlo; q.norms = n->norms;
     total += q.n_ents;
-    n->prepared_version = version; n->prepared_params = params[i];
+    n->prepared_version = versions[i]; n->prepared_params = params[i];
   }
-  if (R.n == 0) return bump_step ? launch_step_bump(bump_step, s) : CRK_OK;
-  R.bump = bump_step;
+  if (R.n == 0) return n_bumps ? launch_step_bump(bump_steps, n_bumps, s) : CRK_OK;
+  for (int i = 0; i < n_bumps; i++) R.bump[i] = bump_steps[i];
+  R.n_bump = n_bumps;
   return launch_weight_prep_multi(R, total, nmax, s);
+}
+// ... of the nets of ONE model: one version, at most one step count
+extern "C" int crk_nets_prepare(int n_nets, void* const* nets, const float* const* params, unsigned long long version,
+                                float* bump_step, void* stream) {
+  if (n_nets < 0 || (n_nets > 0 && (!nets || !params))) return CRK_ERR_ARG;
+  const std::vector<unsigned long long> versions((size_t)n_nets + 1, version);
+  return crk_nets_prepare_models(n_nets, nets, params, versions.data(), bump_step ? 1 : 0, &bump_step, stream);
 }

@@ -756,33 +756,57 @@ __global__ __launch_bounds__(256) void pstack_wgrad_kernel(const PwP p) {
   }
   pstack_wgrad_body<PRECISE, MAXT>(p, blockIdx.x, blockIdx.y, smem);
 }
-// the plain convs of several nets (first conv and head of every generator stack) in one launch: grid row y belongs to the
-// net whose layer range holds it
+// the plain convs of several nets in one launch (first conv and head of every generator stack; the speaker nets of a step):
+// workgroup x belongs to the net whose range holds it, there to (conv, group) = (local / G, local % G) - the order a
+// (G, convs) grid of that net alone is walked in
+__device__ __forceinline__ int pw_net_of_block(const PwMP& m, int bx) {
+  int r = 0;
+  while (r + 1 < m.n && bx >= m.first[r + 1]) r++;
+  return r;
+}
 template <int MAXT>
 __global__ __launch_bounds__(256) void pstack_wgrad_multi_kernel(const PwMP m) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int r = 0;
-  while (r + 1 < m.n && (int)blockIdx.y >= m.first[r + 1]) r++;
+  const int r = pw_net_of_block(m, blockIdx.x);
   const PwP& p = m.q[r];
-  if ((int)blockIdx.x >= p.G) return;
+  const int local = (int)blockIdx.x - m.first[r], layer = local / p.G;
   // (the shared dY fragment of pstack_wgrad_kernel is not used here: two tiles per wave at most, 33.9 -> 35.4 us with it)
-  pstack_wgrad_body<false, MAXT>(p, blockIdx.x, blockIdx.y - m.first[r], smem);
+  pstack_wgrad_body<false, MAXT>(p, local - layer * p.G, layer, smem);
 }
-int launch_pstack_wgrad_multi(const PwMP& m, int total_layers, int max_G, int max_wa, int max_wb, int max_tiles, double flops,
+// ... where a conv has more than two tiles per wave (whole plain nets: 20 - 30 tiles a conv): per workgroup the body
+// pstack_wgrad_kernel<false, ..> runs for that conv launched alone - the instantiation for its tiles per wave (3, 5, 6 or
+// 8; any body that holds the tiles adds the same products in the same order), the dY fragment read once per wave where
+// every tile of a wave lies in one cout band, chunks requested two ahead.  A conv costs here what it costs there.
+__global__ __launch_bounds__(256) void pstack_wgrad_multi_wide_kernel(const PwMP m) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int r = pw_net_of_block(m, blockIdx.x);
+  const PwP& p = m.q[r];
+  const int local = (int)blockIdx.x - m.first[r], layer = local / p.G, g = local - layer * p.G;
+  const PwLayer& Y = p.layers[layer];
+  const int nct = (Y.ca + 31) >> 5;
+  const int per = (nct * ((Y.cb + 31) >> 5) * Y.k + 3) >> 2;
+  const bool sa = (4 % nct) == 0;  // one cout band per wave (pstack_wgrad_body, PW_COMPUTE)
+  if (per <= 3) { if (sa) pstack_wgrad_body<false, 3, true>(p, g, layer, smem); else pstack_wgrad_body<false, 3>(p, g, layer, smem); return; }
+  if (per <= 5) { if (sa) pstack_wgrad_body<false, 5, true>(p, g, layer, smem); else pstack_wgrad_body<false, 5>(p, g, layer, smem); return; }
+  if (per <= 6) { if (sa) pstack_wgrad_body<false, 6, true>(p, g, layer, smem); else pstack_wgrad_body<false, 6>(p, g, layer, smem); return; }
+  if (sa) pstack_wgrad_body<false, PW_MAXT, true>(p, g, layer, smem); else pstack_wgrad_body<false, PW_MAXT>(p, g, layer, smem);
+}
+int launch_pstack_wgrad_multi(const PwMP& m, int total_blocks, int max_wa, int max_wb, int max_tiles, double flops,
                               double bytes, hipStream_t s) {
   const int RA = ((max_wa + 31) & ~31) * 2 + 64, RB = ((max_wb + 31) & ~31) * 2 + 64;
   const int lds = PW_FR * RA + (PW_FR + PW_SPAN) * RB;
+  if (total_blocks < 1) return CRK_ERR_ARG;
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)pstack_wgrad_multi_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)pstack_wgrad_multi_kernel<PW_MAXT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        hipFuncSetAttribute((const void*)pstack_wgrad_multi_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return CRK_ERR_HIP;
     attr_set = true;
   }
   conv_prof_bytes(6, bytes);
   conv_prof_begin(6, flops, s);
-  if (max_tiles <= 8) hipLaunchKernelGGL(pstack_wgrad_multi_kernel<2>, dim3(max_G, total_layers), dim3(256), lds, s, m);  // <= 2 per wave
-  else hipLaunchKernelGGL(pstack_wgrad_multi_kernel<PW_MAXT>, dim3(max_G, total_layers), dim3(256), lds, s, m);
+  if (max_tiles <= 8) hipLaunchKernelGGL(pstack_wgrad_multi_kernel<2>, dim3(total_blocks), dim3(256), lds, s, m);  // <= 2 per wave
+  else hipLaunchKernelGGL(pstack_wgrad_multi_wide_kernel, dim3(total_blocks), dim3(256), lds, s, m);
   conv_prof_end(6, s);
   CRK_CHECK_LAUNCH();
   return CRK_OK;

@@ -69,6 +69,9 @@ class VQVAETrainer(BaseTrainer):
         # the step (its kernels are small and latency bound - 8 layers of 64 channels - and fill the compute units the
         # step's dependent launches leave idle).  Forked here, joined before the loss values are collected; inside a
         # captured step the fork and the join become edges of the graph.  Same values: nothing is shared but the batch.
+        # That is config.cfg.overlap_c = 1 / 2.  The default, 3, keeps the classifier's update in line and gives it and the
+        # speaker-adversarial net's update one set of maintenance launches instead (update_speaker_nets): the second stream
+        # hid 9 us of the classifier's update, the shared launches take 33 us of kernel time off the stream.
         side = self._classifier_stream(batch, phase)
         late = cfg.overlap_c == 2
 
@@ -90,9 +93,12 @@ class VQVAETrainer(BaseTrainer):
             loss = self.forward_spkradv(batch, loss, phase=phase)
         else:
             self._defer_G_tail = False
-            loss = self.forward_spkradv(batch, loss, phase=phase)
-            if side is None:
-                loss = self.forward_spkrclassifier(batch, loss, phase=phase)
+            if side is None and self._speaker_updates_joinable(batch, phase):
+                loss = self.update_speaker_nets(batch, loss, phase=phase)
+            else:
+                loss = self.forward_spkradv(batch, loss, phase=phase)
+                if side is None:
+                    loss = self.forward_spkrclassifier(batch, loss, phase=phase)
         if self._C_tail is not None:  # (nobody took the classifier's message along: its own reduce and step)
             tail, self._C_tail = self._C_tail, None
             tail()
@@ -112,14 +118,72 @@ class VQVAETrainer(BaseTrainer):
 
     def _classifier_stream(self, batch, phase):
         """The stream the classifier's update is enqueued on next to the rest of the step, or None (same stream, in the
-        reference's order): CUDA, single process, training, C read by nobody else; config.cfg.overlap_c = 0 switches it off."""
+        reference's order): CUDA, single process, training, C read by nobody else; config.cfg.overlap_c = 0 switches it off,
+        3 keeps it in line and joins it with the speaker-adversarial net's update (update_speaker_nets)."""
         if not (phase == "train" and self.conf["use_spkr_classifier"] and not parallel.is_dist()
                 and self._classifier_is_independent() and batch["in_feats"].is_cuda
-                and cfg.overlap_c != 0):
+                and cfg.overlap_c not in (0, 3)):
             return None
         if getattr(self, "_c_stream", None) is None:
             self._c_stream = torch.cuda.Stream(device=batch["in_feats"].device)
         return self._c_stream
+
+    def _speaker_updates_joinable(self, batch, phase):
+        """True when the speaker-adversarial net's and the classifier's updates, adjacent at the end of the step, can run
+        as one set of launches (update_speaker_nets): config.cfg.overlap_c = 3, training, single process, both updates on,
+        both models on FlatAdam itself (its own step()) with the same constants and no gradient clipping."""
+        if not (cfg.overlap_c == 3 and phase == "train" and not parallel.is_dist() and batch["in_feats"].is_cuda
+                and self.conf["use_spkradv_training"] and self.conf["use_spkr_classifier"]
+                and getattr(self, "group_stack_maintenance", True)):
+            return False
+        from .utils import FlatAdam
+        opts = [self.optimizer.get(k) for k in ("SPKRADV", "C")]
+        # (the joint update stands in for both optimizers' step(): only where step IS FlatAdam's - not a subclass's, not one
+        # a caller has wrapped on the instance, e.g. to look at the gradients in front of the update)
+        if any(type(o) is not FlatAdam or getattr(o.step, "__func__", None) is not FlatAdam.step or o.grad_reduce_fn is not None
+               for o in opts):
+            return False
+        if any(self.conf["optim"][k]["clip_grad_norm"] != 0 for k in ("SPKRADV", "C")):
+            return False
+        if any(not getattr(self.model[k], "_nets", None) for k in ("SPKRADV", "C")):
+            return False
+        a, b = opts
+        return a.betas == b.betas and a.eps == b.eps and a.clear_grads == b.clear_grads
+
+    def update_speaker_nets(self, batch, loss, phase="train"):
+        """forward_spkradv then forward_spkrclassifier (trainer_vqvae.py:66-68 of the reference) with the two updates'
+        maintenance launches shared: both forwards and cross entropies, both backward chains with their weight gradients
+        and weight-norm backward left pending, then ONE launch each for the weight gradients, the weight-norm backward,
+        Adam and the weight preparation of both models.  The updates read nothing of each other (SPKRADV reads G's new
+        encodings, C the batch), so every value is the one the separate updates compute."""
+        from ... import ops
+        from .utils import flat_adam_step_many
+
+        loss = self.forward_spkradv(batch, loss, phase=phase, step=False)
+        loss = self.forward_spkrclassifier(batch, loss, phase=phase, step=False)
+        names = ("C", "SPKRADV")  # (the classifier's weight-gradient workgroups, the longer ones, are dispatched first)
+        models = [self.model[k] for k in names]
+        for k in names:
+            self.optimizer[k].zero_grad()
+        for m in models:
+            m.defer_wnorm = True
+        try:
+            for k in ("SPKRADV", "C"):
+                torch.autograd.backward(loss[k], _one_like(loss[k]))
+        finally:
+            for m in models:
+                m.defer_wnorm = False
+            if any(getattr(m, "_wnorm_pending", False) for m in models):
+                ops.nets_wnorm_bwd([n for m in models for n, _ in m._nets])
+            for m in models:
+                m._wnorm_pending = False
+                m._keepalive = []
+        opts = [self.optimizer[k] for k in names]
+        flat_adam_step_many(opts, defer_bump=True)
+        ops.nets_prepare_models([n for m in models for n, _ in m._nets],
+                                [m.flat.data_ptr() + 4 * b for m in models for _, b in m._nets],
+                                [m.version for m in models for _ in m._nets], [o.step_dev for o in opts])
+        return loss
 
     def _main_update(self, batch, loss, phase):
         """The generator-side update of a step; the GAN trainers put theirs in front of it."""
@@ -297,7 +361,7 @@ class VQVAETrainer(BaseTrainer):
         self._discard_grads("C", False)
         return loss
 
-    def forward_spkradv(self, batch, loss, phase="train"):
+    def forward_spkradv(self, batch, loss, phase="train", step=True):
         if not self.conf["use_spkradv_training"]:
             return loss
         enc_h, dec_h, spkrvec = self._cond(batch)
@@ -313,16 +377,16 @@ class VQVAETrainer(BaseTrainer):
         encoded = [e[:, er:] for e in outputs["encoded_unmod"]] if er else outputs["encoded_unmod"]
         with torch.set_grad_enabled(grad_on):
             loss["SPKRADV"] = _scaled(self.conf["alpha"]["ce"], self._spkradv_ce(encoded, batch["org_h"][:, er:], detach=True))
-            if phase == "train":
+            if phase == "train" and step:
                 self.step_model(loss, model="SPKRADV")
         return loss
 
-    def forward_spkrclassifier(self, batch, loss, phase="train"):
+    def forward_spkrclassifier(self, batch, loss, phase="train", step=True):
         if not self.conf["use_spkr_classifier"]:
             return loss
         loss["C_real"] = self._classify_ce(batch["in_feats"], batch["org_h"])
         loss.add("C", self.conf["alpha"]["ce"], loss["C_real"])
-        if phase == "train":
+        if phase == "train" and step:
             self.step_model(loss, model="C")
         return loss
 

@@ -108,6 +108,23 @@ class FlatAdam:
                       self.betas[0], self.betas[1], self.eps, clear_grads=self.clear_grads, defer_bump=defer_bump)
 
 
+def flat_adam_step_many(opts, defer_bump=False):
+    """``opt.step(defer_bump)`` of several FlatAdam optimizers with the same betas / eps as ONE launch
+    (``crk_adam_step_multi``): each model's block with its own lr and step count."""
+    first = opts[0]
+    assert all(type(o) is FlatAdam and o.betas == first.betas and o.eps == first.eps and o.clear_grads == first.clear_grads
+               for o in opts)
+    for o in opts:
+        o.reduce_grads()
+        o._reduced = False
+    ops.adam_step_multi([(o.model.flat.data, o.model.grad_flat, o.exp_avg, o.exp_avg_sq, o.lr_dev, o.step_dev) for o in opts],
+                        first.betas[0], first.betas[1], first.eps, clear_grads=first.clear_grads, defer_bump=defer_bump)
+    for o in opts:
+        if o.clear_grads:
+            o.model.grads_clean = True
+        o.model.touch(by_optimizer=True)
+
+
 class FlatRAdam(FlatAdam):
     """torch_optimizer.RAdam(lr) semantics (crank/net/trainer/utils.py:44-45; defaults betas (0.9, 0.999), eps 1e-8, no
     weight decay) on a FlatModel: one launch, lr and step count on the device like FlatAdam's.  The package is absent from

@@ -334,6 +334,17 @@ def nets_wnorm_bwd(nets):
     check(_lib.lib().crk_nets_wnorm_bwd(len(nets), arr, stream_ptr()), "crk_nets_wnorm_bwd")
 
 
+def nets_prepare_models(nets, param_ptrs, versions, bump_steps=()):
+    """nets_prepare over the stacks of several models: a version per net, every step count of ``bump_steps`` advanced in the
+    same launch."""
+    n = len(nets)
+    arr = (ctypes.c_void_p * n)(*[x.handle for x in nets])
+    par = (ctypes.c_void_p * n)(*param_ptrs)
+    ver = (ctypes.c_ulonglong * n)(*versions)
+    bumps = (ctypes.c_void_p * max(len(bump_steps), 1))(*[ptr(b) for b in bump_steps])
+    check(_lib.lib().crk_nets_prepare_models(n, arr, par, ver, len(bump_steps), bumps, stream_ptr()), "crk_nets_prepare_models")
+
+
 def nets_prepare(nets, param_ptrs, version, bump_step=None):
     """Weight preparation of several stacks (parameter blocks at ``param_ptrs``) in one launch; bump_step: an Adam step
     count (adam_step(..., defer_bump=True)) advanced in the same launch."""
@@ -1147,6 +1158,16 @@ def adam_step(flat, grad, exp_avg, exp_avg_sq, lr_dev, step_dev, beta1=0.9, beta
     check(_lib.lib().crk_adam_step(ptr(flat), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), flat.numel(), ptr(lr_dev),
                                    ptr(step_dev), beta1, beta2, eps, (1 if clear_grads else 0) | (2 if defer_bump else 0),
                                    stream_ptr()), "crk_adam_step")
+
+
+def adam_step_multi(blocks, beta1=0.9, beta2=0.999, eps=1e-8, clear_grads=False, defer_bump=False):
+    """adam_step over several blocks - (flat, grad, exp_avg, exp_avg_sq, lr_dev, step_dev) each - in one launch."""
+    rec = (_lib.AdamBlock * len(blocks))()
+    for r, (flat, grad, m, v, lr_dev, step_dev) in zip(rec, blocks):
+        r.params, r.grads, r.exp_avg, r.exp_avg_sq = ptr(flat), ptr(grad), ptr(m), ptr(v)
+        r.n, r.lr_dev, r.step_dev = flat.numel(), ptr(lr_dev), ptr(step_dev)
+    check(_lib.lib().crk_adam_step_multi(len(blocks), rec, beta1, beta2, eps, (1 if clear_grads else 0) | (2 if defer_bump else 0),
+                                         stream_ptr()), "crk_adam_step_multi")
 
 
 def radam_step(flat, grad, exp_avg, exp_avg_sq, lr_dev, step_dev, beta1=0.9, beta2=0.999, eps=1e-8, clear_grads=False,

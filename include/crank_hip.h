@@ -126,6 +126,13 @@ int crk_seed_next(unsigned long long* state, unsigned long long* out, void* stre
 int crk_nets_wnorm_bwd(int n_nets, void* const* nets, void* stream);
 int crk_nets_prepare(int n_nets, void* const* nets, const float* const* params, unsigned long long version,
                      float* bump_step, void* stream);
+/* Both calls take the nets of SEVERAL models whose updates are adjacent in the step and independent of each other (the
+ * speaker-adversarial net and the speaker classifier): crk_nets_wnorm_bwd then also runs the weight gradients their
+ * CRK_FLAG_DEFER_WNORM backward calls left pending - plain-conv nets defer them like the first conv and head of a gated
+ * stack - as one launch over all of them.  crk_nets_prepare_models: crk_nets_prepare with a version per net (each
+ * model counts its own) and up to 4 step counts, each advanced by one in the preparation launch. */
+int crk_nets_prepare_models(int n_nets, void* const* nets, const float* const* params, const unsigned long long* versions,
+                            int n_bumps, float* const* bump_steps, void* stream);
 
 /* ---- VQ codebook (crank/net/module/vqvae2.py:286-347) --------------------------- */
 /* Quantizer.vq + lookup + straight-through value: idx[n] = argmin_k ||x_n - w_k||^2
@@ -294,6 +301,19 @@ int crk_weighted_sum_bwd(int n, const float* weights, const float* gout, float* 
  * (one launch less per optimizer step). */
 int crk_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n, const float* lr_dev,
                   float* step_dev, float beta1, float beta2, float eps, int clear_grads, void* stream);
+/* crk_adam_step over up to CRK_ADAM_MAX_BLOCKS flat blocks in ONE launch: each block with its own parameters,
+ * gradients, moments, length, device lr and device step count; the arithmetic per element and the clear_grads bits are
+ * crk_adam_step's (bit 1 clear: every step count advances by one, in one launch behind the update).  CRK_ERR_ARG, before
+ * any launch, for a null pointer, a negative length, a step count named twice or more blocks than the record holds. */
+#define CRK_ADAM_MAX_BLOCKS 4
+typedef struct crk_adam_block {
+  float *params, *grads, *exp_avg, *exp_avg_sq;
+  long long n;
+  const float* lr_dev;
+  float* step_dev;
+} crk_adam_block;
+int crk_adam_step_multi(int n_blocks, const crk_adam_block* blocks, float beta1, float beta2, float eps, int clear_grads,
+                        void* stream);
 /* torch_optimizer.RAdam(lr) (crank/net/trainer/utils.py:44-45; the package is absent from the reference tree: its
  * published update, Liu et al. Alg. 2 - betas (0.9, 0.999), eps 1e-8, no weight decay, rectified adaptive update where the
  * approximated SMA length N_sma >= 5, momentum-only update below).  Arguments and clear_grads bits as crk_adam_step;
@@ -686,6 +706,10 @@ long long crk_debug_alloc_count(void);
  * split-operand kernel, bit 2 a discriminator (kind 1) runs channel-split, bit 3 a chain of plain convs (kind 2) runs fused.
  * The fallbacks compute the same values more slowly; tests pin the bits at the benchmark shape. */
 int crk_debug_net_paths(void* net, int B, int T);
+/* The weight-gradient partial sums (per group, before the weight-norm backward reduces them) the last backward of shape
+ * (B, T) left in the handle: returns their count and copies the first min(count, cap) floats to `out` (device memory);
+ * -1: the shape is not reserved.  Tests compare one launch over several nets with the single-net launches on them. */
+long long crk_debug_net_partials(void* net, int B, int T, float* out, long long cap, void* stream);
 
 const char* crk_version(void);
 
