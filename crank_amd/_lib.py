@@ -120,6 +120,7 @@ SIGNATURES = {
     "crk_scaler_workspace_bytes": (LL, [I, I]),
     "crk_scaler_moments": (I, [P, I, I, I, LL, P, P, I, P, LL, P]),
     "crk_scaler_merge": (I, [P, LL, I, I, P, P, P, P, I, P, P, P, P]),
+    "crk_hist_accumulate": (I, [P, LL, P, P, P, P, I, I, P, D, D, D, I, P, P, P]),
     "crk_collate_batch": (I, [ctypes.POINTER(CollateDesc), P, I, I, P, P, P, P, P, P, P, P, P]),
     "crk_decode_f0": (I, [P, P, I, I, P, P, D, D, I, P, P, P, P, P, P]),
     "crk_mcd_scratch_bytes": (LL, [I, I, I, I, I]),

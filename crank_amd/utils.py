@@ -1,5 +1,5 @@
 """Small host-side helpers mirroring crank/utils/utils.py: config loading (:67-84) and the Kaldi-style
-list files of a recipe (:33-64)."""
+list files of a recipe (:33-64); the WAV reader of the command lines."""
 import copy
 import os
 
@@ -70,3 +70,16 @@ def open_scpdir(scpdir):
         scp["spkrs"].append(spkr)
         scp["spk2utt"][spkr] = utts
     return scp
+
+
+def read_wav(path):
+    """(fs, samples) of a one-channel WAV as ``scipy.io.wavfile.read`` returns it, cast to float32 and NOT rescaled: an
+    int16 file comes back as int16-valued floats, which is what the reference analyses (generate_histogram.py:95-96).
+    More than one channel raises ValueError."""
+    import numpy as np
+    from scipy.io import wavfile
+
+    fs, x = wavfile.read(os.fspath(path))
+    if x.ndim != 1:
+        raise ValueError(f"{path}: {x.shape[1]} channels, one is needed")
+    return int(fs), np.array(x, dtype=np.float32)

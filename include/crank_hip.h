@@ -416,6 +416,31 @@ int crk_scaler_merge(const void* workspace, long long workspace_bytes, int U, in
                      const int* group_utts, const long long* group_start_host, const int* group_utts_host, int G,
                      double* mean, double* var, long long* count, void* stream);
 
+/* ---- per-speaker histograms of packed contours (csrc/histogram_kernels.hip) ----
+ * The reduction of the recipe's stage 1, crank/bin/generate_histogram.py:31-74,109-146: plt.hist(np.hstack(f0s),
+ * bins=200, range=(40, 700)) and the same over (-70, 20) for the frame power, per speaker.  The counts are
+ * numpy.histogram(x, bins=bins, range=(first, last)), count for count: a value is kept when first <= x <= last (a NaN
+ * or an infinity never is); its index is int((x - first) * norm), an index equal to bins moves down by one, and the
+ * index is then corrected by one step against the edges, down when x < edges[i], up when x >= edges[i + 1] and
+ * i != bins - 1.  The caller makes edges = linspace(first, last, bins + 1) and norm = bins / (last - first) as numpy
+ * does and uploads the edges (bins + 1 doubles, device memory).  Float64 throughout.
+ *
+ * x: N doubles on the device; utterance u is x[utt_start[u] .. utt_start[u + 1]) and belongs to group utt_group[u].
+ * counts [G, bins] and seen [G, 3] (values, kept, not finite) are device memory and are ADDED to, with integer adds:
+ * the result does not depend on the launch shape, on the order of the utterances or on how a call is split, and a
+ * group without an utterance keeps its row.  One workgroup per utterance and tile of 4096 values, an LDS table of
+ * 32-bit counters, the non-zero bins flushed with 64-bit global adds; 16-byte loads where the tile starts on a 16-byte
+ * boundary, 8-byte loads otherwise.
+ *
+ * The entry never allocates and never synchronises; it can be captured into a graph.  It takes the offsets and the
+ * groups twice: the device copies the kernel reads and host copies that are checked before anything is launched.
+ * CRK_ERR_ARG, with nothing launched: U < 1, G < 1, bins < 1, bins > 4096 (the LDS table next to the staged edges),
+ * !(first < last) or a limit that is not finite, norm not positive, an empty utterance, offsets outside [0, N], a
+ * group outside [0, G). */
+int crk_hist_accumulate(const double* x, long long N, const long long* utt_start, const long long* utt_start_host,
+                        const int* utt_group, const int* utt_group_host, int U, int G, const double* edges, double first,
+                        double last, double norm, int bins, long long* counts, long long* seen, void* stream);
+
 #define CRK_COLLATE_MAX_STREAMS 8
 /* one continuous feature of the batch dict: columns [col0, col0 + ncols) of the packed
  * rows src[F_total, ld] -> dst (B, T, ncols), tail-padded with 0.0 */
