@@ -68,7 +68,7 @@ struct PsTables { PsLayer t[4][PS_MAXL]; int L[4]; PwLayer w[PS_MAXL]; int nw; i
 struct ShapeNeed { long long need_s, need_p; int Gs, Gg, cpg, cpg_s, nseg; };
 // The kernels a net runs at a batch shape in one arithmetic (route_of).  It depends on the net, the shape, the arithmetic and
 // the process-wide switches only, never on a call's pointers, so a backward always reads the plane layout its forward wrote.
-// Every other path computes the same values, only slower.
+// Every other path computes the same values, only slower (tests/test_gpu_per_layer.py, tests/test_gpu_fallback.py).
 struct Route {
   bool fused;       // forward, data-gradient chain and weight gradient on the fused kernels (else one kernel per layer)
   bool gen_split;   // generator, plain bf16: forward and chain channel-split, gate planes in the lane-record layout
@@ -91,6 +91,7 @@ struct Shape {
   int B, T;
   ShapeNeed q;
   Route route[2];                    // [precise]
+  bool pair_fused;                   // a bf16x3f forward / backward pair runs the fused kernels (routes_pair_fused)
   std::vector<ConvEntry> abs;        // the conv entries with absolute partial offsets and slot counts ...
   ConvEntry* d_ents = nullptr;       // ... on the device
   PsTables ps;                       // fused plain-conv chain tables (nets of at most PS_MAXL layers) ...
@@ -138,7 +139,8 @@ struct Net {
   // mode 0 plain bf16, 1 split operands with hi + lo planes (CRK_FLAG_PRECISE), 2 split-operand forward that saved what a
   // PLAIN backward reads (CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN); x3f: the channel-split split-operand forward wrote them.
   // crk_net_backward checks its flags against the tag instead of trusting the caller to pair the two calls.
-  struct FwdTag { const float* saved; int B, T; unsigned char mode; bool x3f; };
+  // fused: the fused kernels wrote them (bf16 planes), not the per-layer ones (fp32 planes only).
+  struct FwdTag { const float* saved; int B, T; unsigned char mode; bool x3f, fused; };
   FwdTag fwd_tags[32]; int fwd_tag_next = 0; int fwd_tag_count = 0;
   std::vector<WgradP> jobs;  // weight-gradient problems queued by the running backward
   WgradP* d_jobs = nullptr;
@@ -701,6 +703,11 @@ static Route route_of(const Net* n, int B, int T, bool precise) {
   }
   return r;
 }
+// bf16x3f (mode 2): the forward runs in split-operand arithmetic and reads the precise route, the backward in plain bf16 and
+// reads the plain one, and the planes they exchange differ between the families - the per-layer forward writes fp32 planes
+// only, the fused backward reads bf16 planes.  Both directions therefore take the fused kernels only where both routes are
+// fused (or the plain route plans the x3f forward, which writes that route's own planes), and the per-layer kernels otherwise.
+static bool routes_pair_fused(const Route rt[2]) { return rt[0].x3f || (rt[0].fused && rt[1].fused); }
 static const Shape* find_shape(const Net* n, int B, int T) {
   for (const Shape& r : n->shapes)
     if (r.B == B && r.T == T) return &r;
@@ -734,9 +741,16 @@ static Call call_facts(int flags, unsigned long long seed, bool forward, const f
   return k;
 }
 
-static void tag_forward(Net* n, const float* saved, int B, int T, const Call& k, bool x3f) {
+// the route a call reads: its arithmetic's, with a bf16x3f pair's choice of family on top
+static Route call_route(const Shape* r, const Call& k) {
+  Route rt = r->route[k.precise];
+  if (k.mode == 2 && !r->pair_fused) rt.fused = rt.usums = false;
+  return rt;
+}
+
+static void tag_forward(Net* n, const float* saved, int B, int T, const Call& k, bool x3f, bool fused) {
   if (!saved || !k.keep) return;
-  const Net::FwdTag tag = {saved, B, T, k.mode, x3f};
+  const Net::FwdTag tag = {saved, B, T, k.mode, x3f, fused};
   for (int i = 0; i < n->fwd_tag_count; i++)
     if (n->fwd_tags[i].saved == saved) { n->fwd_tags[i] = tag; return; }
   n->fwd_tags[n->fwd_tag_next] = tag;
@@ -745,11 +759,16 @@ static void tag_forward(Net* n, const float* saved, int B, int T, const Call& k,
 }
 // CRK_ERR_ARG when the backward's flags do not describe the forward that filled `saved` (an unknown workspace - evicted from
 // the ring, or written through another handle - passes: the caller's pairing is all there is then)
-static int check_forward_tag(const Net* n, const float* saved, int B, int T, int flags, int want, bool expects_x3f) {
+static int check_forward_tag(const Net* n, const float* saved, int B, int T, int flags, int want, bool expects_x3f, bool fused) {
   for (int i = 0; i < n->fwd_tag_count; i++) {
     const Net::FwdTag& t = n->fwd_tags[i];
     if (t.saved != saved) continue;
-    if (t.B == B && t.T == T && t.mode == want && (want != 2 || t.x3f == expects_x3f)) return CRK_OK;
+    if (t.B == B && t.T == T && t.mode == want && (want != 2 || t.x3f == expects_x3f)) {
+      if (t.fused == fused) return CRK_OK;
+      fprintf(stderr, "[crank_hip] crk_net_backward: the %s kernels would read a workspace the %s forward wrote (flags 0x%x, B %d, T %d)\n",
+              fused ? "fused" : "per-layer", t.fused ? "fused" : "per-layer", flags, B, T);
+      return CRK_ERR_ARG;
+    }
     fprintf(stderr, "[crank_hip] crk_net_backward: flags 0x%x (plane layout %d%s, B %d, T %d) do not match the forward that wrote this "
                     "workspace (layout %d%s, B %d, T %d): CRK_FLAG_PRECISE pairs with CRK_FLAG_PRECISE, CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN "
                     "with CRK_FLAG_FWD_PRECISE, plain with plain\n", flags, want, expects_x3f ? " x3f" : "", B, T, t.mode, t.x3f ? " x3f" : "", t.B, t.T);
@@ -931,14 +950,14 @@ extern "C" int crk_net_forward(void* h, const float* params, unsigned long long 
   const Call k = call_facts(flags, seed, true, x, ldx, y, ldy, nullptr, nullptr);
   const Shape* r = find_shape(n, B, T);
   if (!r) return not_reserved("crk_net_forward");
-  const Route& rt = r->route[k.precise];
+  const Route rt = call_route(r, k);
   // bf16x3f: split-operand arithmetic that saves the plain route's planes
   const bool x3f = k.mode == 2 && r->route[0].x3f;
   RUN(ensure_prepared(n, params, version, a.s));
-  tag_forward(n, saved, B, T, k, x3f);
   if (n->d.kind != 2 && (!saved || (n->d.aux_ch > 0 && !c))) return CRK_ERR_ARG;
   int form;
   RUN(fwd_form(n, rt, k, x3f, &form));
+  tag_forward(n, saved, B, T, k, x3f, form != FWD_LAYERS && form != FWD_CHAIN_LAYERS);
   switch (form) {
     case FWD_CHAIN: return fwd_chain(n, r, k, a);
     case FWD_CHAIN_LAYERS: return fwd_chain_layers(n, k, a);
@@ -1062,6 +1081,7 @@ extern "C" int crk_net_reserve(void* h, int B, int T) {
   r.B = B; r.T = T; r.q = shape_need(n, B, T);
   r.route[0] = route_of(n, B, T, false);
   r.route[1] = route_of(n, B, T, true);
+  r.pair_fused = routes_pair_fused(r.route);
   RUN(grow(n, &n->scratch, &n->scratch_cap, r.q.need_s));
   RUN(grow(n, &n->partials, &n->partial_cap, r.q.need_p));
   if (!n->d_jobs && NET_MALLOC(&n->d_jobs, sizeof(WgradP) * 256) != hipSuccess) return CRK_ERR_HIP;
@@ -1085,8 +1105,9 @@ long long crk_count_alloc_(void) { return ++g_net_allocs; }
 // which kernel generation the compute entry points pick for a batch shape (its route): bit 0 the generator stack runs
 // channel-split in plain bf16 (stack2_fwd_kernel / stack2_bwd_kernel), bit 1 its bf16x3f forward runs on the channel-split
 // split-operand kernel (stack2x_fwd_kernel), bit 2 the discriminator's blocks and chain run channel-split, bit 3 the net is a
-// chain of plain convs that runs fused (pstack kernels).  Every fallback computes the same values, only slower: a test pins
-// the bits at the benchmark shape so that a plan that starts failing does not pass as a timing.
+// chain of plain convs that runs fused (pstack kernels).  Every fallback computes the same values, only slower - within what
+// tests/test_gpu_per_layer.py and tests/test_gpu_fallback.py compare, DESIGN.md "What reaches the per-layer kernels": a test
+// pins the bits at the benchmark shape so that a plan that starts failing does not pass as a timing.
 extern "C" int crk_debug_net_paths(void* h, int B, int T) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return -1;
@@ -1455,14 +1476,14 @@ static int net_backward_impl(void* h, unsigned long long version, int flags, uns
   const Shape* r = find_shape(n, a.B, a.T);
   if (!r) return not_reserved("crk_net_backward");
   const Call k = call_facts(flags, seed, false, a.dy, a.lddy, a.dx, a.lddx, a.dc, a.grads);
-  const Route& rt = r->route[k.precise];
+  const Route rt = call_route(r, k);
   if (a.ce && !rt.usums) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_embed)
   if (a.dy_num && !(n->d.kind == 2 && rt.fused)) return CRK_ERR_UNSUPPORTED;  // (crk_net_backward_scaled)
   // CRK_FLAG_FWD_PRECISE: how the forward laid its planes out - unless that forward was the channel-split split-operand one
   // (generator stacks of the bf16x3f mode), which writes the plain route's planes
   const bool expects_x3f = k.mode == 2 && r->route[0].x3f;
   const bool planes_precise = k.precise || (k.mode == 2 && !expects_x3f);
-  RUN(check_forward_tag(n, a.saved, a.B, a.T, flags, k.mode, expects_x3f));
+  RUN(check_forward_tag(n, a.saved, a.B, a.T, flags, k.mode, expects_x3f, rt.fused));
   RUN(flush_pending_wnorm(n, a.s));  // a second backward of this net reuses the partial-sum buffer and the gradient planes
   RUN(ensure_prepared(n, a.params, version, a.s));
   n->jobs.clear();
@@ -1510,7 +1531,10 @@ extern "C" int crk_net_backward_scaled(void* h, const float* params, unsigned lo
 extern "C" int crk_net_embed_grad_supported(void* h, int B, int T, int flags) {
   Net* n = (Net*)h;
   if (!n || B <= 0 || T <= 0) return 0;
-  return route_at(n, B, T, flags & CRK_FLAG_PRECISE).usums ? 1 : 0;  // (a shape that is not reserved: from route_of)
+  // (a shape that is not reserved: from route_of); the backward of a bf16x3f pair: only where the pair runs fused
+  const Route rt[2] = {route_at(n, B, T, false), route_at(n, B, T, true)};
+  if (!(flags & CRK_FLAG_PRECISE) && (flags & CRK_FLAG_FWD_PRECISE) && !routes_pair_fused(rt)) return 0;
+  return rt[(flags & CRK_FLAG_PRECISE) ? 1 : 0].usums ? 1 : 0;
 }
 // crk_net_backward for a conditioning input c = [.. | table[idx[u * run]] | ..] whose columns [c0, c0 + E) are one row of an
 // embedding table per utterance (run == T: every frame of utterance u carries the label idx[u * run]) and whose other

@@ -168,7 +168,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradP* __restrict__ j
     if (a_on && r < WG_FR) {                                                                            \
       const float v[4] = {R.a##u.x * asc, R.a##u.y * asc, R.a##u.z * asc, R.a##u.w * asc};              \
       wg_store_row<PRECISE>(at_hi + r * RA + ca4 * 2, at_lo + r * RA + ca4 * 2, v);                     \
-      bs[0] += v[0]; bs[1] += v[1]; bs[2] += v[2]; bs[3] += v[3];                                       \
+      /* the bias gradient sums what the MFMAs consume: plain bf16 the rounded values (as the fused kernels do) */ \
+      for (int j = 0; j < 4; j++) bs[j] += PRECISE ? v[j] : bf2f(f2bf(v[j]));                           \
     }                                                                                                   \
   }
 #define WG_COMMIT_B(u)                                                                                  \

@@ -28,6 +28,25 @@ def wgrad_one_tap_group(cout, cin, k, dil):
     return k * nit <= 10 * (4 // nctp) and -(-(64 + (k - 1) * dil) // rows_per_pass) <= 11
 
 
+PER_LAYER_LDS_LIMIT = 160 * 1024  # conv_kernels.hip launch_conv
+FUSED_MAX_AUX = 64  # the fused gated kernels' conditioning chunk (stack_fwd_plan, stack_bwd_plan, stack_wgrad_supported)
+
+
+def per_layer_gated_lds_bytes(kernel_size, dilation, aux_channels, precise):
+    """LDS bytes of the per-layer gated forward kernel for one block (conv_kernels.hip conv_fill_lds, MODE_RESFWD): the
+    input tile with its halo, the conditioning tile, one weight chunk and the z tile, each as a hi plane and - in
+    split-operand arithmetic - a lo plane."""
+    def al16(n):
+        return (n + 15) // 16 * 16
+
+    aux_pad = 0 if aux_channels <= 0 else (64 if aux_channels <= 64 else (aux_channels + 15) // 16 * 16)
+    rows = 128 + (kernel_size - 1) * dilation
+    stride = lambda ch: ch * 2 + 16  # noqa: E731
+    one = (al16(rows * stride(64)) + (al16(128 * stride(aux_pad)) if aux_pad else 0) + al16(128 * stride(max(64, aux_pad)))
+           + al16(128 * stride(64)))
+    return (2 if precise else 1) * one
+
+
 def _conv_shapes(kind, cin, cout, layers, stacks, conv_ch):
     """(cout, cin, dilation) of every conv with more than one tap (net.hip crk_net_create)."""
     if kind == KIND_PLAIN:  # dilation = layer index (1 for the first and the last conv)
@@ -60,6 +79,17 @@ class HipStack:
                 raise NotImplementedError(
                     f"a {cin} -> {cout} conv of kernel {kernel_size} at dilation {dil}: its weight gradient would be split "
                     f"into tap groups, which the HIP conv stacks do not compute correctly yet (DESIGN.md)")
+        # A conditioning chunk wider than FUSED_MAX_AUX channels always runs on the per-layer kernels, and there its tiles fit
+        # the LDS in plain bf16 only (aux 65, kernel 5: 164992 bytes with lo planes; aux 128: 214144): such a stack computes in
+        # plain bf16 and refuses the split-operand arithmetics when it is called ("What reaches the per-layer kernels")
+        self.plain_bf16_only = None
+        if kind != KIND_PLAIN and aux_channels > FUSED_MAX_AUX:
+            need = max(per_layer_gated_lds_bytes(kernel_size, dil, aux_channels, True)
+                       for _, _, dil in _conv_shapes(kind, in_channels, out_channels, layers, stacks, conv_channels))
+            if need > PER_LAYER_LDS_LIMIT:
+                self.plain_bf16_only = (f"{aux_channels} conditioning channels: more than {FUSED_MAX_AUX} run on the per-layer "
+                                        f"kernels, whose split-operand tiles need {need} bytes of LDS ({PER_LAYER_LDS_LIMIT} "
+                                        f"available) - plain bf16 only")
         self.net = ops.HipNet(
             kind=kind, in_ch=in_channels, out_ch=out_channels, kernel_size=kernel_size, layers=layers,
             stacks=max(stacks, 1), res_ch=64, gate_ch=128, skip_ch=64, aux_ch=max(aux_channels, 0),
@@ -97,6 +127,8 @@ class HipStack:
 
     def __call__(self, x, c=None, dx_scale=1.0, out=None):
         """x: (B,T,in) channel-last; c: (B,T,aux) or None -> (B,T,out); out = (buffer, column): see ops.net_apply."""
+        if self.plain_bf16_only and ops.get_precision() != "bf16":
+            raise NotImplementedError(f"precision {ops.get_precision()}: {self.plain_bf16_only}")
         return ops.net_apply(self.net, self.owner, self.base, x, c, dx_scale, out=out)
 
     def ce(self, x, target, dx_scale=1.0, ignore_index=-100):

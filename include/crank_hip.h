@@ -43,7 +43,9 @@ extern "C" {
 #define CRK_FLAG_BWD_PLAIN 64    /* forward only, with CRK_FLAG_PRECISE: the backward of this call will run WITHOUT
                                   * CRK_FLAG_PRECISE (and with CRK_FLAG_FWD_PRECISE) - the "bf16x3f" pairing: split-operand
                                   * forward (losses within 1e-3 of the fp32 reference), plain-bf16 backward.  Lets the forward
-                                  * save only what that backward reads, in the layout it reads it */
+                                  * save only what that backward reads, in the layout it reads it.  The pair runs the fused
+                                  * kernels only where the shape's routes of BOTH arithmetics do, else both directions run per
+                                  * layer; a backward whose kernel family is not the forward's is CRK_ERR_ARG */
 
 /* ---- convolutional stacks -----------------------------------------------------
  * Replaces the parallel_wavegan networks the reference instantiates (third-party,
@@ -729,7 +731,8 @@ long long crk_debug_alloc_count(void);
 /* which kernel generation crk_net_forward / crk_net_backward pick for batch shape (B, T): bit 0 a generator stack (kind 0) runs
  * the channel-split kernels in plain bf16, bit 1 its CRK_FLAG_PRECISE | CRK_FLAG_BWD_PLAIN forward runs the channel-split
  * split-operand kernel, bit 2 a discriminator (kind 1) runs channel-split, bit 3 a chain of plain convs (kind 2) runs fused.
- * The fallbacks compute the same values more slowly; tests pin the bits at the benchmark shape. */
+ * The fallbacks compute the same values more slowly, as far as tests/test_gpu_per_layer.py and tests/test_gpu_fallback.py
+ * compare them ("What reaches the per-layer kernels"); tests pin the bits at the benchmark shape. */
 int crk_debug_net_paths(void* net, int B, int T);
 /* The weight-gradient partial sums (per group, before the weight-norm backward reduces them) the last backward of shape
  * (B, T) left in the handle: returns their count and copies the first min(count, cap) floats to `out` (device memory);

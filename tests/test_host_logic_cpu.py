@@ -393,6 +393,38 @@ def test_stack_refuses_kernel_sizes_above_five(kind, cin, cout, k):
         HipStack(kind, cin, cout, k, 6 if kind == 0 else 3, stacks=3 if kind == 0 else 1)
 
 
+def test_stack_with_conditioning_wider_than_64_is_plain_bf16_only(monkeypatch):
+    """A conditioning chunk wider than 64 channels (100 speakers one-hot: 102) runs on the per-layer kernels, whose gated
+    forward needs 164992 (aux 65) to 214144 (aux 128) bytes of LDS with hi + lo planes - the figures launch_conv refused on
+    MI355X - against 160 KB: the stack computes in plain bf16 and refuses bf16x3 / bf16x3f when called ("What
+    reaches the per-layer kernels").  The library handle is replaced: the rule is host logic."""
+    import types
+
+    from crank_amd import ops
+    from crank_amd.net.module import pwg
+
+    assert pwg.per_layer_gated_lds_bytes(5, 1, 65, True) == 164992 and pwg.per_layer_gated_lds_bytes(5, 1, 128, True) == 214144
+    assert pwg.per_layer_gated_lds_bytes(5, 2, 128, False) <= pwg.PER_LAYER_LDS_LIMIT   # plain bf16 fits at every width
+    assert pwg.per_layer_gated_lds_bytes(5, 16, 0, True) <= pwg.PER_LAYER_LDS_LIMIT     # so do dilation 16 / 32 without
+    assert pwg.per_layer_gated_lds_bytes(3, 32, 0, True) <= pwg.PER_LAYER_LDS_LIMIT     # conditioning, in both arithmetics
+    monkeypatch.setattr(ops, "HipNet", lambda **kw: types.SimpleNamespace(n_params=0))
+    monkeypatch.setattr(ops, "net_apply", lambda *a, **k: "ran")
+    wide = [pwg.HipStack(pwg.KIND_GENERATOR, 128, 80, 5, 8, stacks=4, aux_channels=a) for a in (65, 102, 128)]
+    fused = pwg.HipStack(pwg.KIND_GENERATOR, 128, 80, 5, 8, stacks=4, aux_channels=64)
+    assert fused.plain_bf16_only is None
+    try:
+        for mode in ("bf16x3", "bf16x3f"):
+            ops.set_precision(mode)
+            assert fused(None) == "ran"
+            for s in wide:
+                with pytest.raises(NotImplementedError, match=f"precision {mode}: .* conditioning channels: .* plain bf16 only"):
+                    s(None)
+        ops.set_precision("bf16")
+        assert all(s(None) == "ran" for s in wide)
+    finally:
+        ops.set_precision("bf16")
+
+
 
 def test_plain_chain_refuses_depths_and_tap_groups_it_cannot_compute():
     """Plain chains deeper than 8 layers (a 30-layer kernel-5 chain: input gradients 1.5e-2 off in bf16x3) and convs whose
