@@ -644,13 +644,7 @@ int launch_wgrad_table(const WgradP* d_jobs, const std::vector<WgradP>& h_jobs, 
     if (l > lds) lds = l;
     fl += 2.0 * (double)B * T * e.ca * (e.grp_aux ? (double)e.cc : (double)e.cx * e.grp_ntap);
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(152 * 1024, wgrad_kernel<true>, wgrad_kernel<false>)
   dim3 grid(max_groups, (unsigned)h_jobs.size()), block(256);
   prof_begin(3, fl, s);
   if (precise) hipLaunchKernelGGL(wgrad_kernel<true>, grid, block, lds, s, d_jobs, B, T);
@@ -832,11 +826,8 @@ int launch_step_bump(float* const* steps, int n, hipStream_t s) {
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
-// nmax: largest cin * k of the entries (LDS: a band of 32 rows of that length)
-static int wp_set_lds(const void* fn, size_t lds) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-  return CRK_OK;
-}
+// nmax: largest cin * k of the entries (LDS: a band of 32 rows of that length; past the default 64 KB of dynamic LDS the
+// launcher raises its kernel's limit, the first time it meets such a band)
 int launch_weight_prep_multi(const NetRefs& R, int total_entries, int nmax, hipStream_t s) {
   const size_t lds = (size_t)WP_BAND * nmax * 4;
   if (lds > 160 * 1024) return CRK_ERR_UNSUPPORTED;
@@ -844,12 +835,12 @@ int launch_weight_prep_multi(const NetRefs& R, int total_entries, int nmax, hipS
     // a small net (3 - 8 convs of 64 channels): 8-row bands - twice the workgroups, half the rows each wave walks in turn
     // (the kernel is a chain of short phases, 11 us for 40 k parameters; any band that is a multiple of 8 writes the same planes)
     // an 8-row band of a cin * k in (2048, 2560] still needs more than the default 64 KB of dynamic LDS
-    if (wp_set_lds((const void*)weight_prep_multi_kernel<8>, lds / 2) != CRK_OK) return CRK_ERR_HIP;
+    if (lds / 2 > 64 * 1024) CRK_RAISE_LDS_ONCE(160 * 1024, weight_prep_multi_kernel<8>)
     hipLaunchKernelGGL(weight_prep_multi_kernel<8>, dim3(total_entries, 128 / 8), dim3(256), lds / 2, s, R);
     CRK_CHECK_LAUNCH();
     return CRK_OK;
   }
-  if (wp_set_lds((const void*)weight_prep_multi_kernel<WP_BAND>, lds) != CRK_OK) return CRK_ERR_HIP;
+  if (lds > 64 * 1024) CRK_RAISE_LDS_ONCE(160 * 1024, weight_prep_multi_kernel<WP_BAND>)
   hipLaunchKernelGGL(weight_prep_multi_kernel<WP_BAND>, dim3(total_entries, 128 / WP_BAND), dim3(256), lds, s, R);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
@@ -859,7 +850,7 @@ int launch_weight_prep(const ConvEntry* d_entries, int n_entries, int nmax, cons
                        uint16_t* wprep_lo, float* norms, hipStream_t s) {
   const size_t lds = (size_t)WP_BAND * nmax * 4;
   if (lds > 160 * 1024) return CRK_ERR_UNSUPPORTED;
-  if (wp_set_lds((const void*)weight_prep_kernel, lds) != CRK_OK) return CRK_ERR_HIP;
+  if (lds > 64 * 1024) CRK_RAISE_LDS_ONCE(160 * 1024, weight_prep_kernel)
   dim3 grid(n_entries, 128 / WP_BAND), block(256);
   hipLaunchKernelGGL(weight_prep_kernel, grid, block, lds, s, d_entries, params, wprep_hi, wprep_lo, norms);
   CRK_CHECK_LAUNCH();

@@ -20,19 +20,8 @@
 #include "stack_common.h"
 
 #define PS2_MAXS 25  // A fragments of one (layer, tile): taps x kp / 16
-// Phase cycles (tools/ps2_phase_cycles.py, -DPS2_PROF): per workgroup and wave [0] prologue [1] fragment wait + MFMAs
+// Phase cycles (tools/phase_cycles.py ps2, -DSK_PROF=1): per workgroup and wave [0] prologue [1] fragment wait + MFMAs
 // [2] next fragments + epilogue [3] barrier [5] whole kernel
-#ifdef PS2_PROF
-__device__ unsigned long long ps2_prof_buf[512 * 4 * 8];
-__device__ unsigned long long ps2_prof_res[1024 * 2];
-extern "C" int crk_debug_ps2_prof(unsigned long long* out, unsigned long long* res) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ps2_prof_buf), sizeof(unsigned long long) * 512 * 4 * 8) != hipSuccess) return 2;
-  return hipMemcpyFromSymbol(res, HIP_SYMBOL(ps2_prof_res), sizeof(unsigned long long) * 1024 * 2) == hipSuccess ? 0 : 2;
-}
-#define PS2_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); pacc_[i] += t_ - plast_; plast_ = t_; }
-#else
-#define PS2_T(i)
-#endif
 #ifndef PS2_DEPTH
 #define PS2_DEPTH 2  // B fragments are read this many steps ahead of their MFMAs (3 spills)
 #endif
@@ -65,24 +54,6 @@ __device__ __forceinline__ void ps2_mma(f32x16 (&acc)[FT], const bf16x8 (&A)[PS2
   }
 #undef PS2_ADDR
 }
-// a layer record from LDS with every field in scalar registers (uniform branches and addresses, not lane-wise ones; read
-// with scalar loads from the global table instead, a record cost a scalar-cache round trip per layer: +15 %)
-__device__ __forceinline__ int ps2_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long ps2_rfl64(long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffffll));
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ PsLayer ps2_uniform(const PsLayer* src) {
-  const PsLayer y = *src;
-  PsLayer r;
-  r.w_off = ps2_rfl64(y.w_off); r.b_off = ps2_rfl64(y.b_off);
-  r.rows = ps2_rfl(y.rows); r.rows_pad = ps2_rfl(y.rows_pad); r.kp = ps2_rfl(y.kp);
-  r.k = ps2_rfl(y.k); r.dil = ps2_rfl(y.dil); r.off0 = ps2_rfl(y.off0);
-  r.epi = ps2_rfl(y.epi); r.mask_w = ps2_rfl(y.mask_w);
-  r.mask_plane = ps2_rfl64(y.mask_plane); r.save_plane = ps2_rfl64(y.save_plane); r.f_off = ps2_rfl64(y.f_off);
-  return r;
-}
 __host__ __device__ __forceinline__ bool ps2_shape_ok(int k, int nkc) {
   return (k == 5 && (nkc == 1 || nkc == 3 || nkc == 4 || nkc == 5)) || (k == 3 && (nkc == 1 || nkc == 4 || nkc == 8));
 }
@@ -103,11 +74,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
   // would need a waterfall loop per load)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mtw = wave & 1, fh = wave >> 1;
-#ifdef PS2_PROF
-  unsigned long long pacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long pstart_ = __builtin_readcyclecounter(), preal_ = __builtin_amdgcn_s_memrealtime();
-  unsigned long long plast_ = pstart_;
-#endif
+  SK_PROF_BEGIN(1)
   const int b = blockIdx.x / p.tiles_per_utt, tile = blockIdx.x - b * p.tiles_per_utt;
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T, N = (long)p.B * p.T;
@@ -178,7 +145,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
     }
   }
 
-  PS2_T(4)
+  SK_T(4)
   // ---- layer table -> LDS; guard rows of both operand tiles (every other row and every column a layer reads is written
   // by its producer) ----
   {
@@ -196,7 +163,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
       reinterpret_cast<sk_u32x4*>(buf1 + (SK_GUARD + R) * p.os_b)[i] = z4;
     }
   }
-  PS2_T(6)
+  SK_T(6)
   {
     float bv[PS2_BU];
 #pragma unroll
@@ -212,7 +179,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
       bias_s[i] = (Y->b_off >= 0 && (i & 127) < Y->rows) ? p.params[Y->b_off + (i & 127)] : 0.f;
     }
   }
-  PS2_T(7)
+  SK_T(7)
   {
     const __amdgpu_buffer_rsrc_t r_sh0 = sk_rsrc16(p.save_hi ? p.save_hi + p.l0_save_plane : (const uint16_t*)p.x, N * kp0);
     // (a cross-entropy's  upstream gradient / count  folded into the chain's input: crk_net_backward_scaled)
@@ -245,15 +212,15 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
   }
   PS2_LOADA_RANGE(p.l0_f_off, p.l0_k * (p.l0_kp >> 4), mtw, mtw < (p.l0_rows_pad >> 5), PS2_A0, PS2_MAXS)
   __syncthreads();
-  PS2_T(0)
+  SK_T(0)
 
   const int row0 = fh * FT * 32 + l31;  // this lane's frame in the wave's first frame tile
   for (int l = 0; l < p.L; l++) {
-    const PsLayer LY = ps2_uniform(lay_s + l);
+    const PsLayer LY = ps_uniform(lay_s + l);
     const int ntile = LY.rows_pad >> 5, nkc = LY.kp >> 4;
     const bool last = l + 1 == p.L;
     const bool fin = last && !p.tail;  // this layer's output is the chain's fp32 output
-    const PsLayer LN = fin ? LY : ps2_uniform(lay_s + l + 1);
+    const PsLayer LN = fin ? LY : ps_uniform(lay_s + l + 1);
     const unsigned char* oc = (l & 1) ? buf1 : buf0;
     unsigned char* on = (l & 1) ? buf0 : buf1;
     const int osc = (l & 1) ? p.os_b : p.os, osn = (l & 1) ? p.os : p.os_b;
@@ -301,7 +268,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
       }
       // the fragments of this wave's next tile - of this layer, or of the next one - behind the MFMAs that read A
       __builtin_amdgcn_sched_barrier(0);
-      PS2_T(1)
+      SK_T(1)
       if (mt + 2 < ntile) PS2_LOADA(LY.f_off, LY.k * nkc, mt + 2, true)
       else if (!last) { PS2_LOADA(LN.f_off, nsn, mtw, mtw < (LN.rows_pad >> 5)) loaded_next = true; }
 
@@ -384,21 +351,14 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
     }
     // a wave without a tile in this layer (32-channel layers: the odd waves) still needs its fragments of the next one
     if (!loaded_next && !last) PS2_LOADA(LN.f_off, nsn, mtw, mtw < (LN.rows_pad >> 5))
-    PS2_T(2)
+    SK_T(2)
     if (last) break;
     __syncthreads();  // the next operand tile is complete; this layer's reads of the other buffer are done
-    PS2_T(3)
+    SK_T(3)
   }
 #undef PS2_LOADA
 #undef PS2_LOADA_RANGE
-#ifdef PS2_PROF
-  pacc_[5] = __builtin_readcyclecounter() - pstart_;
-  if (blockIdx.x < 512 && lane == 0 && wave < 4) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) ps2_prof_buf[(blockIdx.x * 4 + wave) * 8 + i] = pacc_[i];
-  }
-  if (blockIdx.x < 1024 && tid == 0) { ps2_prof_res[blockIdx.x * 2] = preal_; ps2_prof_res[blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+  SK_PROF_END(1, 5)
 }
 
 int pstack2_plan(PsP& p, const PsLayer* host_layers) {
@@ -447,14 +407,7 @@ int pstack2_plan(PsP& p, const PsLayer* host_layers) {
 }
 
 int launch_pstack2(const PsP& p, double flops, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[4] = {(const void*)pstack2_kernel<2, true>, (const void*)pstack2_kernel<2, false>, (const void*)pstack2_kernel<4, true>,
-                          (const void*)pstack2_kernel<4, false>};
-    for (int i = 0; i < 4; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, pstack2_kernel<2, true>, pstack2_kernel<2, false>, pstack2_kernel<4, true>, pstack2_kernel<4, false>)
   dim3 grid(p.B * p.tiles_per_utt);
   conv_prof_bytes(4, p.algo_bytes);
   conv_prof_begin(4, flops, s);

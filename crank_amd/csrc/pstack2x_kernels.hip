@@ -20,23 +20,6 @@
 #define PS2X_RING 4
 #define PS2X_MAXS 25
 
-__device__ __forceinline__ int ps2x_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long ps2x_rfl64(long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffffll));
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
-  return (long long)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ PsLayer ps2x_uniform(const PsLayer* src) {
-  const PsLayer y = *src;
-  PsLayer r;
-  r.w_off = ps2x_rfl64(y.w_off); r.b_off = ps2x_rfl64(y.b_off);
-  r.rows = ps2x_rfl(y.rows); r.rows_pad = ps2x_rfl(y.rows_pad); r.kp = ps2x_rfl(y.kp);
-  r.k = ps2x_rfl(y.k); r.dil = ps2x_rfl(y.dil); r.off0 = ps2x_rfl(y.off0);
-  r.epi = ps2x_rfl(y.epi); r.mask_w = ps2x_rfl(y.mask_w);
-  r.mask_plane = ps2x_rfl64(y.mask_plane); r.save_plane = ps2x_rfl64(y.save_plane); r.f_off = ps2x_rfl64(y.f_off);
-  return r;
-}
-
 // The (KT taps, NKC k-steps) MFMAs of one output tile over the wave's frame tile.  The ring holds k-steps 0 .. PS2X_RING - 1
 // on entry; a slot is refilled with the pair PS2X_RING steps ahead as soon as its MFMAs are issued.  xb: this lane's hi
 // B-fragment address of (tap 0, k-step 0); lo at xb + lo_delta; tstride = dilation x row stride.
@@ -200,11 +183,11 @@ __global__ __launch_bounds__(NP * 128, 1) void pstack2x_kernel(const PsP p) {
   const bool rin = tfr >= 0 && tfr < p.T;
   const bool rout = rin && row >= p.hl && row < p.hl + p.tmo;
   for (int l = 0; l < p.L; l++) {
-    const PsLayer LY = ps2x_uniform(lay_s + l);
+    const PsLayer LY = ps_uniform(lay_s + l);
     const int ntile = LY.rows_pad >> 5, nkc = LY.kp >> 4;
     const bool last = l + 1 == p.L;
     const bool fin = last && !p.tail;
-    const PsLayer LN = fin ? LY : ps2x_uniform(lay_s + l + 1);
+    const PsLayer LN = fin ? LY : ps_uniform(lay_s + l + 1);
     const unsigned char* oc = (l & 1) ? buf1 : buf0;
     unsigned char* on = (l & 1) ? buf0 : buf1;
     const int osc = (l & 1) ? p.os_b : p.os, osn = (l & 1) ? p.os : p.os_b;
@@ -347,13 +330,7 @@ int pstack2x_plan(PsP& p, const PsLayer* host_layers) {
 }
 
 int launch_pstack2x(const PsP& p, double flops, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)pstack2x_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)pstack2x_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, pstack2x_kernel<4>, pstack2x_kernel<6>)
   dim3 grid(p.B * p.tiles_per_utt);
   conv_prof_bytes(4, p.algo_bytes);
   conv_prof_begin(4, flops, s);

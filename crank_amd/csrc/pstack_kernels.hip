@@ -29,19 +29,8 @@
 #ifndef PS_ABL
 #define PS_ABL 0  // ablation builds (tools/ps_ablate.sh): 1 no MFMA, 2 no plane stores, 4 no weight fragment reads, 8 no operand
 #endif            // fragment reads, 16 no weight chunk traffic after the first chunk
-// Phase cycles (tools/ps_phase_cycles.py, -DPS_PROF): per workgroup and wave [0] prologue [1] tap MFMAs [2] waiting at the
+// Phase cycles (tools/phase_cycles.py ps, -DSK_PROF=1): per workgroup and wave [0] prologue [1] tap MFMAs [2] waiting at the
 // chunk barrier [3] weight commit (incl. waiting for the fetch) [4] epilogue (incl. its barrier) [5] whole kernel
-#ifdef PS_PROF
-__device__ unsigned long long ps_prof_buf[256 * 8 * 8];
-__device__ unsigned long long ps_prof_res[1024 * 2];
-extern "C" int crk_debug_ps_prof(unsigned long long* out, unsigned long long* res) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ps_prof_buf), sizeof(unsigned long long) * 256 * 8 * 8) != hipSuccess) return 2;
-  return hipMemcpyFromSymbol(res, HIP_SYMBOL(ps_prof_res), sizeof(unsigned long long) * 1024 * 2) == hipSuccess ? 0 : 2;
-}
-#define PS_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); pacc_[i] += t_ - plast_; plast_ = t_; }
-#else
-#define PS_T(i)
-#endif
 #define PS_WFRAG(ptr) ((PS_ABL & 4) ? xb : lds_frag(ptr))
 #define PS_XFRAG(ptr) ((PS_ABL & 8) ? x0 : lds_frag(ptr))
 #define PS_MAXP(NT) ((NT) == 512 ? 4 : 8)
@@ -59,11 +48,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
   const int OS = p.os;  // row stride of the operand tile: widest K of the chain as bf16 + 16 B pad (a layer's weight rows: its own kp * 2 + 16)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-#ifdef PS_PROF
-  unsigned long long pacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long pstart_ = __builtin_readcyclecounter(), preal_ = __builtin_amdgcn_s_memrealtime();
-  unsigned long long plast_ = pstart_;
-#endif
+  SK_PROF_BEGIN(1)
   const int b = blockIdx.x / p.tiles_per_utt, tile = blockIdx.x - b * p.tiles_per_utt;
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T, N = (long)p.B * p.T;
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
   int cur = 0;
   f32x16 acc[4];
   __syncthreads();  // table, biases, layer-0 operand, first weight chunk: staged
-  PS_T(0)
+  SK_T(0)
 
   for (int l = 0; l < p.L; l++) {
     const int ntl = LY.rows_pad >> 5, nkc = LY.kp >> 4;
@@ -227,7 +212,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
   for (int c0 = 0; c0 < LY.k; c0 += tpc) {                                                                 \
     const int c1 = c0 + tpc < LY.k ? c0 + tpc : LY.k;                                                      \
     __syncthreads(); /* chunk `cur` committed; previous chunk's reads done; operand tile complete */       \
-    PS_T(2)                                                                                                \
+    SK_T(2)                                                                                                \
     const bool more = c1 < LY.k || !last;                                                                  \
     const int nnext = c1 < LY.k ? (LY.k - c1 < tpc ? LY.k - c1 : tpc) : (tpcn < LN.k ? tpcn : LN.k);       \
     if (!(PS_ABL & 16)) {                                                                                  \
@@ -273,14 +258,14 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
       }                                                                                                    \
     }                                                                                                      \
     if (PRECISE) __syncthreads();                                                                          \
-    PS_T(1)                                                                                                \
+    SK_T(1)                                                                                                \
     __builtin_amdgcn_sched_barrier(0); /* keep the commit (and its wait for the prefetch) behind the MFMAs */ \
     if (more && !(PS_ABL & 16)) {                                                                          \
       if (c1 < LY.k) PS_COMMIT(LY, nnext, WS_HI(PRECISE ? 0 : cur ^ 1))                                    \
       else PS_COMMIT(LN, nnext, WS_HI(PRECISE ? 0 : cur ^ 1))                                              \
     }                                                                                                      \
     if (!PRECISE) cur ^= 1;                                                                                \
-    PS_T(3)                                                                                                \
+    SK_T(3)                                                                                                \
   }
     if (ntl == 2) { PS_TAP_LOOP(2) }
     else if (ntl == 1) { PS_TAP_LOOP(1) }
@@ -332,7 +317,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
             __builtin_amdgcn_raw_buffer_store_b128(fl, r_sl, voff_s + kc * 32, 0, 0);
           }
         }
-      PS_T(4)
+      SK_T(4)
       if (last) break;
       LY = LN;
       tpc = tpcn;
@@ -372,15 +357,8 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void pstack_kernel(const 
         }
     }
   }
-#ifdef PS_PROF
-  PS_T(4)
-  pacc_[5] = __builtin_readcyclecounter() - pstart_;
-  if (blockIdx.x < 256 && lane == 0 && wave < 8) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) ps_prof_buf[(blockIdx.x * 8 + wave) * 8 + i] = pacc_[i];
-  }
-  if (blockIdx.x < 1024 && tid == 0) { ps_prof_res[blockIdx.x * 2] = preal_; ps_prof_res[blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+  SK_T(4)
+  SK_PROF_END(1, 5)
 }
 
 int pstack_plan(PsP& p, const PsLayer* host_layers, bool precise) {
@@ -448,13 +426,7 @@ int pstack_plan(PsP& p, const PsLayer* host_layers, bool precise) {
 }
 
 int launch_pstack(const PsP& p, bool precise, double flops, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[3] = {(const void*)pstack_kernel<true, 4>, (const void*)pstack_kernel<false, 4>, (const void*)pstack_kernel<false, 8>};
-    for (int i = 0; i < 3; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, pstack_kernel<true, 4>, pstack_kernel<false, 4>, pstack_kernel<false, 8>)
   dim3 grid(p.B * p.tiles_per_utt);
   conv_prof_bytes(4, p.algo_bytes);
   conv_prof_begin(4, flops, s);
@@ -477,17 +449,8 @@ int launch_pstack(const PsP& p, bool precise, double flops, hipStream_t s) {
 #define PW_FR 64
 #define PW_SPAN 32
 #define PW_MAXT 8
-// Phase cycles (tools/ps2_phase_cycles.py, -DPW_PROF): per workgroup (first 512 of a launch) and wave [0] set-up
+// Phase cycles (tools/phase_cycles.py pw, -DSK_PROF=2): per workgroup and wave [0] set-up
 // [1] barrier + tiles -> LDS + barrier [2] next requests [3] fragments + MFMAs [4] partial sums out [5] whole kernel
-#ifdef PW_PROF
-__device__ unsigned long long pw_prof_buf[512 * 4 * 8];
-extern "C" int crk_debug_pw_prof(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(pw_prof_buf), sizeof(unsigned long long) * 512 * 4 * 8) == hipSuccess ? 0 : 2;
-}
-#define PW_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); pacc_[i] += t_ - plast_; plast_ = t_; }
-#else
-#define PW_T(i)
-#endif
 
 // MAXT: (tap, cin band, cout band) tiles a wave may hold (accumulators: 16 VGPRs each).  8 covers the classifier's widest
 // conv; the 1x1 convs around a gated stack need 2, and a kernel instantiated for 2 keeps twice the workgroups resident.
@@ -495,11 +458,7 @@ template <bool PRECISE, int MAXT = PW_MAXT, bool SA = false>
 __device__ __forceinline__ void pstack_wgrad_body(const PwP& p, int g, int layer, unsigned char* smem) {
   const PwLayer LY = p.layers[layer];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef PW_PROF
-  unsigned long long pacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long pstart_ = __builtin_readcyclecounter();
-  unsigned long long plast_ = pstart_;
-#endif
+  SK_PROF_BEGIN(2)
   const int wa32 = (LY.wa + 31) & ~31, wb32 = (LY.wb + 31) & ~31;
   const int RA = wa32 * 2 + 64, RB = wb32 * 2 + 64;
   const int span = (LY.k - 1) * LY.dil, brn = PW_FR + span;
@@ -653,25 +612,25 @@ __device__ __forceinline__ void pstack_wgrad_body(const PwP& p, int g, int layer
   }
     PW_FETCH2(sa0, sb0)
     PW_FETCH2(sa1, sb1)
-    PW_T(0)
+    SK_T(0)
     // (an odd run ends with one chunk of zeros: every MFMA of it adds 0)
     for (int c = c_beg; c < c_end; c += 2) {
       __syncthreads();  // previous chunk's fragments consumed (first pass: tiles zeroed)
       PW_COMMIT2(sa0, sb0)
       __syncthreads();
-      PW_T(1)
+      SK_T(1)
       PW_FETCH2(sa0, sb0)
-      PW_T(2)
+      SK_T(2)
       PW_COMPUTE(SA)
-      PW_T(3)
+      SK_T(3)
       __syncthreads();
       PW_COMMIT2(sa1, sb1)
       __syncthreads();
-      PW_T(1)
+      SK_T(1)
       PW_FETCH2(sa1, sb1)
-      PW_T(2)
+      SK_T(2)
       PW_COMPUTE(SA)
-      PW_T(3)
+      SK_T(3)
     }
 #undef PW_FETCH2
 #undef PW_COMMIT2
@@ -725,17 +684,8 @@ __device__ __forceinline__ void pstack_wgrad_body(const PwP& p, int g, int layer
     const int co = wave * 32 + l31;
     if (half == 0 && co < LY.ca) p.partials[LY.pb + (long)g * LY.ca + co] = tot;
   }
-#ifdef PW_PROF
-  PW_T(4)
-  pacc_[5] = __builtin_readcyclecounter() - pstart_;
-  {
-    const int wg = blockIdx.y * gridDim.x + blockIdx.x;
-    if (wg < 512 && lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) pw_prof_buf[(wg * 4 + wave) * 8 + i] = pacc_[i];
-    }
-  }
-#endif
+  SK_T(4)
+  SK_PROF_END(2, 5)
 }
 
 template <bool PRECISE, int MAXT = PW_MAXT>
@@ -796,13 +746,7 @@ int launch_pstack_wgrad_multi(const PwMP& m, int total_blocks, int max_wa, int m
   const int RA = ((max_wa + 31) & ~31) * 2 + 64, RB = ((max_wb + 31) & ~31) * 2 + 64;
   const int lds = PW_FR * RA + (PW_FR + PW_SPAN) * RB;
   if (total_blocks < 1) return CRK_ERR_ARG;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)pstack_wgrad_multi_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)pstack_wgrad_multi_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, pstack_wgrad_multi_kernel<2>, pstack_wgrad_multi_wide_kernel)
   conv_prof_bytes(6, bytes);
   conv_prof_begin(6, flops, s);
   if (max_tiles <= 8) hipLaunchKernelGGL(pstack_wgrad_multi_kernel<2>, dim3(total_blocks), dim3(256), lds, s, m);  // <= 2 per wave
@@ -822,14 +766,8 @@ int pstack_wgrad_supported(int ca, int cb, int wa, int wb, int k, int dil) {
 int launch_pstack_wgrad(const PwP& p, int nlayers, int max_wa, int max_wb, bool precise, double flops, hipStream_t s, int max_tiles) {
   const int RA = ((max_wa + 31) & ~31) * 2 + 64, RB = ((max_wb + 31) & ~31) * 2 + 64;
   const int lds = (precise ? 2 : 1) * (PW_FR * RA + (PW_FR + PW_SPAN) * RB);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[6] = {(const void*)pstack_wgrad_kernel<true>, (const void*)pstack_wgrad_kernel<false>, (const void*)pstack_wgrad_kernel<false, 3>,
-                          (const void*)pstack_wgrad_kernel<false, 4>, (const void*)pstack_wgrad_kernel<false, 5>, (const void*)pstack_wgrad_kernel<false, 6>};
-    for (int i = 0; i < 6; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, pstack_wgrad_kernel<true>, pstack_wgrad_kernel<false>, pstack_wgrad_kernel<false, 3>,
+                     pstack_wgrad_kernel<false, 4>, pstack_wgrad_kernel<false, 5>, pstack_wgrad_kernel<false, 6>)
   dim3 grid(p.G, nlayers);
   conv_prof_bytes(6, 2.0 * (max_wa + max_wb) * (double)p.B * p.T * nlayers);  // upper bound: widest planes per conv
   conv_prof_begin(6, flops, s);

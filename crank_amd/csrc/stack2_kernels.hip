@@ -33,42 +33,14 @@
 #define S2_NCU 256
 #define S2_PAIR_FACTOR 1.0  // measured value goes here
 
-// Phase-cycle instrumentation (tools/s2_phase_cycles.py builds a second library with -DS2_PROF): per workgroup and
+// Phase-cycle instrumentation (tools/phase_cycles.py s2 builds a second library with -DSK_PROF=1): per workgroup and
 // wave the shader cycles spent in [0] taps [1] gate [2] wait at barrier A [3] out|skip 1x1 + state update
 // [4] next operand [5] wait at barrier B, summed over the blocks, [6] prologue (its barrier), [7] whole kernel,
 // [8] prologue: first conv / state [9] tables, biases, guard rows [10] conditioning tile [11] block-0 operand
 // [12] bias / table requests [13] weight, conditioning, input requests [14] input tile -> LDS [15] its barrier.
 // Ablation builds (tools/s2_ablate.sh; timing only, results are wrong): S2_ABL bit 0 no transcendentals, bit 1 no
 // MFMAs, bit 2 no LDS fragment reads, bit 3 no weight loads, bit 4 no barriers in the block loop, bit 5 no out|skip 1x1 phase,
-// bit 6 no gate
-#if defined(S2_ABL) && (S2_ABL & 2)
-#define mfma_bf16(a, b, c) s2_fake_mfma(a, b, c)
-__device__ __forceinline__ f32x16 s2_fake_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  asm volatile("" ::"v"(a), "v"(b));
-  return c;
-}
-#endif
-#if defined(S2_ABL) && (S2_ABL & 4)
-#define lds_frag(p) s2_fake_frag(p)
-__device__ __forceinline__ bf16x8 s2_fake_frag(const unsigned char* p) {
-  const unsigned v = (unsigned)(size_t)p;
-  const sk_u32x4 q = {v, v, v, v};
-  return __builtin_bit_cast(bf16x8, q);
-}
-#endif
-#ifdef S2_PROF
-__device__ unsigned long long s2_prof_buf[256 * 8 * 16];
-__device__ unsigned long long s2_prof_res[1024 * 4];  // per workgroup: start, end (s_memrealtime, 100 MHz), HW_ID, XCC_ID
-extern "C" int crk_debug_s2_prof(unsigned long long* host_out) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(s2_prof_buf), sizeof(unsigned long long) * 256 * 8 * 16) == hipSuccess ? 0 : 2;
-}
-extern "C" int crk_debug_s2_res(unsigned long long* host_out) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(s2_prof_res), sizeof(unsigned long long) * 1024 * 4) == hipSuccess ? 0 : 2;
-}
-#define S2_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc_[i] += now_ - plast_; plast_ = now_; }
-#else
-#define S2_T(i)
-#endif
+// bit 6 no gate (bits 1 and 2: the stand-ins of stack_common.h)
 
 // The body of one wave: FT = the frame tiles THIS wave owns, R = the rows of the workgroup's window, rb = the first row of the
 // wave's frame half.  RULE (uneven windows instantiate this body once per tile count and send the two frame halves into
@@ -87,10 +59,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T;
   const long P = (long)p.B * p.T * 64;
-#ifdef S2_PROF
-  unsigned long long pacc_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, plast_ = __builtin_readcyclecounter();
-  const unsigned long long pstart_ = plast_, preal_ = __builtin_amdgcn_s_memrealtime();
-#endif
+  SK_PROF_BEGIN(1)
 
   unsigned char* xs = smem;             // [SK_GUARD + R + SK_GUARD][XS] block input as the conv sees it
   unsigned char* zs = smem + p.o_zs;    // [R][XS] gate output
@@ -175,7 +144,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
       for (int j = 0; j < 4; j++) av[it][j] = (on && c4 + j < p.aux_ch) ? p.c[n * p.ldc + c4 + j] : 0.f;
     }
   }
-  S2_T(12)
+  SK_T(12)
   // biases: a wave's 64 consecutive entries of [L][256] belong to ONE block and ONE of conv | out | skip, so the table entry
   // comes through the scalar cache (no table-in-LDS -> barrier -> bias chain) and the values follow in one vector load each
   constexpr int NBI = 16 * 256 / NT;  // <= 16 blocks
@@ -214,7 +183,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
 
   // ---- state: residual stream (block-0 input) or zero (skip sum) ----
   f32x16 st[FT];
-  S2_T(13)
+  SK_T(13)
   if (FOLD) {
     // bf16 pieces -> the LDS tile [R][kp_first] the first conv reads its B fragments from, and (window's own frames) the plane
     // its weight gradient reads; then the first conv (1x1, in_ch -> 64): A = its weights (tile mt of the residual waves),
@@ -243,9 +212,9 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
       for (int ft = 0; ft < FT; ft++)
 #pragma unroll
         for (int j = 0; j < 4; j++) st[ft][4 * q + j] = bfq[q][j];
-    S2_T(14)
+    SK_T(14)
     __syncthreads();  // the input tile is complete
-    S2_T(15)
+    SK_T(15)
     if (res_wave) {
       const int KF = p.kp_first >> 4;
       const unsigned char* xb = xf + (rb + l31) * xfs + half * 16;
@@ -275,7 +244,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
       }
   }
 
-  S2_T(8)
+  SK_T(8)
   // ---- layer table, biases (requested at the top), guard rows, conditioning tile ----
 #pragma unroll
   for (int u = 0; u < 2; u++)
@@ -290,7 +259,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
     reinterpret_cast<uint4*>(xs)[i] = z4;
     reinterpret_cast<uint4*>(xs + (SK_GUARD + R) * XS)[i] = z4;
   }
-  S2_T(9)
+  SK_T(9)
   if (AKC > 0) {
 #pragma unroll
     for (int it = 0; it < CPER; it++) {
@@ -306,7 +275,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
     }
   }
 
-  S2_T(10)
+  SK_T(10)
   const float rs = 0.70710678118654752440f;
   const float scale = res_wave ? rs : 1.f;
   // the second-dispatched half of the workgroup loses every arbitration for the SIMD it shares with an older wave
@@ -345,9 +314,9 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
 #pragma unroll
     for (int ft = 0; ft < FT; ft++) S2_PUT_OPERAND_FT(ft)
   }
-  S2_T(11)
+  SK_T(11)
   __syncthreads();  // tables, guard rows, conditioning tile, block-0 operand tile
-  S2_T(6)
+  SK_T(6)
 
   f32x16 acc[FT];
   for (int l = 0; l < p.L; l++) {
@@ -492,7 +461,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
 #undef S2_GATE
 #undef S2_B2ADDR
     }
-    S2_T(0)
+    SK_T(0)
     // the next block's first taps: in flight behind the barrier and the 1x1 (every register set is free now)
     if (l + 1 < p.L) {
       const StackLayer LN = lay_s[l + 1];
@@ -501,11 +470,11 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
 #pragma unroll
         for (int kc = 0; kc < 4; kc++) wa[tp][kc] = S2_WLOAD(LN.f_conv + ((tp * 4 + mt) * 4 + kc) * 512);
     }
-    S2_T(1)
+    SK_T(1)
 #if !(defined(S2_ABL) && (S2_ABL & 16))
     __syncthreads();  // gate-output tile complete; every tap read of the operand tile done
 #endif
-    S2_T(2)
+    SK_T(2)
     // ---- out | skip 1x1 on z, frame tile by frame tile: tile mt of [out 0-31 | out 32-63 | skip 0-31 | skip 32-63];
     // the state update and the next operand of tile ft overlap the MFMAs of tile ft + 1 ----
 #if defined(S2_ABL) && (S2_ABL & 32)
@@ -536,12 +505,12 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
         if (res_wave && l + 1 < p.L) S2_PUT_OPERAND_FT(ft)
       }
     }
-    S2_T(3)
-    S2_T(4)
+    SK_T(3)
+    SK_T(4)
 #if !(defined(S2_ABL) && (S2_ABL & 16))
     __syncthreads();  // next operand tile complete; every read of the gate-output tile done
 #endif
-    S2_T(5)
+    SK_T(5)
   }
 
   if (FOLD) {
@@ -664,20 +633,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
         __builtin_amdgcn_raw_buffer_store_b128(v, r_sk, voff_st[ft] + q * 32, 0, 0);
       }
   }
-#ifdef S2_PROF
-  pacc_[7] = __builtin_readcyclecounter() - pstart_;
-  if (blockIdx.x < 256 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) s2_prof_buf[(blockIdx.x * 8 + wave) * 16 + i] = pacc_[i];
-  }
-  if (blockIdx.x < 1024 && tid == 0) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    s2_prof_res[blockIdx.x * 4 + 0] = preal_; s2_prof_res[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    s2_prof_res[blockIdx.x * 4 + 2] = hwid; s2_prof_res[blockIdx.x * 4 + 3] = xcc;
-  }
-#endif
+  SK_PROF_END(1, 7)
 }
 
 template <int KT, int AKC, int FT, int FH, bool DROP, bool FOLD, int FT1 = FT>
@@ -750,22 +706,12 @@ template <int KT, int AKC, bool DROP, bool FOLD>
 static int s2_launch_shape(const StackP& p, dim3 grid, hipStream_t s) {
 #define S2_GO(FTV, FHV)                                                                                              \
   {                                                                                                                  \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (hipFuncSetAttribute((const void*)stack2_fwd_kernel<KT, AKC, FTV, FHV, DROP, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              160 * 1024) != hipSuccess) return CRK_ERR_HIP;                                         \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
+    CRK_RAISE_LDS_ONCE(160 * 1024, stack2_fwd_kernel<KT, AKC, FTV, FHV, DROP, FOLD>)                                 \
     hipLaunchKernelGGL((stack2_fwd_kernel<KT, AKC, FTV, FHV, DROP, FOLD>), grid, dim3(256 * FHV), p.lds_bytes, s, p);       \
   }
   if (p.ft == 2) S2_GO(2, 2) else if (p.ft1 == 0) S2_GO(3, 2)
   else if constexpr (KT == 3 && !DROP) {  // 160 rows: frame half 0 owns three tiles, frame half 1 two
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)stack2_fwd_kernel<KT, AKC, 3, 2, DROP, FOLD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-      attr = true;
-    }
+    CRK_RAISE_LDS_ONCE(160 * 1024, stack2_fwd_kernel<KT, AKC, 3, 2, DROP, FOLD, 2>)
     hipLaunchKernelGGL((stack2_fwd_kernel<KT, AKC, 3, 2, DROP, FOLD, 2>), grid, dim3(512), p.lds_bytes, s, p);
   } else return CRK_ERR_UNSUPPORTED;
 #undef S2_GO

@@ -28,38 +28,15 @@
 
 #include "stack_common.h"
 
-// Phase-cycle instrumentation (tools/s2b_phase_cycles.py builds a second library with -DS2B_PROF): per workgroup and wave the
+// Phase-cycle instrumentation (tools/phase_cycles.py s2b builds a second library with -DSK_PROF=1): per workgroup and wave the
 // shader cycles in [0] prologue (head) [1] phase 1 (1x1 + gate backward) [2] wait at barrier A [3] taps [4] dX epilogue
 // [5] wait at barrier B [6] first-conv epilogue [7] whole kernel
-#ifdef S2B_PROF
-__device__ unsigned long long s2b_prof_buf[256 * 4 * 12];
-extern "C" int crk_debug_s2b_prof(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(s2b_prof_buf), sizeof(unsigned long long) * 256 * 4 * 12) == hipSuccess ? 0 : 2;
-}
-#define S2B_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc_[i] += now_ - plast_; plast_ = now_; }
-#else
-#define S2B_T(i)
-#endif
 #define S2B_GS 272   // row stride of the dG tile: 128 bf16 + 16 B pad (conflict-free ds_read_b128)
 // Ablation builds (tools/s2b_ablate.sh; timing only, results are wrong): S2B_ABL bit 0 no gate arithmetic, bit 1 no MFMAs,
 // bit 2 no LDS fragment reads, bit 3 no weight loads, bit 4 no gate-plane loads, bit 5 no plane stores (= CRK_S2B_DBG=1)
+// (bits 1 and 2: the stand-ins of stack_common.h)
 #ifndef S2B_ABL
 #define S2B_ABL 0
-#endif
-#if S2B_ABL & 2
-#define mfma_bf16(a, b, c) s2b_fake_mfma(a, b, c)
-__device__ __forceinline__ f32x16 s2b_fake_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  asm volatile("" ::"v"(a), "v"(b));
-  return c;
-}
-#endif
-#if S2B_ABL & 4
-#define lds_frag(p) s2b_fake_frag(p)
-__device__ __forceinline__ bf16x8 s2b_fake_frag(const unsigned char* p) {
-  const unsigned v = (unsigned)(size_t)p;
-  const sk_u32x4 q = {v, v, v, v};
-  return __builtin_bit_cast(bf16x8, q);
-}
 #endif
 
 // FOLD (generator stacks): the head's data gradient in front of the chain (dy -> dS) and the first conv's behind it.
@@ -94,10 +71,7 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
   const long nbase = (long)b * p.T;
   const long N = (long)p.B * p.T, P = N * 64;
 
-#ifdef S2B_PROF
-  unsigned long long pacc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, plast_ = __builtin_readcyclecounter();
-  const unsigned long long pstart_ = plast_;
-#endif
+  SK_PROF_BEGIN(1)
   unsigned char* gs = smem;            // [SK_GUARD + R + SK_GUARD][GS] dG_l (prologue: scratch for the dS exchange)
   unsigned char* xt = smem + p.o_dx;   // [R][XS] sqrt(.5) dX_{l+1} as the 1x1's operand (prologue: G1; epilogue: dX_0)
   unsigned char* dst = xt + R * XS;    // [R][XS] bf16 dS: the other half of the 1x1's operand, the same for every block
@@ -302,7 +276,7 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
 #pragma unroll
     for (int i = 0; i < 16; i++) { dxo[ft][i] = 0.f; if (AUX) accc[ft][i] = 0.f; }
 
-  S2B_T(0)
+  SK_T(0)
   const float rs = 0.70710678118654752440f;
   constexpr int NS2 = KT * 8 + (AUX ? 8 : 0);  // weight fragments of phase 2: taps, then the conditioning 1x1
 
@@ -398,9 +372,9 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
 #undef S2B_DZ
 #undef S2B_GATE
     }
-    S2B_T(1)
+    SK_T(1)
     __syncthreads();  // dG tile complete; every read of the 1x1 operand tile done
-    S2B_T(2)
+    SK_T(2)
     // ---------------- phase 2: transposed dilated conv (+ conditioning gradient) ----------------
     {
 #pragma unroll
@@ -447,14 +421,14 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
           ring[s % S2B_RING] = S2B_FRAG2(n_conv, n_aux, s + S2B_RING - NS2);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef S2B_PROF
-        if (s == 0) S2B_T(8)
-        if (s == 8) S2B_T(9)
-        if (s == 16) S2B_T(10)
+#ifdef SK_PROF
+        if (s == 0) SK_T(8)
+        if (s == 8) SK_T(9)
+        if (s == 16) SK_T(10)
 #endif
       }
 #undef S2B_BREAD
-      S2B_T(3)
+      SK_T(3)
       // Every HBM store of the block is issued here, at the very end: the memory counter retires in order, so a load that is
       // waited for (weight fragments, gate planes) must not have a store in front of it - acknowledged stores take thousands
       // of cycles when all CUs write their planes at once.  The wave's own dG pieces come back from the LDS tile.
@@ -522,9 +496,9 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
         __builtin_amdgcn_raw_buffer_store_b128(gpc[ft][3], r_gh, voff_gb[ft] + colr + pg8 + pg1, 0, 0);
       }
     }
-    S2B_T(4)
+    SK_T(4)
     __syncthreads();  // next 1x1 operand tile complete; every tap read of the dG tile done
-    S2B_T(5)
+    SK_T(5)
     c_conv = n_conv; c_aux = n_aux; c_dil = n_dil; c_off0 = n_off0;
   }
 
@@ -572,14 +546,8 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
       }
     }
   }
-#ifdef S2B_PROF
-  S2B_T(6)
-  pacc_[7] = __builtin_readcyclecounter() - pstart_;
-  if (blockIdx.x < 256 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 12; i++) s2b_prof_buf[(blockIdx.x * 4 + wave) * 12 + i] = pacc_[i];
-  }
-#endif
+  SK_T(6)
+  SK_PROF_END(1, 7)
 }
 
 // four waves, one per SIMD: two frame halves of FT tiles each
@@ -617,12 +585,7 @@ template <int KT, bool AUX, bool FOLD = true>
 static int s2b_launch(const StackBP& p, dim3 grid, hipStream_t s) {
 #define S2B_GO(FTV)                                                                                                  \
   {                                                                                                                  \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (hipFuncSetAttribute((const void*)stack2_bwd_kernel<KT, AUX, FTV, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != \
-          hipSuccess) return CRK_ERR_HIP;                                                                            \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
+    CRK_RAISE_LDS_ONCE(160 * 1024, stack2_bwd_kernel<KT, AUX, FTV, FOLD>)                                            \
     hipLaunchKernelGGL((stack2_bwd_kernel<KT, AUX, FTV, FOLD>), grid, dim3(256), p.lds_bytes, s, p);                 \
   }
   if (p.ft == 2) S2B_GO(2)

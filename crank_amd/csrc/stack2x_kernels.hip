@@ -518,12 +518,7 @@ template <int KT, int AKC>
 static int s2x_launch_shape(const StackP& p, dim3 grid, hipStream_t s) {
 #define S2X_GO(FTV, FT1V)                                                                                            \
   {                                                                                                                  \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (hipFuncSetAttribute((const void*)stack2x_fwd_kernel<KT, AKC, FTV, FT1V>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              160 * 1024) != hipSuccess) return CRK_ERR_HIP;                                         \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
+    CRK_RAISE_LDS_ONCE(160 * 1024, stack2x_fwd_kernel<KT, AKC, FTV, FT1V>)                                           \
     hipLaunchKernelGGL((stack2x_fwd_kernel<KT, AKC, FTV, FT1V>), grid, dim3(512), p.lds_bytes, s, p);                \
   }
   if (p.ft1 == 0) S2X_GO(3, 3)

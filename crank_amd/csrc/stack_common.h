@@ -1,4 +1,5 @@
-// Device helpers shared by the fused stack kernels (stack_kernels.hip, pstack_kernels.hip).
+// Device helpers shared by the fused stack kernels (stack*_kernels.hip, pstack*_kernels.hip), their phase timer and their
+// ablation stand-ins.  Include after conv_kernels.h (PsLayer).
 #ifndef CRK_STACK_COMMON_H
 #define CRK_STACK_COMMON_H
 #include "common.h"
@@ -132,5 +133,98 @@ __device__ __forceinline__ float sw_sum8(bf16x8 f) {
   return s;
 }
 
+// a layer record of the plain chains from LDS with every field in scalar registers (uniform branches and addresses, not
+// lane-wise ones; read with scalar loads from the global table instead, a record cost a scalar-cache round trip per layer:
+// +15 %)
+__device__ __forceinline__ int sk_rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ long long sk_rfl64(long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffffll));
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ PsLayer ps_uniform(const PsLayer* src) {
+  const PsLayer y = *src;
+  PsLayer r;
+  r.w_off = sk_rfl64(y.w_off); r.b_off = sk_rfl64(y.b_off);
+  r.rows = sk_rfl(y.rows); r.rows_pad = sk_rfl(y.rows_pad); r.kp = sk_rfl(y.kp);
+  r.k = sk_rfl(y.k); r.dil = sk_rfl(y.dil); r.off0 = sk_rfl(y.off0);
+  r.epi = sk_rfl(y.epi); r.mask_w = sk_rfl(y.mask_w);
+  r.mask_plane = sk_rfl64(y.mask_plane); r.save_plane = sk_rfl64(y.save_plane); r.f_off = sk_rfl64(y.f_off);
+  return r;
+}
+
+// ---- ablation stand-ins of the channel-split gated kernels (S2_ABL / S2B_ABL builds; timing only, results are wrong):
+// bit 1 no MFMAs, bit 2 no LDS fragment reads.  They replace the names for the kernel file that follows this header only.
+#if (defined(S2_ABL) && (S2_ABL & 2)) || (defined(S2B_ABL) && (S2B_ABL & 2))
+__device__ __forceinline__ f32x16 sk_fake_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
+  asm volatile("" ::"v"(a), "v"(b));
+  return c;
+}
+#define mfma_bf16(a, b, c) sk_fake_mfma(a, b, c)
+#endif
+#if (defined(S2_ABL) && (S2_ABL & 4)) || (defined(S2B_ABL) && (S2B_ABL & 4))
+__device__ __forceinline__ bf16x8 sk_fake_frag(const unsigned char* p) {
+  const unsigned v = (unsigned)(size_t)p;
+  const sk_u32x4 q = {v, v, v, v};
+  return __builtin_bit_cast(bf16x8, q);
+}
+#define lds_frag(p) sk_fake_frag(p)
+#endif
+
+// ---- phase timer of the stack kernels (tools/phase_cycles.py builds ONE kernel file with -DSK_PROF=<n>) ----
+// A timed kernel opens with SK_PROF_BEGIN(n), marks the end of phase i with SK_T(i) - the shader cycles since the previous
+// mark are added to slot i of the wave - and closes with SK_PROF_END(n, total): slot `total` gets the wave's whole life, lane
+// 0 of each of the first SK_PROF_WAVES waves writes the wave's slots, and thread 0 the workgroup's row of sk_prof_res: start
+// and end (s_memrealtime, 100 MHz), HW_ID, XCC_ID.  Workgroup 0 also writes the launch's row behind them: workgroups, waves
+// per workgroup.  n says which kernel of the file is timed (pstack_kernels.hip holds two); the other one's marks are dead
+// code.  Workgroups past the first SK_PROF_WGS of a launch are not recorded.  The buffers belong to the translation unit;
+// crk_debug_sk_prof copies them out and clears them, so what the next call returns was written after this one.
+#ifdef SK_PROF
+#define SK_PROF_WGS 1024
+#define SK_PROF_WAVES 8
+#define SK_PROF_SLOTS 16
+__device__ unsigned long long sk_prof_buf[SK_PROF_WGS * SK_PROF_WAVES * SK_PROF_SLOTS];
+__device__ unsigned long long sk_prof_res[(SK_PROF_WGS + 1) * 4];
+extern "C" int crk_debug_sk_prof(unsigned long long* cycles, unsigned long long* res) {
+  void *dc = nullptr, *dr = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&dc, HIP_SYMBOL(sk_prof_buf)) != hipSuccess ||
+      hipGetSymbolAddress(&dr, HIP_SYMBOL(sk_prof_res)) != hipSuccess ||
+      hipMemcpy(cycles, dc, sizeof(sk_prof_buf), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(res, dr, sizeof(sk_prof_res), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemset(dc, 0, sizeof(sk_prof_buf)) != hipSuccess || hipMemset(dr, 0, sizeof(sk_prof_res)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess)
+    return CRK_ERR_HIP;
+  return CRK_OK;
+}
+#define SK_PROF_BEGIN(n)                                                                        \
+  constexpr bool pon_ = (SK_PROF) == (n);                                                       \
+  unsigned long long pacc_[SK_PROF_SLOTS] = {}, plast_ = __builtin_readcyclecounter();          \
+  const unsigned long long pstart_ = plast_, preal_ = __builtin_amdgcn_s_memrealtime();
+#define SK_T(i) { if (pon_) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc_[i] += now_ - plast_; plast_ = now_; } }
+#define SK_PROF_END(n, total)                                                                   \
+  if (pon_) {                                                                                   \
+    pacc_[total] = __builtin_readcyclecounter() - pstart_;                                      \
+    const unsigned pwg_ = blockIdx.y * gridDim.x + blockIdx.x, pwave_ = threadIdx.x >> 6;       \
+    if (pwg_ < SK_PROF_WGS && (threadIdx.x & 63) == 0 && pwave_ < SK_PROF_WAVES) {              \
+      _Pragma("unroll") for (int i = 0; i < SK_PROF_SLOTS; i++)                                 \
+        sk_prof_buf[(pwg_ * SK_PROF_WAVES + pwave_) * SK_PROF_SLOTS + i] = pacc_[i];            \
+    }                                                                                           \
+    if (pwg_ < SK_PROF_WGS && threadIdx.x == 0) {                                               \
+      unsigned hwid_, xcc_;                                                                     \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid_));                       \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));                       \
+      sk_prof_res[pwg_ * 4 + 0] = preal_; sk_prof_res[pwg_ * 4 + 1] = __builtin_amdgcn_s_memrealtime(); \
+      sk_prof_res[pwg_ * 4 + 2] = hwid_; sk_prof_res[pwg_ * 4 + 3] = xcc_;                      \
+      if (pwg_ == 0) {                                                                          \
+        sk_prof_res[SK_PROF_WGS * 4 + 0] = gridDim.x * gridDim.y;                               \
+        sk_prof_res[SK_PROF_WGS * 4 + 1] = blockDim.x >> 6;                                     \
+      }                                                                                         \
+    }                                                                                           \
+  }
+#else
+#define SK_PROF_BEGIN(n)
+#define SK_T(i)
+#define SK_PROF_END(n, total)
+#endif
 
 #endif

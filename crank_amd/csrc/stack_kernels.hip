@@ -400,16 +400,9 @@ int stack_fwd_plan(StackP& p, bool precise) {
 }
 
 int launch_stack_fwd(const StackP& p, bool precise, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[8] = {(const void*)stack_fwd_kernel<true, true, 4>,  (const void*)stack_fwd_kernel<true, false, 4>,
-                          (const void*)stack_fwd_kernel<false, true, 4>, (const void*)stack_fwd_kernel<false, false, 4>,
-                          (const void*)stack_fwd_kernel<false, true, 6>, (const void*)stack_fwd_kernel<false, false, 6>,
-                          (const void*)stack_fwd_kernel<false, true, 8>, (const void*)stack_fwd_kernel<false, false, 8>};
-    for (int i = 0; i < 8; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, stack_fwd_kernel<true, true, 4>, stack_fwd_kernel<true, false, 4>,
+                     stack_fwd_kernel<false, true, 4>, stack_fwd_kernel<false, false, 4>, stack_fwd_kernel<false, true, 6>,
+                     stack_fwd_kernel<false, false, 6>, stack_fwd_kernel<false, true, 8>, stack_fwd_kernel<false, false, 8>)
   dim3 grid(p.B * p.tiles_per_utt);
   const double nfr = (double)p.B * p.T;
   // algorithmic bytes: block-0 input and conditioning read, skip sum written; saving launches add 4 bf16 planes per block
@@ -445,17 +438,8 @@ int launch_stack_fwd(const StackP& p, bool precise, hipStream_t s) {
 // v_permlane32_swap; dS fragments are built once.  Only dG passes through LDS (the taps need
 // it at shifted frames).  HBM traffic per block: ta, sb read; dG_l, dX_l written (the weight
 // gradient consumes them afterwards) - nothing else.
-// Phase cycles (tools/skb_phase_cycles.py, -DSKB_PROF): per workgroup and wave [0] prologue (folded head) [1] waiting at the
+// Phase cycles (tools/phase_cycles.py skb, -DSK_PROF=1): per workgroup and wave [0] prologue (folded head) [1] waiting at the
 // chunk barriers [2] out|skip 1x1 [3] gate backward [4] taps (+ conditioning 1x1) [5] dX epilogue [6] weight commit [7] kernel
-#ifdef SKB_PROF
-__device__ unsigned long long skb_prof_buf[256 * 8 * 12];
-extern "C" int crk_debug_skb_prof(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(skb_prof_buf), sizeof(unsigned long long) * 256 * 8 * 12) == hipSuccess ? 0 : 2;
-}
-#define SKB_T(i) { const unsigned long long t_ = __builtin_readcyclecounter(); pacc_[i] += t_ - plast_; plast_ = t_; }
-#else
-#define SKB_T(i)
-#endif
 #define SKB_GS 272  // row stride of the dG tile and of a [64][128] weight chunk: 128 bf16 + 16 B pad
 
 __device__ __forceinline__ bf16x8 skb_frag8(const sk_u32x4 a, const sk_u32x4 b, bool lo_plane) {
@@ -473,11 +457,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
   constexpr int NT = NW * 64, R = NW * 32, GS = SKB_GS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-#ifdef SKB_PROF
-  unsigned long long pacc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long pstart_ = __builtin_readcyclecounter();
-  unsigned long long plast_ = pstart_;
-#endif
+  SK_PROF_BEGIN(1)
   const int b = blockIdx.x / p.tiles_per_utt, tile = blockIdx.x - b * p.tiles_per_utt;
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T;
@@ -687,7 +667,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
 #pragma unroll
     for (int i = 0; i < 16; i++) { dxo[h2][i] = 0.f; accc[h2][i] = 0.f; }
   SKB_COMMIT(WS_HI(0))
-  SKB_T(0)
+  SK_T(0)
 
   const float rs = 0.70710678118654752440f;
   int cur = 0;
@@ -711,7 +691,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
   // a branch per kind the register allocator copied whole accumulator sets around every chunk.
 #define SKB_OPEN(has, off_expr)                                                                       \
   __syncthreads(); /* chunk `cur` committed; every read of the previous chunk's operands done */      \
-  SKB_T(1)                                                                                            \
+  SK_T(1)                                                                                            \
   have_next = (has);                                                                                  \
   if (have_next) {                                                                                    \
     const long long off_ = (off_expr);                                                                \
@@ -723,7 +703,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
   __builtin_amdgcn_sched_barrier(0); /* keep the commit (and its wait for the prefetch) behind the MFMAs */ \
   if (have_next) SKB_COMMIT(WS_HI(PRECISE ? 0 : cur ^ 1))                                             \
   if (!PRECISE) cur ^= 1;                                                                             \
-  SKB_T(6)
+  SK_T(6)
 
   StackBLayer LYn = p.layers[p.L - 1];
   for (int l = p.L - 1; l >= 0; l--) {
@@ -746,7 +726,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
         pfs[kc] = __builtin_amdgcn_raw_buffer_load_b128(r_sh, voff_bi + (kc * 32), 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);  // (left alone the scheduler sinks the loads back to their uses)
-      SKB_T(8)
+      SK_T(8)
       // ---- dz = [sqrt(.5) dX_{l+1} | dS] . [Wout ; Wskip]^T ----
 #pragma unroll
       for (int h2 = 0; h2 < 2; h2++)
@@ -784,7 +764,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
           }
           xq[kc] = sk_swap_frag(qh[0], qh[1]);
         }
-        SKB_T(9)
+        SK_T(9)
         bf16x8 wq[3][2];
 #define SKB_W1(buf, st) { const int kc_ = (st) < 4 ? 4 + (st) : (st) - 4; wq[buf][0] = lds_frag(wf_hi + kc_ * 32); wq[buf][1] = lds_frag(wf_hi + 32 * GS + kc_ * 32); }
         SKB_W1(0, 0) SKB_W1(1, 1) SKB_W1(2, 2)
@@ -797,7 +777,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
         }
 #undef SKB_W1
       }
-      SKB_T(2)
+      SK_T(2)
       // ---- gate backward -> dG_l (HBM for the weight gradient, LDS for the taps) ----
       const __amdgpu_buffer_rsrc_t r_tl = sk_rsrc16((PRECISE ? p.tb_lo : p.tb_hi) + (long)l * P, P);
       const __amdgpu_buffer_rsrc_t r_sl = sk_rsrc16((PRECISE ? p.sg_lo : p.sg_hi) + (long)l * P, P);
@@ -869,7 +849,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
       for (int h2 = 0; h2 < 2; h2++)
 #pragma unroll
         for (int i = 0; i < 16; i++) acc[h2][i] = 0.f;
-      SKB_T(3)
+      SK_T(3)
       SKB_CLOSE
     }
 // fast mode: the eight k-steps of a 64 x 128 chunk as a software pipeline, fragments of three steps in
@@ -913,13 +893,13 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
     for (int tp = 0; tp + 1 < p.ktaps; tp++) {
       SKB_OPEN(true, LY.w_conv + (long long)(tp + 1) * 64 * 128)
       SKB_TAP(tp)
-      SKB_T(4)
+      SK_T(4)
       SKB_CLOSE
     }
     {
       SKB_OPEN(has_aux || l > 0, after_taps)
       SKB_TAP(p.ktaps - 1)
-      SKB_T(4)
+      SK_T(4)
       // ---- dX_l = sqrt(.5) dX_{l+1} + mask * convT(dG_l); kept in registers for block l-1 ----
       const __amdgpu_buffer_rsrc_t r_x = sk_rsrc(p.dX0, P);
       const int voff_x0 = (l == 0 && !FOLD) ? voff_out : SK_OOB;  // fp32 only for the stack input (folded: consumed below)
@@ -960,7 +940,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
         if (PRECISE)
           __builtin_amdgcn_raw_buffer_store_b128(sk_frag_bits(sk_swap_frag(ql[0], ql[1])), r_dl, voff_b + (kc * 32), 0, 0);
       }
-      SKB_T(5)
+      SK_T(5)
       SKB_CLOSE
     }
     if (has_aux) {
@@ -978,7 +958,7 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
       } else {
         SKB_PIPE(accc, gf_hi)
       }
-      SKB_T(4)
+      SK_T(4)
       SKB_CLOSE
     }
   }
@@ -1038,14 +1018,8 @@ __global__ __launch_bounds__(NW * 64, PRECISE ? 1 : 2) void stack_bwd_kernel(con
       }
     }
   }
-#ifdef SKB_PROF
-  SKB_T(5)
-  pacc_[7] = __builtin_readcyclecounter() - pstart_;
-  if (blockIdx.x < 256 && lane == 0 && wave < 8) {
-#pragma unroll
-    for (int i = 0; i < 12; i++) skb_prof_buf[(blockIdx.x * 8 + wave) * 12 + i] = pacc_[i];
-  }
-#endif
+  SK_T(5)
+  SK_PROF_END(1, 7)
 }
 
 // waves per workgroup the data-gradient chain will run with (CRK_SK_NW=FB: forward digit F, data-gradient digit B; debugging)
@@ -1074,16 +1048,10 @@ int stack_bwd_plan(StackBP& p, bool precise) {
 }
 
 int launch_stack_bwd(const StackBP& p, bool precise, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[8] = {(const void*)stack_bwd_kernel<true, true, 4>,  (const void*)stack_bwd_kernel<true, false, 4>,
-                          (const void*)stack_bwd_kernel<false, true, 4>, (const void*)stack_bwd_kernel<false, false, 4>,
-                          (const void*)stack_bwd_kernel<false, true, 6>, (const void*)stack_bwd_kernel<false, false, 6>,
-                          (const void*)stack_bwd_kernel<false, true, 8>, (const void*)stack_bwd_kernel<false, false, 8>};
-    for (int i = 0; i < 8; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, stack_bwd_kernel<true, true, 4>, stack_bwd_kernel<true, false, 4>,
+                     stack_bwd_kernel<false, true, 4>, stack_bwd_kernel<false, false, 4>, stack_bwd_kernel<false, true, 6>,
+                     stack_bwd_kernel<false, false, 6>, stack_bwd_kernel<false, true, 8>, stack_bwd_kernel<false, false, 8>,
+                     stack_bwd_kernel<false, false, 8, true>)
   dim3 grid(p.B * p.tiles_per_utt);
   const double nfr = (double)p.B * p.T;
   const bool has_aux = p.dc != nullptr && p.aux_ch > 0;
@@ -1093,15 +1061,8 @@ int launch_stack_bwd(const StackBP& p, bool precise, hipStream_t s) {
   conv_prof_begin(2, 2.0 * nfr * p.L * (64.0 * 128.0 * (1 + p.ktaps) + (has_aux ? 128.0 * p.aux_ch : 0.0)), s);
   const bool drop = p.drop_p > 0.f;
 #define SKB_LAUNCH(PR, DR, NWV) hipLaunchKernelGGL((stack_bwd_kernel<PR, DR, NWV>), grid, dim3(NWV * 64), p.lds_bytes, s, p)
-  if (!precise && !drop && p.nw == 8 && p.dy != nullptr) {
-    static bool attr_f = false;
-    if (!attr_f) {
-      if (hipFuncSetAttribute((const void*)stack_bwd_kernel<false, false, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return CRK_ERR_HIP;
-      attr_f = true;
-    }
+  if (!precise && !drop && p.nw == 8 && p.dy != nullptr)
     hipLaunchKernelGGL((stack_bwd_kernel<false, false, 8, true>), grid, dim3(512), p.lds_bytes, s, p);
-  }
   else if (precise) { if (drop) SKB_LAUNCH(true, true, 4); else SKB_LAUNCH(true, false, 4); }
   else if (p.nw == 4) { if (drop) SKB_LAUNCH(false, true, 4); else SKB_LAUNCH(false, false, 4); }
   else if (p.nw == 6) { if (drop) SKB_LAUNCH(false, true, 6); else SKB_LAUNCH(false, false, 6); }
@@ -1383,14 +1344,8 @@ int launch_stack_wgrad(const StackWP& p, bool precise, hipStream_t s) {
   const int FR = precise ? 32 : 64;
   const int plane = 2 * FR * SW_RA + (FR + SW_SPAN) * SW_RB + 2 * FR * SW_RB;
   const int lds = (precise ? 2 : 1) * plane;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[4] = {(const void*)stack_wgrad_kernel<true, 3>, (const void*)stack_wgrad_kernel<true, 5>,
-                          (const void*)stack_wgrad_kernel<false, 3>, (const void*)stack_wgrad_kernel<false, 5>};
-    for (int i = 0; i < 4; i++)
-      if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return CRK_ERR_HIP;
-    attr_set = true;
-  }
+  CRK_RAISE_LDS_ONCE(160 * 1024, stack_wgrad_kernel<true, 3>, stack_wgrad_kernel<true, 5>, stack_wgrad_kernel<false, 3>,
+                     stack_wgrad_kernel<false, 5>)
   dim3 grid(p.G, p.L);
   const double nfr = (double)p.B * p.T;
   conv_prof_bytes(5, nfr * p.L * (768.0 + (p.cb_hi ? 2.0 * p.aux_pad : 0.0)));  // every plane row once per block

@@ -438,3 +438,34 @@ def test_plain_chain_refuses_depths_and_tap_groups_it_cannot_compute():
     assert one_group(8) and one_group(30) and not one_group(31) and not one_group(3, k=17, cin=128)
     with pytest.raises(NotImplementedError, match="layers=9: plain conv chains are verified up to 8 layers only"):
         HipStack(KIND_PLAIN, 80, 14, 5, 9)
+
+
+def test_phase_cycle_tool_follows_the_makefile_and_the_shared_timer():
+    """tools/phase_cycles.py names only sources the Makefile builds, no kernel names more slots than the shared timer of
+    stack_common.h holds, and no tool but build_variant.sh (which reads SRCS) spells out the library's objects by hand."""
+    import importlib.util
+    import os
+    import re
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("phase_cycles", os.path.join(repo, "tools", "phase_cycles.py"))
+    pc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pc)
+    mk = open(os.path.join(repo, "crank_amd", "csrc", "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*:=\s*(.*)$", mk, re.M).group(1).split()
+    hdr = open(os.path.join(repo, "crank_amd", "csrc", "stack_common.h")).read()
+    shape = {n: int(re.search(r"#define SK_PROF_%s (\d+)" % n, hdr).group(1)) for n in ("WGS", "WAVES", "SLOTS")}
+    assert (pc.WGS, pc.WAVES, pc.SLOTS) == (shape["WGS"], shape["WAVES"], shape["SLOTS"])
+    assert set(pc.KERNELS) == {"s2", "s2b", "skb", "ps", "ps2", "pw"}
+    for key, k in pc.KERNELS.items():
+        assert k["src"] in srcs, (key, k["src"])
+        assert len(k["slots"]) <= pc.SLOTS and k["slots"][k["total"]] == "TOTAL", key
+        assert 1 <= k["waves"] <= pc.WAVES and all(i < len(k["slots"]) for i in k["per_block"]), key
+        assert all(e.startswith("CRK_") for e in k["env"]), key
+    # a hand-written object list: three or more *_kernels names on one line
+    for root, _, files in os.walk(os.path.join(repo, "tools")):
+        for f in files:
+            if f == "build_variant.sh" or not f.endswith((".py", ".sh")):
+                continue
+            for ln in open(os.path.join(root, f), errors="replace"):
+                assert len(set(re.findall(r"\w+_kernels\b", ln))) < 3, (f, ln.strip()[:120])

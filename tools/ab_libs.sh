@@ -6,11 +6,11 @@ cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; mkdir -p gpurun_out; O=$PWD/gpur
 TAG=$1; RE=$2; shift 2
 : > $O/${TAG}_ab.txt
 for rep in 1 2 3; do for lib in "$@"; do
-  CRANK_AMD_LIB=$lib timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --no-roofline > /tmp/ab.log 2>/tmp/ab.err || tail -3 /tmp/ab.err
+  CRANK_AMD_LIB=$lib timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras --no-roofline > /tmp/ab.log 2>/tmp/ab.err || { tail -3 /tmp/ab.err; exit 1; }  # nothing more runs on the card after a failed run
   echo "$(basename $lib) rep=$rep ms_per_step=$(grep '^{' /tmp/ab.log | tail -1 | python -c 'import json,sys;print(round(json.loads(sys.stdin.read())["ms_per_step"],4))')" | tee -a $O/${TAG}_ab.txt
 done; done
 for lib in "$@"; do
-  rm -rf /tmp/abp; CRANK_AMD_LIB=$lib timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/abp -- python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-extras --no-roofline > /tmp/abp.log 2>&1 || tail -3 /tmp/abp.log
+  rm -rf /tmp/abp; CRANK_AMD_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/abp -- python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-extras --no-roofline > /tmp/abp.log 2>&1 || { tail -3 /tmp/abp.log; exit 1; }
   f=$(find /tmp/abp -name "*kernel_trace.csv" | head -1)
   python - "$f" "$(basename $lib)" "$RE" <<'PY' | tee -a $O/${TAG}_ab.txt
 import csv, sys, collections, re

@@ -4,13 +4,10 @@
 # backward per variant from a kernel trace.  Bits: 1 no gate arithmetic, 2 no MFMAs, 4 no LDS fragment reads, 8 no weight
 # loads, 16 no gate-plane loads, 32 no plane stores.  Timing only: the results of an ablated build are wrong.
 REPO=$(cd "$(dirname "$0")/.." && pwd)
-CS=$REPO/crank_amd/csrc
 if [ "$1" = "build" ]; then
   shift
   for n in "$@"; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DS2B_ABL=$n -c $CS/stack2b_kernels.hip -o $CS/stack2b_kernels.abl$n.o || exit 1
-    objs=""; for s in conv_kernels stack_kernels stack2_kernels pstack_kernels pstack2_kernels net vq_kernels loss_kernels mlfb_kernels dataset_kernels mcd_kernels; do objs="$objs $CS/$s.o"; done
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs $CS/stack2b_kernels.abl$n.o -o $REPO/crank_amd/libcrank_hip_s2babl$n.so || exit 1
+    bash $REPO/tools/build_variant.sh s2babl$n stack2b_kernels.hip -DS2B_ABL=$n || exit 1
   done
   exit 0
 fi
