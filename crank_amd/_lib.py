@@ -47,6 +47,15 @@ class AdamBlock(ctypes.Structure):
                 ("n", c_longlong), ("lr_dev", c_void_p), ("step_dev", c_void_p)]
 
 
+class StreamDesc(ctypes.Structure):
+    _fields_ = [
+        ("n_stacks", c_int), ("in_ch", c_int), ("out_ch", c_int), ("emb_dim", c_int * 3), ("emb_size", c_int * 3),
+        ("cb_off", c_longlong * 3), ("enc_base", c_longlong * 3), ("dec_base", c_longlong * 3), ("causal", c_int),
+        ("enc_f0", c_int), ("dec_f0", c_int), ("spk_dim", c_int), ("spk_onehot", c_int), ("n_spk", c_int),
+        ("spk_off", c_longlong),
+    ]
+
+
 P, I, LL, ULL, F, D = c_void_p, c_int, c_longlong, c_ulonglong, c_float, c_double
 
 SIGNATURES = {
@@ -165,6 +174,13 @@ SIGNATURES = {
     "crk_gl_run": (I, [P, P, P, P, P, I, LL, LL, I, I, P, P, LL, P]),
     "crk_gl_stft": (I, [P, P, P, P, I, LL, LL, P, P]),
     "crk_gl_istft": (I, [P, P, P, P, I, LL, LL, P, P, LL, P]),
+    "crk_stream_create": (I, [ctypes.POINTER(StreamDesc), P, P, ctypes.POINTER(c_void_p)]),
+    "crk_stream_destroy": (None, [P]),
+    "crk_stream_reserve": (I, [P, I, I]),
+    "crk_stream_state_bytes": (LL, [P, I]),
+    "crk_stream_prepare": (I, [P, P, ULL, P]),
+    "crk_stream_reset": (I, [P, P, I, P]),
+    "crk_stream_push": (I, [P, P, I, P, I, P, I, P, P, I, I, P, P, P, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

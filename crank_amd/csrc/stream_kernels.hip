@@ -1,0 +1,593 @@
+// Streaming conversion for causal generators (gfx950): ONE launch runs the whole generator forward of
+// crank/net/module/vqvae2.py:160-190 - encoders, "enc[n] + dec", codebook search and lookup, decoders, the last decoder on
+// cat[q_top .. q_0] with its conditioning - for a chunk of new frames of S independent streams, carrying each dilated
+// convolution's history between launches.
+//
+// Decomposition.  With use_causal_conv no frame needs a later one and no stream another stream's data, so workgroup s owns
+// stream s: it walks every layer of every stack with the chunk's activations in LDS (tiles of ST_TILE frames; a longer push
+// is a loop over tiles inside the launch, the state handing one tile's history to the next).  No grid-wide synchronisation.
+//
+// State.  Residual layer l of a stack keeps the last halo_l = (k - 1) * dil_l frames of ITS INPUT, per stream, zero at
+// reset - the left zero padding of the reference's causal convolution (ResidualBlock: padding = (k-1)*dil, output cut to
+// the input's length).  One buffer [stream][layer][frame][64 channels]; a push reads a layer's rows in front of the tile's
+// frames and writes back the last halo_l rows of (old state | the n_valid new frames): a push shorter than the halo shifts.
+//
+// Arithmetic: fp32 throughout, every multiply-add an explicit fmaf, contraction off for the rest of the file.  An output
+// element is bias + one chain of fmaf over (tap, input channel) in ascending order whatever thread, tile or chunk computes
+// it, so a frame's result does not depend on where it sits in a chunk or how long the chunk is, bit for bit.  Weight norm is
+// applied once per parameter version by stream_prepare_kernel into a table of effective fp32 weights laid out
+// [tap][input channel (padded to 4)][output channel]: a thread owns an output channel, its weight loads are coalesced and
+// the frame rows are LDS broadcasts.  (The nets' own prepared tables hold bf16 hi / lo planes in MFMA fragment order: not
+// what an fp32 chain reads.)  The codebook search forms the distance exactly as vq_kernels.hip does - w2 and x2 as
+// d-ordered chains of separately rounded squares, the dot product as a d-ordered fmaf chain, (w2 - 2 dot) + x2, lowest index
+// on equal values - so the indices are crk_vq_forward's on the same rows.
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+#include "common.h"
+#include "../../include/crank_hip.h"
+
+#pragma clang fp contract(off)
+
+long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
+
+#define ST_THREADS 256
+#define ST_TILE 64      // frames resident in LDS
+#define ST_HALO 64      // largest (k - 1) * dilation of a layer
+#define ST_LD 128       // row stride (floats) of the io / conditioning / gate tiles
+#define ST_MAX_STACKS 3
+#define ST_MAX_CHUNK 65536
+
+enum { ST_ROLE_FIRST = 0, ST_ROLE_CONV = 1, ST_ROLE_AUX = 2, ST_ROLE_OUT = 3, ST_ROLE_SKIP = 4, ST_ROLE_LAST1 = 5, ST_ROLE_LAST2 = 6 };
+
+// offsets: w_* into the prepared table, b_* into the model's parameter block (-1: no bias), state_off into a stream's state
+struct StLayer { long long w_conv, w_aux, w_os, b_conv, b_out, b_skip, state_off; int dil, halo; };
+struct StNet {
+  long long w_first, w_last1, w_last2, b_first, b_last1, b_last2;
+  int in_ch, in_pad, out_ch, aux_ch, aux_pad, k, L, layer0;
+  float skip_scale;
+};
+// one conv of the prepare pass: rows [row0, row0 + cout) of the launch; element (r, ci, j) of weight_v goes to
+// table[w_off + (j * cin_pad + ci) * ld + col0 + r]
+struct StPrep { long long off_g, off_v, w_off; int row0, cout, cin, cin_pad, k, ld, col0; };
+
+struct StP {
+  StNet enc[ST_MAX_STACKS], dec[ST_MAX_STACKS];
+  int nst, emb_dim[ST_MAX_STACKS], emb_size[ST_MAX_STACKS];
+  long long cb_off[ST_MAX_STACKS], spk_off, state_stride;
+  int enc_f0, dec_f0, spk_dim, spk_onehot, n_spk;
+  const StLayer* layers;
+  const float* wt;
+  const float* params;
+  float* state;
+  const float* x; int ldx;
+  const float* dcond; int ldd;
+  const float* econd; int lde;
+  const long long* spk;
+  const int* n_valid;
+  int C;
+  float* decoded;
+  long long* qidx[ST_MAX_STACKS];
+  float* encoded[ST_MAX_STACKS];
+};
+
+static inline int st_pad4(int c) { return (c + 3) & ~3; }
+static inline size_t st_lds_bytes() {
+  return sizeof(float) * ((size_t)(ST_HALO + ST_TILE) * 64 + 3 * (size_t)ST_TILE * ST_LD + (size_t)ST_TILE * 64 + 10 * ST_TILE);
+}
+
+// ------------------------------------------------------------------------------------------------------------ prepare
+// One wave per output row: ||v|| from lane-strided partial sums met in a fixed order, w = v * (g / ||v||) as
+// torch._weight_norm forms it, stored transposed.  The padded input channels of the table stay zero from the reserve.
+__global__ __launch_bounds__(64) void stream_prepare_kernel(const StPrep* __restrict__ preps, int nprep,
+                                                            const float* __restrict__ params, float* __restrict__ wt) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  int c = 0;
+  while (c + 1 < nprep && preps[c + 1].row0 <= row) c++;
+  const StPrep q = preps[c];
+  const int r = row - q.row0;
+  if (r >= q.cout) return;
+  const int n = q.cin * q.k;
+  const float* v = params + q.off_v + (long long)r * n;
+  float ss = 0.f;
+  for (int i = lane; i < n; i += 64) ss = fmaf(v[i], v[i], ss);
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float scale = params[q.off_g + r] / sqrtf(ss);
+  for (int i = lane; i < n; i += 64) {
+    const int ci = i / q.k, j = i - ci * q.k;
+    wt[q.w_off + ((long long)j * q.cin_pad + ci) * q.ld + q.col0 + r] = v[i] * scale;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ dense
+// out(f, co) for f < nv, co < cout: the fmaf chain over taps j = 0 .. taps-1 and input channels ci = 0 .. cin_pad-1 of
+// W[j][ci][co] * in[f - (taps - 1 - j) * dil][ci], started at 0, handed to epi(f, co, sum).  A thread owns one output channel
+// and FT consecutive frames; rows past nv inside its run are computed from whatever the tile holds and dropped.  `in` points
+// at frame 0's row; rows in front of it are the layer's history.  No barrier inside.
+template <int FT, class Epi>
+__device__ __forceinline__ void st_dense(const float* __restrict__ W, int cout, int cin_pad, int taps, int dil, const float* in,
+                                         int ldi, int nv, Epi epi) {
+  const int slots = cout <= 16 ? 16 : (cout <= 32 ? 32 : (cout <= 64 ? 64 : 128));
+  const int groups = ST_THREADS / slots;
+  const int co = threadIdx.x & (slots - 1), grp = threadIdx.x / slots;
+  if (co >= cout) return;
+  for (int f0 = grp * FT; f0 < nv; f0 += groups * FT) {
+    float acc[FT];
+#pragma unroll
+    for (int i = 0; i < FT; i++) acc[i] = 0.f;
+    for (int j = 0; j < taps; j++) {
+      const float* inj = in + (f0 - (taps - 1 - j) * dil) * ldi;
+      const float* wj = W + (size_t)j * cin_pad * cout + co;
+#pragma unroll 2
+      for (int ci = 0; ci < cin_pad; ci += 4) {
+        const float w0 = wj[(size_t)ci * cout], w1 = wj[(size_t)(ci + 1) * cout], w2 = wj[(size_t)(ci + 2) * cout],
+                    w3 = wj[(size_t)(ci + 3) * cout];
+#pragma unroll
+        for (int i = 0; i < FT; i++) {
+          const f32x4 xv = *reinterpret_cast<const f32x4*>(inj + i * ldi + ci);
+          acc[i] = fmaf(w0, xv[0], acc[i]);
+          acc[i] = fmaf(w1, xv[1], acc[i]);
+          acc[i] = fmaf(w2, xv[2], acc[i]);
+          acc[i] = fmaf(w3, xv[3], acc[i]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < FT; i++)
+      if (f0 + i < nv) epi(f0 + i, co, acc[i]);
+  }
+}
+
+struct StLds { float *xw, *g, *skip, *cond, *io, *red_d, *x2s; int *red_i, *idxs; };
+
+// One PWG generator stack (oracle/pwg.py ParallelWaveGANGenerator.forward, use_causal_conv) on nv frames: `in` (row stride
+// ST_LD, n.in_pad columns) -> m.io (n.out_ch columns).  cond: the conditioning rows (n.aux_pad columns) when n.aux_ch > 0.
+template <int FT>
+__device__ void st_net(const StP& p, const StNet& n, int s, const float* in, int nv, const StLds& m) {
+  const float* P = p.params;
+  const float* W = p.wt;
+  const int tid = threadIdx.x;
+  float* xc = m.xw + ST_HALO * 64;  // frame 0 of the residual stream; the layer's history sits in the rows in front of it
+  float* g = m.g;
+  float* skip = m.skip;
+  st_dense<FT>(W + n.w_first, 64, n.in_pad, 1, 1, in, ST_LD, nv,
+               [&](int f, int co, float a) { xc[f * 64 + co] = P[n.b_first + co] + a; });
+  for (int i = tid; i < nv * 64; i += ST_THREADS) skip[i] = 0.f;
+  __syncthreads();
+  for (int l = 0; l < n.L; l++) {
+    const StLayer y = p.layers[n.layer0 + l];
+    float* st = p.state + (long long)s * p.state_stride + y.state_off;
+    const int hl = y.halo * 64;
+    for (int i = tid; i < hl; i += ST_THREADS) xc[i - hl] = st[i];
+    __syncthreads();
+    st_dense<FT>(W + y.w_conv, 128, 64, n.k, y.dil, xc, 64, nv,
+                 [&](int f, int co, float a) { g[f * ST_LD + co] = (y.b_conv >= 0 ? P[y.b_conv + co] : 0.f) + a; });
+    if (n.aux_ch > 0)  // (the same thread owns (f, co) in both calls)
+      st_dense<FT>(W + y.w_aux, 128, n.aux_pad, 1, 1, m.cond, ST_LD, nv,
+                   [&](int f, int co, float a) { g[f * ST_LD + co] += a; });
+    // the layer's next history: the last halo rows of (old state | the nv new frames)
+    for (int i = tid; i < hl; i += ST_THREADS) st[i] = xc[nv * 64 - hl + i];
+    __syncthreads();
+    for (int i = tid; i < nv * 64; i += ST_THREADS) {
+      const int f = i >> 6, c = i & 63;
+      const float a = g[f * ST_LD + c], b = g[f * ST_LD + 64 + c];
+      g[f * ST_LD + c] = tanhf(a) * (1.f / (1.f + expf(-b)));
+    }
+    __syncthreads();
+    // [out | skip] as one 128-wide conv of z: residual (out + x) * sqrt(.5), skip sum
+    st_dense<FT>(W + y.w_os, 128, 64, 1, 1, g, ST_LD, nv, [&](int f, int co, float a) {
+      if (co < 64)
+        xc[f * 64 + co] = (((y.b_out >= 0 ? P[y.b_out + co] : 0.f) + a) + xc[f * 64 + co]) * 0.70710678118654752440f;
+      else
+        skip[f * 64 + co - 64] += (y.b_skip >= 0 ? P[y.b_skip + co - 64] : 0.f) + a;
+    });
+    __syncthreads();
+  }
+  for (int i = tid; i < nv * 64; i += ST_THREADS) g[(i >> 6) * ST_LD + (i & 63)] = fmaxf(skip[i] * n.skip_scale, 0.f);
+  __syncthreads();
+  st_dense<FT>(W + n.w_last1, 64, 64, 1, 1, g, ST_LD, nv,
+               [&](int f, int co, float a) { skip[f * 64 + co] = fmaxf(P[n.b_last1 + co] + a, 0.f); });
+  __syncthreads();
+  st_dense<FT>(W + n.w_last2, n.out_ch, 64, 1, 1, skip, 64, nv,
+               [&](int f, int co, float a) { m.io[f * ST_LD + co] = P[n.b_last2 + co] + a; });
+  __syncthreads();
+}
+
+// one term of a squared norm, the product rounded on its own: the chain of vq_kernels.hip (vq_sq_acc)
+__device__ __forceinline__ float st_sq_acc(float acc, float e) {
+  const float sq = e * e;
+  return acc + sq;
+}
+
+// Nearest code of the nv rows xs (row stride ST_LD) in cb [K][D]: a thread owns a code (its row in registers), the frames
+// pass by as LDS broadcasts, a wave meets per frame under the (distance, then index) order, the four waves through LDS.
+template <int D>
+__device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int nv, const StLds& m) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < nv) {
+    float x2 = 0.f;
+    for (int d = 0; d < D; d++) x2 = st_sq_acc(x2, xs[tid * ST_LD + d]);
+    m.x2s[tid] = x2;
+  }
+  __syncthreads();
+  for (int k0 = 0; k0 < K; k0 += ST_THREADS) {
+    const int k = k0 + tid;
+    const bool live = k < K;
+    float w[D];
+    const float* wp = cb + (size_t)(live ? k : 0) * D;
+#pragma unroll
+    for (int d = 0; d < D; d += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(wp + d);
+      w[d] = v[0]; w[d + 1] = v[1]; w[d + 2] = v[2]; w[d + 3] = v[3];
+    }
+    float w2 = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; d++) w2 = st_sq_acc(w2, w[d]);
+    for (int f = 0; f < nv; f++) {
+      const float* xr = xs + f * ST_LD;
+      float dot = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; d += 4) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + d);
+        dot = fmaf(xv[0], w[d], dot);
+        dot = fmaf(xv[1], w[d + 1], dot);
+        dot = fmaf(xv[2], w[d + 2], dot);
+        dot = fmaf(xv[3], w[d + 3], dot);
+      }
+      const float dist = (w2 - 2.f * dot) + m.x2s[f];
+      const bool ok = live && dist < INFINITY;  // (a NaN or an infinite distance never wins: the row then takes code 0)
+      float bd = ok ? dist : INFINITY;
+      int bi = ok ? k : 0x7fffffff;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(bd, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+      }
+      if (lane == 0) {
+        const int slot = wave * ST_TILE + f;
+        if (k0 == 0 || bd < m.red_d[slot] || (bd == m.red_d[slot] && bi < m.red_i[slot])) { m.red_d[slot] = bd; m.red_i[slot] = bi; }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < nv) {
+    float bd = m.red_d[tid];
+    int bi = m.red_i[tid];
+    for (int wv = 1; wv < ST_THREADS / 64; wv++) {
+      const float od = m.red_d[wv * ST_TILE + tid];
+      const int oi = m.red_i[wv * ST_TILE + tid];
+      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+    }
+    m.idxs[tid] = bi == 0x7fffffff ? 0 : bi;
+  }
+  __syncthreads();
+}
+
+// frames [r0, r0 + nv) of stream s (rows of the caller's (S, C, .) tensors): vqvae2.py:160-190
+template <int FT>
+__device__ void st_tile(const StP& p, int s, long long r0, int nv, const StLds& m) {
+  const int tid = threadIdx.x;
+  const float* P = p.params;
+  {
+    const int ip = p.enc[0].in_pad, ic = p.enc[0].in_ch;
+    for (int i = tid; i < nv * ip; i += ST_THREADS) {
+      const int f = i / ip, c = i - f * ip;
+      m.io[f * ST_LD + c] = c < ic ? p.x[(r0 + f) * p.ldx + c] : 0.f;
+    }
+    if (p.enc_f0)
+      for (int i = tid; i < nv * 4; i += ST_THREADS) {
+        const int f = i >> 2, c = i & 3;
+        m.cond[f * ST_LD + c] = c < 2 ? p.econd[(r0 + f) * p.lde + c] : 0.f;
+      }
+  }
+  __syncthreads();
+  for (int n = 0; n < p.nst; n++) {
+    st_net<FT>(p, p.enc[n], s, m.io, nv, m);
+    const int D = p.emb_dim[n];
+    for (int i = tid; i < nv * D; i += ST_THREADS) {
+      const int f = i / D, c = i - f * D;
+      p.encoded[n][(r0 + f) * D + c] = m.io[f * ST_LD + c];
+    }
+    __syncthreads();
+  }
+  // the quantized rows side by side in m.cond, top stack first: the last decoder's input
+  int col = 0;
+  for (int n = p.nst - 1; n >= 0; n--) {
+    const int D = p.emb_dim[n];
+    for (int i = tid; i < nv * D; i += ST_THREADS) {
+      const int f = i / D, c = i - f * D;
+      float v = p.encoded[n][(r0 + f) * D + c];
+      if (n != p.nst - 1) v = v + m.io[f * ST_LD + c];  // enc[n] + dec (the top stack adds the integer 0)
+      p.encoded[n][(r0 + f) * D + c] = v;
+      m.g[f * ST_LD + c] = v;
+    }
+    __syncthreads();
+    const float* cb = P + p.cb_off[n];
+    if (D == 64) st_vq<64>(cb, p.emb_size[n], m.g, nv, m);
+    else if (D == 32) st_vq<32>(cb, p.emb_size[n], m.g, nv, m);
+    else if (D == 16) st_vq<16>(cb, p.emb_size[n], m.g, nv, m);
+    else st_vq<128>(cb, p.emb_size[n], m.g, nv, m);
+    for (int i = tid; i < nv * D; i += ST_THREADS) {
+      const int f = i / D, c = i - f * D;
+      const float e = cb[(size_t)m.idxs[f] * D + c], x = m.g[f * ST_LD + c];
+      m.cond[f * ST_LD + col + c] = x + (e - x);  // the straight-through value, two roundings like the reference
+    }
+    if (tid < nv) p.qidx[n][r0 + tid] = (long long)m.idxs[tid];
+    __syncthreads();
+    if (n != 0) st_net<FT>(p, p.dec[n], s, m.cond + col, nv, m);
+    col += D;
+  }
+  for (int i = tid; i < nv * col; i += ST_THREADS) {
+    const int f = i / col, c = i - f * col;
+    m.io[f * ST_LD + c] = m.cond[f * ST_LD + c];
+  }
+  __syncthreads();
+  {
+    const int ap = p.dec[0].aux_pad;
+    long long spk = p.spk[s];
+    spk = spk < 0 ? 0 : (spk >= p.n_spk ? p.n_spk - 1 : spk);
+    for (int i = tid; i < nv * ap; i += ST_THREADS) {
+      const int f = i / ap, c = i - f * ap, e = c - p.dec_f0;
+      float v = 0.f;
+      if (c < p.dec_f0) v = p.dcond[(r0 + f) * p.ldd + c];
+      else if (e < p.spk_dim) v = p.spk_onehot ? (e == (int)spk ? 1.f : 0.f) : P[p.spk_off + spk * p.spk_dim + e];
+      m.cond[f * ST_LD + c] = v;
+    }
+  }
+  __syncthreads();
+  st_net<FT>(p, p.dec[0], s, m.io, nv, m);
+  const int oc = p.dec[0].out_ch;
+  for (int i = tid; i < nv * oc; i += ST_THREADS) {
+    const int f = i / oc, c = i - f * oc;
+    p.decoded[(r0 + f) * oc + c] = m.io[f * ST_LD + c];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(ST_THREADS) void stream_push_kernel(const StP p) {
+  extern __shared__ __attribute__((aligned(16))) float st_lds[];
+  StLds m;
+  m.xw = st_lds;
+  m.g = m.xw + (ST_HALO + ST_TILE) * 64;
+  m.skip = m.g + ST_TILE * ST_LD;
+  m.cond = m.skip + ST_TILE * 64;
+  m.io = m.cond + ST_TILE * ST_LD;
+  m.red_d = m.io + ST_TILE * ST_LD;
+  m.red_i = reinterpret_cast<int*>(m.red_d + 4 * ST_TILE);
+  m.x2s = m.red_d + 8 * ST_TILE;
+  m.idxs = reinterpret_cast<int*>(m.red_d + 9 * ST_TILE);
+  const int s = blockIdx.x;
+  int total = p.n_valid ? p.n_valid[s] : p.C;
+  total = min(max(total, 0), p.C);
+  for (int t0 = 0; t0 < total; t0 += ST_TILE) {
+    const int nv = min(ST_TILE, total - t0);
+    const long long r0 = (long long)s * p.C + t0;
+    // (two run lengths of the same per-element chains: a short tile does not pay for eight frames per thread)
+    if (nv > 8) st_tile<8>(p, s, r0, nv, m);
+    else st_tile<2>(p, s, r0, nv, m);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+struct StreamH {
+  StP p;
+  std::vector<StLayer> layers;
+  std::vector<StPrep> preps;
+  long long wt_floats = 0, state_floats = 0;
+  int rows = 0, S = 0, Cmax = 0;
+  float *wt = nullptr, *state = nullptr;
+  StLayer* d_layers = nullptr;
+  StPrep* d_preps = nullptr;
+  bool prepared = false;
+};
+
+static int st_malloc(void** q, size_t bytes) {
+  if (hipMalloc(q, bytes) != hipSuccess) return CRK_ERR_HIP;
+  crk_count_alloc_();
+  return CRK_OK;
+}
+
+// the conv table of one stack (crk_net_conv_info) as this family's tables; CRK_ERR_UNSUPPORTED for what the kernel does not take
+static int st_add_net(StreamH* h, void* net, long long base, int in_ch, int out_ch, int aux_ch, StNet* out) {
+  if (!net || in_ch < 1 || in_ch > 128 || out_ch < 1 || out_ch > 128 || aux_ch < 0 || aux_ch > 128) return CRK_ERR_UNSUPPORTED;
+  StNet n;
+  memset(&n, 0, sizeof(n));
+  n.in_ch = in_ch; n.in_pad = st_pad4(in_ch); n.out_ch = out_ch; n.aux_ch = aux_ch; n.aux_pad = st_pad4(aux_ch);
+  n.layer0 = (int)h->layers.size();
+  auto table = [&](int cout, int cin, int k) {
+    const long long o = h->wt_floats;
+    h->wt_floats += (long long)k * st_pad4(cin) * cout;
+    return o;
+  };
+  auto prep = [&](const long long* c, long long w_off, int ld, int col0) {
+    StPrep q;
+    q.off_g = base + c[4]; q.off_v = base + c[5]; q.w_off = w_off; q.row0 = h->rows; q.cout = (int)c[0]; q.cin = (int)c[1];
+    q.cin_pad = st_pad4(q.cin); q.k = (int)c[2]; q.ld = ld; q.col0 = col0;
+    h->rows += q.cout;
+    h->preps.push_back(q);
+  };
+  auto bias = [&](const long long* c) { return c[3] >= 0 ? base + c[3] : -1ll; };
+  const int count = crk_net_conv_count(net);
+  bool first = false, last1 = false, last2 = false;
+  for (int i = 0; i < count; i++) {
+    long long c[9];
+    if (crk_net_conv_info(net, i, c) != CRK_OK) return CRK_ERR_ARG;
+    const int cout = (int)c[0], cin = (int)c[1], k = (int)c[2], dil = (int)c[6], role = (int)c[7], layer = (int)c[8];
+    if (role == ST_ROLE_CONV) {
+      if (layer != (int)h->layers.size() - n.layer0 || cout != 128 || cin != 64 || k < 1 || k > 5 || (k - 1) * dil > ST_HALO)
+        return CRK_ERR_UNSUPPORTED;
+      StLayer y;
+      memset(&y, 0, sizeof(y));
+      y.dil = dil; y.halo = (k - 1) * dil; y.state_off = h->state_floats; h->state_floats += (long long)y.halo * 64;
+      y.w_conv = table(128, 64, k); y.b_conv = bias(c); y.w_aux = -1; y.w_os = -1;
+      prep(c, y.w_conv, 128, 0);
+      n.k = k;
+      h->layers.push_back(y);
+      continue;
+    }
+    if (role == ST_ROLE_AUX || role == ST_ROLE_OUT || role == ST_ROLE_SKIP) {
+      if (h->layers.empty() || layer != (int)h->layers.size() - n.layer0 - 1 || k != 1) return CRK_ERR_UNSUPPORTED;
+      StLayer& y = h->layers.back();
+      if (role == ST_ROLE_AUX) {
+        if (cout != 128 || cin != aux_ch) return CRK_ERR_UNSUPPORTED;
+        y.w_aux = table(128, cin, 1);
+        prep(c, y.w_aux, 128, 0);
+      } else {
+        if (cout != 64 || cin != 64) return CRK_ERR_UNSUPPORTED;
+        if (y.w_os < 0) y.w_os = table(128, 64, 1);
+        (role == ST_ROLE_OUT ? y.b_out : y.b_skip) = bias(c);
+        prep(c, y.w_os, 128, role == ST_ROLE_OUT ? 0 : 64);
+      }
+      continue;
+    }
+    if (k != 1 || c[3] < 0) return CRK_ERR_UNSUPPORTED;
+    if (role == ST_ROLE_FIRST && cout == 64 && cin == in_ch) {
+      n.w_first = table(64, cin, 1); n.b_first = bias(c); prep(c, n.w_first, 64, 0); first = true;
+    } else if (role == ST_ROLE_LAST1 && cout == 64 && cin == 64) {
+      n.w_last1 = table(64, 64, 1); n.b_last1 = bias(c); prep(c, n.w_last1, 64, 0); last1 = true;
+    } else if (role == ST_ROLE_LAST2 && cout == out_ch && cin == 64) {
+      n.w_last2 = table(cout, 64, 1); n.b_last2 = bias(c); prep(c, n.w_last2, cout, 0); last2 = true;
+    } else {
+      return CRK_ERR_UNSUPPORTED;
+    }
+  }
+  n.L = (int)h->layers.size() - n.layer0;
+  if (!first || !last1 || !last2 || n.L < 1) return CRK_ERR_UNSUPPORTED;
+  for (int l = 0; l < n.L; l++) {
+    const StLayer& y = h->layers[n.layer0 + l];
+    if (y.w_os < 0 || (aux_ch > 0) != (y.w_aux >= 0)) return CRK_ERR_UNSUPPORTED;
+  }
+  n.skip_scale = (float)sqrt(1.0 / n.L);
+  *out = n;
+  return CRK_OK;
+}
+
+extern "C" int crk_stream_create(const crk_stream_desc* desc_, void* const* enc_nets, void* const* dec_nets, void** handle) {
+  if (!desc_ || !enc_nets || !dec_nets || !handle) return CRK_ERR_ARG;
+  *handle = nullptr;
+  const crk_stream_desc& d = *desc_;
+  if (d.n_stacks < 1 || d.n_stacks > ST_MAX_STACKS || !d.causal) return CRK_ERR_UNSUPPORTED;
+  int qsum = 0;
+  for (int n = 0; n < d.n_stacks; n++) {
+    const int D = d.emb_dim[n];
+    if ((D != 16 && D != 32 && D != 64 && D != 128) || d.emb_size[n] < 1 || d.cb_off[n] < 0) return CRK_ERR_UNSUPPORTED;
+    qsum += D;
+  }
+  const int d_aux = (d.dec_f0 ? 2 : 0) + d.spk_dim;
+  if (qsum > 128 || d.spk_dim < 0 || d_aux > 128 || d.n_spk < 1 || (d.spk_onehot && d.spk_dim != d.n_spk) ||
+      (!d.spk_onehot && d.spk_dim > 0 && d.spk_off < 0))
+    return CRK_ERR_UNSUPPORTED;
+  StreamH* h = new StreamH();
+  memset(&h->p, 0, sizeof(h->p));
+  StP& p = h->p;
+  p.nst = d.n_stacks; p.enc_f0 = d.enc_f0 ? 1 : 0; p.dec_f0 = d.dec_f0 ? 2 : 0; p.spk_dim = d.spk_dim;
+  p.spk_onehot = d.spk_onehot ? 1 : 0; p.n_spk = d.n_spk; p.spk_off = d.spk_off;
+  int rc = CRK_OK;
+  for (int n = 0; n < d.n_stacks && rc == CRK_OK; n++) {
+    p.emb_dim[n] = d.emb_dim[n]; p.emb_size[n] = d.emb_size[n]; p.cb_off[n] = d.cb_off[n];
+    rc = st_add_net(h, enc_nets[n], d.enc_base[n], n == 0 ? d.in_ch : d.emb_dim[n - 1], d.emb_dim[n],
+                    n == 0 && d.enc_f0 ? 2 : 0, &p.enc[n]);
+    if (rc == CRK_OK)
+      rc = st_add_net(h, dec_nets[n], d.dec_base[n], n == 0 ? qsum : d.emb_dim[n], n == 0 ? d.out_ch : d.emb_dim[n - 1],
+                      n == 0 ? d_aux : 0, &p.dec[n]);
+  }
+  if (rc != CRK_OK) { delete h; return rc; }
+  p.state_stride = h->state_floats;
+  *handle = h;
+  return CRK_OK;
+}
+
+extern "C" void crk_stream_destroy(void* hh) {
+  StreamH* h = (StreamH*)hh;
+  if (!h) return;
+  (void)hipFree(h->wt); (void)hipFree(h->state); (void)hipFree(h->d_layers); (void)hipFree(h->d_preps);
+  delete h;
+}
+
+extern "C" long long crk_stream_state_bytes(void* hh, int S) {
+  StreamH* h = (StreamH*)hh;
+  return (!h || S < 0) ? -1 : (long long)S * h->state_floats * 4;
+}
+
+extern "C" int crk_stream_reserve(void* hh, int S, int C_max) {
+  StreamH* h = (StreamH*)hh;
+  if (!h) return CRK_ERR_ARG;
+  if (S < 1 || C_max < 1 || C_max > ST_MAX_CHUNK) return CRK_ERR_UNSUPPORTED;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute((const void*)stream_push_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st_lds_bytes()) !=
+        hipSuccess)
+      return CRK_ERR_HIP;
+    attr_set = true;
+  }
+  if (!h->wt) {
+    int rc = st_malloc((void**)&h->wt, sizeof(float) * h->wt_floats);
+    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_layers, sizeof(StLayer) * h->layers.size());
+    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_preps, sizeof(StPrep) * h->preps.size());
+    if (rc != CRK_OK) return rc;
+    if (hipMemset(h->wt, 0, sizeof(float) * h->wt_floats) != hipSuccess ||
+        hipMemcpy(h->d_layers, h->layers.data(), sizeof(StLayer) * h->layers.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->d_preps, h->preps.data(), sizeof(StPrep) * h->preps.size(), hipMemcpyHostToDevice) != hipSuccess)
+      return CRK_ERR_HIP;
+    h->p.wt = h->wt; h->p.layers = h->d_layers;
+  }
+  if (S > h->S) {  // more streams: a new, zeroed state (every stream starts over)
+    float* st = nullptr;
+    const int rc = st_malloc((void**)&st, sizeof(float) * h->state_floats * S);
+    if (rc != CRK_OK) return rc;
+    if (hipMemset(st, 0, sizeof(float) * h->state_floats * S) != hipSuccess) { (void)hipFree(st); return CRK_ERR_HIP; }
+    (void)hipFree(h->state);
+    h->state = st; h->p.state = st; h->S = S;
+  }
+  if (C_max > h->Cmax) h->Cmax = C_max;
+  return CRK_OK;
+}
+
+extern "C" int crk_stream_prepare(void* hh, const float* params, unsigned long long version, void* stream) {
+  StreamH* h = (StreamH*)hh;
+  (void)version;  // (the caller's bookkeeping: one call per parameter version)
+  if (!h || !params || !h->wt) return CRK_ERR_ARG;
+  hipLaunchKernelGGL(stream_prepare_kernel, dim3(h->rows), dim3(64), 0, (hipStream_t)stream, h->d_preps, (int)h->preps.size(),
+                     params, h->wt);
+  CRK_CHECK_LAUNCH();
+  h->p.params = params;
+  h->prepared = true;
+  return CRK_OK;
+}
+
+extern "C" int crk_stream_reset(void* hh, const int* stream_ids, int n, void* stream) {
+  StreamH* h = (StreamH*)hh;
+  if (!h || !h->state || n < 0) return CRK_ERR_ARG;
+  const size_t one = sizeof(float) * h->state_floats;
+  if (!stream_ids)
+    return hipMemsetAsync(h->state, 0, one * h->S, (hipStream_t)stream) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
+  for (int i = 0; i < n; i++)
+    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
+  for (int i = 0; i < n; i++)
+    if (hipMemsetAsync(h->state + (size_t)stream_ids[i] * h->state_floats, 0, one, (hipStream_t)stream) != hipSuccess)
+      return CRK_ERR_HIP;
+  return CRK_OK;
+}
+
+extern "C" int crk_stream_push(void* hh, const float* x, int ldx, const float* dec_cond, int ldd, const float* enc_cond, int lde,
+                               const long long* spk, const int* n_valid, int S, int C, float* decoded,
+                               long long* const* qidx, float* const* encoded, void* stream) {
+  StreamH* h = (StreamH*)hh;
+  if (!h) return CRK_ERR_ARG;
+  if (S < 1 || S > h->S || C < 1 || C > h->Cmax) return CRK_ERR_UNSUPPORTED;
+  if (!h->prepared || !x || !spk || !decoded || !qidx || !encoded || ldx < h->p.enc[0].in_ch) return CRK_ERR_ARG;
+  if ((h->p.dec_f0 && (!dec_cond || ldd < 2)) || (h->p.enc_f0 && (!enc_cond || lde < 2))) return CRK_ERR_ARG;
+  StP p = h->p;
+  for (int n = 0; n < p.nst; n++) {
+    if (!qidx[n] || !encoded[n]) return CRK_ERR_ARG;
+    p.qidx[n] = qidx[n]; p.encoded[n] = encoded[n];
+  }
+  p.x = x; p.ldx = ldx; p.dcond = dec_cond; p.ldd = ldd; p.econd = enc_cond; p.lde = lde; p.spk = spk; p.n_valid = n_valid;
+  p.C = C; p.decoded = decoded;
+  hipLaunchKernelGGL(stream_push_kernel, dim3(S), dim3(ST_THREADS), st_lds_bytes(), (hipStream_t)stream, p);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}

@@ -1,0 +1,176 @@
+"""Streaming conversion with a causal generator on the MI355X: ``VQVAE2.forward`` (encoders, quantizers, decoders, no
+EMA update) for chunks of new frames of many concurrent streams, one launch per push (csrc/stream_kernels.hip,
+``crk_stream_*``).
+
+A generator trained with ``causal: true`` computes frame t from input frames <= t, so conversion can follow a speaker who
+is still talking.  ``StreamingConverter`` keeps, per stream and per residual layer, the last ``(kernel_size - 1) *
+dilation`` frames of that layer's input on the device and computes only the new frames of a push.  The outputs do not
+depend on how an utterance is cut into pushes - bit for bit - and equal the offline forward within fp32 rounding
+(the kernels are fp32 throughout; ``CRANK_AMD_PRECISION`` does not apply).  There is no torch or CPU fallback.
+
+What stays with the caller: the acoustic front end that produces the scaled input features, the F0 conversion
+(``BaseTrainer._decode_f0`` / ``crk_decode_f0`` work frame by frame, so they apply to a chunk as they do to an utterance),
+and waveform synthesis.
+"""
+import ctypes
+
+import torch
+
+from crank_amd import _lib
+from crank_amd._lib import StreamDesc, check, stream_ptr
+from crank_amd._ragged import made, release, require_gpu
+
+MAX_STACKS = 3
+MAX_CHANNELS = 128      # inputs, outputs, conditioning and the last decoder's concatenated input (stream_kernels.hip)
+MAX_KERNEL_SIZE = 5     # as net/module/pwg.py
+MAX_HALO = 64           # (kernel_size - 1) * dilation of a layer: the rows in front of a tile in LDS
+VQ_DIMS = (16, 32, 64, 128)  # as net/module/vqvae2.py
+
+
+def receptive_chain(conf):
+    """Frames of context in front of a frame that the generator's output depends on: the sum over the encoder and decoder
+    stacks of (kernel_size - 1) * sum of dilations (132 for the default shapes: 48 + 18 + 18 + 48)."""
+    total = 0
+    for n in range(conf["n_vq_stacks"]):
+        dil = sum(2 ** (i % conf["n_layers"][n]) for i in range(conf["n_layers"][n] * conf["n_layers_stacks"][n]))
+        total += 2 * (conf["kernel_size"][n] - 1) * dil
+    return total
+
+
+def check_stream_conf(conf, spkr_size):
+    """Refuse what cannot be streamed, naming the configuration key.  Touches neither the library nor the device."""
+    if not conf["causal"]:
+        raise NotImplementedError(
+            f"causal = {conf['causal']}: only a generator built with causal: true can be streamed - this one's output at "
+            f"frame t needs {receptive_chain(conf) // 2} frames after t (its stacks look as far ahead as behind)")
+    if conf["use_raw"]:
+        raise NotImplementedError("use_raw = true: the on-the-fly log-mel layer is not streamed; feed scaled features")
+    nst = conf["n_vq_stacks"]
+    if not 1 <= nst <= MAX_STACKS:
+        raise NotImplementedError(f"n_vq_stacks = {nst}: the streaming kernel takes 1 .. {MAX_STACKS}")
+    for n in range(nst):
+        if conf["emb_dim"][n] not in VQ_DIMS:
+            raise NotImplementedError(f"emb_dim[{n}] = {conf['emb_dim'][n]}: the streaming kernel supports emb_dim in {VQ_DIMS}")
+        k = conf["kernel_size"][n]
+        if not 1 <= k <= MAX_KERNEL_SIZE:
+            raise NotImplementedError(f"kernel_size[{n}] = {k}: the streaming kernel takes 1 .. {MAX_KERNEL_SIZE}")
+        halo = (k - 1) * 2 ** (conf["n_layers"][n] - 1)
+        if halo > MAX_HALO:
+            raise NotImplementedError(f"n_layers[{n}] = {conf['n_layers'][n]} with kernel_size[{n}] = {k}: a layer would keep "
+                                      f"{halo} frames of history, above the {MAX_HALO} the streaming kernel holds")
+    d_aux = (2 if conf["decoder_f0"] else 0) + (conf["spkr_embedding_size"] if conf["use_spkr_embedding"] else spkr_size)
+    for key, ch in (("input_size", conf["input_size"]), ("output_size", conf["output_size"]),
+                    ("emb_dim", sum(conf["emb_dim"][:nst])),
+                    ("spkr_embedding_size" if conf["use_spkr_embedding"] else "use_spkr_embedding", d_aux)):
+        if not 1 <= ch <= MAX_CHANNELS:
+            raise NotImplementedError(f"{key}: {ch} channels (for emb_dim: their sum; for the speaker key: the last decoder's "
+                                      f"conditioning), the streaming kernel takes 1 .. {MAX_CHANNELS}")
+    if spkr_size < 1:
+        raise NotImplementedError(f"spkr_size = {spkr_size}: the last decoder is conditioned on a speaker")
+
+
+class StreamingConverter:
+    """``push`` runs generator ``G`` (a ``VQVAE2`` with ``causal: true``) on the next frames of up to ``n_streams``
+    independent streams, at most ``max_chunk`` frames each per push.  Stream i is row i of every argument."""
+
+    def __init__(self, G, n_streams, max_chunk, device="cuda"):
+        conf = G.conf
+        check_stream_conf(conf, G.spkr_size)
+        if n_streams < 1 or max_chunk < 1:
+            raise ValueError(f"n_streams = {n_streams}, max_chunk = {max_chunk}: both must be at least 1")
+        self.device = torch.device(device)
+        require_gpu(self.device, "streaming conversion", "the converter's device")
+        self.G, self.conf, self.n_streams, self.max_chunk = G, conf, int(n_streams), int(max_chunk)
+        self.nst = nst = conf["n_vq_stacks"]
+        self.dims = [conf["emb_dim"][n] for n in range(nst)]
+        d = StreamDesc()
+        d.n_stacks, d.in_ch, d.out_ch = nst, conf["input_size"], conf["output_size"]
+        for n in range(nst):
+            d.emb_dim[n], d.emb_size[n] = conf["emb_dim"][n], conf["emb_size"][n]
+            d.cb_off[n] = G.quantizers[n].cb_offset
+            d.enc_base[n], d.dec_base[n] = G.encoders[n].base, G.decoders[n].base
+        d.causal, d.enc_f0, d.dec_f0 = 1, int(bool(conf["encoder_f0"])), int(bool(conf["decoder_f0"]))
+        d.spk_onehot = int(not conf["use_spkr_embedding"])
+        d.spk_dim = conf["spkr_embedding_size"] if conf["use_spkr_embedding"] else G.spkr_size
+        d.n_spk = G.spkr_size
+        d.spk_off = G.emb_offset if conf["use_spkr_embedding"] else 0
+        nets = ctypes.c_void_p * nst
+        enc = nets(*[G.encoders[n].net.handle for n in range(nst)])
+        dec = nets(*[G.decoders[n].net.handle for n in range(nst)])
+        h = ctypes.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            check(L.crk_stream_create(ctypes.byref(d), enc, dec, ctypes.byref(h)), "crk_stream_create")
+            self._handle = made(h, "crk_stream_create")
+            check(L.crk_stream_reserve(self._handle, self.n_streams, self.max_chunk), "crk_stream_reserve")
+        self._prepared = None
+        self._ptrs = ctypes.c_void_p * nst
+
+    def __del__(self):
+        release(self, "_handle", "crk_stream_destroy")
+
+    @property
+    def state_bytes(self):
+        return int(_lib.lib().crk_stream_state_bytes(self._handle, self.n_streams))
+
+    def _prepare(self):
+        """Effective weights for the generator's current parameters; again after any parameter or codebook write."""
+        G = self.G
+        key = (G.version, G.codebook_epoch, G.flat.data_ptr())
+        if key != self._prepared:
+            check(_lib.lib().crk_stream_prepare(self._handle, G.flat.data_ptr(), G.version, stream_ptr()), "crk_stream_prepare")
+            self._prepared = key
+
+    def reset(self, streams=None):
+        """Zero the carried history of ``streams`` (all of them by default): their next frame is an utterance's first."""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            if streams is None:
+                check(L.crk_stream_reset(self._handle, None, 0, stream_ptr()), "crk_stream_reset")
+            else:
+                ids = [int(s) for s in streams]
+                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
+                check(L.crk_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_stream_reset")
+
+    def empty_outputs(self, S, C):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
+        dev = self.device
+        return {"decoded": torch.empty(S, C, self.conf["output_size"], device=dev),
+                "qidx": [torch.empty(S, C, dtype=torch.int64, device=dev) for _ in range(self.nst)],
+                "encoded": [torch.empty(S, C, D, device=dev) for D in self.dims]}
+
+    def _f32(self, t, S, C, last, what):
+        if t is None:
+            raise ValueError(f"{what} is required by this configuration")
+        if t.device.type != "cuda" or t.dtype != torch.float32 or tuple(t.shape) != (S, C, last):
+            raise ValueError(f"{what}: a float32 ({S}, {C}, {last}) tensor on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    def push(self, feats, lcf0, uv, spkr, n_valid=None, enc_lcf0_uv=None, out=None):
+        """feats (S, C, input_size) scaled features, lcf0 / uv (S, C, 1) the scaled (already converted) F0 contour and the
+        voicing flags, spkr (S,) int64 target speakers, n_valid (S,) frames that count per stream (default: C),
+        enc_lcf0_uv (S, C, 2) the encoder's conditioning when ``encoder_f0``.  Returns ``decoded`` (S, C, output_size),
+        ``qidx`` [(S, C) int64 per stack, bottom first] and ``encoded`` [(S, C, emb_dim) per stack: the quantizer's input] -
+        the keys of ``VQVAE2.make_dict``.  Rows at and past ``n_valid`` are not written.  out: buffers to write into
+        (``empty_outputs``), e.g. the static ones of a captured graph."""
+        S, C = int(feats.shape[0]), int(feats.shape[1])
+        conf = self.conf
+        feats = self._f32(feats, S, C, conf["input_size"], "feats")
+        dcond = None
+        if conf["decoder_f0"]:
+            dcond = torch.cat([self._f32(lcf0, S, C, 1, "lcf0"), self._f32(uv, S, C, 1, "uv")], dim=-1)
+        econd = self._f32(enc_lcf0_uv, S, C, 2, "enc_lcf0_uv") if conf["encoder_f0"] else None
+        if spkr.device.type != "cuda" or spkr.dtype != torch.int64 or tuple(spkr.shape) != (S,):
+            raise ValueError(f"spkr: an int64 ({S},) tensor on the GPU, got {spkr.dtype} {tuple(spkr.shape)} on {spkr.device}")
+        if n_valid is not None:
+            if n_valid.device.type != "cuda" or tuple(n_valid.shape) != (S,):
+                raise ValueError(f"n_valid: an integer ({S},) tensor on the GPU")
+            n_valid = n_valid.to(torch.int32).contiguous()
+        out = self.empty_outputs(S, C) if out is None else out
+        with torch.cuda.device(self.device):
+            self._prepare()
+            check(_lib.lib().crk_stream_push(
+                self._handle, feats.data_ptr(), feats.shape[-1], _lib.ptr(dcond), 2, _lib.ptr(econd), 2, spkr.data_ptr(),
+                _lib.ptr(n_valid), S, C, out["decoded"].data_ptr(), self._ptrs(*[t.data_ptr() for t in out["qidx"]]),
+                self._ptrs(*[t.data_ptr() for t in out["encoded"]]), stream_ptr()), "crk_stream_push")
+        return out

@@ -725,6 +725,48 @@ int crk_gl_istft(void* gl, const double* spec, const long long* frame_offsets, c
                  long long total_frames, long long total_samples, double* y, void* workspace, long long workspace_bytes,
                  void* stream);
 
+/* ---- streaming conversion for causal generators (csrc/stream_kernels.hip) ----
+ * The generator forward of crank/net/module/vqvae2.py:160-190 (encoders, "enc[n] + dec", codebook search and lookup, decoders,
+ * the last decoder on cat[q_top .. q_0] with cat[lcf0, uv, speaker embedding or one-hot code]) for a chunk of C new frames of S
+ * independent streams in ONE launch, one workgroup per stream, fp32.  use_causal_conv only: every residual layer keeps the
+ * last (k - 1) * dilation frames of its input per stream (zero after a reset) in the handle's state buffer
+ * [stream][layer][frame][64 channels]; a frame's result does not depend on how the utterance is cut into pushes, bit for bit.
+ * No EMA update.  The codebook indices are crk_vq_forward's on the same rows.
+ *
+ * crk_stream_create reads the conv tables of the model's existing stack handles (crk_net_conv_info); offsets in the
+ * descriptor are element offsets into the model's flat fp32 parameter block.  CRK_ERR_UNSUPPORTED: not causal, n_stacks
+ * outside 1..3, emb_dim not 16/32/64/128, more than 128 channels anywhere (inputs, outputs, conditioning, sum of emb_dim),
+ * kernel size above 5, (k - 1) * dilation above 64.
+ * crk_stream_reserve is the only call that allocates (weight table, state, layer tables; it synchronises): S streams, pushes
+ * of at most C_max frames (any C_max >= 1; the kernel walks a push in tiles of 64 frames).  Asking for more streams than
+ * before replaces the state by a zeroed one.  crk_stream_state_bytes: the size of the state of S streams.
+ * crk_stream_prepare: effective weights g * v / ||v|| of every conv for the parameters at `params`, once per parameter
+ * version; `params` (biases, codebooks, the speaker table are read from it by every push) must stay valid.
+ * crk_stream_reset: zeroes the state of the n streams listed in the HOST array stream_ids (NULL: every stream).
+ * crk_stream_push: x [S][C][in_ch] (row stride ldx), dec_cond [S][C][2] = (lcf0, uv) when decoder_f0 (row stride ldd),
+ * enc_cond likewise when encoder_f0, spk [S] int64, n_valid [S] int32 in 0..C (NULL: C for every stream) on the device.
+ * Frames past n_valid[s] are neither computed into the state nor written; a stream with 0 is left as it was.  Outputs,
+ * contiguous: decoded [S][C][out_ch], qidx[n] [S][C] int64 and encoded[n] [S][C][emb_dim[n]] (the quantizer's input x_n) for
+ * n = 0 .. n_stacks-1, bottom stack first; qidx / encoded are HOST arrays of device pointers.  Never allocates, never
+ * synchronises, one launch: capturable.  CRK_ERR_UNSUPPORTED without a launch for S or C beyond what was reserved. */
+typedef struct crk_stream_desc {
+  int n_stacks, in_ch, out_ch;
+  int emb_dim[3], emb_size[3];
+  long long cb_off[3], enc_base[3], dec_base[3];
+  int causal, enc_f0, dec_f0;   /* encoder_f0 / decoder_f0: two conditioning columns (lcf0, uv) */
+  int spk_dim, spk_onehot, n_spk; /* speaker columns of the last decoder's conditioning; one-hot: spk_dim == n_spk */
+  long long spk_off;            /* the embedding table [n_spk][spk_dim] (not read when spk_onehot) */
+} crk_stream_desc;
+int crk_stream_create(const crk_stream_desc* desc, void* const* enc_nets, void* const* dec_nets, void** handle);
+void crk_stream_destroy(void* st);
+int crk_stream_reserve(void* st, int S, int C_max);
+long long crk_stream_state_bytes(void* st, int S);
+int crk_stream_prepare(void* st, const float* params, unsigned long long version, void* stream);
+int crk_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_stream_push(void* st, const float* x, int ldx, const float* dec_cond, int ldd, const float* enc_cond, int lde,
+                    const long long* spk, const int* n_valid, int S, int C, float* decoded, long long* const* qidx,
+                    float* const* encoded, void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 
