@@ -18,9 +18,9 @@
 // applied once per parameter version by stream_prepare_kernel into a table of effective fp32 weights laid out
 // [tap][input channel (padded to 4)][output channel]: a thread owns an output channel, its weight loads are coalesced and
 // the frame rows are LDS broadcasts.  (The nets' own prepared tables hold bf16 hi / lo planes in MFMA fragment order: not
-// what an fp32 chain reads.)  The codebook search forms the distance exactly as vq_kernels.hip does - w2 and x2 as
-// d-ordered chains of separately rounded squares, the dot product as a d-ordered fmaf chain, (w2 - 2 dot) + x2, lowest index
-// on equal values - so the indices are crk_vq_forward's on the same rows.
+// what an fp32 chain reads.)  The codebook search is built from the device bodies of vq_common.h - the ones every search
+// kernel of vq_kernels.hip is built from: norms, dot product, distance, (distance, then index) order, NaN pin and
+// straight-through value - so the indices are crk_vq_forward's on the same rows by construction.
 #include <math.h>
 #include <string.h>
 
@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "../../include/crank_hip.h"
+#include "vq_common.h"
 
 #pragma clang fp contract(off)
 
@@ -195,22 +196,12 @@ __device__ void st_net(const StP& p, const StNet& n, int s, const float* in, int
   __syncthreads();
 }
 
-// one term of a squared norm, the product rounded on its own: the chain of vq_kernels.hip (vq_sq_acc)
-__device__ __forceinline__ float st_sq_acc(float acc, float e) {
-  const float sq = e * e;
-  return acc + sq;
-}
-
 // Nearest code of the nv rows xs (row stride ST_LD) in cb [K][D]: a thread owns a code (its row in registers), the frames
 // pass by as LDS broadcasts, a wave meets per frame under the (distance, then index) order, the four waves through LDS.
 template <int D>
 __device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int nv, const StLds& m) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < nv) {
-    float x2 = 0.f;
-    for (int d = 0; d < D; d++) x2 = st_sq_acc(x2, xs[tid * ST_LD + d]);
-    m.x2s[tid] = x2;
-  }
+  if (tid < nv) m.x2s[tid] = vq_norm<D>(vq_row16(xs + tid * ST_LD));
   __syncthreads();
   for (int k0 = 0; k0 < K; k0 += ST_THREADS) {
     const int k = k0 + tid;
@@ -222,21 +213,9 @@ __device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int 
       const f32x4 v = *reinterpret_cast<const f32x4*>(wp + d);
       w[d] = v[0]; w[d + 1] = v[1]; w[d + 2] = v[2]; w[d + 3] = v[3];
     }
-    float w2 = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d++) w2 = st_sq_acc(w2, w[d]);
+    const float w2 = vq_norm<D>(w);
     for (int f = 0; f < nv; f++) {
-      const float* xr = xs + f * ST_LD;
-      float dot = 0.f;
-#pragma unroll
-      for (int d = 0; d < D; d += 4) {
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + d);
-        dot = fmaf(xv[0], w[d], dot);
-        dot = fmaf(xv[1], w[d + 1], dot);
-        dot = fmaf(xv[2], w[d + 2], dot);
-        dot = fmaf(xv[3], w[d + 3], dot);
-      }
-      const float dist = (w2 - 2.f * dot) + m.x2s[f];
+      const float dist = vq_dist(w2, vq_dot<D>(vq_row16(xs + f * ST_LD), w), m.x2s[f]);
       const bool ok = live && dist < INFINITY;  // (a NaN or an infinite distance never wins: the row then takes code 0)
       float bd = ok ? dist : INFINITY;
       int bi = ok ? k : 0x7fffffff;
@@ -244,11 +223,11 @@ __device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int 
       for (int o = 32; o > 0; o >>= 1) {
         const float od = __shfl_xor(bd, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+        if (vq_better(od, oi, bd, bi)) { bd = od; bi = oi; }
       }
       if (lane == 0) {
         const int slot = wave * ST_TILE + f;
-        if (k0 == 0 || bd < m.red_d[slot] || (bd == m.red_d[slot] && bi < m.red_i[slot])) { m.red_d[slot] = bd; m.red_i[slot] = bi; }
+        if (k0 == 0 || vq_better(bd, bi, m.red_d[slot], m.red_i[slot])) { m.red_d[slot] = bd; m.red_i[slot] = bi; }
       }
     }
   }
@@ -259,9 +238,9 @@ __device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int 
     for (int wv = 1; wv < ST_THREADS / 64; wv++) {
       const float od = m.red_d[wv * ST_TILE + tid];
       const int oi = m.red_i[wv * ST_TILE + tid];
-      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+      if (vq_better(od, oi, bd, bi)) { bd = od; bi = oi; }
     }
-    m.idxs[tid] = bi == 0x7fffffff ? 0 : bi;
+    m.idxs[tid] = vq_pin(bi, K);
   }
   __syncthreads();
 }
@@ -313,7 +292,7 @@ __device__ void st_tile(const StP& p, int s, long long r0, int nv, const StLds& 
     for (int i = tid; i < nv * D; i += ST_THREADS) {
       const int f = i / D, c = i - f * D;
       const float e = cb[(size_t)m.idxs[f] * D + c], x = m.g[f * ST_LD + c];
-      m.cond[f * ST_LD + col + c] = x + (e - x);  // the straight-through value, two roundings like the reference
+      m.cond[f * ST_LD + col + c] = vq_st(x, e);
     }
     if (tid < nv) p.qidx[n][r0 + tid] = (long long)m.idxs[tid];
     __syncthreads();

@@ -8,10 +8,13 @@
 //
 // The distance is evaluated with the reference's own fp32 expression
 //   dist = (sum_d W^2 - 2 * x.w) + sum_d x^2
-// (two roundings after the dot product, same association as torch evaluates it).
-// The codebook (K x D fp32 <= 128 KiB) lives in LDS; a 512-thread workgroup scores
-// 128 frames: lane = frame, the 8 waves split {2 frame groups} x {4 code groups} and
-// the per-frame minimum is reduced across the code groups through LDS.
+// (two roundings after the dot product, same association as torch evaluates it).  Four kernels search - frame per lane
+// (any D, any K: the codebook passes through LDS in chunks), code per lane, fp32 MFMA and split-f16 MFMA with an exact
+// re-scoring (D = 64, K <= 512) - and every one of them takes each piece of that arithmetic from vq_common.h: the norm
+// chains, the dot product's steps, the distance, the (distance, then index) order where partial results meet, the NaN pin,
+// the straight-through value, the commitment term.  What differs between the kernels is who holds what and how the minimum
+// is reduced, never a rounding: identical indices by construction (test_vq_every_search_path_agrees_on_near_ties_and_edges).
+// The two matrix-pipe kernels share one gather epilogue (vq_gather_epilogue), the two entry points one route (vq_route).
 //
 // EMA sums are accumulated in 64-bit fixed point (2^-28 resolution): integer adds are
 // associative, so the statistics - and the codebook derived from them - are bitwise
@@ -19,6 +22,7 @@
 // integer all-reduce, whatever order the adds land in.
 #include "common.h"
 #include "switches.h"
+#include "vq_common.h"
 // (conv_kernels.hip: HIP-event timing per kernel class for bench.py's roofline leg; class 7 = the codebook search)
 void conv_prof_begin(int cls, double flops, hipStream_t s);
 void conv_prof_end(int cls, hipStream_t s);
@@ -28,6 +32,9 @@ void conv_prof_bytes(int cls, double bytes);
 #define VQ_FIX_SCALE 268435456.0f        // 2^28
 #define VQ_FIX_INV 3.7252902984619140625e-9f  // 2^-28
 
+// Frame per lane: the codebook (a chunk of it: K x D fp32 <= 128 KiB) lives in LDS; a 512-thread workgroup scores
+// 128 frames: lane = frame, the 8 waves split {2 frame groups} x {4 code groups} and
+// the per-frame minimum is reduced across the code groups through LDS.
 template <int D>
 __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict__ x, int ldx,
                                                          const float* __restrict__ cb, int N, int K, int kchunk,
@@ -53,8 +60,7 @@ __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict
       float4 f = *reinterpret_cast<const float4*>(xp + d);
       xr[d] = f.x; xr[d + 1] = f.y; xr[d + 2] = f.z; xr[d + 3] = f.w;
     }
-#pragma unroll
-    for (int d = 0; d < D; d++) x2 += xr[d] * xr[d];
+    x2 = vq_norm<D>(xr);
   } else {
 #pragma unroll
     for (int d = 0; d < D; d++) xr[d] = 0.f;
@@ -68,20 +74,11 @@ __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict
     for (int i = tid; i < kc * (D / 4); i += 512)
       reinterpret_cast<float4*>(cbs)[i] = reinterpret_cast<const float4*>(cb + (size_t)k0 * D)[i];
     __syncthreads();
-    for (int k = tid; k < kc; k += 512) {
-      float s = 0.f;
-      const float4* wp = reinterpret_cast<const float4*>(cbs + k * D);
-#pragma unroll
-      for (int d4 = 0; d4 < D / 4; d4++) {  // same d order as a scalar loop, 4x fewer LDS reads
-        const float4 w = wp[d4];
-        s += w.x * w.x; s += w.y * w.y; s += w.z * w.z; s += w.w * w.w;
-      }
-      w2s[k] = s;
-    }
+    for (int k = tid; k < kc; k += 512) w2s[k] = vq_norm<D>(vq_row16(cbs + k * D));
     __syncthreads();
     const int per = (kc + 3) >> 2;
     const int kb = cg * per, ke = min(kc, kb + per);
-    // four codes in flight: each code's dot product is still one d-ordered fmaf chain
+    // four codes in flight: each code's dot product is still one d-ordered chain of vq_dot_step
     // (the numerics per code are unchanged), the four chains hide each other's latency
     int k = kb;
     for (; k + 4 <= ke; k += 4) {
@@ -91,31 +88,20 @@ __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict
       for (int d4 = 0; d4 < D / 4; d4++) {
         const float4 w0 = wp[d4], w1 = wp[D / 4 + d4], w2 = wp[2 * (D / 4) + d4], w3 = wp[3 * (D / 4) + d4];
         const float a = xr[4 * d4], b = xr[4 * d4 + 1], c = xr[4 * d4 + 2], e = xr[4 * d4 + 3];
-        dot0 = fmaf(a, w0.x, dot0); dot1 = fmaf(a, w1.x, dot1); dot2 = fmaf(a, w2.x, dot2); dot3 = fmaf(a, w3.x, dot3);
-        dot0 = fmaf(b, w0.y, dot0); dot1 = fmaf(b, w1.y, dot1); dot2 = fmaf(b, w2.y, dot2); dot3 = fmaf(b, w3.y, dot3);
-        dot0 = fmaf(c, w0.z, dot0); dot1 = fmaf(c, w1.z, dot1); dot2 = fmaf(c, w2.z, dot2); dot3 = fmaf(c, w3.z, dot3);
-        dot0 = fmaf(e, w0.w, dot0); dot1 = fmaf(e, w1.w, dot1); dot2 = fmaf(e, w2.w, dot2); dot3 = fmaf(e, w3.w, dot3);
+        dot0 = vq_dot_step(a, w0.x, dot0); dot1 = vq_dot_step(a, w1.x, dot1); dot2 = vq_dot_step(a, w2.x, dot2); dot3 = vq_dot_step(a, w3.x, dot3);
+        dot0 = vq_dot_step(b, w0.y, dot0); dot1 = vq_dot_step(b, w1.y, dot1); dot2 = vq_dot_step(b, w2.y, dot2); dot3 = vq_dot_step(b, w3.y, dot3);
+        dot0 = vq_dot_step(c, w0.z, dot0); dot1 = vq_dot_step(c, w1.z, dot1); dot2 = vq_dot_step(c, w2.z, dot2); dot3 = vq_dot_step(c, w3.z, dot3);
+        dot0 = vq_dot_step(e, w0.w, dot0); dot1 = vq_dot_step(e, w1.w, dot1); dot2 = vq_dot_step(e, w2.w, dot2); dot3 = vq_dot_step(e, w3.w, dot3);
       }
-      const float d0 = (w2s[k] - 2.f * dot0) + x2, d1 = (w2s[k + 1] - 2.f * dot1) + x2;
-      const float d2 = (w2s[k + 2] - 2.f * dot2) + x2, d3 = (w2s[k + 3] - 2.f * dot3) + x2;
+      const float d0 = vq_dist(w2s[k], dot0, x2), d1 = vq_dist(w2s[k + 1], dot1, x2);
+      const float d2 = vq_dist(w2s[k + 2], dot2, x2), d3 = vq_dist(w2s[k + 3], dot3, x2);
       if (d0 < best) { best = d0; besti = k0 + k; }
       if (d1 < best) { best = d1; besti = k0 + k + 1; }
       if (d2 < best) { best = d2; besti = k0 + k + 2; }
       if (d3 < best) { best = d3; besti = k0 + k + 3; }
     }
     for (; k < ke; k++) {
-      const float4* wp = reinterpret_cast<const float4*>(cbs + k * D);
-      float dot = 0.f;
-#pragma unroll
-      for (int d4 = 0; d4 < D / 4; d4++) {
-        float4 w = wp[d4];
-        dot = fmaf(xr[4 * d4], w.x, dot);
-        dot = fmaf(xr[4 * d4 + 1], w.y, dot);
-        dot = fmaf(xr[4 * d4 + 2], w.z, dot);
-        dot = fmaf(xr[4 * d4 + 3], w.w, dot);
-      }
-      const float t = w2s[k] - 2.f * dot;
-      const float dist = t + x2;
+      const float dist = vq_dist(w2s[k], vq_dot<D>(xr, vq_row16(cbs + k * D)), x2);
       if (dist < best) { best = dist; besti = k0 + k; }
     }
   }
@@ -129,24 +115,16 @@ __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict
     for (int g = 1; g < 4; g++) {
       const float d2 = red_d[g * VQ_FRAMES + fl];
       const int i2 = red_i[g * VQ_FRAMES + fl];
-      if (d2 < bd || (d2 == bd && i2 < bi)) { bd = d2; bi = i2; }
+      if (vq_better(d2, i2, bd, bi)) { bd = d2; bi = i2; }
     }
-    if (bi == 0x7fffffff) bi = 0;  // all-NaN row: torch.argmin would pick a NaN slot; pin to 0
+    bi = vq_pin(bi, K);
     idx_out[n] = (long long)bi;
     const float* ep = cb + (size_t)bi * D;
 #pragma unroll
     for (int d = 0; d < D; d += 4) {
       float4 e = *reinterpret_cast<const float4*>(ep + d);
       if (e_out) *reinterpret_cast<float4*>(e_out + n * lde + d) = e;
-      if (qx_out) {
-        // straight-through value x + (e - x), two roundings like the reference
-        float4 q;
-        q.x = xr[d] + (e.x - xr[d]);
-        q.y = xr[d + 1] + (e.y - xr[d + 1]);
-        q.z = xr[d + 2] + (e.z - xr[d + 2]);
-        q.w = xr[d + 3] + (e.w - xr[d + 3]);
-        *reinterpret_cast<float4*>(qx_out + n * ldq + d) = q;
-      }
+      if (qx_out) *reinterpret_cast<float4*>(qx_out + n * ldq + d) = vq_st4(make_float4(xr[d], xr[d + 1], xr[d + 2], xr[d + 3]), e);
     }
   }
 }
@@ -159,7 +137,7 @@ __global__ __launch_bounds__(512) void vq_forward_kernel(const float* __restrict
 // codebook from LDS by broadcast and is bound by that).  Per frame a DPP reduction gives the wave's
 // minimum, a ballot the lowest lane that attains it (= lowest code index: ties go to the first
 // index like torch.argmin); the eight wave results meet in LDS once per block.
-// Arithmetic per (frame, code) is the same d-ordered chain as above: identical indices.
+// Arithmetic per (frame, code): the bodies of vq_common.h, as above.
 // ------------------------------------------------------------------------------
 #define VQL_FB 64  // frames per workgroup
 
@@ -205,31 +183,16 @@ __global__ __launch_bounds__(512) void vq_forward_lc_kernel(const float* __restr
       w[d] = f.x; w[d + 1] = f.y; w[d + 2] = f.z; w[d + 3] = f.w;
     }
   }
-  float w2 = 0.f;
-#pragma unroll
-  for (int d = 0; d < D; d++) w2 += w[d] * w[d];
-  for (int f = tid; f < nf; f += 512) {
-    const float* xp = x + (n0 + f) * ldx;
-    float s = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(xp + d);
-      s += v.x * v.x; s += v.y * v.y; s += v.z * v.z; s += v.w * v.w;
-    }
-    x2s[f] = s;
-  }
+  const float w2 = vq_norm<D>(w);
+  for (int f = tid; f < nf; f += 512) x2s[f] = vq_norm<D>(vq_row16(x + (n0 + f) * ldx));
   __syncthreads();
 
   for (int f = 0; f < nf; f++) {
     const float* xp = x + (n0 + f) * ldx;  // uniform: the row is fetched with scalar loads
-    float dot = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d++) dot = fmaf(xp[d], w[d], dot);
-    float dist = (w2 - 2.f * dot) + x2s[f];
-    dist = kv ? dist : INFINITY;
+    const float dist = kv ? vq_dist(w2, vq_dot<D>(xp, w), x2s[f]) : INFINITY;
     const float m = vq_dpp_min(dist);
-    const unsigned long long hit = __ballot(dist == m);
-    const int first = hit ? (int)__builtin_ctzll(hit) : 0x7fffffff - wave * 64;  // all NaN: no lane attains the minimum
+    const unsigned long long hit = __ballot(dist == m && m < INFINITY);  // (an infinite distance never wins, as in the scans' strict <)
+    const int first = hit ? (int)__builtin_ctzll(hit) : 0x7fffffff - wave * 64;  // all NaN or infinite: no lane attains a minimum
     if (lane == 0) {
       red_d[wave][f] = m;
       red_i[wave][f] = wave * 64 + first;
@@ -243,28 +206,20 @@ __global__ __launch_bounds__(512) void vq_forward_lc_kernel(const float* __restr
     for (int g = 1; g < 8; g++) {
       const float d2 = red_d[g][f];
       const int i2 = red_i[g][f];
-      if (d2 < bd || (d2 == bd && i2 < bi)) { bd = d2; bi = i2; }
+      if (vq_better(d2, i2, bd, bi)) { bd = d2; bi = i2; }
     }
-    if (bi >= K) bi = 0;  // all-NaN row (see above): pin to 0
+    bi = vq_pin(bi, K);
     best_s[f] = bi;
     idx_out[n0 + f] = (long long)bi;
   }
   __syncthreads();
-  // gathered code vectors and the straight-through value x + (e - x), two roundings like the reference
+  // gathered code vectors and the straight-through value
   for (int i = tid; i < nf * (D / 4); i += 512) {
     const int f = i / (D / 4), c = (i - f * (D / 4)) * 4;
     const long n = n0 + f;
     const float4 e = *reinterpret_cast<const float4*>(cb + (size_t)best_s[f] * D + c);
     if (e_out) *reinterpret_cast<float4*>(e_out + n * lde + c) = e;
-    if (qx_out) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + n * ldx + c);
-      float4 q;
-      q.x = xv.x + (e.x - xv.x);
-      q.y = xv.y + (e.y - xv.y);
-      q.z = xv.z + (e.z - xv.z);
-      q.w = xv.w + (e.w - xv.w);
-      *reinterpret_cast<float4*>(qx_out + n * ldq + c) = q;
-    }
+    if (qx_out) *reinterpret_cast<float4*>(qx_out + n * ldq + c) = vq_st4(*reinterpret_cast<const float4*>(x + n * ldx + c), e);
   }
 }
 
@@ -279,7 +234,7 @@ __global__ __launch_bounds__(512) void vq_forward_lc_kernel(const float* __restr
 // end.  The codebook sits in LDS in fragment order ([tile][d/8][lane][4 consecutive d pairs]: one ds_read_b128
 // feeds four MFMAs), the frame rows in registers.  Workgroup = 4 waves = 128 frames, one wave per SIMD: 250
 // workgroups for the 32 000 frames of the benchmark batch, 512 MFMAs x 64 cycles each.
-// dist = (sum_d w^2 - 2 dot) + sum_d x^2 with both sums formed exactly as above: identical indices.
+// dist = vq_dist(w2, dot, x2) with both norms chains of vq_sq_acc like everywhere else.
 #define VQM_FB 128
 typedef float vq_f32x4 __attribute__((ext_vector_type(4)));
 #ifdef VQ_PROF
@@ -303,14 +258,53 @@ struct VqFuse {
   const unsigned char* img;  // prepared codebook image (crk_vq_image_build_multi; vq_forward_f16_kernel only), or null
   int xsum_early;            // vq_forward_f16_kernel, image path: xsum is stored where x + add is formed (see there)
 };
-// One term of a code's squared norm, w2 + e * e with the product rounded on its own (NOT an fma): the chain every search kernel
-// of this file forms and the one the exact re-scoring compares against.  Spelled out because the compiler's contraction
-// depends on the surroundings - the same source line became v_pk_mul + v_add in one kernel and v_fmac in another, one ulp
-// apart, which is enough to send a near-tie to the other code.
-__device__ __forceinline__ float vq_sq_acc(float w2, float e) {
-#pragma clang fp contract(off)
-  const float sq = e * e;
-  return w2 + sq;
+// The gather epilogue of the two matrix-pipe kernels: the chosen code vectors, the input (x, + add) again, `xsum` unless the
+// kernel stored it where it formed the sum (xsum_early), the commitment partial and the straight-through value.  16 lanes
+// per row (16 bytes each), four frames per instruction: whole cache lines per access (a lane walking its own row touches 64
+// lines per instruction).  The two waves (TP = 2) of a frame group split its eight row groups, and every load of a wave's row
+// groups (code vector, x, add, mask byte) is requested before the first is used - a load behind a per-group branch on the
+// frame's validity and its mask byte was one memory round trip per group, in series.  `besti`: lane f of the wave holds the
+// code of frame f of its group.  `red`: 8 * TP floats of LDS for the workgroup's {sum, count}.
+template <int TP>
+__device__ __forceinline__ void vq_gather_epilogue(const float* __restrict__ x, int ldx, const float* __restrict__ cb, int N,
+                                                   float* __restrict__ e_out, int lde, float* __restrict__ qx_out, int ldq,
+                                                   const VqFuse& fz, bool xsum_early, int besti, int fg, int tp, float* red) {
+  constexpr int D = 64, NG = 8 / TP;
+  const int lane = threadIdx.x & 63, sub = lane >> 4, c4 = (lane & 15) * 4;
+  const long nw = (long)blockIdx.x * VQM_FB + fg * 32;
+  const bool late_sum = fz.xsum && !xsum_early;
+  const bool want_x = qx_out || late_sum || fz.cpart;
+  float csum = 0.f, ccnt = 0.f;
+  long nfs[NG];
+  float4 ev[NG], xs[NG], as[NG];
+  unsigned char mk[NG];
+#pragma unroll
+  for (int u = 0; u < NG; u++) {
+    const int f = 4 * (tp * NG + u) + sub;
+    const int bi = __shfl(besti, f, 64);
+    nfs[u] = nw + f;
+    const long nc = nfs[u] < N ? nfs[u] : 0;  // (a frame past the end reads frame 0 and stores nothing)
+    ev[u] = *reinterpret_cast<const float4*>(cb + (size_t)bi * D + c4);
+    xs[u] = want_x ? *reinterpret_cast<const float4*>(x + nc * (long)ldx + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    as[u] = (want_x && fz.add) ? *reinterpret_cast<const float4*>(fz.add + nc * (long)fz.ldadd + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    mk[u] = (fz.cpart && fz.mask) ? fz.mask[nc] : (unsigned char)1;
+  }
+#pragma unroll
+  for (int u = 0; u < NG; u++) {
+    const long nf = nfs[u];
+    if (nf < N) {
+      const float4 e = ev[u];
+      if (e_out) *reinterpret_cast<float4*>(e_out + nf * (long)lde + c4) = e;
+      float4 xv = xs[u];
+      if (want_x && fz.add) {  // the same sum as the search took, element for element
+        xv.x += as[u].x; xv.y += as[u].y; xv.z += as[u].z; xv.w += as[u].w;
+      }
+      if (late_sum) *reinterpret_cast<float4*>(fz.xsum + nf * (long)fz.ldsum + c4) = xv;
+      if (fz.cpart && mk[u]) { csum = vq_commit_acc(csum, xv, e); ccnt += 4.f; }
+      if (qx_out) *reinterpret_cast<float4*>(qx_out + nf * (long)ldq + c4) = vq_st4(xv, e);
+    }
+  }
+  if (fz.cpart) vq_commit_reduce(csum, ccnt, red, 4 * TP, fz.cpart);  // (uniform)
 }
 // TP = 2: eight waves - two per SIMD - share the workgroup's 128 frames: wave (fg, tp) takes the code tiles tp, tp + 2, ... of
 // frame group fg, the two candidates of a frame meet through LDS under the same (distance, then index) rule.  The argmin's
@@ -416,7 +410,7 @@ __global__ __launch_bounds__(256 * TP, 1) void vq_forward_mfma_kernel(const floa
 #define VQM_PICK(accv, ct)                                                                                   \
   _Pragma("unroll") for (int r = 0; r < 16; r++) {                                                           \
     const int kk = (ct) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;                                            \
-    const float dist = (w2s[kk] - 2.f * accv[r]) + x2;                                                       \
+    const float dist = vq_dist(w2s[kk], accv[r], x2);                                                        \
     if (dist < best) { best = dist; besti = kk; }                                                            \
   }
   // Two accumulators: the selection over tile ct (80 VALU instructions) is issued between the MFMAs of tile ct + 1
@@ -452,70 +446,20 @@ __global__ __launch_bounds__(256 * TP, 1) void vq_forward_mfma_kernel(const floa
   {
     const float ob = __shfl_xor(best, 32, 64);
     const int oi = __shfl_xor(besti, 32, 64);
-    if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+    if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
   }
   if (TP > 1) {  // the other wave of this frame group holds the other tiles' candidate
     if (half == 0) { vq_xb[tp][fg * 32 + l31] = best; vq_xi[tp][fg * 32 + l31] = besti; }
     __syncthreads();
     const float ob = vq_xb[tp ^ (TP - 1)][fg * 32 + l31];
     const int oi = vq_xi[tp ^ (TP - 1)][fg * 32 + l31];
-    if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+    if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
   }
-  if (besti >= K) besti = 0;  // all-NaN row: torch.argmin would pick a NaN slot; pin to 0 like the other kernels
+  besti = vq_pin(besti, K);
   VQ_T(1)
   if (valid && half == 0 && tp == 0) idx_out[n] = (long long)besti;
-  // gathered code vectors and the straight-through value x + (e - x), two roundings like the reference.  16 lanes per
-  // row (16 bytes each), four frames per instruction: whole cache lines per access (a lane walking its own row
-  // touches 64 lines per instruction, and this phase took a third of the kernel).
-  float csum = 0.f, ccnt = 0.f;
-  {
-    const int sub = lane >> 4, c4 = (lane & 15) * 4;
-    const long nw = (long)blockIdx.x * VQM_FB + fg * 32;
-#pragma unroll
-    for (int g = tp * (8 / TP); g < (tp + 1) * (8 / TP); g++) {  // (the two waves of a frame group split its rows)
-      const int f = 4 * g + sub;
-      const int bi = __shfl(besti, f, 64);
-      const long nf = nw + f;
-      if (nf < N) {
-        const float4 e = *reinterpret_cast<const float4*>(cb + (size_t)bi * D + c4);
-        if (e_out) *reinterpret_cast<float4*>(e_out + nf * (long)lde + c4) = e;
-        float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (qx_out || fz.xsum || fz.cpart) {
-          xv = *reinterpret_cast<const float4*>(x + nf * (long)ldx + c4);
-          if (fz.add) {  // the same sum as the search took, element for element
-            const float4 av = *reinterpret_cast<const float4*>(fz.add + nf * (long)fz.ldadd + c4);
-            xv.x += av.x; xv.y += av.y; xv.z += av.z; xv.w += av.w;
-          }
-          if (fz.xsum) *reinterpret_cast<float4*>(fz.xsum + nf * (long)fz.ldsum + c4) = xv;
-        }
-        if (fz.cpart && (!fz.mask || fz.mask[nf])) {
-          const float d0 = xv.x - e.x, d1 = xv.y - e.y, d2 = xv.z - e.z, d3 = xv.w - e.w;
-          csum += d0 * d0; csum += d1 * d1; csum += d2 * d2; csum += d3 * d3;
-          ccnt += 4.f;
-        }
-        if (qx_out) {
-          float4 o;
-          o.x = xv.x + (e.x - xv.x);
-          o.y = xv.y + (e.y - xv.y);
-          o.z = xv.z + (e.z - xv.z);
-          o.w = xv.w + (e.w - xv.w);
-          *reinterpret_cast<float4*>(qx_out + nf * (long)ldq + c4) = o;
-        }
-      }
-    }
-  }
-  if (fz.cpart) {  // (uniform)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { csum += __shfl_xor(csum, o, 64); ccnt += __shfl_xor(ccnt, o, 64); }
-    if (lane == 0) { vq_red[wave] = csum; vq_red[4 * TP + wave] = ccnt; }
-    __syncthreads();
-    if (tid == 0) {
-      float a = vq_red[0], c = vq_red[4 * TP];
-#pragma unroll
-      for (int w = 1; w < 4 * TP; w++) { a += vq_red[w]; c += vq_red[4 * TP + w]; }
-      fz.cpart[2 * blockIdx.x] = a; fz.cpart[2 * blockIdx.x + 1] = c;
-    }
-  }
+  // (fz.xsum_early belongs to the split-f16 kernel's image path: this kernel forms no early sum)
+  vq_gather_epilogue<TP>(x, ldx, cb, N, e_out, lde, qx_out, ldq, fz, false, besti, fg, tp, vq_red);
   VQ_T(2)
 }
 
@@ -960,8 +904,8 @@ __global__ __launch_bounds__(256 * TP, 1) void vq_forward_f16_kernel(const float
   const bool full = !sure && !two;
   int besti = t.i1;
   if (__builtin_amdgcn_ballot_w64(two)) {
-    // exact chain for code i1 (half-0 lane of the frame) and i2 (half-1 lane): fma over d ascending from 0, then
-    // (w2 - 2 dot) + x2 - the expression of vq_forward_mfma_kernel / the VALU kernels
+    // exact chain for code i1 (half-0 lane of the frame) and i2 (half-1 lane): vq_dot_step over d ascending from 0 (the row is
+    // x + add formed on the fly), then vq_dist - the bodies of vq_forward_mfma_kernel / the VALU kernels
     float dist = INFINITY;
     const int kc_ = half ? t.i2 : t.i1;
     if (two && kc_ < K) {
@@ -975,15 +919,14 @@ __global__ __launch_bounds__(256 * TP, 1) void vq_forward_f16_kernel(const float
         vq_f32x4 xv = *reinterpret_cast<const vq_f32x4*>(xp + 4 * q);
         if (ap) xv += *reinterpret_cast<const vq_f32x4*>(ap + 4 * q);
 #pragma unroll
-        for (int j = 0; j < 4; j++) dot = __builtin_fmaf(wv[j], xv[j], dot);
+        for (int j = 0; j < 4; j++) dot = vq_dot_step(xv[j], wv[j], dot);
       }
-      dist = (w2s[kc_] - 2.f * dot) + x2;
+      dist = vq_dist(w2s[kc_], dot, x2);
     }
     const float od = __shfl_xor(dist, 32, 64);
     const int oi = __shfl_xor(kc_, 32, 64);
     if (two) {
-      const bool other = od < dist || (od == dist && oi < kc_);
-      besti = other ? oi : kc_;
+      besti = vq_better(od, oi, dist, kc_) ? oi : kc_;
       if (!(dist < INFINITY) && !(od < INFINITY)) besti = 0x7fffffff;  // (cannot happen for finite rows; keeps the NaN rule)
     }
   }
@@ -1005,133 +948,95 @@ __global__ __launch_bounds__(256 * TP, 1) void vq_forward_f16_kernel(const float
     float bd = INFINITY;
     int bi = 0x7fffffff;
     for (int k = lane; k < K; k += 64) {
-      const float* wp = cb + (size_t)k * D;
-      float dot = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; q++) {
-        const vq_f32x4 wv = *reinterpret_cast<const vq_f32x4*>(wp + 4 * q);
-        const vq_f32x4 xv = *reinterpret_cast<const vq_f32x4*>(&vq_xrow[wave][4 * q]);
-#pragma unroll
-        for (int j = 0; j < 4; j++) dot = __builtin_fmaf(wv[j], xv[j], dot);
-      }
-      const float dist = (w2s[k] - 2.f * dot) + fx2;
+      const float dist = vq_dist(w2s[k], vq_dot<D>(vq_row16(vq_xrow[wave]), vq_row16(cb + (size_t)k * D)), fx2);
       if (dist < bd) { bd = dist; bi = k; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float od = __shfl_xor(bd, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+      if (vq_better(od, oi, bd, bi)) { bd = od; bi = oi; }
     }
     if (l31 == f) besti = bi;  // (both half lanes of the frame)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the slot is rewritten by the next frame
   }
-  if (besti >= K) besti = 0;  // all-NaN row: torch.argmin would pick a NaN slot; pin to 0 like the other kernels
+  besti = vq_pin(besti, K);
   VQ_T(1)
   if (valid && half == 0 && tp == 0) {
     idx_out[n] = (long long)besti;
     if (!sure) atomicAdd(&vq_f16_flag_counts[two ? 1 : 2], 1ull);
   }
-  // ---- gathered code vectors and the straight-through value: as vq_forward_mfma_kernel, with every load of the wave's
-  // 8 / TP row groups (code vector, x, add, mask byte) requested before the first is used - a load behind a per-group branch on
-  // the frame's validity and its mask byte was one memory round trip per group, in series ----
-  float csum = 0.f, ccnt = 0.f;
-  {
-    constexpr int NG = 8 / TP;  // (the two waves of a frame group split its rows)
-    const int sub = lane >> 4, c4 = (lane & 15) * 4;
-    const long nw = (long)blockIdx.x * VQM_FB + fg * 32;
-    const bool want_x = qx_out || (fz.xsum && !fz.xsum_early) || fz.cpart;
-    long nfs[NG];
-    float4 ev[NG], xs[NG], as[NG];
-    unsigned char mk[NG];
-#pragma unroll
-    for (int u = 0; u < NG; u++) {
-      const int f = 4 * (tp * NG + u) + sub;
-      const int bi = __shfl(besti, f, 64);
-      nfs[u] = nw + f;
-      const long nc = nfs[u] < N ? nfs[u] : 0;  // (a frame past the end reads frame 0 and stores nothing)
-      ev[u] = *reinterpret_cast<const float4*>(cb + (size_t)bi * D + c4);
-      xs[u] = want_x ? *reinterpret_cast<const float4*>(x + nc * (long)ldx + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      as[u] = (want_x && fz.add) ? *reinterpret_cast<const float4*>(fz.add + nc * (long)fz.ldadd + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      mk[u] = (fz.cpart && fz.mask) ? fz.mask[nc] : (unsigned char)1;
-    }
-#pragma unroll
-    for (int u = 0; u < NG; u++) {
-      const long nf = nfs[u];
-      if (nf < N) {
-        const float4 e = ev[u];
-        if (e_out) *reinterpret_cast<float4*>(e_out + nf * (long)lde + c4) = e;
-        float4 xv = xs[u];
-        if (want_x && fz.add) {  // the same sum as the search took, element for element
-          xv.x += as[u].x; xv.y += as[u].y; xv.z += as[u].z; xv.w += as[u].w;
-        }
-        if (fz.xsum && !fz.xsum_early) *reinterpret_cast<float4*>(fz.xsum + nf * (long)fz.ldsum + c4) = xv;
-        if (fz.cpart && mk[u]) {
-          const float d0 = xv.x - e.x, d1 = xv.y - e.y, d2 = xv.z - e.z, d3 = xv.w - e.w;
-          csum += d0 * d0; csum += d1 * d1; csum += d2 * d2; csum += d3 * d3;
-          ccnt += 4.f;
-        }
-        if (qx_out) {
-          float4 o;
-          o.x = xv.x + (e.x - xv.x);
-          o.y = xv.y + (e.y - xv.y);
-          o.z = xv.z + (e.z - xv.z);
-          o.w = xv.w + (e.w - xv.w);
-          *reinterpret_cast<float4*>(qx_out + nf * (long)ldq + c4) = o;
-        }
-      }
-    }
-  }
-  if (fz.cpart) {  // (uniform)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { csum += __shfl_xor(csum, o, 64); ccnt += __shfl_xor(ccnt, o, 64); }
-    if (lane == 0) { vq_red[wave] = csum; vq_red[4 * TP + wave] = ccnt; }
-    __syncthreads();
-    if (tid == 0) {
-      float a = vq_red[0], c = vq_red[4 * TP];
-#pragma unroll
-      for (int w = 1; w < 4 * TP; w++) { a += vq_red[w]; c += vq_red[4 * TP + w]; }
-      fz.cpart[2 * blockIdx.x] = a; fz.cpart[2 * blockIdx.x + 1] = c;
-    }
-  }
+  vq_gather_epilogue<TP>(x, ldx, cb, N, e_out, lde, qx_out, ldq, fz, fz.xsum_early != 0, besti, fg, tp, vq_red);
   VQ_T(2)
 }
 
-static int vq_mfma_attrs() {
+// ---- the host route: which search runs a call of shape (D, K, N), and with what launch geometry.  The ONE place that reads
+// the CRK_VQ_LC / CRK_VQ_F16 switches and names a search kernel; crk_vq_forward and crk_vq_forward_fused launch what it says.
+enum { VQ_K_NONE = 0, VQ_K_GENERIC, VQ_K_LC, VQ_K_MFMA1, VQ_K_MFMA2, VQ_K_F16 };
+struct VqRoute { int kernel, kt, nblk; size_t lds; };  // kt: 32-code tiles (matrix pipe), codes per LDS chunk (generic)
+// CRK_VQ_LC: 0 the frame-per-lane kernel for every shape, 1 code-per-lane, 2 (default) the matrix pipe - the latter two where
+// D = 64 and K <= 512.  CRK_VQ_F16 (default on): the split-f16 search on the matrix pipe, else the fp32-MFMA search.
+static int vq_lc_mode = -1, vq_f16_mode = -1;
+extern "C" int crk_debug_vq_set_f16(int on) { vq_f16_mode = on ? 1 : 0; return 0; }  // (tests: every search in one process)
+extern "C" int crk_debug_vq_set_lc(int mode) { vq_lc_mode = mode; return 0; }
+static VqRoute vq_route(int D, int K, int N, bool fused) {
+  if (vq_lc_mode < 0) vq_lc_mode = crk_sw().vq_lc;
+  if (vq_f16_mode < 0) vq_f16_mode = crk_sw().vq_f16;
+  VqRoute r{VQ_K_NONE, 0, 0, 0};
+  const bool small = D == 64 && K <= 512;
+  if (small && vq_lc_mode == 2) {
+    r.kt = ((K + 63) / 64) * 2;
+    r.nblk = (N + VQM_FB - 1) / VQM_FB;
+    // eight waves where the tile count splits evenly between two waves per frame group
+    r.kernel = r.kt % 4 ? VQ_K_MFMA1 : (vq_f16_mode ? VQ_K_F16 : VQ_K_MFMA2);
+    r.lds = r.kernel == VQ_K_F16 ? (size_t)r.kt * 32 * VQH_WS * 4 + (size_t)r.kt * 32 * 4 * 3  // fp32 image (the f16 planes reuse it) + 3 per-code tables
+                                 : (size_t)r.kt * 32 * (D + 1) * 4;
+    if (fused && r.nblk > 1024) r.kernel = VQ_K_NONE;  // (the commitment partials' scratch)
+  } else if (fused) {
+    // the fusions live in the matrix-pipe kernels only: the caller composes the separate entry points
+  } else if (small && vq_lc_mode) {
+    r.kernel = VQ_K_LC;
+    r.nblk = (N + VQL_FB - 1) / VQL_FB;
+  } else if (D == 64 || D == 32 || D == 128 || D == 16) {
+    r.kernel = VQ_K_GENERIC;
+    r.kt = K;
+    const int max_floats = (150 * 1024 - 4 * VQ_FRAMES * 8) / 4;
+    while ((size_t)r.kt * (D + 1) > (size_t)max_floats) r.kt = (r.kt + 1) / 2;
+    r.lds = ((size_t)r.kt * (D + 1) + 4 * VQ_FRAMES * 2) * 4;
+    r.nblk = (N + VQ_FRAMES - 1) / VQ_FRAMES;
+  }
+  return r;
+}
+static int vq_launch(const VqRoute& r, hipStream_t s, const float* x, int ldx, const float* cb, int N, int D, int K, long long* idx,
+                     float* e, int lde, float* qx, int ldq, const VqFuse& fz) {
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vq_forward_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vq_forward_mfma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess ||
-        hipFuncSetAttribute((const void*)vq_forward_f16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 12288) != hipSuccess)
-      return CRK_ERR_HIP;
+    const void* big[] = {(const void*)vq_forward_mfma_kernel<1>, (const void*)vq_forward_mfma_kernel<2>, (const void*)vq_forward_f16_kernel<2>,
+                         (const void*)vq_forward_kernel<16>, (const void*)vq_forward_kernel<32>, (const void*)vq_forward_kernel<64>,
+                         (const void*)vq_forward_kernel<128>};
+    const int bytes[] = {160 * 1024 - 4096, 160 * 1024 - 4096, 160 * 1024 - 12288, 160 * 1024, 160 * 1024, 160 * 1024, 160 * 1024};
+    for (int i = 0; i < 7; i++)
+      if (hipFuncSetAttribute(big[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes[i]) != hipSuccess) return CRK_ERR_HIP;
     attr_set = true;
   }
-  return CRK_OK;
-}
-// the split-f16 search (default; CRK_VQ_F16=0: the fp32-MFMA search, for A/B runs and the equality test)
-static int vq_f16_mode = -1;
-extern "C" int crk_debug_vq_set_f16(int on) { vq_f16_mode = on ? 1 : 0; return 0; }  // (tests: both searches in one process)
-static bool vq_use_f16(int kt) {
-  if (vq_f16_mode < 0) vq_f16_mode = crk_sw().vq_f16;
-  return vq_f16_mode != 0 && kt % 4 == 0;
-}
-// eight waves where the tile count splits evenly between two waves per frame group
-static void vq_mfma_launch(int nblk, int kt, size_t lds, hipStream_t s, const float* x, int ldx, const float* cb, int N, int K,
-                           long long* idx, float* e, int lde, float* qx, int ldq, const VqFuse& fz) {
-  // algorithmic bytes of a quantizer call = N x (64 x 4 read + 8 index + 64 x 4 gathered code) = 520 B per frame
-  conv_prof_bytes(7, 520.0 * N);
-  conv_prof_begin(7, 2.0 * N * (double)K * 64.0, s);
-  if (vq_use_f16(kt)) {
-    const size_t lds16 = (size_t)kt * 32 * VQH_WS * 4 + (size_t)kt * 32 * 4 * 3;  // fp32 image (the f16 planes reuse it) + 3 per-code tables
-    hipLaunchKernelGGL(vq_forward_f16_kernel<2>, dim3(nblk), dim3(512), lds16, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz);
-    conv_prof_end(7, s);
-    return;
+  const dim3 grid(r.nblk);
+  if (r.kernel >= VQ_K_MFMA1) {
+    // algorithmic bytes of a quantizer call = N x (64 x 4 read + 8 index + 64 x 4 gathered code) = 520 B per frame
+    conv_prof_bytes(7, 520.0 * N);
+    conv_prof_begin(7, 2.0 * N * (double)K * 64.0, s);
   }
-  if (kt % 4 == 0)
-    hipLaunchKernelGGL(vq_forward_mfma_kernel<2>, dim3(nblk), dim3(512), lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz);
-  else
-    hipLaunchKernelGGL(vq_forward_mfma_kernel<1>, dim3(nblk), dim3(256), lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz);
-  conv_prof_end(7, s);
+  switch (r.kernel) {
+    case VQ_K_F16: hipLaunchKernelGGL(vq_forward_f16_kernel<2>, grid, dim3(512), r.lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz); break;
+    case VQ_K_MFMA2: hipLaunchKernelGGL(vq_forward_mfma_kernel<2>, grid, dim3(512), r.lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz); break;
+    case VQ_K_MFMA1: hipLaunchKernelGGL(vq_forward_mfma_kernel<1>, grid, dim3(256), r.lds, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq, fz); break;
+    case VQ_K_LC: hipLaunchKernelGGL(vq_forward_lc_kernel<64>, grid, dim3(512), 0, s, x, ldx, cb, N, K, idx, e, lde, qx, ldq); break;
+#define VQ_GENERIC(DD) hipLaunchKernelGGL(vq_forward_kernel<DD>, grid, dim3(512), r.lds, s, x, ldx, cb, N, K, r.kt, idx, e, lde, qx, ldq)
+    default:
+      if (D == 64) VQ_GENERIC(64); else if (D == 32) VQ_GENERIC(32); else if (D == 128) VQ_GENERIC(128); else VQ_GENERIC(16);
+#undef VQ_GENERIC
+  }
+  if (r.kernel >= VQ_K_MFMA1) conv_prof_end(7, s);
+  return CRK_OK;
 }
 
 __global__ __launch_bounds__(256) void vq_commit_final_kernel(const float* __restrict__ part, int nblocks, float* __restrict__ out) {
@@ -1184,13 +1089,9 @@ extern "C" int crk_vq_forward_fused(const float* x, int ldx, const float* add, i
   if (!x || !codebook || !idx || N <= 0 || K <= 0) return CRK_ERR_ARG;
   if ((ldx & 3) || (lde & 3) || (ldq & 3) || (add && (ldadd & 3)) || (xsum && (ldsum & 3))) return CRK_ERR_ARG;
   if (commit_out2 && !scratch) return CRK_ERR_ARG;
-  const int lc_env = crk_sw().vq_lc;  // (0: frame-per-lane kernel for every shape, 1: code-per-lane, 2: MFMA)
-  const int nblk = (N + VQM_FB - 1) / VQM_FB;
-  if (lc_env != 2 || D != 64 || K > 512 || nblk > 1024) return CRK_ERR_UNSUPPORTED;
+  const VqRoute r = vq_route(D, K, N, true);
+  if (r.kernel == VQ_K_NONE) return CRK_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (vq_mfma_attrs() != CRK_OK) return CRK_ERR_HIP;
-  const int kt = ((K + 63) / 64) * 2;
-  const size_t lds = (size_t)kt * 32 * (D + 1) * 4;
   VqFuse fz; fz.add = add; fz.ldadd = ldadd; fz.xsum = xsum; fz.ldsum = ldsum; fz.mask = mask; fz.cpart = commit_out2 ? scratch : nullptr;
   fz.img = (const unsigned char*)image;
   {
@@ -1203,8 +1104,8 @@ extern "C" int crk_vq_forward_fused(const float* x, int ldx, const float* add, i
     };
     fz.xsum_early = (fz.img && xsum && !overlaps(x, ldx) && !overlaps(add, ldadd)) ? 1 : 0;
   }
-  vq_mfma_launch(nblk, kt, lds, s, x, ldx, codebook, N, K, idx, e, lde, qx, ldq, fz);
-  if (commit_out2) hipLaunchKernelGGL(vq_commit_final_kernel, dim3(1), dim3(256), 0, s, scratch, nblk, commit_out2);
+  if (vq_launch(r, s, x, ldx, codebook, N, D, K, idx, e, lde, qx, ldq, fz) != CRK_OK) return CRK_ERR_HIP;
+  if (commit_out2) hipLaunchKernelGGL(vq_commit_final_kernel, dim3(1), dim3(256), 0, s, scratch, r.nblk, commit_out2);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -1213,45 +1114,9 @@ extern "C" int crk_vq_forward(const float* x, int ldx, const float* codebook, in
                               float* e, int lde, float* qx, int ldq, void* stream) {
   if (!x || !codebook || !idx || N <= 0 || K <= 0) return CRK_ERR_ARG;
   if ((ldx & 3) || (lde & 3) || (ldq & 3)) return CRK_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const int lc_env = crk_sw().vq_lc;  // (0: frame-per-lane kernel for every shape, 1: code-per-lane, 2: MFMA)
-  if (lc_env == 2 && D == 64 && K <= 512) {
-    if (vq_mfma_attrs() != CRK_OK) return CRK_ERR_HIP;
-    const int kt = ((K + 63) / 64) * 2;
-    const size_t lds = (size_t)kt * 32 * (D + 1) * 4;
-    VqFuse fz{};
-    vq_mfma_launch((N + VQM_FB - 1) / VQM_FB, kt, lds, s, x, ldx, codebook, N, K, idx, e, lde, qx, ldq, fz);
-    CRK_CHECK_LAUNCH();
-    return CRK_OK;
-  }
-  if (lc_env && D == 64 && K <= 512) {
-    hipLaunchKernelGGL(vq_forward_lc_kernel<64>, dim3((N + VQL_FB - 1) / VQL_FB), dim3(512), 0, s, x, ldx, codebook, N, K, idx,
-                       e, lde, qx, ldq);
-    CRK_CHECK_LAUNCH();
-    return CRK_OK;
-  }
-  int kchunk = K;
-  const int max_floats = (150 * 1024 - 4 * VQ_FRAMES * 8) / 4;
-  while ((size_t)kchunk * (D + 1) > (size_t)max_floats) kchunk = (kchunk + 1) / 2;
-  const size_t lds = ((size_t)kchunk * (D + 1) + 4 * VQ_FRAMES * 2) * 4;
-  dim3 grid((N + VQ_FRAMES - 1) / VQ_FRAMES), block(512);
-#define VQ_LAUNCH(DD)                                                                                          \
-  {                                                                                                            \
-    static bool attr_set = false;                                                                              \
-    if (!attr_set) {                                                                                           \
-      if (hipFuncSetAttribute((const void*)vq_forward_kernel<DD>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                              160 * 1024) != hipSuccess) return CRK_ERR_HIP;                                   \
-      attr_set = true;                                                                                         \
-    }                                                                                                          \
-    hipLaunchKernelGGL(vq_forward_kernel<DD>, grid, block, lds, s, x, ldx, codebook, N, K, kchunk, idx, e,     \
-                       lde, qx, ldq);                                                                          \
-  }
-  if (D == 64) VQ_LAUNCH(64)
-  else if (D == 32) VQ_LAUNCH(32)
-  else if (D == 128) VQ_LAUNCH(128)
-  else if (D == 16) VQ_LAUNCH(16)
-  else return CRK_ERR_UNSUPPORTED;
-#undef VQ_LAUNCH
+  const VqRoute r = vq_route(D, K, N, false);
+  if (r.kernel == VQ_K_NONE) return CRK_ERR_UNSUPPORTED;
+  if (vq_launch(r, (hipStream_t)stream, x, ldx, codebook, N, D, K, idx, e, lde, qx, ldq, VqFuse{}) != CRK_OK) return CRK_ERR_HIP;
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }

@@ -519,6 +519,7 @@ int crk_prof_report_bytes(int cls, double* total_bytes);
  * crk_debug_vq_set_f16(0) selects the exact fp32-MFMA search instead (A/B runs, the equality test);
  * crk_debug_vq_flags: frames decided by [1] the two-candidate re-scoring, [2] the full exact scan since the last reset. */
 int crk_debug_vq_set_f16(int on);
+int crk_debug_vq_set_lc(int mode); /* CRK_VQ_LC from here on: 0 frame-per-lane, 1 code-per-lane, 2 matrix pipe (tests: all in one process) */
 int crk_debug_vq_flags(unsigned long long* host_out3, int reset);
 
 /* Measurement aid: bytes > 0 puts a read-modify-write pass over a private buffer of that size (choose > 256 MiB, the

@@ -115,20 +115,12 @@ def _vq_flags(reset=False):
     return int(out[1]), int(out[2])
 
 
-@pytest.mark.parametrize("case", ["normal", "tiny_codebook", "scaled_1e-4", "scaled_3e3", "duplicates", "near_ties", "zeros_and_padding",
-                                  "small_K_384", "outliers", "ema_dead_codes", "ragged_K_100", "nan_and_inf_rows",
-                                  "zero_rows_zero_codes"])
-def test_vq_split_f16_search_equals_the_exact_fp32_search(case):
-    """The default search (split-f16 on the matrix pipe + exact re-scoring of the undecided frames) against the exact
-    fp32-MFMA search (crk_debug_vq_set_f16(0)): identical indices on 32 000 frames per case - random data at several
-    scales, duplicated rows (exact ties -> lowest index), rows pulled 1e-7 apart (near ties), zero frames, a ragged frame
-    count, a codebook that does not fill its tiles, activations with outliers.  The counters say how often the
-    re-scoring paths ran: a fraction of a percent on random data, every frame that sits on a tie."""
-    from crank_amd import _lib, ops
+def _vq_search_case(case, N=32000, K=512):
+    """Inputs of the search equality tests: (x (N, 64), w (K', 64)).  The positions are those of N = 32 000, K = 512, scaled."""
+    def k(i):
+        return i * K // 512
 
-    L = _lib.lib()
     g = torch.Generator(device="cpu").manual_seed(5)
-    N, K = 32000, 512
     x = torch.randn(N, 64, generator=g)
     w = torch.randn(K, 64, generator=g) * 0.5
     if case == "tiny_codebook":
@@ -138,14 +130,14 @@ def test_vq_split_f16_search_equals_the_exact_fp32_search(case):
     elif case == "scaled_3e3":
         x, w = x * 3e3, w * 2e3
     elif case == "duplicates":
-        w[100], w[300], w[301] = w[7], w[7], w[7]  # three copies: the full-scan path
-        w[450] = w[20]                             # two copies: the two-candidate path
-        x[:4000] = w[7] + 0.01 * x[:4000]
-        x[4000:8000] = w[20] + 0.01 * x[4000:8000]
+        w[k(100)], w[k(300)], w[k(300) + 1] = w[7], w[7], w[7]  # three copies: the full-scan path
+        w[k(450)] = w[20]                            # two copies: the two-candidate path
+        x[:N // 8] = w[7] + 0.01 * x[:N // 8]
+        x[N // 8:N // 4] = w[20] + 0.01 * x[N // 8:N // 4]
     elif case == "near_ties":
-        w[200] = w[10] * (1 + 1e-7)
-        w[201] = w[10] + 1e-7
-        x[:8000] = w[10] + 0.05 * x[:8000]
+        w[k(200)] = w[10] * (1 + 1e-7)
+        w[k(200) + 1] = w[10] + 1e-7
+        x[:N // 4] = w[10] + 0.05 * x[:N // 4]
     elif case == "zeros_and_padding":
         x[::3] = 0.0
         x, N = x[:31987], 31987
@@ -168,6 +160,23 @@ def test_vq_split_f16_search_equals_the_exact_fp32_search(case):
     elif case == "outliers":
         x[:, 5] *= 300.0
         x[::7, 40] = 1e-12
+    return x, w
+
+
+@pytest.mark.parametrize("case", ["normal", "tiny_codebook", "scaled_1e-4", "scaled_3e3", "duplicates", "near_ties", "zeros_and_padding",
+                                  "small_K_384", "outliers", "ema_dead_codes", "ragged_K_100", "nan_and_inf_rows",
+                                  "zero_rows_zero_codes"])
+def test_vq_split_f16_search_equals_the_exact_fp32_search(case):
+    """The default search (split-f16 on the matrix pipe + exact re-scoring of the undecided frames) against the exact
+    fp32-MFMA search (crk_debug_vq_set_f16(0)): identical indices on 32 000 frames per case - random data at several
+    scales, duplicated rows (exact ties -> lowest index), rows pulled 1e-7 apart (near ties), zero frames, a ragged frame
+    count, a codebook that does not fill its tiles, activations with outliers.  The counters say how often the
+    re-scoring paths ran: a fraction of a percent on random data, every frame that sits on a tie."""
+    from crank_amd import _lib, ops
+
+    L = _lib.lib()
+    x, w = _vq_search_case(case)
+    N, K = x.shape[0], w.shape[0]
     xc, wc = x.cuda().contiguous(), w.cuda().contiguous()
     try:
         _lib.check(L.crk_debug_vq_set_f16(0), "set")
@@ -200,6 +209,65 @@ def test_vq_split_f16_search_equals_the_exact_fp32_search(case):
         assert full >= 3000 and two >= 3000, (two, full)
     if case == "zero_rows_zero_codes":
         assert (i1.reshape(-1)[::3] == 2).all() and two >= N // 3, two
+
+
+@pytest.mark.parametrize("K", [512, 100])
+@pytest.mark.parametrize("case", ["near_ties", "duplicates", "nan_and_inf_rows"])
+def test_vq_every_search_path_agrees_on_near_ties_and_edges(case, K):
+    """The four searches of one D = 64 codebook - frame-per-lane (crk_debug_vq_set_lc(0)), code-per-lane (1), fp32 MFMA
+    (2, split-f16 off) and split-f16 (2, on) - in one process on the inputs where a rounding decides: rows between codes
+    1e-7 apart, exact duplicates, NaN / infinite rows.  N = 2085: sixteen full 128-frame workgroups and a ragged one of 37
+    (the code-per-lane kernel's 64-frame blocks end ragged too); K = 100 leaves the last code tile partly padding.  All four
+    are built from the device bodies of csrc/vq_common.h: indices, code vectors and straight-through values are equal."""
+    import os
+
+    from crank_amd import _lib, ops
+
+    L = _lib.lib()
+    N = 2085
+    x, w = _vq_search_case(case, N, K)
+    xc, wc = x.cuda().contiguous().view(1, N, 64), w.cuda().contiguous()
+    out = {}
+    try:
+        for name, lc, f16 in (("frame-per-lane", 0, 0), ("code-per-lane", 1, 0), ("fp32 mfma", 2, 0), ("split f16", 2, 1)):
+            _lib.check(L.crk_debug_vq_set_lc(lc), "set")
+            _lib.check(L.crk_debug_vq_set_f16(f16), "set")
+            out[name] = ops.vq_apply(xc, wc)
+        torch.cuda.synchronize()
+    finally:
+        L.crk_debug_vq_set_lc(int(os.environ.get("CRK_VQ_LC", "2")))
+        L.crk_debug_vq_set_f16(1)
+    e0, q0, i0 = out["frame-per-lane"]
+    for name, (e, q, i) in out.items():
+        differ = int((i != i0).sum())
+        print(f"[vq paths {case} K={K}] {name}: {differ} of {N} indices differ from the frame-per-lane kernel's")
+        assert differ == 0, (name, (i != i0).nonzero()[:5].tolist())
+        assert torch.equal(e, e0), name
+        assert torch.equal(torch.isnan(q), torch.isnan(q0)) and torch.equal(torch.nan_to_num(q), torch.nan_to_num(q0)), name
+    if case == "near_ties":
+        assert len(torch.unique(i0[0, : N // 4])) > 1  # the twins do take frames
+    if case == "nan_and_inf_rows":
+        assert i0[0, 7] == 0 and i0[0, 11] == 0 and i0[0, 13] == 0
+
+
+@pytest.mark.parametrize("D,K", [(16, 40), (16, 600), (32, 40), (32, 600), (128, 40), (128, 600)])
+def test_vq_frame_per_lane_search_equals_the_restated_chain_on_near_ties(D, K):
+    """vq_forward_kernel<D> (every D other than 64 takes it; at D = 128, K = 600 the codebook passes through LDS in chunks)
+    against tests/vq_search_ref.py - norms by separately rounded squares, the dot product an fma chain, (w2 - 2 dot) + x2,
+    first index on equal values - on 300 rows that sit between a code and its (1 + 1e-7) and + 1e-7 twins: the same index on
+    every frame the restatement can vouch for (all of them, for the seeds in use; never fewer than 99.9 %)."""
+    from crank_amd import ops
+    from tests.vq_search_ref import NEAR_TIE_FRAMES, NEAR_TIE_SEEDS, near_tie_case, vq_search_ref
+
+    x, w = near_tie_case(D, K, NEAR_TIE_FRAMES, NEAR_TIE_SEEDS[D, K])
+    ref, clean = vq_search_ref(x, w)
+    assert (~clean).sum() <= 0.001 * len(clean), int((~clean).sum())
+    e, qx, idx = ops.vq_apply(cu(x[None]), cu(w))
+    got = idx.cpu().numpy()[0]
+    bad = np.nonzero((got != ref) & clean)[0]
+    print(f"[vq chain D={D} K={K}] {len(bad)} of {int(clean.sum())} kept frames differ, codes in use {np.unique(got[:200]).tolist()}")
+    assert len(bad) == 0, (bad[:5].tolist(), got[bad[:5]].tolist(), ref[bad[:5]].tolist())
+    assert torch.equal(e[0], cu(w)[idx[0]])
 
 
 def test_codebook_image_follows_every_write_to_the_codebook():
