@@ -156,6 +156,11 @@ SIGNATURES = {
     "crk_wana_mcep": (I, [P, P, P, P, P, I, LL, LL, LL, I, P, P, P, LL, P]),
     "crk_wana_npow": (I, [P, P, P, I, LL, P, P, LL, P]),
     "crk_wana_frame_shapes": (I, [P, P, P, I, LL, P, P, P]),
+    "crk_wana_d4c_workspace_bytes": (LL, [I, LL]),
+    "crk_wana_d4c_draws_per_frame": (I, [P]),
+    "crk_wana_d4c": (I, [P, P, P, P, P, I, LL, LL, LL, D, P, P, P, LL, P]),
+    "crk_wana_d4c_code": (I, [P, P, LL, P, P]),
+    "crk_wana_d4c_frame_shapes": (I, [P, P, P, P, P, I, LL, LL, LL, D, P, P, P, P, P, LL, P]),
     "crk_f0_create": (P, [I, I, P]),
     "crk_f0_destroy": (None, [P]),
     "crk_f0_reserve": (I, [P, LL]),

@@ -45,18 +45,20 @@ __device__ __forceinline__ int w_find(const long long* off, int n, long long v, 
   return lo;
 }
 
-__device__ __forceinline__ int w_brev(int n) { return (int)(__brev((unsigned)n) >> (32 - W_LOGN)); }
+template <int LOGN> __device__ __forceinline__ int w_brev_n(int n) { return (int)(__brev((unsigned)n) >> (32 - LOGN)); }
+__device__ __forceinline__ int w_brev(int n) { return w_brev_n<W_LOGN>(n); }
 
 // a handle's twiddle table (WTables::add_twiddles(W_N, W_N / 2)) into the workgroup's LDS; no barrier
 __device__ __forceinline__ void w_stage_twiddles(double* tc, double* ts, const double* twc, const double* tws) {
   for (int m = threadIdx.x; m < W_N / 2; m += W_THREADS) { tc[m] = twc[m]; ts[m] = tws[m]; }
 }
 
-// in-place radix-2 DIT FFT of W_N points in LDS, input in bit-reversed order; sign -1 forward, +1 inverse (unnormalised)
-__device__ void w_fft(double2* x, const double* twc, const double* tws, double sign) {
-  for (int half = 1; half < W_N; half <<= 1) {
-    const int stride = W_N / (2 * half);
-    for (int b = threadIdx.x; b < W_N / 2; b += W_THREADS) {
+// in-place radix-2 DIT FFT of N points in LDS, input in bit-reversed order; sign -1 forward, +1 inverse (unnormalised);
+// twc / tws: cos, sin of 2 pi m / N for m < N / 2, in LDS or in global memory
+template <int N> __device__ void w_fft_n(double2* x, const double* twc, const double* tws, double sign) {
+  for (int half = 1; half < N; half <<= 1) {
+    const int stride = N / (2 * half);
+    for (int b = threadIdx.x; b < N / 2; b += W_THREADS) {
       const int pos = b & (half - 1);
       const int i = ((b - pos) << 1) + pos, j = i + half;
       const double c = twc[pos * stride], s = sign * tws[pos * stride];
@@ -68,6 +70,9 @@ __device__ void w_fft(double2* x, const double* twc, const double* tws, double s
     __syncthreads();
   }
 }
+
+// the W_N-point transform, twiddles staged by w_stage_twiddles
+__device__ void w_fft(double2* x, const double* twc, const double* tws, double sign) { w_fft_n<W_N>(x, twc, tws, sign); }
 
 // ---------------------------------------------------------------------------------------------------------- host
 // WORLD randn after randn_reseed: the first n values of the stream

@@ -19,6 +19,7 @@
 //  * wana_power_kernel / wana_npow_kernel: per-frame power by one wave, then the utterance's mean in a fixed order.
 #include "../../include/crank_hip.h"
 #include "signal_common.h"
+#include "wana.h"
 
 #define WA_MAX_ORDER1 128
 #define WA_MAX_TAPS 256
@@ -28,15 +29,6 @@
 #define WA_EPS 2.220446049250313e-16
 #define WA_NOISE 1e-12
 #define WA_Q1 (-0.15)
-
-struct Wana {
-  int fs, m1;
-  double shiftms, alpha;
-  double* tables;  // one device block: tw cos [W_N/2], tw sin [W_N/2], at [m1][W_K]
-  const double *twc, *tws, *at;
-  double* noise;
-  long long noise_len;
-};
 
 // ---------------------------------------------------------------------------------------------------------- frame shape
 struct WaShape {
@@ -130,17 +122,6 @@ struct WaFrame {
   double* sp; double* cep;
   int fs; double shiftms;
 };
-
-// linear interpolation on the knots x0 + j dx (j < len) by index arithmetic; zero slope from the last knot on.  No
-// contraction: y0 + (y1 - y0) * s fused rounds once where the restatement rounds twice, which on a cumulative spectrum
-// moves a bin 1e5 below the frame's peak by 1e-11 in the rare case where the two differ (seen in 3 of 54 frames).
-__device__ __forceinline__ double wa_interp(const double* y, int len, double x0, double dx, double xi) {
-#pragma clang fp contract(off)
-  const double fr = (xi - x0) / dx;
-  const int base = max(0, min((int)fr, len - 1));
-  const double y0 = y[base], y1 = base + 1 < len ? y[base + 1] : y0;
-  return y0 + (y1 - y0) * (fr - base);
-}
 
 __global__ __launch_bounds__(W_THREADS) void wana_cheaptrick_kernel(WaFrame a) {
 #pragma clang fp contract(off)  // x w + noise and wav - w coef round as the restatement's do: on a locally constant signal
@@ -364,6 +345,21 @@ extern "C" void* crk_wana_create(int fs, int fftl, double shiftms, double alpha,
   wa_freqt_matrix(order1, alpha, at);
   WTables tb;
   const size_t o_tw = tb.add_twiddles(W_N, W_N / 2), o_at = tb.add(at);
+  // D4C at the rates whose two transforms are D4_N points: its twiddles and the Nuttall window of the band slices
+  const bool d4 = fs >= D4_FS_MIN && fs <= D4_FS_MAX;
+  size_t o_tw2 = 0, o_nut = 0;
+  if (d4) {
+    w->d4_half = (int)(3000.0 * D4_N / fs);
+    w->d4_bands = (int)(fmin(15000.0, fs / 2.0 - 3000.0) / 3000.0);
+    const int len = 2 * w->d4_half + 1;
+    std::vector<double> nut(len);
+    for (int i = 0; i < len; ++i) {
+      const double u = i / (len - 1.0);
+      nut[i] = 0.355768 - 0.487396 * cos(2.0 * M_PI * u) + 0.144232 * cos(4.0 * M_PI * u) - 0.012604 * cos(6.0 * M_PI * u);
+    }
+    o_tw2 = tb.add_twiddles(D4_N, D4_N / 2);
+    o_nut = tb.add(nut);
+  }
   if (!tb.upload(&w->tables)) {
     delete w;
     return nullptr;
@@ -371,6 +367,11 @@ extern "C" void* crk_wana_create(int fs, int fftl, double shiftms, double alpha,
   w->twc = w->tables + o_tw;
   w->tws = w->twc + W_N / 2;
   w->at = w->tables + o_at;
+  if (d4) {
+    w->twc2 = w->tables + o_tw2;
+    w->tws2 = w->twc2 + D4_N / 2;
+    w->nuttall = w->tables + o_nut;
+  }
   return w;
 }
 

@@ -2,11 +2,14 @@
 
 ``Feature`` mirrors the reference's ``crank/feature/feature.py``: ``analyze_batch`` runs the stage-1 kernels the package
 already has - log-mel (net/module/mlfb.py), low cut, Harvest, ``convert_continuos_f0`` with ``lf0`` / ``lcf0``,
-CheapTrick, ``sp2mc`` and ``npow`` (world.py) - over a ragged batch of utterances and files the results in a
-``FeatureStore`` under the names the reference gives its HDF5 datasets.  It adds no arithmetic of its own: every key is
-what the entry point it wraps returns, as float32 (``_save_hdf5``, feature.py:59-65, stores float64 as float32).
+CheapTrick, ``sp2mc``, ``npow``, D4C coded aperiodicity with its ``ccap`` / ``cap_uv`` (world.py) - over a ragged batch
+of utterances and files the results in a ``FeatureStore`` under the names the reference gives its HDF5 datasets.  It adds
+no arithmetic of its own: every key is what the entry point it wraps returns, as float32 (``_save_hdf5``,
+feature.py:59-65, stores float64 as float32).
 
-Not produced: ``ap``, ``cap``, ``ccap`` and ``cap_uv`` (D4C aperiodicity is not implemented), ``spc``, and the
+``cap``, ``ccap`` and ``cap_uv`` are filed under the reference's own condition for ``mcep`` (fftl not 256, fs above
+16 kHz) at the rates the D4C kernels take (up to 24052 Hz; above, the store has ``mcep`` without ``cap``, as before);
+``ap`` only with ``keep_ap=True`` (nothing in the package reads it).  Not produced: ``spc`` and the
 ``synth_flag`` outputs (analysis-synthesis and Griffin-Lim wavs, plots).
 
 ``FeatureStore`` is the reference's directory of ``.h5`` files held on the device: ``{utterance: {name: tensor}}``, callable
@@ -116,11 +119,12 @@ class Feature:
     the reference reads from disk - each waveform as ``soundfile.read`` returns it, its label ``<speaker>/<utterance>`` and
     its speaker's ``{"minf0": .., "maxf0": ..}`` - and returns the ``FeatureStore`` it filled."""
 
-    def __init__(self, conf, device="cuda"):
+    def __init__(self, conf, device="cuda", keep_ap=False):
         from crank_amd.net.module.mlfb import LogMelFilterBankLayer
-        from crank_amd.world import WorldAnalyzer
+        from crank_amd.world import D4C_FS_MAX, D4C_FS_MIN, WorldAnalyzer, check_d4c_fs
 
         self.conf = conf
+        self.keep_ap = bool(keep_ap)
         self.device = torch.device(device)
         windows = list(conf["window_types"])
         assert "hann" in windows  # feature.py:171
@@ -136,9 +140,13 @@ class Feature:
         }
         self.world = WorldAnalyzer(conf["fs"], conf["fftl"], conf["shiftms"], self.device)
         self.with_mcep = conf["fftl"] != 256 and conf["fs"] > 16000  # feature.py:92
+        # 44.1 / 48 kHz recipes keep what they got before D4C: mcep and npow, no cap (the store's KeyError says so)
+        self.with_cap = self.with_mcep and D4C_FS_MIN <= conf["fs"] <= D4C_FS_MAX
+        if self.keep_ap:
+            check_d4c_fs(conf["fs"])
 
     def analyze_batch(self, waves, flbls, spkr_confs, store=None):
-        from crank_amd.world import continuous_f0_batch
+        from crank_amd.world import cap_postprocess_batch, continuous_f0_batch
 
         if not (len(waves) == len(flbls) == len(spkr_confs)) or len(waves) < 1:
             raise ValueError("waves, flbls and spkr_confs must be lists of the same non-zero length")
@@ -165,4 +173,13 @@ class Feature:
             for lbl, mc, npow in zip(flbls, mceps, self.world.npow_of_sp_batch(sps)):
                 store.put(lbl, "mcep", f32(mc))
                 store.put(lbl, "npow", f32(npow))
+        if self.with_cap:
+            # feature.py:98-107: the coded aperiodicity with its maxima zeroed, its continuous form and its mask
+            caps = self.world.codeap_batch(raws, f0s, low_cut=70)
+            for lbl, (cap, ccap, cap_uv) in zip(flbls, cap_postprocess_batch(caps, dev)):
+                for name, t in (("cap", cap), ("ccap", ccap), ("cap_uv", cap_uv)):
+                    store.put(lbl, name, f32(t))
+        if self.keep_ap:
+            for lbl, ap in zip(flbls, self.world.d4c_batch(raws, f0s, low_cut=70)):
+                store.put(lbl, "ap", f32(ap))
         return store

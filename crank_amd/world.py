@@ -10,8 +10,10 @@ library every call raises.
 ``WorldAnalyzer`` is the other direction, the spectral half of WORLD analysis (csrc/world_analysis_kernels.hip,
 crk_wana_*): what the reference's ``crank/bin/evaluate_mcd.py`` runs on a converted waveform - ``low_cut_filter``, pyworld
 ``cheaptrick``, pysptk ``sp2mc``, sprocket ``spc2npow`` - for a ragged batch of waveforms.  Its stage methods take the F0 contour from
-the caller; ``analyze_batch`` estimates it first with ``HarvestF0``, as the reference does.  Aperiodicity (D4C) is not
-implemented.  The oracle is tests/world_analysis_ref.py; parity with pyworld / pysptk is unpinned.
+the caller; ``analyze_batch`` estimates it first with ``HarvestF0``, as the reference does.  Aperiodicity is pyworld
+``d4c`` and ``code_aperiodicity`` (csrc/d4c_kernels.hip, crk_wana_d4c*: ``d4c_batch``, ``codeap_batch``,
+``code_aperiodicity_batch``) at 13640 .. 24052 Hz, and ``cap_postprocess_batch`` the recipe's ``ccap`` / ``cap_uv``.  The
+oracles are tests/world_analysis_ref.py and tests/d4c_ref.py; parity with pyworld / pysptk is unpinned.
 
 ``HarvestF0`` is pyworld ``harvest`` (csrc/f0_kernels.hip, crk_f0_*) for a ragged batch of waveforms with a search range
 each, and ``continuous_f0_batch`` the reference's ``convert_continuos_f0`` with ``lf0`` / ``lcf0``.  The oracle is
@@ -222,10 +224,32 @@ DRAWS_PER_FRAME = 2 * (FFTL // 2 - 1) + 1 + K  # the most randn values one Cheap
 LOWCUT_TAPS = 255
 
 
+D4C_FFT = 2048  # both of D4C's transforms at the supported rates
+D4C_FS_MIN, D4C_FS_MAX = 13640, 24052
+D4C_MAX_BANDS = 3
+
+
+def d4c_fft_sizes(fs):
+    """(Love-Train, D4C) transform sizes of WORLD at fs."""
+    return (2 ** (1 + int(np.log2(3.0 * fs / 40.0 + 1))), 2 ** (1 + int(np.log2(4.0 * fs / 47.0 + 1))))
+
+
+def check_d4c_fs(fs):
+    lt, d4 = d4c_fft_sizes(fs)
+    if (lt, d4) != (D4C_FFT, D4C_FFT):
+        raise ValueError(f"fs {fs}: D4C would need a {lt}-point Love-Train transform and a {d4}-point one; the kernels "
+                         f"implement {D4C_FFT} for both ({D4C_FS_MIN} <= fs <= {D4C_FS_MAX})")
+
+
+def d4c_draws_per_frame(fs):
+    """The most randn values one D4C frame draws: the Love-Train window at 40 Hz and the general pass's three at 47 Hz."""
+    return (2 * int(1.5 * fs / 40.0 + 0.5) + 1) + 3 * (2 * int(2.0 * fs / 47.0 + 0.5) + 1)
+
+
 class WorldAnalyzer:
-    """sprocket's ``FeatureExtractor(analyzer="world", fs, fftl, shiftms)`` without F0 estimation and aperiodicity:
-    CheapTrick spectral envelope, mel-cepstrum and normalised power of waveforms whose F0 contours are given, run by the
-    kernels on a ragged batch.  Frame i of an utterance is centred at i * shiftms ms and ``len(f0)`` frames come back."""
+    """sprocket's ``FeatureExtractor(analyzer="world", fs, fftl, shiftms)``: CheapTrick spectral envelope, mel-cepstrum,
+    normalised power and D4C aperiodicity (plain and coded) of waveforms whose F0 contours are given, run by the kernels
+    on a ragged batch; ``analyze_batch`` estimates the contours with Harvest first.  Frame i of an utterance is centred at i * shiftms ms and ``len(f0)`` frames come back."""
 
     def __init__(self, fs=22050, fftl=FFTL, shiftms=5.0, device="cuda"):
         if int(fftl) != FFTL:
@@ -383,6 +407,89 @@ class WorldAnalyzer:
         """sprocket ``FeatureExtractor.npow()`` of each waveform: list of (T,)."""
         return self.npow_of_sp_batch(self.cheaptrick_batch(waves, f0s))
 
+    # -- aperiodicity
+    def _d4c(self, waves, f0s, threshold, low_cut, want_ap, want_cap):
+        check_d4c_fs(self.fs)
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must be a number")
+        b = self._batch(waves, f0s)
+        x = self._waves(waves, torch.float64) if low_cut is None else torch.cat(self.low_cut_batch(waves, low_cut))
+        n, F, S = len(b["lens"]), sum(b["lens"]), sum(b["slens"])
+        ws, draws = self.reserve_d4c(n, F, max(b["lens"]))
+        dev = self.device
+        ap = torch.empty(F, K, dtype=torch.float64, device=dev) if want_ap else None
+        cap = torch.empty(F, n_bands(self.fs), dtype=torch.float64, device=dev) if want_cap else None
+        check(_lib.lib().crk_wana_d4c(self.handle(), x.data_ptr(), b["f0"].data_ptr(), b["foff"].data_ptr(),
+                                      b["soff"].data_ptr(), n, F, S, draws, threshold, _lib.ptr(ap), _lib.ptr(cap),
+                                      ws.data_ptr(), ws.numel(), stream_ptr()), "crk_wana_d4c")
+        return [None if t is None else list(t.split(b["lens"])) for t in (ap, cap)]
+
+    def reserve_d4c(self, n_utts, total_frames, max_frames):
+        """Workspace of a D4C call of that size and the randn table for utterances of up to max_frames frames (a frame
+        draws at most ``d4c_draws_per_frame(fs)`` values).  Returns (workspace, the draw count the table covers)."""
+        ws = self._workspace.ensure(int(_lib.lib().crk_wana_d4c_workspace_bytes(n_utts, total_frames)),
+                                    "crk_wana_d4c_workspace_bytes")
+        key = (1, 0.0)
+        draws = int(max_frames) * d4c_draws_per_frame(self.fs)
+        if draws > self._reserved.get(key, 0):
+            check(_lib.lib().crk_wana_reserve(self.handle(*key), draws), "crk_wana_reserve")
+            self._reserved[key] = draws
+        return ws, draws
+
+    def d4c_batch(self, waves, f0s, threshold=0.85, low_cut=None):
+        """pyworld ``d4c(x, f0, time_axis, fs, threshold, fft_size=1024)`` of each waveform at its F0 contour: list of
+        (T, 513).  ``low_cut`` as in ``mcep_batch`` (None: the waveform as given, float64)."""
+        return self._d4c(waves, f0s, threshold, low_cut, True, False)[0]
+
+    def codeap_batch(self, waves, f0s, threshold=0.85, low_cut=None):
+        """sprocket ``FeatureExtractor.codeap()``: pyworld ``code_aperiodicity`` of the D4C table, list of (T, bands) in
+        dB.  The 513-bin table is not formed: a band reads the two bins around its knot."""
+        return self._d4c(waves, f0s, threshold, low_cut, False, True)[1]
+
+    def code_aperiodicity_batch(self, aps):
+        """pyworld ``code_aperiodicity(ap, fs)`` of each (T, 513) table: list of (T, bands) in dB."""
+        bands = n_bands(self.fs)
+        if bands < 1:
+            raise ValueError(f"fs {self.fs}: WORLD's coded aperiodicity has no band below fs / 2 - 3 kHz")
+        if bands > D4C_MAX_BANDS:
+            raise ValueError(f"fs {self.fs}: {bands} bands; the kernels code up to {D4C_MAX_BANDS}")
+        lens = [int(a.shape[0]) for a in aps]
+        if not lens or min(lens) < 1 or any(a.dim() != 2 or a.shape[1] != K for a in aps):
+            raise ValueError(f"aperiodicity tables must be (frames >= 1, {K})")
+        self._on_device()
+        ap = torch.cat([f64(a, self.device) for a in aps]).contiguous()
+        cap = torch.empty(sum(lens), bands, dtype=torch.float64, device=self.device)
+        check(_lib.lib().crk_wana_d4c_code(self.handle(), ap.data_ptr(), sum(lens), cap.data_ptr(), stream_ptr()),
+              "crk_wana_d4c_code")
+        return list(cap.split(lens))
+
+    def d4c_frame_shapes_batch(self, waves, f0s, threshold=0.85):
+        """Per utterance what the D4C kernels form before the general pass (debug; on the host): dict of origin, half_lt,
+        half_gb, origin_c1, origin_c2, dc_limit, bound_half, bound_full, passed, lt_offset, gb_offset."""
+        check_d4c_fs(self.fs)
+        b = self._batch(waves, f0s)
+        x = self._waves(waves, torch.float64)
+        n, F, S = len(b["lens"]), sum(b["lens"]), sum(b["slens"])
+        ws, draws = self.reserve_d4c(n, F, max(b["lens"]))
+        dev = self.device
+        shapes = torch.empty(F, 8, dtype=torch.int32, device=dev)
+        passed = torch.empty(F, dtype=torch.int32, device=dev)
+        lt, gb = (torch.empty(F, dtype=torch.int64, device=dev) for _ in range(2))
+        check(_lib.lib().crk_wana_d4c_frame_shapes(self.handle(), x.data_ptr(), b["f0"].data_ptr(), b["foff"].data_ptr(),
+                                                   b["soff"].data_ptr(), n, F, S, draws, float(threshold), shapes.data_ptr(),
+                                                   passed.data_ptr(), lt.data_ptr(), gb.data_ptr(), ws.data_ptr(),
+                                                   ws.numel(), stream_ptr()), "crk_wana_d4c_frame_shapes")
+        cuts = np.cumsum(b["lens"])[:-1]
+        host = lambda t: np.split(t.cpu().numpy().astype(np.int64), cuts)  # noqa: E731
+        names = ("origin", "half_lt", "half_gb", "origin_c1", "origin_c2", "dc_limit", "bound_half", "bound_full")
+        out = []
+        for s, p, a, g in zip(host(shapes), host(passed), host(lt), host(gb)):
+            d = {k: s[:, i] for i, k in enumerate(names)}
+            d.update(passed=p.astype(bool), lt_offset=a, gb_offset=g)
+            out.append(d)
+        return out
+
     def analyze_mcep(self, wave, f0, dim=34, alpha=0.455, low_cut=70):
         """One utterance: evaluate_mcd.py's ``get_world_features`` with the F0 given."""
         return self.mcep_batch([wave], [f0], dim, alpha, low_cut)[0]
@@ -421,9 +528,12 @@ class WorldAnalyzer:
         return self.mcep_batch(list(waves), [d["f0"] for d in outputs], dim, alpha, low_cut)
 
 
-    def analyze_batch(self, waves, minf0s, maxf0s, low_cut=70):
-        """sprocket ``FeatureExtractor.analyze`` without ``ap`` for each waveform: the reference's low cut (None: none),
-        Harvest at the utterance's search range, CheapTrick at that F0.  Returns (f0s, sps): lists of (T,) and (T, 513)."""
+    def analyze_batch(self, waves, minf0s, maxf0s, low_cut=70, return_ap=False):
+        """sprocket ``FeatureExtractor.analyze`` for each waveform: the reference's low cut (None: none), Harvest at the
+        utterance's search range, CheapTrick at that F0 and, with ``return_ap``, D4C.  Returns (f0s, sps) or
+        (f0s, sps, aps): lists of (T,), (T, 513) and (T, 513)."""
+        if return_ap:
+            check_d4c_fs(self.fs)
         if self.shiftms != round(self.shiftms):
             raise ValueError(f"shiftms {self.shiftms}: Harvest takes an integer frame period")
         if self._harvest is None:
@@ -431,6 +541,8 @@ class WorldAnalyzer:
         self._harvest.check(waves, minf0s, maxf0s)
         xs = [f64(w, self.device).reshape(-1) for w in waves] if low_cut is None else self.low_cut_batch(waves, low_cut)
         f0s = self._harvest.harvest_batch(xs, minf0s, maxf0s)
+        if return_ap:
+            return f0s, self.cheaptrick_batch(xs, f0s), self.d4c_batch(xs, f0s)
         return f0s, self.cheaptrick_batch(xs, f0s)
 
 
@@ -659,6 +771,28 @@ def continuous_f0_batch(f0s, device="cuda", return_filled=False):
         raise ValueError(f"utterance {bad[0]} has no voiced frame")
     outs = [t.split(lens) for t in ((uv, cf0, lf0, lcf0, filled) if return_filled else (uv, cf0, lf0, lcf0))]
     return [tuple(o[u] for o in outs) for u in range(len(lens))]
+
+
+def cap_postprocess_batch(caps, device="cuda"):
+    """The recipe's post-processing of coded aperiodicity (feature.py:98-107) for each (T, bands) table: per band column
+    every frame equal to the column's maximum is set to 0, then ``convert_continuos_f0`` of the column.  Returns per
+    utterance (cap, ccap, cap_uv), float64 / float64 / float32; ``cap`` is the column as that function left it (its ends
+    filled in place).  A column without a non-zero frame raises ValueError like ``continuous_f0_batch``."""
+    dev = torch.device(device)
+    caps = [f64(c, dev) for c in caps]
+    if not caps or any(c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 1 for c in caps):
+        raise ValueError("coded aperiodicity must be (frames >= 1, bands >= 1)")
+    cols = []
+    for c in caps:
+        c = torch.where(c == c.max(0, keepdim=True).values, torch.zeros_like(c), c)
+        cols += list(c.t().contiguous())
+    outs = continuous_f0_batch(cols, dev, return_filled=True)
+    res, i = [], 0
+    for c in caps:
+        o = outs[i:i + c.shape[1]]
+        i += c.shape[1]
+        res.append((torch.stack([t[4] for t in o], 1), torch.stack([t[1] for t in o], 1), torch.stack([t[0] for t in o], 1)))
+    return res
 
 
 def world2wav(f0, mcep, codeap, rmcep=None, wavf=None, fs=22050, fftl=1024, shiftms=10, alpha=0.455):

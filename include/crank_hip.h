@@ -640,6 +640,36 @@ int crk_wana_npow(void* wana, const double* sp, const long long* frame_offsets, 
 int crk_wana_frame_shapes(void* wana, const double* f0, const long long* frame_offsets, int n_utts, long long total_frames,
                           int* shapes, long long* draw_offsets, void* stream);
 
+/* ---- D4C aperiodicity and its coding (csrc/d4c_kernels.hip), on the crk_wana handle ----
+ * pyworld d4c(x, f0, i * shiftms / 1000, fs, threshold, fft_size = 1024) and code_aperiodicity in float64 for a ragged
+ * batch with a GIVEN F0 contour (0 = unvoiced, at most fs / 4); x, f0 and the offset arrays as above.  The oracle is
+ * tests/d4c_ref.py; parity with pyworld is unpinned.  Handles of 13640 <= fs <= 24052 only (both of D4C's transforms are
+ * 2048 points there): any other is CRK_ERR_UNSUPPORTED.
+ *
+ * The randn stream is the handle's (crk_wana_reserve).  A voiced frame draws 2 round(1.5 fs / max(f0, 40)) + 1 values in
+ * the Love-Train pass and, where it passes the threshold, 3 (2 round(2 fs / max(f0, 47)) + 1) in the general pass, so
+ * frames * crk_wana_d4c_draws_per_frame() bounds an utterance.  max_draws above the reservation is CRK_ERR_ARG.
+ * workspace: at least crk_wana_d4c_workspace_bytes(n_utts, total_frames) bytes.  The compute entries never allocate and
+ * never synchronise. */
+long long crk_wana_d4c_workspace_bytes(int n_utts, long long total_frames);
+int crk_wana_d4c_draws_per_frame(void* wana);
+/* ap: [total_frames][513] and / or cap: [total_frames][bands] in dB, bands = int(min(15000, fs / 2 - 3000) / 3000); either
+ * may be NULL, not both.  cap alone evaluates only the two bins around each band's knot. */
+int crk_wana_d4c(void* wana, const double* x, const double* f0, const long long* frame_offsets,
+                 const long long* sample_offsets, int n_utts, long long total_frames, long long total_samples,
+                 long long max_draws, double threshold, double* ap, double* cap, void* workspace, long long workspace_bytes,
+                 void* stream);
+/* cap of a given ap table (any handle whose fs has 1 .. 3 bands) */
+int crk_wana_d4c_code(void* wana, const double* ap, long long total_frames, double* cap, void* stream);
+/* debug: what the kernels form before the general pass: shapes [total_frames][8] = frame origin, Love-Train half window,
+ * general half window, the two centroid origins, DC-correction limit, smoothing boundaries of width f0 / 2 and f0 (zero
+ * but the origin for an unvoiced frame); pass [total_frames] = 1 where the general pass runs; lt_offsets, gb_offsets
+ * [total_frames] = where the frame's draws of either pass start in its utterance's stream */
+int crk_wana_d4c_frame_shapes(void* wana, const double* x, const double* f0, const long long* frame_offsets,
+                              const long long* sample_offsets, int n_utts, long long total_frames, long long total_samples,
+                              long long max_draws, double threshold, int* shapes, int* pass, long long* lt_offsets,
+                              long long* gb_offsets, void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- Harvest F0 estimation (csrc/f0_kernels.hip) ----
  * pyworld.harvest as sprocket's FeatureExtractor.analyze calls it, in float64, for a ragged batch of utterances with a
  * search range each.  The definition is tests/harvest_ref.py; parity with pyworld is unpinned.
