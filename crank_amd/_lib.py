@@ -139,6 +139,12 @@ SIGNATURES = {
     "crk_voc_workspace_bytes": (LL, [P, I, I]),
     "crk_voc_forward": (I, [P, P, P, I, I, P, P, P, LL, I, P]),
     "crk_voc_upsample": (I, [P, P, P, I, I, P, P, LL, P]),
+    "crk_voc_stream_create": (I, [P, I, I, ctypes.POINTER(c_void_p)]),
+    "crk_voc_stream_destroy": (None, [P]),
+    "crk_voc_stream_state_bytes": (LL, [P]),
+    "crk_voc_stream_lookahead": (I, [P]),
+    "crk_voc_stream_reset": (I, [P, P, I, P]),
+    "crk_voc_stream_push": (I, [P, P, P, P, P, I, I, P, P, I, P]),
     "crk_world_create": (P, [I, I, D, D, I, I, I]),
     "crk_world_destroy": (None, [P]),
     "crk_world_reserve": (I, [P, LL]),

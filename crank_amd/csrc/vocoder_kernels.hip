@@ -18,45 +18,25 @@
 //  * weights (weight norm folded by the caller) are laid out once by crk_voc_create as MFMA A fragments: one 16-byte
 //    bf16x8 per lane and k-step.  A workgroup copies the layer's hi fragments into LDS once and then walks sample tiles;
 //    CRK_FLAG_PRECISE adds the lo fragments (read from L2) and the split operands: hi.hi + hi.lo + lo.hi per product.
+//  * the arithmetic of all three kernels lives in voc_common.h and voc_layer_tile.inc, one body per piece, shared with the
+//    streaming kernels (voc_stream_kernels.hip); the kernels here say where a position's operands are in the flat planes
+//    of a ragged batch.
 #include "common.h"
+#include "voc_common.h"
 #include "../../include/crank_hip.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
 
-#define VOC_RES 64
-#define VOC_GATE 128
-#define VOC_MAX_AUX 128
-#define VOC_MAX_SCALES 8
-#define VOC_MAX_SCALE 16
-#define VOC_WAVES 8
-#define VOC_FRAG 512  // bf16 elements of one A fragment set: 64 lanes x 8
-
 long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
-struct Voc {
-  int layers, stacks, aux, auxp, win, n_scales, hop, kq, n_cu;
-  int scales[VOC_MAX_SCALES];
-  unsigned char* block;  // the one device allocation of the handle
-  const float* first;    // w[64], b[64]
-  const float* conv_in;  // [aux][aux][2 win + 1]
-  const float* up[VOC_MAX_SCALES];
-  const uint16_t *gate_hi, *gate_lo;  // per layer [4 tiles][kq][64 lanes][8]
-  const float* gate_b;                // per layer [128]
-  const uint16_t *os_hi, *os_lo;      // per layer [4 tiles: out 0-1, skip 2-3][4 k-steps][64][8]
-  const float* os_b;                  // per layer [128]: out bias 64, skip bias 64
-  const uint16_t *t1_hi, *t1_lo;      // [2][4][64][8]
-  const float* tail;                  // b1[64], w2[64], b2
-};
-
 struct VocLayerArgs {
+  VocLayerW w;
   const float* xin; float* xout; float* skip;
-  const float* noise; const float* first;
-  const uint16_t* chi; const uint16_t* clo; int auxp;
-  const uint16_t* gw_hi; const uint16_t* gw_lo; const float* gb;
-  const uint16_t* ow_hi; const uint16_t* ow_lo; const float* ob;
-  const uint16_t* tw_hi; const uint16_t* tw_lo; const float* tail; float* y; float skip_scale;
-  const long long* foff; int n_utts, hop, N, dil, kq;
+  const float* noise;
+  const uint16_t* chi; const uint16_t* clo;
+  float* y;
+  const long long* foff; int n_utts, hop, N, dil;
 };
 
 // the utterance u of frame f: largest u with off[u] <= f
@@ -76,21 +56,12 @@ __global__ void voc_conv_in_kernel(const float* __restrict__ c, const float* __r
   const int f = (int)(idx / aux), o = (int)(idx % aux);
   const int u = voc_find_utt(off, n_utts, f);
   const int s = (int)off[u], e = (int)off[u + 1];
-  const int K = 2 * win + 1;
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) {
-    const int fr = min(max(f - win + k, s), e - 1);  // ReplicationPad1d(aux_context_window)
-    const float* cr = c + (size_t)fr * aux;
-    const float* wr = w + (size_t)o * aux * K + k;
-    for (int i = 0; i < aux; ++i) acc = fmaf(wr[(size_t)i * K], cr[i], acc);
-  }
-  out[idx] = acc;
+  out[idx] = voc_conv_in_value([&](int fr) { return c + (size_t)fr * aux; }, w, f, o, s, e, aux, win);
 }
 
-// One upsampling stage: out[t] = sum_k w[k] * stretch(in)[t + k - s], stretch(in)[t'] = in[t' / s] inside the
-// utterance and 0 outside it (the Conv2d's zero padding (0, s) at the stage's edges).  in_rate / in_rate * s samples
-// per frame before / after the stage.  The last stage writes bf16 hi / lo planes [n][auxp] (zeros in the padding
-// channels) and, when `out` is given, fp32 [n][aux].
+// One upsampling stage (voc_common.h: voc_upsample_value); in_rate / in_rate * s samples per frame before / after the
+// stage.  The last stage writes bf16 hi / lo planes [n][auxp] (zeros in the padding channels) and, when `out` is given,
+// fp32 [n][aux].
 __global__ void voc_upsample_kernel(const float* __restrict__ in, int in_rate, int s, const float* __restrict__ w,
                                     const long long* __restrict__ off, int n_utts, long long n_out, int aux, int auxp,
                                     float* __restrict__ out, uint16_t* __restrict__ ohi, uint16_t* __restrict__ olo) {
@@ -107,65 +78,33 @@ __global__ void voc_upsample_kernel(const float* __restrict__ in, int in_rate, i
   const long long out_rate = (long long)in_rate * s;
   const int u = voc_find_utt(off, n_utts, t / out_rate);
   const long long S = off[u] * out_rate, E = off[u + 1] * out_rate, Sin = off[u] * in_rate;
-  float acc = 0.f;
-  for (int k = 0; k <= 2 * s; ++k) {
-    const long long tt = t + k - s;
-    if (tt >= S && tt < E) acc = fmaf(w[k], in[(Sin + (tt - S) / s) * aux + ch], acc);
-  }
+  const float acc = voc_upsample_value([&](long long j) { return in[(Sin + j) * aux + ch]; }, w, s, t, S, E);
   if (out) out[t * aux + ch] = acc;
-  if (ohi) {
-    const __bf16 hb = (__bf16)acc;
-    ohi[idx] = __builtin_bit_cast(uint16_t, hb);
-    if (olo) olo[idx] = f2bf(acc - (float)hb);
-  }
+  if (ohi) voc_cond_store(acc, ohi + idx, olo ? olo + idx : nullptr);
 }
 
-__device__ __forceinline__ bf16x8 voc_pack8(const float* v) {
-  uint4 u = make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
-  return __builtin_bit_cast(bf16x8, u);
-}
-// hi = bf16(v), lo = bf16(v - hi)
-template <bool P>
-__device__ __forceinline__ void voc_split8(const float* v, bf16x8& hi, bf16x8& lo) {
-  hi = voc_pack8(v);
-  if (P) {
-    float r[8];
-    for (int j = 0; j < 8; ++j) r[j] = v[j] - (float)hi[j];
-    lo = voc_pack8(r);
-  }
-}
-template <bool P>
-__device__ __forceinline__ f32x16 voc_mma(f32x16 acc, bf16x8 ah, const uint16_t* al_ptr, bf16x8 bh, bf16x8 bl) {
-  acc = mfma_bf16(ah, bh, acc);
-  if (P) {
-    const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(al_ptr));
-    acc = mfma_bf16(ah, bl, acc);
-    acc = mfma_bf16(al, bh, acc);
-  }
-  return acc;
-}
-__device__ __forceinline__ float voc_sigmoid(float v) { return 1.f / (1.f + __expf(-v)); }
-__device__ __forceinline__ float voc_tanh(float v) { return 1.f - 2.f / (__expf(2.f * v) + 1.f); }
+// where the offline kernel's samples live: flat planes over the ragged batch, utterance [us, ue) of the lane's sample
+struct VocFlatLoc {
+  const VocLayerArgs& a;
+  int us, ue;
+  __device__ __forceinline__ bool inside(int m) const { return m >= us && m < ue; }
+  __device__ __forceinline__ float noise(int m) const { return a.noise[m]; }
+  __device__ __forceinline__ const float* xin(int m) const { return a.xin + (size_t)m * VOC_RES; }
+  __device__ __forceinline__ float* xout(int n) const { return a.xout + (size_t)n * VOC_RES; }
+  __device__ __forceinline__ float* skip(int n) const { return a.skip + (size_t)n * VOC_RES; }
+  __device__ __forceinline__ const uint16_t* chi(int n) const { return a.chi + (size_t)n * a.w.auxp; }
+  __device__ __forceinline__ const uint16_t* clo(int n) const { return a.clo + (size_t)n * a.w.auxp; }
+  __device__ __forceinline__ float* y(int n) const { return a.y + n; }
+};
 
 template <bool P, bool FIRST, bool LAST>
 __global__ __launch_bounds__(64 * VOC_WAVES) void voc_layer_kernel(VocLayerArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char voc_lds[];
-  const int kq = a.kq;
-  const int gate_units = 4 * kq * 64, os_units = 16 * 64;  // 16-byte fragments
-  {
-    uint4* l4 = reinterpret_cast<uint4*>(voc_lds);
-    const uint4* g4 = reinterpret_cast<const uint4*>(a.gw_hi);
-    const uint4* o4 = reinterpret_cast<const uint4*>(a.ow_hi);
-    for (int i = threadIdx.x; i < gate_units; i += blockDim.x) l4[i] = g4[i];
-    for (int i = threadIdx.x; i < os_units; i += blockDim.x) l4[gate_units + i] = o4[i];
-  }
+  voc_layer_fill_lds(a.w, voc_lds);
   __syncthreads();
-  const unsigned char* lgate = voc_lds;
-  const unsigned char* los = voc_lds + (size_t)gate_units * 16;
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x & 63, r = lane & 31;
   const int wave = threadIdx.x >> 6;
   const int ntiles = (a.N + 31) >> 5;
-  const float rs = 0.70710678118654752f;  // sqrt(0.5)
   for (int tile = blockIdx.x * VOC_WAVES + wave; tile < ntiles; tile += gridDim.x * VOC_WAVES) {
     const int n = tile * 32 + r;
     const bool valid = n < a.N;
@@ -175,133 +114,9 @@ __global__ __launch_bounds__(64 * VOC_WAVES) void voc_layer_kernel(VocLayerArgs 
       us = (int)a.foff[u] * a.hop;
       ue = (int)a.foff[u + 1] * a.hop;
     }
-    f32x16 acc[4];
-    for (int t = 0; t < 4; ++t) acc[t] = (f32x16){0.f};
-    // gate conv: three dilated taps of x (k-steps 0..11) ...
-#pragma unroll 1
-    for (int tap = 0; tap < 3; ++tap) {
-      const int m = n + (tap - 1) * a.dil;
-      const bool in = valid && m >= us && m < ue;
-      for (int cb = 0; cb < 4; ++cb) {
-        float v[8];
-        const int c0 = cb * 16 + 8 * h;
-        if (in) {
-          if (FIRST) {
-            const float nz = a.noise[m];
-            for (int j = 0; j < 8; ++j) v[j] = fmaf(a.first[c0 + j], nz, a.first[VOC_RES + c0 + j]);
-          } else {
-            const float4 p = *reinterpret_cast<const float4*>(a.xin + (size_t)m * VOC_RES + c0);
-            const float4 q = *reinterpret_cast<const float4*>(a.xin + (size_t)m * VOC_RES + c0 + 4);
-            v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w; v[4] = q.x; v[5] = q.y; v[6] = q.z; v[7] = q.w;
-          }
-        } else {
-          for (int j = 0; j < 8; ++j) v[j] = 0.f;
-        }
-        bf16x8 bh, bl;
-        voc_split8<P>(v, bh, bl);
-        const int q = tap * 4 + cb;
-        for (int t = 0; t < 4; ++t) {
-          const size_t fi = ((size_t)(t * kq + q) * 64 + lane);
-          acc[t] = voc_mma<P>(acc[t], lds_frag(lgate + fi * 16), a.gw_lo + fi * 8, bh, bl);
-        }
-      }
-    }
-    // ... and the upsampled conditioning (k-steps 12..kq-1): conv1x1_aux
-#pragma unroll 1
-    for (int cb = 0; cb < (a.auxp >> 4); ++cb) {
-      uint4 uh = make_uint4(0, 0, 0, 0), ul = make_uint4(0, 0, 0, 0);
-      if (valid) {
-        const size_t o = (size_t)n * a.auxp + cb * 16 + 8 * h;
-        uh = *reinterpret_cast<const uint4*>(a.chi + o);
-        if (P) ul = *reinterpret_cast<const uint4*>(a.clo + o);
-      }
-      const bf16x8 bh = __builtin_bit_cast(bf16x8, uh), bl = __builtin_bit_cast(bf16x8, ul);
-      const int q = 12 + cb;
-      for (int t = 0; t < 4; ++t) {
-        const size_t fi = ((size_t)(t * kq + q) * 64 + lane);
-        acc[t] = voc_mma<P>(acc[t], lds_frag(lgate + fi * 16), a.gw_lo + fi * 8, bh, bl);
-      }
-    }
-    // gate: z[c] = tanh(a[c]) * sigmoid(a[c + 64]); register i of tile t holds row (i&3) + 8(i>>2) + 4h
-    bf16x8 zh[4], zl[4];
-    for (int mt = 0; mt < 2; ++mt) {
-      float z[16];
-      for (int i = 0; i < 16; ++i) {
-        const int c = 32 * mt + (i & 3) + 8 * (i >> 2) + 4 * h;
-        z[i] = voc_tanh(acc[mt][i] + a.gb[c]) * voc_sigmoid(acc[mt + 2][i] + a.gb[64 + c]);
-      }
-      // registers 8s..8s+7 are the B fragment of k-step (mt, s); the A fragments carry the matching k permutation
-      voc_split8<P>(z, zh[2 * mt], zl[2 * mt]);
-      voc_split8<P>(z + 8, zh[2 * mt + 1], zl[2 * mt + 1]);
-    }
-    f32x16 o[4];
-    for (int t = 0; t < 4; ++t) {
-      o[t] = (f32x16){0.f};
-      for (int ks = 0; ks < 4; ++ks) {
-        const size_t fi = ((size_t)(t * 4 + ks) * 64 + lane);
-        o[t] = voc_mma<P>(o[t], lds_frag(los + fi * 16), a.ow_lo + fi * 8, zh[ks], zl[ks]);
-      }
-    }
-    // epilogue: x' = (out + b + x) sqrt(.5); skip += s + b
-    for (int g = 0; g < 4; ++g) {
-      if (!LAST && valid) {
-        for (int t = 0; t < 2; ++t) {
-          const int c = 32 * t + 8 * g + 4 * h;
-          float xr[4];
-          if (FIRST) {
-            const float nz = a.noise[n];
-            for (int k = 0; k < 4; ++k) xr[k] = fmaf(a.first[c + k], nz, a.first[VOC_RES + c + k]);
-          } else {
-            const float4 p = *reinterpret_cast<const float4*>(a.xin + (size_t)n * VOC_RES + c);
-            xr[0] = p.x; xr[1] = p.y; xr[2] = p.z; xr[3] = p.w;
-          }
-          float4 w;
-          w.x = (o[t][4 * g + 0] + a.ob[c + 0] + xr[0]) * rs;
-          w.y = (o[t][4 * g + 1] + a.ob[c + 1] + xr[1]) * rs;
-          w.z = (o[t][4 * g + 2] + a.ob[c + 2] + xr[2]) * rs;
-          w.w = (o[t][4 * g + 3] + a.ob[c + 3] + xr[3]) * rs;
-          *reinterpret_cast<float4*>(a.xout + (size_t)n * VOC_RES + c) = w;
-        }
-      }
-      for (int t = 2; t < 4; ++t) {
-        const int c = 32 * (t - 2) + 8 * g + 4 * h;
-        float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (!FIRST && valid) p = *reinterpret_cast<const float4*>(a.skip + (size_t)n * VOC_RES + c);
-        p.x += o[t][4 * g + 0] + a.ob[64 + c + 0];
-        p.y += o[t][4 * g + 1] + a.ob[64 + c + 1];
-        p.z += o[t][4 * g + 2] + a.ob[64 + c + 2];
-        p.w += o[t][4 * g + 3] + a.ob[64 + c + 3];
-        if (LAST) {
-          o[t][4 * g + 0] = p.x; o[t][4 * g + 1] = p.y; o[t][4 * g + 2] = p.z; o[t][4 * g + 3] = p.w;
-        } else if (valid) {
-          *reinterpret_cast<float4*>(a.skip + (size_t)n * VOC_RES + c) = p;
-        }
-      }
-    }
-    if (LAST) {
-      // tail: y = w2 . relu(W1 relu(skip sqrt(1/L)) + b1) + b2; the skip tiles are W1's B operand in place
-      bf16x8 sh[4], sl[4];
-      for (int mt = 0; mt < 2; ++mt) {
-        float v[16];
-        for (int i = 0; i < 16; ++i) v[i] = fmaxf(o[mt + 2][i] * a.skip_scale, 0.f);
-        voc_split8<P>(v, sh[2 * mt], sl[2 * mt]);
-        voc_split8<P>(v + 8, sh[2 * mt + 1], sl[2 * mt + 1]);
-      }
-      float part = 0.f;
-      for (int t = 0; t < 2; ++t) {
-        f32x16 y1 = (f32x16){0.f};
-        for (int ks = 0; ks < 4; ++ks) {
-          const size_t fi = ((size_t)(t * 4 + ks) * 64 + lane);
-          const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(a.tw_hi + fi * 8));
-          y1 = voc_mma<P>(y1, ah, a.tw_lo + fi * 8, sh[ks], sl[ks]);
-        }
-        for (int i = 0; i < 16; ++i) {
-          const int c = 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
-          part = fmaf(a.tail[64 + c], fmaxf(y1[i] + a.tail[c], 0.f), part);
-        }
-      }
-      part += __shfl_xor(part, 32);
-      if (valid && h == 0) a.y[n] = part + a.tail[128];
+    {
+      const VocLayerW& aw = a.w; const VocFlatLoc loc{a, us, ue}; const int dil = a.dil; const unsigned char* lds = voc_lds;
+#include "voc_layer_tile.inc"
     }
   }
 }
@@ -337,8 +152,6 @@ static VocWs voc_ws(const Voc* v, long long F, unsigned char* base) {
   w.bytes = o;
   return w;
 }
-
-static size_t voc_lds_bytes(const Voc* v) { return (size_t)(4 * v->kq + 16) * 64 * 16; }
 
 template <bool P, bool FIRST, bool LAST>
 static void* voc_layer_fn() { return (void*)voc_layer_kernel<P, FIRST, LAST>; }
@@ -592,19 +405,12 @@ extern "C" int crk_voc_forward(void* voc, const float* c, const long long* frame
     a.xin = l ? xb[(l - 1) & 1] : nullptr;
     a.xout = xb[l & 1];
     a.skip = w.skip;
-    a.noise = noise; a.first = v->first;
-    a.chi = w.chi; a.clo = w.clo; a.auxp = v->auxp;
-    a.gw_hi = v->gate_hi + (size_t)l * 4 * v->kq * VOC_FRAG;
-    a.gw_lo = v->gate_lo + (size_t)l * 4 * v->kq * VOC_FRAG;
-    a.gb = v->gate_b + (size_t)l * VOC_GATE;
-    a.ow_hi = v->os_hi + (size_t)l * 16 * VOC_FRAG;
-    a.ow_lo = v->os_lo + (size_t)l * 16 * VOC_FRAG;
-    a.ob = v->os_b + (size_t)l * VOC_GATE;
-    a.tw_hi = v->t1_hi; a.tw_lo = v->t1_lo; a.tail = v->tail; a.y = out;
-    a.skip_scale = sqrtf(1.f / (float)v->layers);
+    a.w = voc_layer_weights(v, l);
+    a.noise = noise;
+    a.chi = w.chi; a.clo = w.clo;
+    a.y = out;
     a.foff = frame_offsets; a.n_utts = n_utts; a.hop = v->hop; a.N = N;
     a.dil = 1 << (l % lps);
-    a.kq = v->kq;
     void* fn = voc_pick(P, l == 0, l + 1 == v->layers);
     void* args[] = {&a};
     if (hipLaunchKernel(fn, dim3(grid), dim3(64 * VOC_WAVES), args, lds, st) != hipSuccess) return CRK_ERR_HIP;

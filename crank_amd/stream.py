@@ -10,7 +10,7 @@ depend on how an utterance is cut into pushes - bit for bit - and equal the offl
 
 What stays with the caller: the acoustic front end that produces the scaled input features, the F0 conversion
 (``BaseTrainer._decode_f0`` / ``crk_decode_f0`` work frame by frame, so they apply to a chunk as they do to an utterance),
-and waveform synthesis.
+and waveform synthesis: ``crank_amd.vocoder.StreamingVocoder`` turns the decoded chunks into sound, 16 frames behind them.
 """
 import ctypes
 

@@ -15,7 +15,7 @@ import torch
 
 from crank_amd import _lib, ops
 from crank_amd._lib import check, stream_ptr
-from crank_amd._ragged import Workspace, made, offsets, release
+from crank_amd._ragged import Workspace, made, offsets, release, require_gpu
 
 MAX_AUX = 128
 MAX_SCALE = 16
@@ -68,6 +68,21 @@ def generator_params(config):
     refuse(any(not 1 <= s <= MAX_SCALE for s in scales), f"an upsample scale outside 1..{MAX_SCALE}")
     p["upsample_params"] = dict(up, upsample_scales=scales)
     return p
+
+
+def lookahead_frames(params):
+    """Frames a streamed generator runs behind its input (``StreamingVocoder``): win + ceil((D + A) / H), with H the hop,
+    D the sum of the layers' dilations and A = sum_i H / prod_{j<i} s_j the forward reach of the upsampling network in
+    samples (each stage can ask for one more input sample of its own rate).  16 for the published default
+    (D = 3069, A = 340, H = 256, win = 2)."""
+    scales = [int(s) for s in params["upsample_params"]["upsample_scales"]]
+    lps = params["layers"] // params["stacks"]
+    D = sum(2 ** (l % lps) for l in range(params["layers"]))
+    H, A, rate = int(np.prod(scales)), 0, 1
+    for s in scales:
+        A += H // rate
+        rate *= s
+    return int(params["aux_context_window"]) + -(-(D + A) // H)
 
 
 def expected_keys(p):
@@ -272,6 +287,10 @@ class ParallelWaveGANVocoder:
               "crk_voc_forward")
         return list(out.split([n * self.hop_size for n in lens]))
 
+    def streaming(self, n_streams, max_chunk):
+        """A ``StreamingVocoder`` on this generator's weights: up to ``n_streams`` streams, ``max_chunk`` frames a push."""
+        return StreamingVocoder(self, n_streams, max_chunk)
+
     def inference(self, c, x=None):
         """The published ``inference(c, x)``: c (frames, aux) -> waveform (frames * hop,)."""
         return self.inference_batch([c], None if x is None else [x])[0]
@@ -284,3 +303,102 @@ class ParallelWaveGANVocoder:
             return {k: self.vocode_eval_outputs(v) for k, v in outputs.items()}
         return self.inference_batch([self.normalize(d["feats"]) for d in outputs])
 
+
+
+class StreamingVocoder:
+    """``push`` vocodes the next frames of up to ``n_streams`` independent streams, at most ``max_chunk`` frames each per
+    push (csrc/voc_stream_kernels.hip, ``crk_voc_stream_*``).  Stream i is row i of every argument.
+
+    The generator is not causal, so a stream runs ``lookahead`` frames behind its input: after T frames of an utterance
+    it has emitted max(0, T - lookahead) * hop samples, and the push that carries the stream's ``end`` flag emits the rest
+    and starts a new utterance.  The emitted samples equal ``inference_batch`` on the whole utterance with the same noise
+    bit for bit, in every precision and however the utterance is cut into pushes.  Every layer's history and every
+    position stay on the device; a push neither allocates nor reads back.  There is no torch or CPU fallback."""
+
+    def __init__(self, vocoder, n_streams, max_chunk):
+        if n_streams < 1 or max_chunk < 1:
+            raise ValueError(f"n_streams = {n_streams}, max_chunk = {max_chunk}: both must be at least 1")
+        self.vocoder, self.device = vocoder, vocoder.device
+        require_gpu(self.device, "streaming vocoding", "the vocoder's device")
+        self.n_streams, self.max_chunk = int(n_streams), int(max_chunk)
+        self.hop_size, self.aux_channels = vocoder.hop_size, vocoder.aux_channels
+        self.lookahead = lookahead_frames(vocoder.params)
+        h = ctypes.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            check(L.crk_voc_stream_create(vocoder.handle(), self.n_streams, self.max_chunk, ctypes.byref(h)),
+                  "crk_voc_stream_create")
+            self._handle = made(h, "crk_voc_stream_create")
+        if int(L.crk_voc_stream_lookahead(self._handle)) != self.lookahead:
+            raise RuntimeError(f"crk_voc_stream_lookahead = {L.crk_voc_stream_lookahead(self._handle)}, "
+                               f"lookahead_frames = {self.lookahead}")
+
+    def __del__(self):
+        release(self, "_handle", "crk_voc_stream_destroy")
+
+    @property
+    def state_bytes(self):
+        return int(_lib.lib().crk_voc_stream_state_bytes(self._handle))
+
+    def reset(self, streams=None):
+        """``streams`` (all of them by default) start a new utterance; what they had not emitted yet is dropped."""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            if streams is None:
+                check(L.crk_voc_stream_reset(self._handle, None, 0, stream_ptr()), "crk_voc_stream_reset")
+            else:
+                ids = [int(s) for s in streams]
+                if any(not 0 <= i < self.n_streams for i in ids):
+                    raise ValueError(f"streams {ids}: stream ids are 0 .. {self.n_streams - 1}")
+                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
+                check(L.crk_voc_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_voc_stream_reset")
+
+    def empty_outputs(self, S, C):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
+        return {"wave": torch.empty(S, (C + self.lookahead) * self.hop_size, device=self.device),
+                "n_out": torch.empty(S, dtype=torch.int32, device=self.device)}
+
+    def _flags(self, t, S, what):
+        if t is None:
+            return None
+        if t.device.type != "cuda" or tuple(t.shape) != (S,) or t.dtype not in (torch.int32, torch.int64, torch.bool):
+            raise ValueError(f"{what}: an integer ({S},) tensor on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.to(torch.int32).contiguous()
+
+    def push(self, c, noise=None, n_valid=None, end=None, out=None):
+        """c (S, C, aux) normalised features, noise (S, C * hop) or None (drawn on the device from the vocoder's
+        generator), n_valid (S,) frames that count per stream (default: C), end (S,) non-zero where this push ends the
+        stream's utterance.  Returns ``wave`` (S, (C + lookahead) * hop) and ``n_out`` (S,) int32: the samples written at
+        the start of each row; samples past ``n_out`` are not written.  out: buffers to write into (``empty_outputs``),
+        e.g. the static ones of a captured graph."""
+        if c.dim() != 3:
+            raise ValueError(f"c: a float32 (S, C, {self.aux_channels}) tensor on the GPU, got {tuple(c.shape)}")
+        S, C = int(c.shape[0]), int(c.shape[1])
+        if c.device.type != "cuda" or c.dtype != torch.float32 or tuple(c.shape) != (S, C, self.aux_channels):
+            raise ValueError(f"c: a float32 ({S}, {C}, {self.aux_channels}) tensor on the GPU, got {c.dtype} "
+                             f"{tuple(c.shape)} on {c.device}")
+        if not 1 <= S <= self.n_streams:
+            raise ValueError(f"S = {S}: this StreamingVocoder holds n_streams = {self.n_streams}")
+        if not 1 <= C <= self.max_chunk:
+            raise ValueError(f"C = {C}: a push takes 1 .. max_chunk = {self.max_chunk} frames")
+        N = C * self.hop_size
+        if noise is None:
+            noise = torch.randn(S, N, generator=self.vocoder.generator, device=self.device)
+        elif noise.device.type != "cuda" or noise.dtype != torch.float32 or tuple(noise.shape) != (S, N):
+            raise ValueError(f"noise: a float32 ({S}, {N}) tensor on the GPU, got {noise.dtype} {tuple(noise.shape)} on "
+                             f"{noise.device}")
+        n_valid, end = self._flags(n_valid, S, "n_valid"), self._flags(end, S, "end")
+        if out is None:
+            out = self.empty_outputs(S, C)
+        else:
+            w, n = out["wave"], out["n_out"]
+            if (w.device.type != "cuda" or w.dtype != torch.float32 or tuple(w.shape) != (S, (C + self.lookahead) * self.hop_size)
+                    or not w.is_contiguous() or n.device.type != "cuda" or n.dtype != torch.int32 or tuple(n.shape) != (S,)):
+                raise ValueError(f"out: wave float32 ({S}, {(C + self.lookahead) * self.hop_size}) and n_out int32 ({S},) "
+                                 "on the GPU (empty_outputs)")
+        flags = ops.CRK_FLAG_PRECISE if ops.get_precision() in ("bf16x3", "bf16x3f") else 0
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_voc_stream_push(
+                self._handle, c.contiguous().data_ptr(), noise.contiguous().data_ptr(), _lib.ptr(n_valid), _lib.ptr(end),
+                S, C, out["wave"].data_ptr(), out["n_out"].data_ptr(), flags, stream_ptr()), "crk_voc_stream_push")
+        return out

@@ -556,6 +556,34 @@ int crk_voc_forward(void* voc, const float* c, const long long* frame_offsets, i
 int crk_voc_upsample(void* voc, const float* c, const long long* frame_offsets, int n_utts, int total_frames, float* out,
                      void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Streaming Parallel WaveGAN vocoding ------------------------------------------------------------------------
+ * The generator of a crk_voc handle (its weights and fragments are shared, nothing is laid out twice) for chunks of new
+ * frames of up to n_streams concurrent streams, at most max_chunk frames each per push.  The published generator is not
+ * causal: a stream runs LA = win + ceil((D + A) / H) frames behind its input (H = prod(scales), D = sum of the layers'
+ * dilations, A = sum_i H / prod_{j<i} scales[j]; 16 frames for the published default).  A stream that has received T
+ * frames of its utterance has emitted max(0, T - LA) H samples; a push whose end flag is set for a stream emits
+ * everything up to T H with the utterance's right-edge rules and returns that stream to the start-of-utterance state.
+ * The emitted samples equal crk_voc_forward's for the whole utterance with the same noise bit for bit, in both
+ * precisions and however the utterance is cut into pushes.  An utterance holds at most 2^30 - 1 samples: frames past
+ * that are not taken (n_out tells).
+ *
+ * crk_voc_stream_create is the one call that allocates (state of every stream; it synchronises); the crk_voc handle must
+ * outlive it.  crk_voc_stream_state_bytes: the size of that allocation.  crk_voc_stream_lookahead: LA.
+ * crk_voc_stream_reset: the streams listed in the HOST array stream_ids (NULL: every stream) start a new utterance.
+ * crk_voc_stream_push: c fp32 [S][C][aux], noise fp32 [S][C * H], n_valid / end DEVICE int32 [S] (NULL: C / 0; frames
+ * and noise at and past n_valid are ignored), wave fp32 [S][(C + LA) * H], n_out DEVICE int32 [S]: the samples written
+ * per stream, from the start of its row; samples past n_out are not written.  S <= n_streams, C <= max_chunk; stream i
+ * is row i.  Every position lives on the device: a push never allocates and reads nothing back (it can be captured in
+ * a graph), and launches 3 + n_scales + layers kernels whatever S, C, n_valid and end are.
+ * flags: CRK_FLAG_PRECISE as crk_voc_forward. */
+int crk_voc_stream_create(void* voc, int n_streams, int max_chunk, void** handle);
+void crk_voc_stream_destroy(void* st);
+long long crk_voc_stream_state_bytes(void* st);
+int crk_voc_stream_lookahead(void* st);
+int crk_voc_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_voc_stream_push(void* st, const float* c, const float* noise, const int* n_valid, const int* end, int S, int C,
+                        float* wave, int* n_out, int flags, void* stream);
+
 /* ---- WORLD waveform synthesis for mel-cepstral models (recipe stage 5, output_feat_type mcep) ---------------------
  * Replaces the reference's world2wav (sprocket Synthesizer.synthesis: mod_power, pysptk mc2sp, pyworld
  * decode_aperiodicity + synthesize), all in float64, for a ragged batch of utterances.  Parity with pyworld / pysptk is
