@@ -12,8 +12,7 @@
 #pragma once
 #include <vector>
 
-#include "common.h"
-#include "switches.h"
+#include "runtime.h"
 
 #define CRK_TM 128  // frames per workgroup tile (4 waves x 32 rows)
 
@@ -297,29 +296,6 @@ int launch_stack2_fwd(const StackP& p, hipStream_t s);
 // windows and the same saved hi planes as stack2_fwd_kernel, so the plain-bf16 backward kernels follow it unchanged
 int stack2x_fwd_plan(StackP& p);
 int launch_stack2x_fwd(const StackP& p, hipStream_t s);
-#define CRK_PROF_CLASSES 9  // 0-6: conv kernels (crank_hip.h); 7 the VQ search; 8 the on-the-fly log-mel kernel
-void conv_prof_begin(int cls, double flops, hipStream_t s);
-void conv_prof_end(int cls, hipStream_t s);
-void conv_prof_bytes(int cls, double bytes);
-
-// Raises the dynamic-LDS limit of a group of kernel instantiations to `bytes`, all of them on the first call that reaches the
-// statement and never again (one flag per call site and process; a steady-state launch pays one load of it).  Leaves the
-// enclosing launcher with CRK_ERR_HIP where the runtime refuses.
-template <typename... K>
-inline int crk_raise_lds(int bytes, K*... kernels) {
-  for (const void* f : {(const void*)kernels...})
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return CRK_ERR_HIP;
-  return CRK_OK;
-}
-#define CRK_RAISE_LDS_ONCE(bytes, ...)                                        \
-  {                                                                           \
-    static bool lds_raised_ = false;                                          \
-    if (!lds_raised_) {                                                       \
-      if (crk_raise_lds(bytes, __VA_ARGS__) != CRK_OK) return CRK_ERR_HIP;    \
-      lds_raised_ = true;                                                     \
-    }                                                                         \
-  }
-
 void conv_fill_lds(ConvP& p, int mode, bool precise);
 int launch_conv(const ConvP& p, int mode, bool precise, hipStream_t s);
 int wgrad_expand(const WgradP& job, bool precise, std::vector<WgradP>& out);

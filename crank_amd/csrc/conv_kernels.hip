@@ -1,124 +1,12 @@
 // Channel-last Conv1d kernels for gfx950: implicit-GEMM tile conv on
 // v_mfma_f32_32x32x16_bf16 with LDS-staged operands, the fused gated residual block
 // forward, the gate backward, the weight-gradient GEMM and the weight-norm kernels.
+// (The process switches and the HIP-event timing that once lived here: runtime.hip.)
 //
 // Replaces the torch op clusters K1-K4/K12 of SURVEY.md section 2.2 (reference call
 // sites: the parallel_wavegan stacks built at crank/net/module/vqvae2.py:237-273,
 // crank/net/module/spkradv.py:49-60, crank/bin/train.py:78-128).
 #include "conv_kernels.h"
-
-#include <vector>
-
-static inline int al16(int x) { return (x + 15) & ~15; }
-
-static int sw_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-const CrkSwitches& crk_sw() {
-  static const CrkSwitches s = [] {
-    CrkSwitches v;
-    v.sk_v = sw_int("CRK_SK_V", 2); v.skb_v = sw_int("CRK_SKB_V", 2); v.ps_v = sw_int("CRK_PS_V", 2);
-    v.no_fuse = sw_int("CRK_NO_FUSE", 0); v.s2x = sw_int("CRK_S2X", 1); v.disc_split = sw_int("CRK_DISC_SPLIT", 1);
-    v.s2_cfg = sw_int("CRK_S2_CFG", 0);
-    const int nw = sw_int("CRK_SK_NW", 0);
-    v.sk_nw_fwd = nw > 10 ? nw / 10 : nw; v.sk_nw_bwd = nw > 10 ? nw % 10 : nw;
-    v.ps_nw = sw_int("CRK_PS_NW", 0);
-    v.wg_groups = sw_int("CRK_WG_GROUPS", 32); if (v.wg_groups < 1) v.wg_groups = 32;
-    v.wg_cpg = sw_int("CRK_WG_CPG", 0); v.wg_fill = sw_int("CRK_WG_FILL", 1) != 0;
-    v.vq_f16 = sw_int("CRK_VQ_F16", 1) != 0; v.vq_lc = sw_int("CRK_VQ_LC", 2); v.logmel_wave = sw_int("CRK_LOGMEL_WAVE", 1);
-    return v;
-  }();
-  return s;
-}
-
-// ------------------------------------------------------------------------------
-// optional per-kernel-class timing with HIP events on the launch stream (bench.py's
-// roofline leg).  One class per kernel: 0 conv_tile_kernel (generic per-layer conv, all modes),
-// 1 stack_fwd_kernel, 2 stack_bwd_kernel, 3 wgrad_kernel (table), 4 pstack_kernel,
-// 5 stack_wgrad_kernel, 6 pstack_wgrad_kernel.
-// ------------------------------------------------------------------------------
-struct ProfClass {
-  std::vector<hipEvent_t> ev;  // start/stop pairs
-  size_t used = 0;
-  double flops = 0.0;
-  double bytes = 0.0;  // algorithmic HBM bytes (what the launch must move: DESIGN.md section 3)
-};
-static bool g_prof = false;
-static ProfClass g_pc[CRK_PROF_CLASSES];
-
-static void prof_begin(int cls, double flops, hipStream_t s) {
-  if (!g_prof) return;
-  ProfClass& c = g_pc[cls];
-  if (c.used + 2 > c.ev.size()) {
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    c.ev.push_back(a); c.ev.push_back(b);
-  }
-  (void)hipEventRecord(c.ev[c.used], s);
-  c.flops += flops;
-}
-static void prof_end(int cls, hipStream_t s) {
-  if (!g_prof) return;
-  ProfClass& c = g_pc[cls];
-  if (c.used + 2 > c.ev.size()) return;
-  (void)hipEventRecord(c.ev[c.used + 1], s);
-  c.used += 2;
-}
-// Measurement aid (crk_debug_flush_before): a read-modify-write pass over a private buffer larger than the 256 MiB Infinity
-// Cache in front of every profiled conv kernel, so that nothing its producer left in a cache is still there - the A/B that
-// separates what a kernel reads from HBM from what it reads out of the last-level cache.
-static long long g_flush_bytes = 0;
-static float* g_flush_buf = nullptr;
-static long long g_flush_cap = 0;
-__global__ void cache_flush_kernel(float4* buf, long long n16) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n16; i += (long long)gridDim.x * blockDim.x) {
-    float4 v = buf[i];
-    v.x += 1.f;
-    buf[i] = v;
-  }
-}
-extern "C" int crk_debug_flush_before(long long bytes) {
-  if (bytes < 0) return CRK_ERR_ARG;
-  if (bytes > g_flush_cap) {
-    if (g_flush_buf) (void)hipFree(g_flush_buf);
-    g_flush_buf = nullptr; g_flush_cap = 0;
-    if (hipMalloc(&g_flush_buf, (size_t)bytes) != hipSuccess) return CRK_ERR_HIP;
-    if (hipMemset(g_flush_buf, 0, (size_t)bytes) != hipSuccess) return CRK_ERR_HIP;
-    g_flush_cap = bytes;
-  }
-  g_flush_bytes = bytes;
-  return CRK_OK;
-}
-void conv_prof_begin(int cls, double flops, hipStream_t s) {
-  if (g_flush_bytes > 0) hipLaunchKernelGGL(cache_flush_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<float4*>(g_flush_buf), g_flush_bytes / 16);
-  prof_begin(cls, flops, s);
-}
-void conv_prof_end(int cls, hipStream_t s) { prof_end(cls, s); }
-void conv_prof_bytes(int cls, double bytes) { if (g_prof) g_pc[cls].bytes += bytes; }
-extern "C" int crk_prof_enable(int on) {
-  g_prof = on != 0;
-  if (on) for (auto& c : g_pc) { c.used = 0; c.flops = 0.0; c.bytes = 0.0; }
-  return CRK_OK;
-}
-// summed algorithmic HBM bytes of one class since crk_prof_enable(1)
-extern "C" int crk_prof_report_bytes(int cls, double* total_bytes) {
-  if (cls < 0 || cls >= CRK_PROF_CLASSES || !total_bytes) return CRK_ERR_ARG;
-  *total_bytes = g_pc[cls].bytes;
-  return CRK_OK;
-}
-// synchronises on the recorded events; returns launches, summed kernel time and the
-// summed algorithmic FLOPs of one class since crk_prof_enable(1)
-extern "C" int crk_prof_report(int cls, long long* count, double* total_ms, double* total_flops) {
-  if (cls < 0 || cls >= CRK_PROF_CLASSES || !count || !total_ms || !total_flops) return CRK_ERR_ARG;
-  ProfClass& c = g_pc[cls];
-  double ms = 0.0;
-  for (size_t i = 0; i + 1 < c.used; i += 2) {
-    if (hipEventSynchronize(c.ev[i + 1]) != hipSuccess) return CRK_ERR_HIP;
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, c.ev[i], c.ev[i + 1]) != hipSuccess) return CRK_ERR_HIP;
-    ms += t;
-  }
-  *count = (long long)(c.used / 2); *total_ms = ms; *total_flops = c.flops;
-  return CRK_OK;
-}
 
 // MFMA fragment maps (32x32x16 bf16): A lane l holds A[i=l&31][k=8*(l>>5)..+8];
 // B lane l holds B[k=8*(l>>5)..+8][j=l&31]; C/D lane l, reg r holds
@@ -186,7 +74,6 @@ __device__ __forceinline__ float gate_sigmoid(float x, bool precise) {
 
 // named fields instead of an array: the prefetch registers live across the (runtime)
 // chunk loop and an indexed local array ends up in scratch
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct WRegs {
   u32x4 h0, h1, h2, h3, h4, h5, h6, h7;
   u32x4 l0, l1, l2, l3, l4, l5, l6, l7;
@@ -535,17 +422,17 @@ void conv_fill_lds(ConvP& p, int mode, bool precise) {
   p.ws_stride = kmax * 2 + 16;
   p.zs_stride = 64 * 2 + 16;
   int off = 0;
-  const int xbytes = al16(rows * p.xs_stride);
+  const int xbytes = round_up(rows * p.xs_stride, 16);
   off += xbytes;
   p.o_xlo = off; if (precise) off += xbytes;
-  const int cbytes = (mode == MODE_RESFWD && p.cinC > 0) ? al16(CRK_TM * p.cs_stride) : 0;
+  const int cbytes = (mode == MODE_RESFWD && p.cinC > 0) ? round_up(CRK_TM * p.cs_stride, 16) : 0;
   p.o_chi = off; off += cbytes;
   p.o_clo = off; if (precise) off += cbytes;
   const int wrows = (mode == MODE_RESFWD) ? 128 : p.cout_pad;
-  const int wbytes = al16(wrows * p.ws_stride);
+  const int wbytes = round_up(wrows * p.ws_stride, 16);
   p.o_whi = off; off += wbytes;
   p.o_wlo = off; if (precise) off += wbytes;
-  const int zbytes = (mode == MODE_RESFWD) ? al16(CRK_TM * p.zs_stride) : 0;
+  const int zbytes = (mode == MODE_RESFWD) ? round_up(CRK_TM * p.zs_stride, 16) : 0;
   p.o_zhi = off; off += zbytes;
   p.o_zlo = off; if (precise) off += zbytes;
   p.lds_bytes = off;
@@ -595,9 +482,9 @@ int launch_conv(const ConvP& p, int mode, bool precise, hipStream_t s) {
   const double nfr = (double)p.B * p.T;
   double fl = 2.0 * nfr * p.cout * p.cin * p.ktaps;
   if (mode == MODE_RESFWD) fl += 2.0 * nfr * 128.0 * (p.cinC + 64);
-  prof_begin(0, fl, s);
+  conv_prof_begin(0, fl, s);
   hipLaunchKernelGGL(f, grid, block, p.lds_bytes, s, p);
-  prof_end(0, s);
+  conv_prof_end(0, s);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
@@ -646,10 +533,10 @@ int launch_wgrad_table(const WgradP* d_jobs, const std::vector<WgradP>& h_jobs, 
   }
   CRK_RAISE_LDS_ONCE(152 * 1024, wgrad_kernel<true>, wgrad_kernel<false>)
   dim3 grid(max_groups, (unsigned)h_jobs.size()), block(256);
-  prof_begin(3, fl, s);
+  conv_prof_begin(3, fl, s);
   if (precise) hipLaunchKernelGGL(wgrad_kernel<true>, grid, block, lds, s, d_jobs, B, T);
   else hipLaunchKernelGGL(wgrad_kernel<false>, grid, block, lds, s, d_jobs, B, T);
-  prof_end(3, s);
+  conv_prof_end(3, s);
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }

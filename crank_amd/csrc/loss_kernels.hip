@@ -11,6 +11,8 @@
 
 #include "common.h"
 
+#include "../../include/crank_hip.h"
+
 __device__ __forceinline__ float block_sum_256(float v, float* sh) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -1245,13 +1247,6 @@ extern "C" int crk_adam_step(float* params, float* grads, float* exp_avg, float*
 // ... over several blocks (the models whose updates of a step are adjacent and independent) in ONE launch: workgroup x
 // belongs to the block whose range holds it and walks that block exactly as adam_kernel walks it alone - each block with
 // its own lr and step count, the same arithmetic per element
-#define CRK_ADAM_MAX_BLOCKS 4
-struct crk_adam_block {  // (the C ABI's record, include/crank_hip.h)
-  float *params, *grads, *exp_avg, *exp_avg_sq;
-  long long n;
-  const float* lr_dev;
-  float* step_dev;
-};
 struct AdamBlocks { crk_adam_block b[CRK_ADAM_MAX_BLOCKS]; int first[CRK_ADAM_MAX_BLOCKS + 1]; int n; };
 template <bool CLEAR>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamBlocks A, float beta1, float beta2, float eps) {

@@ -9,11 +9,9 @@
 // magnitudes stay in LDS and the mel projection is a dense matvec against the
 // L2-resident filterbank (only each filter's nonzero run of bins).  HBM traffic is the raw samples once (hop/n_fft overlap is
 // served by L2) plus n_mels floats per frame.
-#include "common.h"
-#include "switches.h"
-void conv_prof_begin(int cls, double flops, hipStream_t s);  // (conv_kernels.hip: bench.py's per-class HIP-event timing; class 8)
-void conv_prof_end(int cls, hipStream_t s);
-void conv_prof_bytes(int cls, double bytes);
+#include "runtime.h"  // (bench.py's per-class HIP-event timing: class 8)
+
+#include "../../include/crank_hip.h"
 
 #define MLFB_MAX_FFT 2048
 
@@ -334,5 +332,3 @@ extern "C" int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples
   CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
-
-extern "C" const char* crk_version(void) { return "crank_hip 0.1 (gfx950)"; }

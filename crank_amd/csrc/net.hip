@@ -19,16 +19,7 @@
 
 #include "conv_kernels.h"
 
-struct crk_net_desc {
-  int kind;
-  int in_ch, out_ch, kernel_size, layers, stacks;
-  int res_ch, gate_ch, skip_ch, aux_ch;
-  int conv_ch;
-  int causal;
-  int use_bias;
-  float slope;
-  float dropout;
-};
+#include "../../include/crank_hip.h"
 
 enum { ROLE_FIRST = 0, ROLE_CONV = 1, ROLE_AUX = 2, ROLE_OUT = 3, ROLE_SKIP = 4, ROLE_LAST1 = 5, ROLE_LAST2 = 6, ROLE_PLAIN = 7 };
 
@@ -60,7 +51,7 @@ static int not_reserved(const char* what) {
 }
 
 #define PS_MAXL 16
-// host copies of the fused plain-conv chain tables (pstack_kernels.hip): [0] first/forward, [1] head forward / backward,
+// host copies of the fused plain-conv chain tables (pstack_kernels.hip, pstack_wgrad_kernels.hip): [0] first/forward, [1] head forward / backward,
 // [2] head backward, [3] first backward; w: the weight-gradient table
 struct PsTables { PsLayer t[4][PS_MAXL]; int L[4]; PwLayer w[PS_MAXL]; int nw; int max_wa, max_wb, max_tiles; double wflops_per_frame; };
 // what a batch shape needs: scratch / partial-sum floats, the slot counts of the two weight-gradient regions, the 64-frame

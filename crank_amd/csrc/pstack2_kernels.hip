@@ -74,7 +74,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
   // would need a waterfall loop per load)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mtw = wave & 1, fh = wave >> 1;
-  SK_PROF_BEGIN(1)
+  SK_PROF_BEGIN()
   const int b = blockIdx.x / p.tiles_per_utt, tile = blockIdx.x - b * p.tiles_per_utt;
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T, N = (long)p.B * p.T;
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(NFH * 128, NFH == 2 ? 2 : 1) void pstack2_kernel(co
   }
 #undef PS2_LOADA
 #undef PS2_LOADA_RANGE
-  SK_PROF_END(1, 5)
+  SK_PROF_END(5)
 }
 
 int pstack2_plan(PsP& p, const PsLayer* host_layers) {

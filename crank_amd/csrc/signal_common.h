@@ -4,7 +4,7 @@
 // stream, SPTK freqt of a unit vector, a handle's block of host-made tables, a grow-only device table and the carving of a
 // caller's workspace.
 #pragma once
-#include "common.h"
+#include "runtime.h"
 #include <math.h>
 #include <stddef.h>
 #include <algorithm>
@@ -15,7 +15,6 @@
 #define W_LOGN 10
 #define W_THREADS 256
 
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 static size_t w_align(size_t b) { return (b + 255) & ~(size_t)255; }
 

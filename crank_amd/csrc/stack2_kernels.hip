@@ -59,7 +59,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
   const int t0 = tile * p.tmo;
   const long nbase = (long)b * p.T;
   const long P = (long)p.B * p.T * 64;
-  SK_PROF_BEGIN(1)
+  SK_PROF_BEGIN()
 
   unsigned char* xs = smem;             // [SK_GUARD + R + SK_GUARD][XS] block input as the conv sees it
   unsigned char* zs = smem + p.o_zs;    // [R][XS] gate output
@@ -633,7 +633,7 @@ __device__ __forceinline__ void s2_wave(const StackP& p, unsigned char* smem, co
         __builtin_amdgcn_raw_buffer_store_b128(v, r_sk, voff_st[ft] + q * 32, 0, 0);
       }
   }
-  SK_PROF_END(1, 7)
+  SK_PROF_END(7)
 }
 
 template <int KT, int AKC, int FT, int FH, bool DROP, bool FOLD, int FT1 = FT>

@@ -71,7 +71,7 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
   const long nbase = (long)b * p.T;
   const long N = (long)p.B * p.T, P = N * 64;
 
-  SK_PROF_BEGIN(1)
+  SK_PROF_BEGIN()
   unsigned char* gs = smem;            // [SK_GUARD + R + SK_GUARD][GS] dG_l (prologue: scratch for the dS exchange)
   unsigned char* xt = smem + p.o_dx;   // [R][XS] sqrt(.5) dX_{l+1} as the 1x1's operand (prologue: G1; epilogue: dX_0)
   unsigned char* dst = xt + R * XS;    // [R][XS] bf16 dS: the other half of the 1x1's operand, the same for every block
@@ -547,7 +547,7 @@ __device__ __forceinline__ void s2b_wave(const StackBP& p, unsigned char* smem, 
     }
   }
   SK_T(6)
-  SK_PROF_END(1, 7)
+  SK_PROF_END(7)
 }
 
 // four waves, one per SIMD: two frame halves of FT tiles each

@@ -1,8 +1,8 @@
 // Device helpers shared by the fused stack kernels (stack*_kernels.hip, pstack*_kernels.hip), their phase timer and their
-// ablation stand-ins.  Include after conv_kernels.h (PsLayer).
+// ablation stand-ins.
 #ifndef CRK_STACK_COMMON_H
 #define CRK_STACK_COMMON_H
-#include "common.h"
+#include "conv_kernels.h"  // PsLayer (ps_uniform)
 
 #define SK_GUARD 16  // zero guard rows above and below the operand tile (>= largest tap offset)
 #define SK_XS 144    // operand row stride: 64 bf16 + 16 B pad (conflict-free ds_read_b128)
@@ -171,13 +171,12 @@ __device__ __forceinline__ bf16x8 sk_fake_frag(const unsigned char* p) {
 #define lds_frag(p) sk_fake_frag(p)
 #endif
 
-// ---- phase timer of the stack kernels (tools/phase_cycles.py builds ONE kernel file with -DSK_PROF=<n>) ----
-// A timed kernel opens with SK_PROF_BEGIN(n), marks the end of phase i with SK_T(i) - the shader cycles since the previous
-// mark are added to slot i of the wave - and closes with SK_PROF_END(n, total): slot `total` gets the wave's whole life, lane
+// ---- phase timer of the stack kernels (tools/phase_cycles.py builds ONE kernel file with -DSK_PROF=1) ----
+// A file holds at most one timed kernel.  It opens with SK_PROF_BEGIN(), marks the end of phase i with SK_T(i) - the shader cycles
+// since the previous mark are added to slot i of the wave - and closes with SK_PROF_END(total): slot `total` gets the wave's whole life, lane
 // 0 of each of the first SK_PROF_WAVES waves writes the wave's slots, and thread 0 the workgroup's row of sk_prof_res: start
 // and end (s_memrealtime, 100 MHz), HW_ID, XCC_ID.  Workgroup 0 also writes the launch's row behind them: workgroups, waves
-// per workgroup.  n says which kernel of the file is timed (pstack_kernels.hip holds two); the other one's marks are dead
-// code.  Workgroups past the first SK_PROF_WGS of a launch are not recorded.  The buffers belong to the translation unit;
+// per workgroup.  Workgroups past the first SK_PROF_WGS of a launch are not recorded.  The buffers belong to the translation unit;
 // crk_debug_sk_prof copies them out and clears them, so what the next call returns was written after this one.
 #ifdef SK_PROF
 #define SK_PROF_WGS 1024
@@ -196,13 +195,12 @@ extern "C" int crk_debug_sk_prof(unsigned long long* cycles, unsigned long long*
     return CRK_ERR_HIP;
   return CRK_OK;
 }
-#define SK_PROF_BEGIN(n)                                                                        \
-  constexpr bool pon_ = (SK_PROF) == (n);                                                       \
+#define SK_PROF_BEGIN()                                                                         \
   unsigned long long pacc_[SK_PROF_SLOTS] = {}, plast_ = __builtin_readcyclecounter();          \
   const unsigned long long pstart_ = plast_, preal_ = __builtin_amdgcn_s_memrealtime();
-#define SK_T(i) { if (pon_) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc_[i] += now_ - plast_; plast_ = now_; } }
-#define SK_PROF_END(n, total)                                                                   \
-  if (pon_) {                                                                                   \
+#define SK_T(i) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc_[i] += now_ - plast_; plast_ = now_; }
+#define SK_PROF_END(total)                                                                      \
+  {                                                                                             \
     pacc_[total] = __builtin_readcyclecounter() - pstart_;                                      \
     const unsigned pwg_ = blockIdx.y * gridDim.x + blockIdx.x, pwave_ = threadIdx.x >> 6;       \
     if (pwg_ < SK_PROF_WGS && (threadIdx.x & 63) == 0 && pwave_ < SK_PROF_WAVES) {              \
@@ -222,9 +220,9 @@ extern "C" int crk_debug_sk_prof(unsigned long long* cycles, unsigned long long*
     }                                                                                           \
   }
 #else
-#define SK_PROF_BEGIN(n)
+#define SK_PROF_BEGIN()
 #define SK_T(i)
-#define SK_PROF_END(n, total)
+#define SK_PROF_END(total)
 #endif
 
 #endif

@@ -26,13 +26,12 @@
 
 #include <vector>
 
-#include "common.h"
+#include "runtime.h"
 #include "../../include/crank_hip.h"
 #include "vq_common.h"
 
 #pragma clang fp contract(off)
 
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 #define ST_THREADS 256
 #define ST_TILE 64      // frames resident in LDS

@@ -1,4 +1,4 @@
-// The library's A/B switches, read from the environment ONCE per process (crk_sw(), conv_kernels.hip).  None is needed in
+// The library's A/B switches, read from the environment ONCE per process (crk_sw(), runtime.hip).  None is needed in
 // normal use: each selects an older generation of a kernel that stays in the library as the reference of a bitwise test
 // (tests/test_gpu_properties.py), or a shape parameter of a measurement (tools/).  Defaults in brackets.
 //   CRK_SK_V [2]        1: frame-split forward kernels without the folds (stack_fwd_kernel)

@@ -16,14 +16,13 @@
 // T = 0 and nothing else.  The arithmetic is the offline kernels' own (voc_common.h), one launch per stage over all
 // streams: 2 + 1 + n_scales + layers launches per push whatever S, C, n_valid and end are; grids cover the worst case
 // and a workgroup past its stream's range exits before it touches LDS.
-#include "common.h"
+#include "runtime.h"
 #include "voc_common.h"
 #include "../../include/crank_hip.h"
 #include <limits.h>
 #include <math.h>
 #include <vector>
 
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 #define VS_MAX_SAMPLES 0x3fffffff  // an utterance's samples: positions and position + dilation stay inside int
 

@@ -21,14 +21,13 @@
 //  * the arithmetic of all three kernels lives in voc_common.h and voc_layer_tile.inc, one body per piece, shared with the
 //    streaming kernels (voc_stream_kernels.hip); the kernels here say where a position's operands are in the flat planes
 //    of a ragged batch.
-#include "common.h"
+#include "runtime.h"
 #include "voc_common.h"
 #include "../../include/crank_hip.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
 
-long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count
 
 struct VocLayerArgs {
   VocLayerW w;

@@ -20,13 +20,10 @@
 // associative, so the statistics - and the codebook derived from them - are bitwise
 // reproducible run to run and identical on every data-parallel rank after an
 // integer all-reduce, whatever order the adds land in.
-#include "common.h"
-#include "switches.h"
+#include "runtime.h"  // (HIP-event timing per kernel class for bench.py's roofline leg; class 7 = the codebook search)
 #include "vq_common.h"
-// (conv_kernels.hip: HIP-event timing per kernel class for bench.py's roofline leg; class 7 = the codebook search)
-void conv_prof_begin(int cls, double flops, hipStream_t s);
-void conv_prof_end(int cls, hipStream_t s);
-void conv_prof_bytes(int cls, double bytes);
+
+#include "../../include/crank_hip.h"
 
 #define VQ_FRAMES 128
 #define VQ_FIX_SCALE 268435456.0f        // 2^28

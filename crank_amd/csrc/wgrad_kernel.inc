@@ -275,6 +275,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradP* __restrict__ j
 int wgrad_entry_lds(const WgradP& p, bool precise) {
   const int cxp = p.grp_aux ? p.cc_pad : p.cx_pad;
   const int nfs = WG_FR + (p.grp_aux ? 0 : (p.grp_ntap - 1) * p.dil);
-  const int abytes = al16(WG_FR * wg_row_stride(p.ca_pad)), bbytes = al16(nfs * wg_row_stride(cxp));
+  const int abytes = round_up(WG_FR * wg_row_stride(p.ca_pad), 16), bbytes = round_up(nfs * wg_row_stride(cxp), 16);
   return (precise ? 2 : 1) * (abytes + bbytes);
 }

@@ -19,7 +19,7 @@ WGS, WAVES, SLOTS = 1024, 8, 16
 GATED = (("enc0", 80, 64, 5, 8, 4, 0), ("dec0", 128, 80, 5, 8, 4, 34), ("enc1", 64, 64, 3, 6, 3, 0))
 PLAIN = ("C", "SPKRADV")
 
-# src / flag: the one source built with the timer on and the flag that selects the kernel in it.  slots: the names of the
+# src / flag: the one source built with the timer on (a source holds one timed kernel) and the flag that turns it on.  slots: the names of the
 # kernel's slots in its own numbering (the comment above the kernel), total: the slot of the wave's whole life.  waves: how many
 # waves of a workgroup the report shows.  env: the CRK_* switches (csrc/switches.h) that make the route choose the kernel.
 # work: what runs (below).  per_block: slots also printed divided by the stack's block count.
@@ -43,7 +43,7 @@ KERNELS = {
                 slots=["pro: operand -> LDS + barrier", "fragment wait + MFMAs", "next fragments + epilogue", "barrier", "pro: requests",
                        "TOTAL", "pro: table, guards", "pro: biases"],
                 per_block=()),
-    "pw": dict(src="pstack_kernels.hip", flag="-DSK_PROF=2", kernel="pstack_wgrad_body", work="plain_wgrad", waves=4, total=5, env={},
+    "pw": dict(src="pstack_wgrad_kernels.hip", flag="-DSK_PROF=1", kernel="pstack_wgrad_body", work="plain_wgrad", waves=4, total=5, env={},
                slots=["set-up", "barrier + tiles -> LDS + barrier", "next requests", "fragments + MFMAs", "partial sums out", "TOTAL"],
                per_block=()),
 }
