@@ -33,6 +33,9 @@ def mcd_fastdtw(cv_mceps, cv_f0s, gt_mceps, gt_f0s, radius=1, return_paths=False
             raise ValueError("all mel-cepstra must be (frames, D) with the same D")
         if a.shape[0] == 0:
             raise ValueError("an utterance has no voiced frame")
+        if not np.isfinite(a).all():
+            # the package's backtrack dies on these (KeyError); the kernel would return a truncated path and a NaN
+            raise ValueError("a voiced frame holds a non-finite value")
     nx, ny = [a.shape[0] for a in cv], [a.shape[0] for a in gt]
     dev = torch.device(device)
     up = lambda arrs: torch.as_tensor(np.concatenate(arrs), device=dev)  # noqa: E731

@@ -240,11 +240,13 @@ extern "C" long long crk_mcd_scratch_bytes(int P, int max_nx, int max_ny, int D,
 extern "C" int crk_mcd_fastdtw(const double* cv, const long long* cv_off, const double* gt, const long long* gt_off, int P,
                                int D, int radius, int max_nx, int max_ny, double* mcd, int* path_len, int* path_out,
                                long long path_stride, void* scratch, int* status, void* stream) {
-  if (!cv || !cv_off || !gt || !gt_off || !mcd || !path_len || !scratch || !status || P <= 0 || D <= 0 || radius < 1)
-    return CRK_ERR_ARG;
-  const int wmax = max_ny + 2 > max_nx + 2 ? max_ny + 2 : max_nx + 2;  // row costs; also the int scratch of the window expansion
+  if (P <= 0 || D <= 0 || radius < 1 || max_nx <= 0 || max_ny <= 0) return CRK_ERR_ARG;
+  // the size envelope is judged before the pointers, so that it can be probed without a launch
+  const long long wlong = (long long)(max_ny > max_nx ? max_ny : max_nx) + 2;
+  if (3 * wlong * (long long)sizeof(double) > 150 * 1024) return CRK_ERR_UNSUPPORTED;  // more than 6398 voiced frames
+  if (!cv || !cv_off || !gt || !gt_off || !mcd || !path_len || !scratch || !status) return CRK_ERR_ARG;
+  const int wmax = (int)wlong;  // row costs; also the int scratch of the window expansion
   const size_t lds = (size_t)3 * wmax * sizeof(double);
-  if (lds > 150 * 1024) return CRK_ERR_UNSUPPORTED;  // sequences longer than ~6000 voiced frames
   static bool attr_set = false;
   if (!attr_set) {
     if (hipFuncSetAttribute((const void*)mcd_dtw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)

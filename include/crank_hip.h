@@ -494,7 +494,9 @@ int crk_decode_f0(const float* lcf0, const float* uv, int B, int T, const int* o
  * restated from its published algorithm, oracle/mcd.py) and mcd[p] = mean over the path of
  * 10 / ln 10 * sqrt(2 * sum_d (cv - gt)^2).  path_out (optional): path_stride ints per pair,
  * (i, j) pairs from start to end; path_len[p] = number of pairs.  status[p] = 1: pair too long
- * for the scratch / LDS sizing (max_nx, max_ny must bound every pair).  One wavefront per pair. */
+ * for the scratch / LDS sizing (max_nx, max_ny must bound every pair).  One wavefront per pair.
+ * CRK_ERR_ARG for a non-positive count or a null pointer, CRK_ERR_UNSUPPORTED for max(max_nx, max_ny)
+ * above 6398 (three rows of max + 2 doubles must fit 150 KB of LDS); the sizes are judged first. */
 long long crk_mcd_scratch_bytes(int P, int max_nx, int max_ny, int D, int radius);
 int crk_mcd_fastdtw(const double* cv, const long long* cv_off, const double* gt, const long long* gt_off, int P, int D,
                     int radius, int max_nx, int max_ny, double* mcd, int* path_len, int* path_out,
