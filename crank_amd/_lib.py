@@ -125,6 +125,12 @@ SIGNATURES = {
     "crk_concat_embed_run": (I, [P, I, I, P, I, I, P, I, P, LL, LL, P, I, P]),
     "crk_embed_bwd_run": (I, [P, I, I, I, P, LL, LL, I, P, P, P]),
     "crk_logmel_fwd": (I, [P, I, I, I, I, I, I, I, P, P, I, F, P, P, P, I, I, P]),
+    "crk_logmel_stream_create": (I, [I, I, I, P, P, I, F, P, P, I, I, I, ctypes.POINTER(c_void_p)]),
+    "crk_logmel_stream_destroy": (None, [P]),
+    "crk_logmel_stream_state_bytes": (LL, [P]),
+    "crk_logmel_stream_max_frames": (I, [P]),
+    "crk_logmel_stream_reset": (I, [P, P, I, P]),
+    "crk_logmel_stream_push": (I, [P, P, I, P, P, I, I, P, I, P, P]),
     "crk_scaler_apply": (I, [P, I, P, I, LL, I, P, P, I, P]),
     "crk_scaler_workspace_bytes": (LL, [I, I]),
     "crk_scaler_moments": (I, [P, I, I, I, LL, P, P, I, P, LL, P]),

@@ -9,10 +9,14 @@ Only the fixed-window variants are implemented ("hann", "hamming", ... =
 ``torch.<name>_window``); the trainable "param" / "conv" window variants of the
 reference's STFTLayer (mlfb.py:64-90) are rejected.
 """
+import ctypes
+
 import numpy as np
 import torch
 
-from ... import ops
+from ... import _lib, ops
+from ..._lib import check, stream_ptr
+from ..._ragged import made, release, require_gpu
 
 
 def slaney_mel_basis(sr, n_fft, n_mels, fmin, fmax):
@@ -77,6 +81,116 @@ class LogMelFilterBankLayer(torch.nn.Module):
             T = 1 + (x.shape[1] - self.fft_size) // self.hop_size
         return ops.logmel(x, T, self.fft_size, self.hop_size, self.win_length, self.window, self.mel_basis, self.eps,
                           self.mean, self.std, center=self.center)
+
+    def streaming(self, n_streams, max_samples):
+        """A ``StreamingLogMel`` with this layer's framing, basis and scaler: up to ``n_streams`` streams, ``max_samples``
+        samples a push."""
+        return StreamingLogMel(self, n_streams, max_samples)
+
+
+def frames_ready(n_total, fft_size, hop_size, center, end=False):
+    """Frames of an utterance that exist once ``n_total`` samples of it have arrived (``end``: it is over at ``n_total``)."""
+    h = fft_size // 2
+    if center:
+        if n_total <= h:
+            return 0  # reflect padding needs more than h samples: the offline call refuses such an utterance
+        return 1 + n_total // hop_size if end else (n_total - h) // hop_size + 1
+    return 0 if n_total < fft_size else (n_total - fft_size) // hop_size + 1
+
+
+class StreamingLogMel:
+    """``push`` takes the next samples of up to ``n_streams`` independent streams, at most ``max_samples`` each per push,
+    and returns the log-mel frames that have become computable (csrc/logmel_stream_kernels.hip, ``crk_logmel_stream_*``).
+    Stream i is row i of every argument.
+
+    The frames of an utterance are those of the layer on the whole signal - the same count, and values within fp32
+    rounding of the offline kernel's - and they do not depend, bit for bit, on how the signal is cut into pushes, on S
+    or on the row.  A centred layer emits frame t once sample ``t * hop + fft_size // 2 - 1`` has arrived; the push that
+    carries the stream's ``end`` flag emits the frames that need the right mirror and starts a new utterance.  An
+    uncentred layer has nothing to flush: ``end`` only starts a new utterance.  The last ``fft_size`` samples and both
+    counts of every stream stay on the device; a push launches two kernels, neither allocates nor reads back, and can be
+    captured in a graph.  There is no torch or CPU fallback.
+
+    ``n_frames`` goes straight into ``StreamingConverter.push(..., n_valid=n_frames)`` with ``feats`` as the chunk: build
+    that converter with ``max_chunk >= max_frames``."""
+
+    def __init__(self, layer, n_streams, max_samples):
+        if n_streams < 1 or max_samples < 1:
+            raise RuntimeError(f"n_streams = {n_streams}, max_samples = {max_samples}: both must be at least 1")
+        self.layer, self.device = layer, layer.mel_basis.device
+        require_gpu(self.device, "the streaming log-mel front end", "the layer's device")
+        self.n_streams, self.max_samples = int(n_streams), int(max_samples)
+        self.fft_size, self.hop_size, self.center = layer.fft_size, layer.hop_size, layer.center
+        self.n_mels = int(layer.mel_basis.shape[1])
+        h = ctypes.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            check(L.crk_logmel_stream_create(
+                layer.fft_size, layer.hop_size, layer.win_length, layer.window.contiguous().data_ptr(),
+                layer.mel_basis.contiguous().data_ptr(), self.n_mels, float(layer.eps), _lib.ptr(layer.mean),
+                _lib.ptr(layer.std), 1 if layer.center else 0, self.n_streams, self.max_samples, ctypes.byref(h)),
+                "crk_logmel_stream_create")
+            self._handle = made(h, "crk_logmel_stream_create")
+        self.max_frames = int(L.crk_logmel_stream_max_frames(self._handle))
+
+    def __del__(self):
+        release(self, "_handle", "crk_logmel_stream_destroy")
+
+    @property
+    def state_bytes(self):
+        return int(_lib.lib().crk_logmel_stream_state_bytes(self._handle))
+
+    def frames_ready(self, n_total, end=False):
+        """Frames of an utterance emitted once ``n_total`` samples of it were pushed (``end``: with the end flag)."""
+        return frames_ready(n_total, self.fft_size, self.hop_size, self.center, end)
+
+    def reset(self, streams=None):
+        """``streams`` (all of them by default) start a new utterance; frames not emitted yet are dropped."""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            if streams is None:
+                check(L.crk_logmel_stream_reset(self._handle, None, 0, stream_ptr()), "crk_logmel_stream_reset")
+            else:
+                ids = [int(s) for s in streams]
+                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
+                check(L.crk_logmel_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_logmel_stream_reset")
+
+    def empty_outputs(self, S):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
+        return {"feats": torch.empty(S, self.max_frames, self.n_mels, device=self.device),
+                "n_frames": torch.empty(S, dtype=torch.int32, device=self.device)}
+
+    def _flags(self, t, S, what):
+        if t is None:
+            return None
+        if t.device.type != "cuda" or tuple(t.shape) != (S,) or t.dtype not in (torch.int32, torch.int64, torch.bool):
+            raise ValueError(f"{what}: an integer ({S},) tensor on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.to(torch.int32).contiguous()
+
+    def push(self, x, n_valid=None, end=None, out=None):
+        """x (S, C) float32 samples, n_valid (S,) samples that count per stream (default: C; 0 is allowed), end (S,)
+        non-zero where this push ends the stream's utterance.  Returns ``feats`` (S, max_frames, n_mels) and ``n_frames``
+        (S,) int32: the frames written at the start of each stream's block; frames past ``n_frames`` are not written.
+        S above ``n_streams`` or C above ``max_samples`` is refused by the library (RuntimeError) before anything runs.
+        out: buffers to write into (``empty_outputs``), e.g. the static ones of a captured graph."""
+        if x.dim() != 2 or x.device.type != "cuda" or x.dtype != torch.float32:
+            raise ValueError(f"x: a float32 (S, C) tensor on the GPU, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        S, C = int(x.shape[0]), int(x.shape[1])
+        x = x.contiguous()
+        n_valid, end = self._flags(n_valid, S, "n_valid"), self._flags(end, S, "end")
+        if out is None:
+            out = self.empty_outputs(S)
+        else:
+            f, n = out["feats"], out["n_frames"]
+            if (f.device.type != "cuda" or f.dtype != torch.float32 or tuple(f.shape) != (S, self.max_frames, self.n_mels)
+                    or not f.is_contiguous() or n.device.type != "cuda" or n.dtype != torch.int32 or tuple(n.shape) != (S,)):
+                raise ValueError(f"out: feats float32 ({S}, {self.max_frames}, {self.n_mels}) and n_frames int32 ({S},) on "
+                                 "the GPU (empty_outputs)")
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_logmel_stream_push(
+                self._handle, x.data_ptr(), C, _lib.ptr(n_valid), _lib.ptr(end), S, C, out["feats"].data_ptr(), self.n_mels,
+                out["n_frames"].data_ptr(), stream_ptr()), "crk_logmel_stream_push")
+        return out
 
 
 _LAYERS = {}

@@ -8,9 +8,14 @@ dilation`` frames of that layer's input on the device and computes only the new 
 depend on how an utterance is cut into pushes - bit for bit - and equal the offline forward within fp32 rounding
 (the kernels are fp32 throughout; ``CRANK_AMD_PRECISION`` does not apply).  There is no torch or CPU fallback.
 
-What stays with the caller: the acoustic front end that produces the scaled input features, the F0 conversion
-(``BaseTrainer._decode_f0`` / ``crk_decode_f0`` work frame by frame, so they apply to a chunk as they do to an utterance),
-and waveform synthesis: ``crank_amd.vocoder.StreamingVocoder`` turns the decoded chunks into sound, 16 frames behind them.
+The stages either side are in the package too: ``LogMelFilterBankLayer.streaming`` (``crank_amd.net.module.mlfb.
+StreamingLogMel``) turns pushes of samples into the scaled log-mel frames that have become computable - its ``n_frames``
+is this class's ``n_valid``, so build the converter with ``max_chunk >= StreamingLogMel.max_frames`` - and
+``crank_amd.vocoder.StreamingVocoder`` turns the decoded chunks into sound, 16 frames behind them.
+
+What stays with the caller: the F0 contour of ``decoder_f0`` / ``encoder_f0`` models (Harvest here sees whole utterances;
+the conversion itself, ``BaseTrainer._decode_f0`` / ``crk_decode_f0``, works frame by frame, so it applies to a chunk as
+it does to an utterance), and ``use_raw`` models, which ``check_stream_conf`` refuses: feed them scaled features.
 """
 import ctypes
 

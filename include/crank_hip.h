@@ -365,6 +365,46 @@ int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples, int T, in
                    const float* window, const float* mel_basis /* [n_bins][n_mels] */, int n_mels, float eps,
                    const float* mean, const float* std, float* out, int ldo, int center, void* stream);
 
+/* ---- Streaming log-mel front end ---------------------------------------------------------------------------------
+ * crk_logmel_fwd's frames for up to n_streams concurrent streams that receive their utterances as pushes of new samples,
+ * at most max_samples each per push.  With n the samples a stream has received in its utterance and h = n_fft / 2:
+ *   center = 1: frame t covers [t hop - h, t hop + h) with the reflect rule at both ends; ready(n) = 0 for n <= h, else
+ *     (n - h) / hop + 1.  A push whose end flag is set for a stream emits everything up to 1 + n / hop, the right mirror
+ *     taken at the final n (nothing when n <= h: the offline call refuses such an utterance), and returns that stream to
+ *     the start-of-utterance state.
+ *   center = 0: frame t covers [t hop, t hop + n_fft); ready(n) = 0 for n < n_fft, else (n - n_fft) / hop + 1; the end flag
+ *     emits nothing more and resets the stream.
+ * A push emits frames ready(before) .. ready(after) - 1 and nothing else; over an utterance these are the frames of
+ * crk_logmel_fwd on the whole signal, however it is cut into pushes.  Every frame is transformed alone: its bits
+ * depend on its own n_fft samples and the configuration alone (not on the cut, S, the row or the frames beside it), and
+ * agree with crk_logmel_fwd's within fp32 rounding, not bit for bit (its n_fft = 1024 kernel pairs frames).  Clamp, log10,
+ * the value of a clamped cell and (v - mean) / std are crk_logmel_fwd's.
+ *
+ * crk_logmel_stream_create is the one call that allocates (it synchronises): per stream a ring of the last n_fft samples
+ * and two 64-bit counts, and the handle's own copies of window [win_length], mel_basis [n_bins][n_mels], mean / std
+ * [n_mels] (both or neither; host or device pointers) with the twiddle and filter-run tables made from them.
+ * CRK_ERR_ARG: n_fft not a power of two in 256 .. 2048, win_length outside 1 .. n_fft, hop < 1, n_mels outside 1 .. 256,
+ * n_streams or max_samples < 1, a null window, basis or handle.  crk_logmel_stream_state_bytes: the size of the
+ * allocation.  crk_logmel_stream_max_frames: the largest count one push can emit over all histories, the end flush
+ * included - (max_samples + hop - 1) / hop uncentred, 1 + (h + max_samples) / hop centred.
+ * crk_logmel_stream_reset: the streams listed in the HOST array stream_ids (NULL: every stream) start a new utterance.
+ * crk_logmel_stream_push: x fp32 [S][C] with row stride ldx, n_valid / end DEVICE int32 [S] (NULL: C / 0; samples at and
+ * past n_valid are ignored, n_valid may be 0), out fp32 [S][max_frames][n_mels] with row stride ldo, n_frames DEVICE
+ * int32 [S]: the frames written per stream from the start of its block, written for every stream; frames at and past
+ * n_frames are not written.  Stream i is row i.  Judged before any launch, output and state untouched: CRK_ERR_ARG for
+ * a null pointer, S < 1, C < 0, ldx < C, ldo < n_mels; CRK_ERR_UNSUPPORTED for S > n_streams or C > max_samples.  Every
+ * position lives on the device: a push never allocates, never synchronises and reads nothing back (it can be captured in
+ * a graph), and launches 2 kernels whatever S, C, n_valid and end are. */
+int crk_logmel_stream_create(int n_fft, int hop, int win_length, const float* window, const float* mel_basis, int n_mels,
+                             float eps, const float* mean, const float* stdv, int center, int n_streams, int max_samples,
+                             void** handle);
+void crk_logmel_stream_destroy(void* st);
+long long crk_logmel_stream_state_bytes(void* st);
+int crk_logmel_stream_max_frames(void* st);
+int crk_logmel_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_logmel_stream_push(void* st, const float* x, int ldx, const int* n_valid, const int* end, int S, int C, float* out,
+                           int ldo, int* n_frames, void* stream);
+
 /* ---- batch assembly from an HBM-resident corpus -----------------
  * Replaces the numpy work of BaseDataset.__getitem__ in the reference's DataLoader workers,
  * torch's default collate and the per-batch host->device copy
