@@ -34,9 +34,7 @@
 #include <vector>
 
 #define LS_MIN_FFT 256
-#define LS_MAX_FFT 2048
-#define LS_THREADS 256
-#define LS_WTAB 2048
+#define LS_THREADS 256  // (lm_radix2_magnitudes is written for a workgroup of 256)
 
 struct LsGeom {
   int n_fft, log2n, hop, n_mels, center, scaler, max_frames;
@@ -48,7 +46,7 @@ struct LsGeom {
   const float* wnd;       // the window zero-padded to n_fft around its centre
   const float* mel;       // [n_bins][n_mels]
   const int *mel_lo, *mel_hi;  // each filter's nonzero run of bins [lo, hi); (n_bins, 0) for an all-zero filter
-  const float* wtab;      // the runs' weights packed side by side, LS_WTAB floats at the most (the n_fft = 1024 kernel's LDS table)
+  const float* wtab;      // the runs' weights packed side by side, LM_WTAB floats at the most (the n_fft = 1024 kernel's LDS table)
   const int* mel_off;     // where a filter's run starts in wtab; -1: no room, its weights are read from mel
   int wtab_n;             // floats of wtab in use
   const float *mean, *stdv;
@@ -86,8 +84,8 @@ __device__ __forceinline__ void ls_push_range(const LsGeom& g, int s, const int*
 __global__ __launch_bounds__(LS_THREADS) void ls_frame_kernel(LsGeom g, const float* __restrict__ x, int ldx,
                                                               const int* __restrict__ n_valid, const int* __restrict__ end,
                                                               int C, float* __restrict__ out, int ldo) {
-  __shared__ float re[LS_MAX_FFT], im[LS_MAX_FFT];
-  __shared__ float twr[LS_MAX_FFT], twi[LS_MAX_FFT];
+  __shared__ float re[LM_MAX_FFT], im[LM_MAX_FFT];
+  __shared__ float twr[LM_MAX_FFT], twi[LM_MAX_FFT];
   const int tid = threadIdx.x, s = blockIdx.y;
   long long n0, f0, f1;
   int nv, e;
@@ -99,11 +97,7 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame_kernel(LsGeom g, const fl
   const float* src = x + (long)s * ldx;
   for (int j = tid; j < n_fft; j += LS_THREADS) {
     long long pos = t * g.hop + j;
-    if (g.center) {  // torch.stft center=True, pad_mode="reflect"; the right mirror is taken at the final count
-      pos -= n_fft / 2;
-      if (pos < 0) pos = -pos;
-      if (pos >= n1) pos = 2 * (n1 - 1) - pos;
-    }
+    if (g.center) pos = lm_reflect(pos - n_fft / 2, n1);  // (the right mirror is taken at the final count)
     float v = 0.f;
     if (pos >= 0 && pos < n1) v = pos < n0 ? ring[(int)(pos & mask)] : src[pos - n0];
     const int r = (int)(__brev((unsigned)j) >> (32 - g.log2n));
@@ -113,28 +107,16 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame_kernel(LsGeom g, const fl
     twr[j] = w.x; twi[j] = w.y;
   }
   __syncthreads();
-  for (int st = 0; st < g.log2n; st++) {
-    const int half = 1 << st;
-    for (int bf = tid; bf < n_fft / 2; bf += LS_THREADS) {
-      const int grp = bf >> st, p = bf & (half - 1);
-      const int i0 = (grp << (st + 1)) + p, i1 = i0 + half;
-      const float wr = twr[half + p], wi = twi[half + p];
-      const float xr = re[i1] * wr - im[i1] * wi;
-      const float xi = re[i1] * wi + im[i1] * wr;
-      const float ar = re[i0], ai = im[i0];
-      re[i0] = ar + xr; im[i0] = ai + xi;
-      re[i1] = ar - xr; im[i1] = ai - xi;
-    }
-    __syncthreads();
-  }
-  const int n_bins = n_fft / 2 + 1;
-  for (int k = tid; k < n_bins; k += LS_THREADS) re[k] = sqrtf(re[k] * re[k] + im[k] * im[k]);
-  __syncthreads();
+  lm_radix2_magnitudes(re, im, twr, twi, n_fft, g.log2n, tid);
   for (int m = tid; m < g.n_mels; m += LS_THREADS) {
+    // The projection and the cell as logmel_kernel writes them, not through shared bodies: this serial loop of L2 reads is
+    // most of a workgroup's time at n_fft 2048, and with either part behind a function of logmel_common.h a push of
+    // 256 x 8192 samples measured 1.9 % slower, from code that differs in its scheduling only
+    // (profiles/logmel_one_body_ab.txt).
     float acc = 0.f;
     const int k_hi = g.mel_hi[m];
     for (int k = g.mel_lo[m]; k < k_hi; k++) acc += re[k] * g.mel[(long)k * g.n_mels + m];
-    float v = acc > g.eps ? log10f(acc) : g.log_eps;  // (log_eps: see crk_logmel_fwd)
+    float v = acc > g.eps ? log10f(acc) : g.log_eps;  // (lm_log_clamped, lm_standardised)
     if (g.scaler) v = (v - g.mean[m]) / g.stdv[m];
     out[((long)s * g.max_frames + blockIdx.x) * ldo + m] = v;
   }
@@ -152,12 +134,11 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame_kernel(LsGeom g, const fl
 // The waves of a workgroup meet at one barrier, behind the transform: in front of it the workgroup copies the filters'
 // packed runs of weights (made at create time) into LDS, under the transforms' own loads.  Magnitudes go to a per-wave
 // LDS strip; the mel projection reads each filter's run of bins, both frames of the wave per lane.
-#define LS_ZS 1088  // complex slots per wave: 4 rows x 16 x 17 (padded transposes) >= 2 x 512 (the two spectra)
 // One wave: the magnitudes of frame t (lanes 0 .. 31) and t + 1 (lanes 32 .. 63) of the stream into mag[0] and mag[1];
-// live: this half's frame exists (a half without one transforms zeros).  zw: the wave's LS_ZS complex slots.
+// live: this half's frame exists (a half without one transforms zeros).  zw: the wave's LM_ZS complex slots.
 __device__ __forceinline__ void ls_magnitudes1024(const LsGeom& g, long long t, bool live, long long n0, long long n1,
                                                   const float* __restrict__ ring, const float* __restrict__ src, int lane,
-                                                  lm_c* zw, float (*mag)[520]) {
+                                                  lm_c* zw, float (*mag)[LM_MAG]) {
   constexpr int N = 1024, NH = 512, NB = 513;
   const int hw = lane >> 5, l = lane & 31, q = lane & 15, r = (lane >> 4) & 1;
   const lm_c* tw = reinterpret_cast<const lm_c*>(g.tw1024);
@@ -166,10 +147,7 @@ __device__ __forceinline__ void ls_magnitudes1024(const LsGeom& g, long long t, 
   const long long base = t * g.hop - (g.center ? N / 2 : 0);
   auto sample = [&](int n) -> float {
     long long pos = base + n;
-    if (g.center) {  // torch.stft center=True, pad_mode="reflect"; the right mirror is taken at the final count
-      pos = pos < 0 ? -pos : pos;
-      pos = pos >= n1 ? 2 * (n1 - 1) - pos : pos;
-    }
+    if (g.center) pos = lm_reflect(pos, n1);  // (the right mirror is taken at the final count)
     const bool ok = live && pos >= 0 && pos < n1;
     const float* p = !ok ? ring : (pos < n0 ? ring + (int)(pos & (N - 1)) : src + (pos - n0));
     const float val = *p;
@@ -194,14 +172,7 @@ __device__ __forceinline__ void ls_magnitudes1024(const LsGeom& g, long long t, 
     u = r ? lm_sub(o, u) : lm_add(u, o);     // C[r] = B[p = 0] + (-1)^r B[p = 1]
     v[k1] = lm_mul(u, twb);
   }
-  // 16 x 16 transpose inside each row of 16 lanes (row stride 17 complex: conflict-free 8-byte accesses)
-  const int rowb = (lane >> 4) * (16 * 17);
-#pragma unroll
-  for (int k1 = 0; k1 < 16; k1++) zw[rowb + k1 * 17 + q] = v[k1];
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-  for (int qq = 0; qq < 16; qq++) v[qq] = zw[rowb + q * 17 + qq];
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  lm_transpose16(v, zw + (lane >> 4) * (16 * 17), q);
   lm_fft16(v);  // over q -> s
   lm_c* zh = zw + hw * NH;
 #pragma unroll
@@ -223,9 +194,9 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame1024_kernel(LsGeom g, cons
                                                                   const int* __restrict__ n_valid,
                                                                   const int* __restrict__ end, int C,
                                                                   float* __restrict__ out, int ldo) {
-  __shared__ lm_c zb[4][LS_ZS];
-  __shared__ float mag[4][2][520];
-  __shared__ float wtab[LS_WTAB];
+  __shared__ lm_c zb[4][LM_ZS];
+  __shared__ float mag[4][2][LM_MAG];
+  __shared__ float wtab[LM_WTAB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = blockIdx.y;
   long long n0, f0, f1;
   int nv, e;
@@ -252,13 +223,22 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame1024_kernel(LsGeom g, cons
     float sa = 0.f, sb = 0.f;
     if (mine) {
       const int lo = g.mel_lo[m], hi = g.mel_hi[m], off = g.mel_off[m];
-      if (off >= 0) {
-        const float* wp = wtab + off - lo;
-        for (int k = lo + part; k < hi; k += 1 << gsh) { const float w = wp[k]; sa += mag[wave][0][k] * w; sb += mag[wave][1][k] * w; }
-      } else {  // a filter the table had no room for: its weights are read from the basis itself
+      if (off >= 0) lm_run_dot2(mag[wave][0], mag[wave][1], wtab + off - lo, 1, lo + part, hi, 1 << gsh, sa, sb);
+      else {  // a filter the table had no room for: its weights are read from the basis itself, four loads in flight.
+        // Not lm_run_dot2: the rounding below is what the compiler first made of this loop unrolled by four (the leading
+        // steps % 4 fused, then groups of four whose products are rounded before they are added), and such a filter's
+        // cells have had these bits since; written out, they no longer depend on the code around the loop.
         const float* wp = g.mel + m;
+        const int step = 1 << gsh;
+        int k = lo + part;
+        for (int i = k < hi ? ((hi - k + step - 1) >> gsh) & 3 : 0; i > 0; i--, k += step) {
+          const float w = wp[(long)k * g.n_mels];
+          sa = fmaf(mag[wave][0][k], w, sa);
+          sb = fmaf(mag[wave][1][k], w, sb);
+        }
 #pragma unroll 4
-        for (int k = lo + part; k < hi; k += 1 << gsh) {
+        for (; k < hi; k += step) {
+#pragma clang fp contract(off)
           const float w = wp[(long)k * g.n_mels];
           sa += mag[wave][0][k] * w;
           sb += mag[wave][1][k] * w;
@@ -268,8 +248,8 @@ __global__ __launch_bounds__(LS_THREADS) void ls_frame1024_kernel(LsGeom g, cons
     if (gsh >= 1) { sa += __shfl_xor(sa, 1, 64); sb += __shfl_xor(sb, 1, 64); }
     if (gsh >= 2) { sa += __shfl_xor(sa, 2, 64); sb += __shfl_xor(sb, 2, 64); }
     if (mine && part == 0) {
-      float va = sa > g.eps ? log10f(sa) : g.log_eps, vb = sb > g.eps ? log10f(sb) : g.log_eps;
-      if (g.scaler) { va = (va - g.mean[m]) / g.stdv[m]; vb = (vb - g.mean[m]) / g.stdv[m]; }
+      float va = lm_log_clamped(sa, g.eps, g.log_eps), vb = lm_log_clamped(sb, g.eps, g.log_eps);
+      if (g.scaler) { va = lm_standardised(va, g.mean[m], g.stdv[m]); vb = lm_standardised(vb, g.mean[m], g.stdv[m]); }
       out[((long)s * g.max_frames + ja) * ldo + m] = va;
       if (two) out[((long)s * g.max_frames + ja + 1) * ldo + m] = vb;
     }
@@ -307,8 +287,8 @@ static size_t ls_align(size_t b) { return (b + 255) & ~(size_t)255; }
 extern "C" int crk_logmel_stream_create(int n_fft, int hop, int win_length, const float* window, const float* mel_basis,
                                         int n_mels, float eps, const float* mean, const float* stdv, int center,
                                         int n_streams, int max_samples, void** handle) {
-  if (!window || !mel_basis || !handle || n_fft < LS_MIN_FFT || n_fft > LS_MAX_FFT || (n_fft & (n_fft - 1)) ||
-      win_length < 1 || win_length > n_fft || hop < 1 || n_mels < 1 || n_mels > 256 || n_streams < 1 || max_samples < 1 ||
+  if (!window || !mel_basis || !handle || n_fft < LS_MIN_FFT || n_fft > LM_MAX_FFT || (n_fft & (n_fft - 1)) ||
+      win_length < 1 || win_length > n_fft || hop < 1 || n_mels < 1 || n_mels > LM_MAX_MELS || n_streams < 1 || max_samples < 1 ||
       (mean == nullptr) != (stdv == nullptr))
     return CRK_ERR_ARG;
   const long long mf = ls_max_frames(n_fft, hop, center != 0, max_samples);
@@ -322,8 +302,7 @@ extern "C" int crk_logmel_stream_create(int n_fft, int hop, int win_length, cons
     ok = hipMemcpy(mu.data(), mean, mu.size() * 4, hipMemcpyDefault) == hipSuccess &&
          hipMemcpy(sd.data(), stdv, sd.size() * 4, hipMemcpyDefault) == hipSuccess;
   if (!ok) return CRK_ERR_HIP;
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) log2n++;
+  const int log2n = lm_log2n(n_fft);
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t at = o; o += ls_align(bytes); return at; };
   const size_t o_counts = take((size_t)n_streams * 16), o_ring = take((size_t)n_streams * n_fft * 4);
@@ -331,7 +310,7 @@ extern "C" int crk_logmel_stream_create(int n_fft, int hop, int win_length, cons
   const size_t o_tw = take((size_t)n_fft * 8), o_tw1024 = take(1024 * 8), o_wnd = take((size_t)n_fft * 4),
                o_mel = take(fb.size() * 4);
   const size_t o_lo = take((size_t)n_mels * 4), o_hi = take((size_t)n_mels * 4), o_mu = take((size_t)n_mels * 4),
-               o_sd = take((size_t)n_mels * 4), o_wtab = take(LS_WTAB * 4), o_off = take((size_t)n_mels * 4);
+               o_sd = take((size_t)n_mels * 4), o_wtab = take(LM_WTAB * 4), o_off = take((size_t)n_mels * 4);
   std::vector<char> host(o - o_tables, 0);
   auto at = [&](size_t off) { return host.data() + (off - o_tables); };
   float* tw = reinterpret_cast<float*>(at(o_tw));
@@ -365,7 +344,7 @@ extern "C" int crk_logmel_stream_create(int n_fft, int hop, int win_length, cons
   int wtab_n = 0;
   for (int m = 0; m < n_mels; m++) {  // filters in order while their runs fit; one that does not fit is read from the basis
     const int len = hi[m] > lo[m] ? hi[m] - lo[m] : 0;
-    off[m] = wtab_n + len <= LS_WTAB ? wtab_n : -1;
+    off[m] = wtab_n + len <= LM_WTAB ? wtab_n : -1;
     if (off[m] < 0) continue;
     for (int k = 0; k < len; k++) wt[wtab_n + k] = fb[(size_t)(lo[m] + k) * n_mels + m];
     wtab_n += len;
@@ -388,7 +367,7 @@ extern "C" int crk_logmel_stream_create(int n_fft, int hop, int win_length, cons
   g.n_fft = n_fft; g.log2n = log2n; g.hop = hop; g.n_mels = n_mels; g.center = center != 0; g.scaler = mean != nullptr;
   g.max_frames = (int)mf;
   g.eps = eps;
-  g.log_eps = (float)log10((double)eps);  // as crk_logmel_fwd: the correctly rounded value of every clamped cell
+  g.log_eps = lm_log_eps(eps);
   g.counts = reinterpret_cast<long long*>(h->block + o_counts);
   g.ring = reinterpret_cast<float*>(h->block + o_ring);
   g.tw = reinterpret_cast<const float2*>(h->block + o_tw);

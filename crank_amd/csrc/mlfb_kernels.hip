@@ -14,17 +14,15 @@
 
 #include "../../include/crank_hip.h"
 
-#define MLFB_MAX_FFT 2048
-
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ raw, int ld_raw, int n_samples, int T,
                                                      int n_fft, int log2n, int hop, int win, const float* __restrict__ window,
                                                      const float* __restrict__ mel, int n_mels, float eps, float log_eps,
                                                      const float* __restrict__ mean, const float* __restrict__ stdv,
                                                      float* __restrict__ out, int ldo, int frames_per_block, int center) {
-  __shared__ float re[MLFB_MAX_FFT], im[MLFB_MAX_FFT];
-  __shared__ float twr[MLFB_MAX_FFT], twi[MLFB_MAX_FFT];  // stage st's twiddles at [2^st, 2^(st+1)): consecutive lanes, consecutive words
-  __shared__ float wnd[MLFB_MAX_FFT];
-  __shared__ int mel_lo[256], mel_hi[256];  // nonzero bin range of each (triangular) mel filter
+  __shared__ float re[LM_MAX_FFT], im[LM_MAX_FFT];
+  __shared__ float twr[LM_MAX_FFT], twi[LM_MAX_FFT];  // stage st's twiddles at [2^st, 2^(st+1)): consecutive lanes, consecutive words
+  __shared__ float wnd[LM_MAX_FFT];
+  __shared__ int mel_lo[LM_MAX_MELS], mel_hi[LM_MAX_MELS];  // nonzero bin range of each (triangular) mel filter
   const int tid = threadIdx.x;
   const int b = blockIdx.y;
   const int lpad = (n_fft - win) / 2;
@@ -59,38 +57,19 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ r
     const float* src = raw + (long)b * ld_raw;
     for (int j = tid; j < n_fft; j += 256) {
       const int r = (int)(__brev((unsigned)j) >> (32 - log2n));
-      long pos = (long)t * hop + j;
-      if (center) {  // torch.stft / librosa center=True, pad_mode="reflect": n_fft/2 mirrored samples either side, edge not repeated
-        pos -= n_fft / 2;
-        if (pos < 0) pos = -pos;
-        if (pos >= n_samples) pos = 2L * (n_samples - 1) - pos;
-      }
+      long long pos = (long long)t * hop + j;
+      if (center) pos = lm_reflect(pos - n_fft / 2, n_samples);
       re[r] = (pos >= 0 && pos < n_samples) ? src[pos] * wnd[j] : 0.f;
       im[r] = 0.f;
     }
     __syncthreads();
-    for (int st = 0; st < log2n; st++) {
-      const int half = 1 << st;
-      for (int bf = tid; bf < n_fft / 2; bf += 256) {
-        const int grp = bf >> st, pos = bf & (half - 1);
-        const int i0 = (grp << (st + 1)) + pos, i1 = i0 + half;
-        const float wr = twr[half + pos], wi = twi[half + pos];
-        const float xr = re[i1] * wr - im[i1] * wi;
-        const float xi = re[i1] * wi + im[i1] * wr;
-        const float ar = re[i0], ai = im[i0];
-        re[i0] = ar + xr; im[i0] = ai + xi;
-        re[i1] = ar - xr; im[i1] = ai - xi;
-      }
-      __syncthreads();
-    }
-    for (int k = tid; k < n_bins; k += 256) re[k] = sqrtf(re[k] * re[k] + im[k] * im[k]);
-    __syncthreads();
+    lm_radix2_magnitudes(re, im, twr, twi, n_fft, log2n, tid);
     for (int m = tid; m < n_mels; m += 256) {
-      float acc = 0.f;
+      float acc = 0.f;  // (this loop and ls_frame_kernel's stay twins: see there)
       const int k_hi = mel_hi[m];
       for (int k = mel_lo[m]; k < k_hi; k++) acc += re[k] * mel[(long)k * n_mels + m];
-      float v = acc > eps ? log10f(acc) : log_eps;  // (log_eps: see crk_logmel_fwd)
-      if (mean) v = (v - mean[m]) / stdv[m];
+      float v = lm_log_clamped(acc, eps, log_eps);
+      if (mean) v = lm_standardised(v, mean[m], stdv[m]);
       out[((long)b * T + t) * ldo + m] = v;
     }
   }
@@ -107,7 +86,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ r
 //   before the current pair's transform.  Magnitudes of both frames go to a per-wave LDS strip; the mel projection reads each
 //   triangular filter's run of bins against a compact weight table in LDS built once per workgroup.
 // profiles/round5_logmel_kernel.txt: 617 us -> see there, B = 64 x 65 023 samples.
-// (lm_c, its arithmetic and lm_fft16, the in-register DFT-16: logmel_common.h, shared with the streaming kernel)
+// (lm_c, its arithmetic, lm_fft16 and lm_transpose16: logmel_common.h, shared with the streaming kernel)
 // exp(-2 pi i m / 1024), m = 0 .. 1023: a constant of the library, (re)written by EVERY call's lm_prep_kernel on the call's own
 // stream and device (the same 8 KB every time).  As first written it was filled once per process by a launch on the first
 // caller's stream behind a plain static flag: a second GPU of the process never got its table, a first call inside a stream
@@ -121,8 +100,8 @@ __device__ __forceinline__ lm_c lm_w1024(int m) { return lm_tw[m]; }
 // more than the transforms: 270 us per call.)
 #define LM_RUN 64
 #define LM_NSCR 8
-__device__ float lm_melw[LM_NSCR][256 * LM_RUN];
-__device__ int lm_mello[LM_NSCR][256], lm_melhi[LM_NSCR][256];
+__device__ float lm_melw[LM_NSCR][LM_MAX_MELS * LM_RUN];
+__device__ int lm_mello[LM_NSCR][LM_MAX_MELS], lm_melhi[LM_NSCR][LM_MAX_MELS];
 __global__ __launch_bounds__(64) void lm_prep_kernel(const float* __restrict__ mel, int n_mels, int n_bins, int slot) {
   const int m = blockIdx.x, lane = threadIdx.x;
   for (int i = m * 64 + lane; i < 1024; i += gridDim.x * 64) {  // the twiddle table: this call's transform kernel reads it
@@ -138,8 +117,6 @@ __global__ __launch_bounds__(64) void lm_prep_kernel(const float* __restrict__ m
   if (lane == 0) { lm_mello[slot][m] = lo; lm_melhi[slot][m] = hi; }
   if (hi - lo <= LM_RUN && lo + lane < hi) lm_melw[slot][m * LM_RUN + lane] = mel[(long)(lo + lane) * n_mels + m];
 }
-#define LM_WTAB 2048
-#define LM_ZS 1088  // complex slots per wave: 4 rows x 16 x 17 (padded transposes) >= 1024 (the spectrum)
 __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restrict__ raw, int ld_raw, int n_samples, int T, int hop,
                                                           int win, const float* __restrict__ window, const float* __restrict__ mel,
                                                           int n_mels, float eps, float log_eps, const float* __restrict__ mean,
@@ -147,9 +124,9 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
                                                           int pairs_per_wave, int center, int slot) {
   constexpr int N = 1024, NB = 513;
   __shared__ lm_c zb[4][LM_ZS];
-  __shared__ float mag[4][2][520];
+  __shared__ float mag[4][2][LM_MAG];
   __shared__ float wtab[LM_WTAB];
-  __shared__ int mlo[256], mhi[256], moff[256];
+  __shared__ int mlo[LM_MAX_MELS], mhi[LM_MAX_MELS], moff[LM_MAX_MELS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
   // ---- per workgroup: the filters' runs (lm_prep_kernel) packed side by side into LDS ----
   for (int m = tid; m < n_mels; m += 256) { mlo[m] = lm_mello[slot][m]; mhi[m] = lm_melhi[slot][m]; }
@@ -186,12 +163,8 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
   const int pair0 = (blockIdx.x * 4 + wave) * pairs_per_wave;
 
   auto sample = [&](int t, int n) -> float {
-    long pos = (long)t * hop + n;
-    if (center) {  // torch.stft / librosa center=True, pad_mode="reflect"
-      pos -= N / 2;
-      if (pos < 0) pos = -pos;
-      if (pos >= n_samples) pos = 2L * (n_samples - 1) - pos;
-    }
+    long long pos = (long long)t * hop + n;
+    if (center) pos = lm_reflect(pos - N / 2, n_samples);
     return (t < T && pos >= 0 && pos < n_samples) ? src[pos] : 0.f;
   };
   float xa[16], xb[16];
@@ -221,14 +194,7 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
       u = hi4 ? lm_sub(o, u) : lm_add(u, o);           // C[r = s + 2 p0] = E[s] +- W_4^s O[s]
       v[k1] = lm_mul(u, twb);
     }
-    // 16 x 16 transpose inside each row of 16 lanes (row stride 17 complex: conflict-free 8-byte accesses)
-    const int rowb = (lane >> 4) * (16 * 17);
-#pragma unroll
-    for (int k1 = 0; k1 < 16; k1++) zw[rowb + k1 * 17 + q] = v[k1];
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-    for (int qq = 0; qq < 16; qq++) v[qq] = zw[rowb + q * 17 + qq];
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    lm_transpose16(v, zw + (lane >> 4) * (16 * 17), q);
     lm_fft16(v);  // over q -> s
 #pragma unroll
     for (int sx = 0; sx < 16; sx++) zw[q + 16 * r + 64 * sx] = v[sx];  // Z[k1 + 16 k2], k2 = r + 4 s
@@ -244,14 +210,10 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
     for (int m = lane; m < n_mels; m += 64) {
       const int lo = mlo[m], hi = mhi[m];
       float sa = 0.f, sb = 0.f;
-      if (moff[m] >= 0) {
-        const float* wp = wtab + moff[m] - lo;
-        for (int k = lo; k < hi; k++) { const float w = wp[k]; sa += mag[wave][0][k] * w; sb += mag[wave][1][k] * w; }
-      } else {
-        for (int k = lo; k < hi; k++) { const float w = mel[(long)k * n_mels + m]; sa += mag[wave][0][k] * w; sb += mag[wave][1][k] * w; }
-      }
-      float va = sa > eps ? log10f(sa) : log_eps, vb = sb > eps ? log10f(sb) : log_eps;
-      if (mean) { va = (va - mean[m]) / stdv[m]; vb = (vb - mean[m]) / stdv[m]; }
+      if (moff[m] >= 0) lm_run_dot2(mag[wave][0], mag[wave][1], wtab + moff[m] - lo, 1, lo, hi, 1, sa, sb);
+      else lm_run_dot2(mag[wave][0], mag[wave][1], mel + m, n_mels, lo, hi, 1, sa, sb);  // (from the basis itself)
+      float va = lm_log_clamped(sa, eps, log_eps), vb = lm_log_clamped(sb, eps, log_eps);
+      if (mean) { va = lm_standardised(va, mean[m], stdv[m]); vb = lm_standardised(vb, mean[m], stdv[m]); }
       out[((long)b * T + ta) * ldo + m] = va;
       if (tb < T) out[((long)b * T + tb) * ldo + m] = vb;
     }
@@ -262,19 +224,16 @@ __global__ __launch_bounds__(256) void logmel_wave_kernel(const float* __restric
 extern "C" int crk_logmel_fwd(const float* raw, int ld_raw, int B, int n_samples, int T, int n_fft, int hop,
                               int win_length, const float* window, const float* mel_basis, int n_mels, float eps,
                               const float* mean, const float* stdv, float* out, int ldo, int center, void* stream) {
-  if (!raw || !window || !mel_basis || !out || n_fft > MLFB_MAX_FFT || (n_fft & (n_fft - 1)) || win_length > n_fft ||
-      n_mels > 256)
+  if (!raw || !window || !mel_basis || !out || n_fft > LM_MAX_FFT || (n_fft & (n_fft - 1)) || win_length > n_fft ||
+      n_mels > LM_MAX_MELS)
     return CRK_ERR_ARG;
   // a grid dimension of 0 (B, T), a frame step that never advances (hop), log2n = 0 (n_fft 1: the bit reversal shifts by 32),
   // an empty window or basis, an output row shorter than its values
   if (B <= 0 || T <= 0 || hop <= 0 || n_fft < 2 || win_length <= 0 || n_mels <= 0 || n_samples <= 0 || ldo < n_mels || ld_raw < n_samples)
     return CRK_ERR_ARG;
   if (center && n_samples <= n_fft / 2) return CRK_ERR_ARG;  // reflect padding needs pad < length, like torch.stft
-  int log2n = 0;
-  while ((1 << log2n) < n_fft) log2n++;
-  // The value of every clamped cell, rounded from double on the host: the device's log10f(1e-10f) is -10.000001f, one ulp
-  // below the correctly rounded -10.0f that torch.log10 returns for the reference's clamp.  Cells above eps are untouched.
-  const float log_eps = (float)log10((double)eps);
+  const int log2n = lm_log2n(n_fft);
+  const float log_eps = lm_log_eps(eps);
   static int wave_env = -1;  // CRK_LOGMEL_WAVE=0: the radix-2 workgroup-per-frame kernel for every size (A/B measurements)
   if (wave_env < 0) wave_env = crk_sw().logmel_wave;
   if (n_fft == 1024 && wave_env) {

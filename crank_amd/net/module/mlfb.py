@@ -73,12 +73,9 @@ class LogMelFilterBankLayer(torch.nn.Module):
     def forward(self, x):
         """x: (B, n_samples) -> (B, T, n_mels); T = 1 + (n_samples - fft_size)//hop, or 1 + n_samples//hop
         when centred (torch.stft's frame count over the padded signal)."""
-        if self.center:
-            if x.shape[1] <= self.fft_size // 2:
-                raise ValueError(f"reflect padding of {self.fft_size // 2} samples needs a longer signal than {x.shape[1]}")
-            T = 1 + x.shape[1] // self.hop_size
-        else:
-            T = 1 + (x.shape[1] - self.fft_size) // self.hop_size
+        if self.center and x.shape[1] <= self.fft_size // 2:
+            raise ValueError(f"reflect padding of {self.fft_size // 2} samples needs a longer signal than {x.shape[1]}")
+        T = frames_ready(x.shape[1], self.fft_size, self.hop_size, self.center, end=True)
         return ops.logmel(x, T, self.fft_size, self.hop_size, self.win_length, self.window, self.mel_basis, self.eps,
                           self.mean, self.std, center=self.center)
 

@@ -1,5 +1,5 @@
 """Streaming log-mel front end (crank_amd.net.module.mlfb.StreamingLogMel, crk_logmel_stream_push) on one MI355X:
-microseconds per push for S concurrent streams x C new samples per push at the recipe's framing (22 050 Hz, n_fft 1024,
+microseconds per push for S concurrent streams x C new samples per push at the recipe's framing (22 050 Hz, n_fft 1024 or --fft-size,
 hop 128, 80 mels, centred, with a scaler), each push replayed from a HIP graph captured on static buffers.
 
 Beside it, measured in the same process, what a caller does without it: a device-side tail of n_fft - hop samples per
@@ -22,7 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-FS, N_FFT, HOP, N_MELS = 22050, 1024, 128, 80
+FS, HOP, N_MELS = 22050, 128, 80
 
 
 class Scaler:
@@ -54,16 +54,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16, 256])
     ap.add_argument("--chunks", type=int, nargs="+", default=[128, 512, 2048, 8192])
+    ap.add_argument("--fft-size", type=int, default=1024, help="1024: ls_frame1024_kernel; another power of two: ls_frame_kernel")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--burst", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "logmel_stream_bench_mi355x.txt"))
     args = ap.parse_args()
+    n_fft = args.fft_size
     assert torch.cuda.is_available(), "bench_logmel_stream needs the MI355X"
     from crank_amd import ops
     from crank_amd.net.module.mlfb import LogMelFilterBankLayer
 
-    layer = LogMelFilterBankLayer(fs=FS, hop_size=HOP, fft_size=N_FFT, n_mels=N_MELS, fmin=80, fmax=7600, center=True,
+    layer = LogMelFilterBankLayer(fs=FS, hop_size=HOP, fft_size=n_fft, n_mels=N_MELS, fmin=80, fmax=7600, center=True,
                                   scaler=Scaler())
     gen = torch.Generator("cuda").manual_seed(1)
     rows, lines = [], []
@@ -81,12 +83,12 @@ def main():
             push_us = timed(graph.replay, args.warmup, args.reps, args.burst)
             frames = int(out["n_frames"][0])  # the steady state: C / hop frames per push when hop divides C
             # the sliding-window call
-            tail = 0.1 * torch.randn(S, N_FFT - HOP, device="cuda", generator=gen)
-            T = 1 + (N_FFT - HOP + C - N_FFT) // HOP
+            tail = 0.1 * torch.randn(S, n_fft - HOP, device="cuda", generator=gen)
+            T = 1 + (n_fft - HOP + C - n_fft) // HOP
 
             def slide():
                 buf = torch.cat([tail, x], 1)
-                feats = ops.logmel(buf, T, N_FFT, HOP, layer.win_length, layer.window, layer.mel_basis, layer.eps, layer.mean,
+                feats = ops.logmel(buf, T, n_fft, HOP, layer.win_length, layer.window, layer.mel_basis, layer.eps, layer.mean,
                                    layer.std, center=False)
                 tail.copy_(buf[:, C:])
                 return feats
@@ -107,7 +109,7 @@ def main():
             rows.append(res)
             del graph, g2
     lines.append(f"streaming log-mel push (HIP graph replay) vs tail + chunk -> ops.logmel(center=False) (graph replay / eager), "
-                 f"{FS} Hz, n_fft {N_FFT}, hop {HOP}, {N_MELS} mels, centred, scaler; median of {args.reps} x {args.burst}")
+                 f"{FS} Hz, n_fft {n_fft}, hop {HOP}, {N_MELS} mels, centred, scaler; median of {args.reps} x {args.burst}")
     lines.append(f"{'S':>4} {'C':>5} {'frames':>6} {'push us':>9} {'RTF':>9} {'slide graph us':>15} {'x':>6} {'slide eager us':>15} {'x':>6}")
     for r in rows:
         lines.append(f"{r['streams']:>4} {r['samples']:>5} {r['frames']:>6} {r['push_us']:>9.1f} {r['real_time_factor']:>9.6f} "
