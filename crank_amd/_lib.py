@@ -56,6 +56,12 @@ class StreamDesc(ctypes.Structure):
     ]
 
 
+class F0StreamRound(ctypes.Structure):
+    _fields_ = [("ids", c_void_p), ("utt", c_void_p), ("range", c_void_p), ("chan_bf", c_void_p), ("chan", c_void_p),
+                ("n_ready", c_int), ("total_samples", c_longlong), ("total_channels", c_longlong),
+                ("total_frames", c_longlong), ("total_events", c_longlong)]
+
+
 P, I, LL, ULL, F, D = c_void_p, c_int, c_longlong, c_ulonglong, c_float, c_double
 
 SIGNATURES = {
@@ -184,6 +190,16 @@ SIGNATURES = {
     "crk_f0_refine": (I, [P, P, P, P, P, I, LL, P, P, P]),
     "crk_f0_contour": (I, [P, P, P, P, I, LL, P, P, LL, P]),
     "crk_f0_continuous": (I, [P, P, I, LL, P, P, P, P, P, P, P]),
+    "crk_f0_stream_create": (I, [I, I, I, I, I, I, P, I, I, I, ctypes.POINTER(c_void_p)]),
+    "crk_f0_stream_destroy": (None, [P]),
+    "crk_f0_stream_state_bytes": (LL, [P]),
+    "crk_f0_stream_max_frames": (I, [P]),
+    "crk_f0_stream_max_rounds": (I, [P]),
+    "crk_f0_stream_reset": (I, [P, P, I, P]),
+    "crk_f0_stream_plan": (I, [P, P, P, I, I, P, P, P, P]),
+    "crk_f0_stream_push": (I, [P, P, P, I, P, P, P, P, I, I, ctypes.POINTER(F0StreamRound), I, P, P, P, P, I, D, D, I, P, P,
+                               P, P, P, P, LL, P]),
+    "crk_f0_stream_status": (I, [P, P, P]),
     "crk_gl_create": (I, [I, I, I, I, I, P, ctypes.POINTER(c_void_p)]),
     "crk_gl_destroy": (None, [P]),
     "crk_gl_workspace_bytes": (LL, [I, LL, LL]),

@@ -13,9 +13,12 @@ StreamingLogMel``) turns pushes of samples into the scaled log-mel frames that h
 is this class's ``n_valid``, so build the converter with ``max_chunk >= StreamingLogMel.max_frames`` - and
 ``crank_amd.vocoder.StreamingVocoder`` turns the decoded chunks into sound, 16 frames behind them.
 
-What stays with the caller: the F0 contour of ``decoder_f0`` / ``encoder_f0`` models (Harvest here sees whole utterances;
-the conversion itself, ``BaseTrainer._decode_f0`` / ``crk_decode_f0``, works frame by frame, so it applies to a chunk as
-it does to an utterance), and ``use_raw`` models, which ``check_stream_conf`` refuses: feed them scaled features.
+The ``lcf0`` / ``uv`` rows of a ``decoder_f0`` model come from ``crank_amd.world.StreamingF0``: Harvest on a window around
+each block of 80 ms of the same pushes of samples, converted to the target speaker and scaled, at most 180 ms behind the
+signal - the caller holds the log-mel frames until their F0 frames arrive.
+
+What stays with the caller: ``encoder_f0`` conditioning (the same rows unconverted: ``StreamingF0`` with ``cv_spk = org_spk``),
+and ``use_raw`` models, which ``check_stream_conf`` refuses: feed them scaled features.
 """
 import ctypes
 

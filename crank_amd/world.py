@@ -17,7 +17,9 @@ oracles are tests/world_analysis_ref.py and tests/d4c_ref.py; parity with pyworl
 
 ``HarvestF0`` is pyworld ``harvest`` (csrc/f0_kernels.hip, crk_f0_*) for a ragged batch of waveforms with a search range
 each, and ``continuous_f0_batch`` the reference's ``convert_continuos_f0`` with ``lf0`` / ``lcf0``.  The oracle is
-tests/harvest_ref.py; parity with pyworld is unpinned.
+tests/harvest_ref.py; parity with pyworld is unpinned.  ``StreamingF0`` runs it on a window around
+each block of a live stream's frames and finishes the contour into the ``lcf0`` / ``uv`` rows streaming conversion takes
+(csrc/f0_stream_kernels.hip, crk_f0_stream_*; the definition is tests/f0_stream_ref.py).
 """
 import ctypes
 
@@ -771,6 +773,204 @@ def continuous_f0_batch(f0s, device="cuda", return_filled=False):
         raise ValueError(f"utterance {bad[0]} has no voiced frame")
     outs = [t.split(lens) for t in ((uv, cf0, lf0, lcf0, filled) if return_filled else (uv, cf0, lf0, lcf0))]
     return [tuple(o[u] for o in outs) for u in range(len(lens))]
+
+
+class StreamingF0:
+    """``push`` takes the next samples of ``len(minf0s)`` independent streams, at most ``max_samples`` each per push, and
+    returns the ``lcf0`` / ``uv`` rows ``StreamingConverter.push`` takes for a ``decoder_f0`` model, already converted to
+    the target speaker and scaled (csrc/f0_stream_kernels.hip, ``crk_f0_stream_*``).  Stream i is
+    row i of every argument and has its own search range.
+
+    Harvest is not streamed bit for bit (its contour rules reach arbitrarily far along a voiced run): the 1 ms frames of a
+    stream are cut into blocks of ``block_ms``, and block j's contour is Harvest - this module's kernels, through
+    ``HarvestF0(fs, 1)`` - of the window from ``back_ms`` before the block to ``ahead_ms`` after it, truncated at the
+    stream's start and, at the ``end`` flag, at its last sample.  A block is emitted by the push that completes its
+    window, so the algorithmic latency is at most ``ahead_ms + block_ms``.  Output frame t sits at 1 ms frame
+    ``t * shiftms`` (``HarvestF0``'s grid), or with ``hop_size`` at the 1 ms frame nearest ``t * hop_size`` samples (the
+    centre of ``StreamingLogMel``'s centred frame t); give exactly one.  With ``low_cut`` the stream is first filtered by
+    ``crank.utils.low_cut_filter`` with zero history at its start, bit for bit ``WorldAnalyzer.low_cut_batch`` of the whole
+    signal.  The outputs do not depend on how the signal is cut into pushes.
+
+    The sample history, the counts and the carry of every stream stay on the device; ``n_valid`` and ``end`` are host
+    integers, so the host knows which blocks are ready.  A push with no ready block is one launch, nothing is read back,
+    and an overflowing Harvest event stream sets a sticky flag that ``status()`` raises on.  A push cannot be captured in a
+    graph (what it launches depends on the counts).  There is no torch or CPU fallback."""
+
+    def __init__(self, fs, minf0s, maxf0s, spk_lcf0_mean, spk_lcf0_std, max_samples, shiftms=None, hop_size=None,
+                 lcf0_scaler=None, back_ms=300, ahead_ms=100, block_ms=80, low_cut=70, device="cuda"):
+        if (shiftms is None) == (hop_size is None):
+            raise ValueError("the output frame grid is exactly one of shiftms and hop_size")
+        if int(fs) != fs or not 8000 <= int(fs) <= 48000:
+            raise ValueError(f"fs {fs}: Harvest takes 8000 .. 48000 Hz")
+        fs = int(fs)
+        grid = shiftms if hop_size is None else hop_size
+        if int(grid) != grid or int(grid) < 1 or (shiftms is not None and grid > 1000):
+            raise ValueError(f"shiftms / hop_size {grid}: a positive integer (shiftms at most 1000)")
+        if hop_size is not None and 1000 * int(hop_size) < fs:
+            raise ValueError(f"hop_size {hop_size}: below 1 ms at {fs} Hz, finer than the 1 ms contour")
+        for name, ms in (("back_ms", back_ms), ("ahead_ms", ahead_ms), ("block_ms", block_ms)):
+            if int(ms) != ms or not 1 <= int(ms) <= 10000 or (int(ms) * fs) % 1000:
+                raise ValueError(f"{name} {ms}: whole milliseconds in 1 .. 10000 that end on a whole sample at {fs} Hz")
+        if min(int(back_ms), int(block_ms)) * fs // 1000 < HARVEST_MIN_SAMPLES:
+            raise ValueError(f"back_ms {back_ms}, block_ms {block_ms}: each window must hold Harvest's {HARVEST_MIN_SAMPLES} samples")
+        if len(minf0s) < 1 or len(minf0s) != len(maxf0s):
+            raise ValueError("minf0s and maxf0s must be lists of the same non-zero length")
+        for lo, hi in zip(minf0s, maxf0s):
+            if not (np.isfinite(lo) and np.isfinite(hi) and 40.0 <= lo < hi <= 800.0):
+                raise ValueError(f"search range {lo} .. {hi} Hz: Harvest takes 40 <= minf0 < maxf0 <= 800")
+        if int(max_samples) < 1:
+            raise ValueError(f"max_samples = {max_samples}: must be at least 1")
+        self.device = torch.device(device)
+        require_gpu(self.device, "streaming F0")
+        self.fs, self.n_streams, self.max_samples = fs, len(minf0s), int(max_samples)
+        self.minf0s, self.maxf0s = [float(v) for v in minf0s], [float(v) for v in maxf0s]
+        self.shiftms, self.hop_size = (int(shiftms), None) if hop_size is None else (None, int(hop_size))
+        self.back_ms, self.ahead_ms, self.block_ms = int(back_ms), int(ahead_ms), int(block_ms)
+        self.spk_mean = f64(spk_lcf0_mean, self.device).reshape(-1).contiguous()
+        self.spk_std = f64(spk_lcf0_std, self.device).reshape(-1).contiguous()
+        if self.spk_mean.numel() < 1 or self.spk_mean.numel() != self.spk_std.numel():
+            raise ValueError("spk_lcf0_mean and spk_lcf0_std: one value per speaker each")
+        self.lcf0_scaler = None if lcf0_scaler is None else (float(lcf0_scaler[0]), float(lcf0_scaler[1]))
+        self._harvest = HarvestF0(fs, 1, self.device)
+        self._rounds = {}  # (ready streams, window lengths) -> the round's tables; one entry in steady lock-step
+        taps, n_taps = None, 0
+        if low_cut is not None:
+            from scipy.signal import firwin
+
+            n_taps = LOWCUT_TAPS
+            taps = (ctypes.c_double * n_taps)(*firwin(n_taps, low_cut / (fs // 2), pass_zero=False))
+        h = ctypes.c_void_p()
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            self._harvest.handle()
+            check(L.crk_f0_stream_create(fs, self.back_ms, self.ahead_ms, self.block_ms, self.shiftms or 0,
+                                         self.hop_size or 0, taps, n_taps, self.n_streams, self.max_samples,
+                                         ctypes.byref(h)), "crk_f0_stream_create")
+            self._handle = made(h, "crk_f0_stream_create")
+        self.max_frames = int(L.crk_f0_stream_max_frames(self._handle))
+        self.max_rounds = int(L.crk_f0_stream_max_rounds(self._handle))
+
+    def __del__(self):
+        release(self, "_handle", "crk_f0_stream_destroy")
+
+    @property
+    def state_bytes(self):
+        return int(_lib.lib().crk_f0_stream_state_bytes(self._handle))
+
+    def reset(self, streams=None):
+        """``streams`` (all of them by default) return to their start state; blocks not emitted yet are dropped."""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            if streams is None:
+                check(L.crk_f0_stream_reset(self._handle, None, 0, stream_ptr()), "crk_f0_stream_reset")
+            else:
+                ids = [int(s) for s in streams]
+                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
+                check(L.crk_f0_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_f0_stream_reset")
+
+    def status(self):
+        """Synchronises; raises if a Harvest event stream overflowed in a window of any stream since its last reset."""
+        flags = (ctypes.c_int * self.n_streams)()
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_f0_stream_status(self._handle, flags, stream_ptr()), "crk_f0_stream_status")
+        bad = [s for s in range(self.n_streams) if flags[s] & 2]
+        if bad:
+            raise RuntimeError(f"streaming F0: the tables of streams {bad} did not fit the device's counts")
+        HarvestF0._status(torch.tensor([f & 1 for f in flags]))
+
+    def empty_outputs(self, S, raw=False, cv_f0=False):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns; ``raw`` (the contour) and
+        ``cv_f0`` (exp(cv_lcf0) uv) are float64 and optional."""
+        out = {"lcf0": torch.empty(S, self.max_frames, 1, device=self.device),
+               "uv": torch.empty(S, self.max_frames, 1, device=self.device),
+               "n_frames": torch.empty(S, dtype=torch.int32, device=self.device)}
+        for name, want in (("raw", raw), ("cv_f0", cv_f0)):
+            if want:
+                out[name] = torch.empty(S, self.max_frames, 1, dtype=torch.float64, device=self.device)
+        return out
+
+    def _host_ints(self, v, S, C, what):
+        if v is None:
+            return None, None
+        a = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)
+        if a.shape != (S,) or a.dtype.kind not in "iub":
+            raise ValueError(f"{what}: {S} host integers, got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a, np.int32)
+        if what == "n_valid" and (a.min() < 0 or a.max() > C):
+            raise ValueError(f"n_valid: 0 .. {C}")
+        return a, torch.as_tensor(a, device=self.device)
+
+    def _spk(self, t, S, what):
+        if (not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.int32
+                or tuple(t.shape) != (S,)):
+            raise ValueError(f"{what}: an int32 ({S},) tensor on the GPU")
+        return t.contiguous()
+
+    def _round(self, ids, lens):
+        key = (tuple(ids), tuple(lens))
+        r = self._rounds.get(key)
+        if r is None:
+            if len(self._rounds) >= 256:  # a stream's first back_ms and ragged schedules make new layouts; steady state one
+                self._rounds.clear()
+            L = self._harvest._layout(list(lens), [self.minf0s[s] for s in ids], [self.maxf0s[s] for s in ids])
+            L["ids"] = torch.as_tensor(np.asarray(ids, np.int32), device=self.device)
+            L["desc"] = _lib.F0StreamRound(L["ids"].data_ptr(), L["utt"].data_ptr(), L["range"].data_ptr(),
+                                           L["chan_bf"].data_ptr(), L["chan"].data_ptr(), L["n"], L["S"], L["C"], L["F"],
+                                           L["E"])
+            r = self._rounds[key] = L
+        return r
+
+    def push(self, x, org_spk, cv_spk, n_valid=None, end=None, out=None):
+        """x (S, C) float32 samples on the GPU; n_valid, end: S host integers (default: C, 0; n_valid may be 0) - the
+        samples that count per stream and non-zero where this push ends the stream's utterance; org_spk, cv_spk int32
+        (S,) on the GPU.  Returns ``lcf0`` and ``uv`` (S, max_frames, 1) float32 and ``n_frames`` (S,) int32: the frames
+        written at the start of each stream's rows; frames past ``n_frames`` are not written.  Anything refused leaves
+        outputs and state untouched.  out: buffers to write into (``empty_outputs``)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.device.type != "cuda" or x.dtype != torch.float32:
+            raise ValueError("x: a float32 (S, C) tensor on the GPU")
+        S, C = int(x.shape[0]), int(x.shape[1])
+        if S != self.n_streams:
+            raise ValueError(f"x: {S} rows for {self.n_streams} streams")
+        x = x.contiguous()
+        nv_h, nv_d = self._host_ints(n_valid, S, C, "n_valid")
+        end_h, end_d = self._host_ints(end, S, C, "end")
+        org_spk, cv_spk = self._spk(org_spk, S, "org_spk"), self._spk(cv_spk, S, "cv_spk")
+        if out is None:
+            out = self.empty_outputs(S)
+        else:
+            for name, dt in (("lcf0", torch.float32), ("uv", torch.float32), ("raw", torch.float64), ("cv_f0", torch.float64)):
+                t = out.get(name)
+                if t is None and name in ("raw", "cv_f0"):
+                    continue
+                if (t is None or t.device.type != "cuda" or t.dtype != dt or tuple(t.shape) != (S, self.max_frames, 1)
+                        or not t.is_contiguous()):
+                    raise ValueError(f"out[{name!r}]: {dt} ({S}, {self.max_frames}, 1) on the GPU (empty_outputs)")
+            n = out.get("n_frames")
+            if n is None or n.device.type != "cuda" or n.dtype != torch.int32 or tuple(n.shape) != (S,):
+                raise ValueError(f"out['n_frames']: int32 ({S},) on the GPU (empty_outputs)")
+        L = _lib.lib()
+        ip = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        n_rounds = ctypes.c_int()
+        round_n = (ctypes.c_int * self.max_rounds)()
+        ids = (ctypes.c_int * (self.max_rounds * S))()
+        lens = (ctypes.c_longlong * (self.max_rounds * S))()
+        check(L.crk_f0_stream_plan(self._handle, ip(nv_h), ip(end_h), S, C, ctypes.byref(n_rounds), round_n, ids, lens),
+              "crk_f0_stream_plan")
+        rounds = [self._round(ids[r * S:r * S + round_n[r]], lens[r * S:r * S + round_n[r]]) for r in range(n_rounds.value)]
+        descs = (_lib.F0StreamRound * max(len(rounds), 1))(*[r["desc"] for r in rounds])
+        ws = None
+        for r in rounds:
+            ws = self._harvest.reserve(r["n"], r["S"], r["F"], r["C"], r["E"])
+        mean, scale = self.lcf0_scaler or (0.0, 1.0)
+        with torch.cuda.device(self.device):
+            check(L.crk_f0_stream_push(
+                self._handle, self._harvest.handle(), x.data_ptr(), C, ip(nv_h), ip(end_h), _lib.ptr(nv_d), _lib.ptr(end_d),
+                S, C, descs, len(rounds), org_spk.data_ptr(), cv_spk.data_ptr(), self.spk_mean.data_ptr(),
+                self.spk_std.data_ptr(), int(self.spk_mean.numel()), mean, scale, 1 if self.lcf0_scaler else 0,
+                out["lcf0"].data_ptr(), out["uv"].data_ptr(), out["n_frames"].data_ptr(), _lib.ptr(out.get("raw")),
+                _lib.ptr(out.get("cv_f0")), _lib.ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()),
+                "crk_f0_stream_push")
+        return out
 
 
 def cap_postprocess_batch(caps, device="cuda"):

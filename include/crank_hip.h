@@ -790,6 +790,72 @@ int crk_f0_contour(void* f0h, const double* refined, const double* scores, const
 int crk_f0_continuous(const double* f0, const long long* frame_offsets, int n_utts, long long total_frames, float* uv,
                       double* f0_filled, double* cf0, double* lf0, double* lcf0, int* status, void* stream);
 
+/* ---- streaming F0 conditioning: Harvest on a block grid (csrc/f0_stream_kernels.hip) ----
+ * Samples in, the lcf0 / uv rows crk_stream_push takes for a decoder_f0 model out, for up to n_streams concurrent streams
+ * of at most max_samples each per push (the definition is tests/f0_stream_ref.py).  All grid
+ * arithmetic is in whole milliseconds and integers.  Block j = the stream's 1 ms frames [j block, (j + 1) block); it is
+ * ready once the stream holds ((j + 1) block + ahead) ms; its window is the signal over [max(j block - back, 0) ms,
+ * ((j + 1) block + ahead) ms), truncated at the stream's start and, under the end flag, at the last sample; its 1 ms contour
+ * is those frames of crk_f0_harvest of the window alone, through f0h, a crk_f0_create handle with a frame period of 1 ms.
+ * Output frame t sits at 1 ms frame t shiftms, or with hop_size at (2000 t hop + fs) / (2 fs); exactly one of the two is
+ * positive.  With n_taps > 0 the signal is first filtered by the causal FIR taps (HOST float64), zero history at the
+ * stream's start, by crk_wana_lowcut's arithmetic.  A push with the end flag emits every remaining block up to the one
+ * holding the last 1 ms frame int(1000 n / fs), the frames below the offline count (int(1000 n / fs / shiftms) + 1, or
+ * 1 + n / hop) with their 1 ms index clamped to that frame - nothing when n < 64 - and returns the stream to its start
+ * state.  Per window: g = the contour at the output frames the window holds; uv, cf0 = convert_continuos_f0 of g as
+ * crk_f0_continuous has it, or uv = 0 and cf0 = the stream's carry (the last cf0 it emitted; exp(spk_lcf0_mean[org_spk])
+ * before any) where g has no voiced frame; lcf0 = convert_f0(log cf0) org -> cv as crk_decode_f0, then (v - lcf0_mean) /
+ * lcf0_scale if has_lcf0_scaler; float64, rounded once.  Only the block's frames are written.
+ *
+ * crk_f0_stream_create allocates once (synchronises): per stream a power-of-two ring of raw samples holding back + block +
+ * ahead ms, the n_taps - 1 samples the filter reaches back and one push, two 64-bit counts, the carry and a flag word;
+ * and one round's windows and contours.  CRK_ERR_ARG: fs outside 8000 .. 48000; back, ahead or block outside 1 .. 10000 ms
+ * or not on a whole sample ((ms fs) % 1000 != 0); block or back below 64 samples; both or neither of shiftms, hop_size;
+ * hop_size below 1 ms; n_taps outside 0 .. 256.  crk_f0_stream_max_frames: the most frames one push emits over all
+ * histories, the end flush included.  crk_f0_stream_max_rounds: the most rounds.  crk_f0_stream_reset: the streams in the
+ * HOST array stream_ids (NULL: all) return to their start state, flags cleared.
+ *
+ * The handle keeps the counts on the host too.  A ROUND of a push is the streams with a further block ready.
+ * crk_f0_stream_plan (host only): n_valid / end HOST int32 [S] (NULL: C / 0); writes n_rounds, round_n [max_rounds],
+ * ids and lens [max_rounds][S] (row stride S): per round the ready streams, ascending, and their windows' samples.  The
+ * caller lays each round out as crk_f0_harvest's batch (utterance u = stream ids[u], lens[u] samples, output frames = 1 ms
+ * frames) and passes the DEVICE tables in crk_f0_stream_round, ids as DEVICE int32 [n_ready].
+ * crk_f0_stream_push: x fp32 [S][C], row stride ldx; n_valid / end on the HOST and the same values as DEVICE int32 [S]
+ * (n_valid_dev / end_dev; both NULL or neither); org_spk / cv_spk DEVICE int32 [S], spk_lcf0_mean / std DEVICE double
+ * [n_spk]; lcf0, uv fp32 [S][max_frames]; n_frames DEVICE int32 [S], written for every stream; raw (the contour) and cv_f0
+ * (exp(cv_lcf0) uv) double [S][max_frames], optional; workspace as crk_f0_harvest takes it, for the largest round, whose
+ * events crk_f0_reserve covers.  Judged before any launch, state and outputs untouched, sizes before pointers:
+ * CRK_ERR_ARG for S < 1, C < 0, ldx < C, n_valid outside 0 .. C, rounds that are not this push's plan, a null pointer;
+ * CRK_ERR_UNSUPPORTED for S > n_streams, C > max_samples.  A push never allocates, never synchronises and reads nothing
+ * back; it launches 1 kernel when no block is ready and 2 + crk_f0_harvest's per round otherwise.  It cannot be captured
+ * in a graph: what it launches depends on the counts.  crk_f0_stream_status synchronises and copies the sticky flags to
+ * HOST int32 [n_streams]: 1 a Harvest event stream overflowed, 2 a round's tables did not fit the device's counts. */
+typedef struct crk_f0_stream_round {
+  const int* ids;
+  const long long* utt;
+  const double* range;
+  const double* chan_bf;
+  const long long* chan;
+  int n_ready;
+  long long total_samples, total_channels, total_frames, total_events;
+} crk_f0_stream_round;
+int crk_f0_stream_create(int fs, int back_ms, int ahead_ms, int block_ms, int shiftms, int hop_size, const double* taps,
+                         int n_taps, int n_streams, int max_samples, void** handle);
+void crk_f0_stream_destroy(void* st);
+long long crk_f0_stream_state_bytes(void* st);
+int crk_f0_stream_max_frames(void* st);
+int crk_f0_stream_max_rounds(void* st);
+int crk_f0_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_f0_stream_plan(void* st, const int* n_valid, const int* end, int S, int C, int* n_rounds, int* round_n, int* ids,
+                       long long* lens);
+int crk_f0_stream_push(void* st, void* f0h, const float* x, int ldx, const int* n_valid, const int* end,
+                       const int* n_valid_dev, const int* end_dev, int S, int C, const crk_f0_stream_round* rounds,
+                       int n_rounds, const int* org_spk, const int* cv_spk, const double* spk_lcf0_mean,
+                       const double* spk_lcf0_std, int n_spk, double lcf0_mean, double lcf0_scale, int has_lcf0_scaler,
+                       float* lcf0, float* uv, int* n_frames, double* raw, double* cv_f0, void* workspace,
+                       long long workspace_bytes, void* stream);
+int crk_f0_stream_status(void* st, int* flags, void* stream);
+
 /* ---- Griffin-Lim waveform synthesis for log-mel models (csrc/griffin_lim_kernels.hip) ----
  * Replaces the reference's mlfb2wav (crank/utils/utils.py:94-107, 210-269: logmelspc_to_linearspc, griffin_lim -> librosa.griffinlim
  * with momentum 0.99, centred reflect-padded STFT, periodic Hann window; called by BaseTrainer._save_decoded_mlfb,
