@@ -214,6 +214,14 @@ SIGNATURES = {
     "crk_stream_prepare": (I, [P, P, ULL, P]),
     "crk_stream_reset": (I, [P, P, I, P]),
     "crk_stream_push": (I, [P, P, I, P, I, P, I, P, P, I, I, P, P, P, P]),
+    "crk_join_create": (I, [I, I, I, I, I, I, I, ctypes.POINTER(c_void_p)]),
+    "crk_join_destroy": (None, [P]),
+    "crk_join_state_bytes": (LL, [P]),
+    "crk_join_max_frames": (I, [P]),
+    "crk_join_reset": (I, [P, P, I, P]),
+    "crk_join_push": (I, [P, P, I, P, P, I, P, P, I, P, I, P, I, I, P, P, P, P]),
+    "crk_join_status": (I, [P, P, P]),
+    "crk_feat_renorm": (I, [P, I, P, P, P, P, P, I, I, I, P, I, P]),
     "crk_prof_enable": (I, [I]),
     "crk_prof_report": (I, [I, ctypes.POINTER(c_longlong), ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     "crk_prof_report_bytes": (I, [I, ctypes.POINTER(c_double)]),

@@ -57,7 +57,7 @@ class LogMelFilterBankLayer(torch.nn.Module):
         if center and pad_mode != "reflect":
             raise NotImplementedError("center=True is implemented for pad_mode='reflect' only")
         self.center = bool(center)
-        self.hop_size, self.fft_size = hop_size, fft_size
+        self.fs, self.hop_size, self.fft_size = fs, hop_size, fft_size
         self.win_length = fft_size if win_length is None else win_length
         self.eps = eps
         fmin = 0 if fmin is None else fmin

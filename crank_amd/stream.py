@@ -15,7 +15,8 @@ is this class's ``n_valid``, so build the converter with ``max_chunk >= Streamin
 
 The ``lcf0`` / ``uv`` rows of a ``decoder_f0`` model come from ``crank_amd.world.StreamingF0``: Harvest on a window around
 each block of 80 ms of the same pushes of samples, converted to the target speaker and scaled, at most 180 ms behind the
-signal - the caller holds the log-mel frames until their F0 frames arrive.
+signal - ``crank_amd.live.LiveConverter`` holds the log-mel frames on the device until their F0 frames arrive and runs all
+four stages in one call.
 
 What stays with the caller: ``encoder_f0`` conditioning (the same rows unconverted: ``StreamingF0`` with ``cv_spk = org_spk``),
 and ``use_raw`` models, which ``check_stream_conf`` refuses: feed them scaled features.
@@ -154,10 +155,13 @@ class StreamingConverter:
             raise ValueError(f"{what}: a float32 ({S}, {C}, {last}) tensor on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
         return t.contiguous()
 
-    def push(self, feats, lcf0, uv, spkr, n_valid=None, enc_lcf0_uv=None, out=None):
+    def push(self, feats, lcf0, uv, spkr, n_valid=None, enc_lcf0_uv=None, out=None, lcf0_uv=None):
         """feats (S, C, input_size) scaled features, lcf0 / uv (S, C, 1) the scaled (already converted) F0 contour and the
-        voicing flags, spkr (S,) int64 target speakers, n_valid (S,) frames that count per stream (default: C),
-        enc_lcf0_uv (S, C, 2) the encoder's conditioning when ``encoder_f0``.  Returns ``decoded`` (S, C, output_size),
+        voicing flags - or, with both of them None, lcf0_uv (S, C, 2) the two packed as ``FrameJoin`` emits them, which is
+        passed to the kernel as it is (giving both forms, or lcf0_uv to a model without ``decoder_f0``, is a ValueError) -,
+        spkr (S,) int64 target speakers, n_valid (S,)
+        frames that count per stream (default: C), enc_lcf0_uv (S, C, 2) the encoder's conditioning when ``encoder_f0``.
+        Returns ``decoded`` (S, C, output_size),
         ``qidx`` [(S, C) int64 per stack, bottom first] and ``encoded`` [(S, C, emb_dim) per stack: the quantizer's input] -
         the keys of ``VQVAE2.make_dict``.  Rows at and past ``n_valid`` are not written.  out: buffers to write into
         (``empty_outputs``), e.g. the static ones of a captured graph."""
@@ -165,7 +169,13 @@ class StreamingConverter:
         conf = self.conf
         feats = self._f32(feats, S, C, conf["input_size"], "feats")
         dcond = None
-        if conf["decoder_f0"]:
+        if lcf0_uv is not None:
+            if lcf0 is not None or uv is not None:
+                raise ValueError("lcf0_uv: the packed rows replace lcf0 and uv; give one form, not both")
+            if not conf["decoder_f0"]:
+                raise ValueError("lcf0_uv: this model has decoder_f0 = false and takes no F0 rows")
+            dcond = self._f32(lcf0_uv, S, C, 2, "lcf0_uv")
+        elif conf["decoder_f0"]:
             dcond = torch.cat([self._f32(lcf0, S, C, 1, "lcf0"), self._f32(uv, S, C, 1, "uv")], dim=-1)
         econd = self._f32(enc_lcf0_uv, S, C, 2, "enc_lcf0_uv") if conf["encoder_f0"] else None
         if spkr.device.type != "cuda" or spkr.dtype != torch.int64 or tuple(spkr.shape) != (S,):

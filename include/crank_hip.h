@@ -934,6 +934,48 @@ int crk_stream_push(void* st, const float* x, int ldx, const float* dec_cond, in
                     const long long* spk, const int* n_valid, int S, int C, float* decoded, long long* const* qidx,
                     float* const* encoded, void* stream);
 
+/* ---- Frame join and the live loop's back-half affine (join_kernels.hip) -----------------------
+ * crk_join_*: a two-input row join for up to n_streams streams.  Input A has rows of width_a floats, input B rows of
+ * width_b floats (the live loop: log-mel frames and [lcf0, uv]); row k of A and row k of B of an utterance leave together
+ * as pair k.  Per stream the handle keeps a ring of at most cap_a waiting A rows, one of at most cap_b waiting B rows
+ * (either may be 0), the waiting counts and `first`, the pairs emitted so far in this utterance.
+ * crk_join_create is the one call that allocates (it synchronises).  max_in_a / max_in_b: the most rows a push brings
+ * per side.  CRK_ERR_ARG: a null handle, n_streams, a width or a max_in below 1, a negative capacity; CRK_ERR_UNSUPPORTED:
+ * more than 65535 streams, or a side above 2^20 rows or floats per row.  crk_join_state_bytes: the size of the allocation.
+ * crk_join_max_frames: min(cap_a + max_in_a, cap_b + max_in_b), the most pairs one push can emit.
+ * crk_join_reset: the streams listed in the HOST array stream_ids (NULL: every stream) drop what waits, start at pair 0
+ * and clear their overflow flags.
+ * crk_join_push: a fp32 [S][max_in_a] rows with row stride lda, n_a DEVICE int32 [S] (clamped to 0 .. max_in_a): rows
+ * [0, n_a[s]) of stream s are new; b, ldb, n_b likewise; end DEVICE int32 [S] or NULL.  With a0, b0 the waiting counts,
+ * take = min(a0 + n_a, b0 + n_b) pairs leave: row j of out_a [S][C_out] rows (row stride ldoa) and of out_b (ldob) is
+ * pair first + j - waiting rows first, oldest first, then new ones; rows at and past take are not written.  The longer
+ * side's surplus waits in its ring; what does not fit is not kept (the newest rows go) and sets the stream's sticky
+ * overflow flag (bit 0: ring A, bit 1: ring B).  With end[s] != 0 the surplus is discarded instead, its count goes to
+ * n_dropped[s] (0 otherwise) and the stream starts over at pair 0 with empty rings; that is no error.  n_out (= take),
+ * first_out (`first` before the push) and n_dropped, DEVICE int32 [S], are written for every stream.  Judged before any
+ * launch, outputs and state untouched: CRK_ERR_ARG for a null pointer (end excepted), S < 1, a row stride below its
+ * width, C_out < crk_join_max_frames; CRK_ERR_UNSUPPORTED for S > n_streams or a stream's block (max_in or C_out rows
+ * times the row stride) above INT_MAX floats.  Two launches whose grids depend on the
+ * handle and S alone; never allocates, never synchronises: capturable.
+ * crk_join_status synchronises and copies the overflow flags of all n_streams streams to the HOST array flags.
+ *
+ * crk_feat_renorm: out[s][j][c] = ((x[s][j][c] * scale[c] + mean[c]) - vmean[c]) / vscale[c] for j < n_valid[s] (DEVICE
+ * int32 [S], clamped to 0 .. C), x and out [S][C] rows of `width` floats with row strides ldx / ldo; four separately
+ * rounded fp32 operations, nothing contracted.  Rows at and past n_valid are not written.  One launch, capturable.
+ * Nothing launched: CRK_ERR_ARG for a null pointer, S, C or width below 1, a stride below width; CRK_ERR_UNSUPPORTED for
+ * S > 65535 or C rows times the width or a stride above INT_MAX floats. */
+int crk_join_create(int n_streams, int width_a, int width_b, int max_in_a, int max_in_b, int cap_a, int cap_b, void** handle);
+void crk_join_destroy(void* st);
+long long crk_join_state_bytes(void* st);
+int crk_join_max_frames(void* st);
+int crk_join_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_join_push(void* st, const float* a, int lda, const int* n_a, const float* b, int ldb, const int* n_b, const int* end,
+                  int S, float* out_a, int ldoa, float* out_b, int ldob, int C_out, int* n_out, int* first_out,
+                  int* n_dropped, void* stream);
+int crk_join_status(void* st, int* flags, void* stream);
+int crk_feat_renorm(const float* x, int ldx, const float* scale, const float* mean, const float* vmean, const float* vscale,
+                    const int* n_valid, int S, int C, int width, float* out, int ldo, void* stream);
+
 /* number of device allocations net handles have made since the library was loaded (tests pin "none inside the step") */
 long long crk_debug_alloc_count(void);
 
