@@ -214,6 +214,14 @@ SIGNATURES = {
     "crk_stream_prepare": (I, [P, P, ULL, P]),
     "crk_stream_reset": (I, [P, P, I, P]),
     "crk_stream_push": (I, [P, P, I, P, I, P, I, P, P, I, I, P, P, P, P]),
+    "crk_lstream_create": (I, [ctypes.POINTER(StreamDesc), P, P, ctypes.POINTER(c_void_p)]),
+    "crk_lstream_destroy": (None, [P]),
+    "crk_lstream_lookahead": (I, [P]),
+    "crk_lstream_reserve": (I, [P, I, I]),
+    "crk_lstream_state_bytes": (LL, [P, I]),
+    "crk_lstream_prepare": (I, [P, P, ULL, P]),
+    "crk_lstream_reset": (I, [P, P, I, P]),
+    "crk_lstream_push": (I, [P, P, I, P, I, P, I, P, P, P, I, I, I, P, P, P, P, P, P]),
     "crk_join_create": (I, [I, I, I, I, I, I, I, ctypes.POINTER(c_void_p)]),
     "crk_join_destroy": (None, [P]),
     "crk_join_state_bytes": (LL, [P]),

@@ -21,37 +21,10 @@
 // what an fp32 chain reads.)  The codebook search is built from the device bodies of vq_common.h - the ones every search
 // kernel of vq_kernels.hip is built from: norms, dot product, distance, (distance, then index) order, NaN pin and
 // straight-through value - so the indices are crk_vq_forward's on the same rows by construction.
-#include <math.h>
 #include <string.h>
 
-#include <vector>
-
-#include "runtime.h"
+#include "stream_common.h"
 #include "../../include/crank_hip.h"
-#include "vq_common.h"
-
-#pragma clang fp contract(off)
-
-
-#define ST_THREADS 256
-#define ST_TILE 64      // frames resident in LDS
-#define ST_HALO 64      // largest (k - 1) * dilation of a layer
-#define ST_LD 128       // row stride (floats) of the io / conditioning / gate tiles
-#define ST_MAX_STACKS 3
-#define ST_MAX_CHUNK 65536
-
-enum { ST_ROLE_FIRST = 0, ST_ROLE_CONV = 1, ST_ROLE_AUX = 2, ST_ROLE_OUT = 3, ST_ROLE_SKIP = 4, ST_ROLE_LAST1 = 5, ST_ROLE_LAST2 = 6 };
-
-// offsets: w_* into the prepared table, b_* into the model's parameter block (-1: no bias), state_off into a stream's state
-struct StLayer { long long w_conv, w_aux, w_os, b_conv, b_out, b_skip, state_off; int dil, halo; };
-struct StNet {
-  long long w_first, w_last1, w_last2, b_first, b_last1, b_last2;
-  int in_ch, in_pad, out_ch, aux_ch, aux_pad, k, L, layer0;
-  float skip_scale;
-};
-// one conv of the prepare pass: rows [row0, row0 + cout) of the launch; element (r, ci, j) of weight_v goes to
-// table[w_off + (j * cin_pad + ci) * ld + col0 + r]
-struct StPrep { long long off_g, off_v, w_off; int row0, cout, cin, cin_pad, k, ld, col0; };
 
 struct StP {
   StNet enc[ST_MAX_STACKS], dec[ST_MAX_STACKS];
@@ -73,10 +46,6 @@ struct StP {
   float* encoded[ST_MAX_STACKS];
 };
 
-static inline int st_pad4(int c) { return (c + 3) & ~3; }
-static inline size_t st_lds_bytes() {
-  return sizeof(float) * ((size_t)(ST_HALO + ST_TILE) * 64 + 3 * (size_t)ST_TILE * ST_LD + (size_t)ST_TILE * 64 + 10 * ST_TILE);
-}
 
 // ------------------------------------------------------------------------------------------------------------ prepare
 // One wave per output row: ||v|| from lane-strided partial sums met in a fixed order, w = v * (g / ||v||) as
@@ -101,46 +70,6 @@ __global__ __launch_bounds__(64) void stream_prepare_kernel(const StPrep* __rest
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------ dense
-// out(f, co) for f < nv, co < cout: the fmaf chain over taps j = 0 .. taps-1 and input channels ci = 0 .. cin_pad-1 of
-// W[j][ci][co] * in[f - (taps - 1 - j) * dil][ci], started at 0, handed to epi(f, co, sum).  A thread owns one output channel
-// and FT consecutive frames; rows past nv inside its run are computed from whatever the tile holds and dropped.  `in` points
-// at frame 0's row; rows in front of it are the layer's history.  No barrier inside.
-template <int FT, class Epi>
-__device__ __forceinline__ void st_dense(const float* __restrict__ W, int cout, int cin_pad, int taps, int dil, const float* in,
-                                         int ldi, int nv, Epi epi) {
-  const int slots = cout <= 16 ? 16 : (cout <= 32 ? 32 : (cout <= 64 ? 64 : 128));
-  const int groups = ST_THREADS / slots;
-  const int co = threadIdx.x & (slots - 1), grp = threadIdx.x / slots;
-  if (co >= cout) return;
-  for (int f0 = grp * FT; f0 < nv; f0 += groups * FT) {
-    float acc[FT];
-#pragma unroll
-    for (int i = 0; i < FT; i++) acc[i] = 0.f;
-    for (int j = 0; j < taps; j++) {
-      const float* inj = in + (f0 - (taps - 1 - j) * dil) * ldi;
-      const float* wj = W + (size_t)j * cin_pad * cout + co;
-#pragma unroll 2
-      for (int ci = 0; ci < cin_pad; ci += 4) {
-        const float w0 = wj[(size_t)ci * cout], w1 = wj[(size_t)(ci + 1) * cout], w2 = wj[(size_t)(ci + 2) * cout],
-                    w3 = wj[(size_t)(ci + 3) * cout];
-#pragma unroll
-        for (int i = 0; i < FT; i++) {
-          const f32x4 xv = *reinterpret_cast<const f32x4*>(inj + i * ldi + ci);
-          acc[i] = fmaf(w0, xv[0], acc[i]);
-          acc[i] = fmaf(w1, xv[1], acc[i]);
-          acc[i] = fmaf(w2, xv[2], acc[i]);
-          acc[i] = fmaf(w3, xv[3], acc[i]);
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < FT; i++)
-      if (f0 + i < nv) epi(f0 + i, co, acc[i]);
-  }
-}
-
-struct StLds { float *xw, *g, *skip, *cond, *io, *red_d, *x2s; int *red_i, *idxs; };
 
 // One PWG generator stack (oracle/pwg.py ParallelWaveGANGenerator.forward, use_causal_conv) on nv frames: `in` (row stride
 // ST_LD, n.in_pad columns) -> m.io (n.out_ch columns).  cond: the conditioning rows (n.aux_pad columns) when n.aux_ch > 0.
@@ -170,18 +99,14 @@ __device__ void st_net(const StP& p, const StNet& n, int s, const float* in, int
     // the layer's next history: the last halo rows of (old state | the nv new frames)
     for (int i = tid; i < hl; i += ST_THREADS) st[i] = xc[nv * 64 - hl + i];
     __syncthreads();
-    for (int i = tid; i < nv * 64; i += ST_THREADS) {
-      const int f = i >> 6, c = i & 63;
-      const float a = g[f * ST_LD + c], b = g[f * ST_LD + 64 + c];
-      g[f * ST_LD + c] = tanhf(a) * (1.f / (1.f + expf(-b)));
-    }
+    st_gate(g, nv);
     __syncthreads();
     // [out | skip] as one 128-wide conv of z: residual (out + x) * sqrt(.5), skip sum
     st_dense<FT>(W + y.w_os, 128, 64, 1, 1, g, ST_LD, nv, [&](int f, int co, float a) {
       if (co < 64)
-        xc[f * 64 + co] = (((y.b_out >= 0 ? P[y.b_out + co] : 0.f) + a) + xc[f * 64 + co]) * 0.70710678118654752440f;
+        st_residual(&xc[f * 64 + co], P, y.b_out, co, a, &xc[f * 64 + co]);
       else
-        skip[f * 64 + co - 64] += (y.b_skip >= 0 ? P[y.b_skip + co - 64] : 0.f) + a;
+        skip[f * 64 + co - 64] += st_skip_term(P, y.b_skip, co, a);
     });
     __syncthreads();
   }
@@ -195,54 +120,6 @@ __device__ void st_net(const StP& p, const StNet& n, int s, const float* in, int
   __syncthreads();
 }
 
-// Nearest code of the nv rows xs (row stride ST_LD) in cb [K][D]: a thread owns a code (its row in registers), the frames
-// pass by as LDS broadcasts, a wave meets per frame under the (distance, then index) order, the four waves through LDS.
-template <int D>
-__device__ void st_vq(const float* __restrict__ cb, int K, const float* xs, int nv, const StLds& m) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < nv) m.x2s[tid] = vq_norm<D>(vq_row16(xs + tid * ST_LD));
-  __syncthreads();
-  for (int k0 = 0; k0 < K; k0 += ST_THREADS) {
-    const int k = k0 + tid;
-    const bool live = k < K;
-    float w[D];
-    const float* wp = cb + (size_t)(live ? k : 0) * D;
-#pragma unroll
-    for (int d = 0; d < D; d += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wp + d);
-      w[d] = v[0]; w[d + 1] = v[1]; w[d + 2] = v[2]; w[d + 3] = v[3];
-    }
-    const float w2 = vq_norm<D>(w);
-    for (int f = 0; f < nv; f++) {
-      const float dist = vq_dist(w2, vq_dot<D>(vq_row16(xs + f * ST_LD), w), m.x2s[f]);
-      const bool ok = live && dist < INFINITY;  // (a NaN or an infinite distance never wins: the row then takes code 0)
-      float bd = ok ? dist : INFINITY;
-      int bi = ok ? k : 0x7fffffff;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float od = __shfl_xor(bd, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (vq_better(od, oi, bd, bi)) { bd = od; bi = oi; }
-      }
-      if (lane == 0) {
-        const int slot = wave * ST_TILE + f;
-        if (k0 == 0 || vq_better(bd, bi, m.red_d[slot], m.red_i[slot])) { m.red_d[slot] = bd; m.red_i[slot] = bi; }
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < nv) {
-    float bd = m.red_d[tid];
-    int bi = m.red_i[tid];
-    for (int wv = 1; wv < ST_THREADS / 64; wv++) {
-      const float od = m.red_d[wv * ST_TILE + tid];
-      const int oi = m.red_i[wv * ST_TILE + tid];
-      if (vq_better(od, oi, bd, bi)) { bd = od; bi = oi; }
-    }
-    m.idxs[tid] = vq_pin(bi, K);
-  }
-  __syncthreads();
-}
 
 // frames [r0, r0 + nv) of stream s (rows of the caller's (S, C, .) tensors): vqvae2.py:160-190
 template <int FT>
@@ -350,26 +227,22 @@ __global__ __launch_bounds__(ST_THREADS) void stream_push_kernel(const StP p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-struct StreamH {
+struct StreamH : StTables {
   StP p;
-  std::vector<StLayer> layers;
-  std::vector<StPrep> preps;
-  long long wt_floats = 0, state_floats = 0;
-  int rows = 0, S = 0, Cmax = 0;
+  int S = 0, Cmax = 0;
   float *wt = nullptr, *state = nullptr;
   StLayer* d_layers = nullptr;
   StPrep* d_preps = nullptr;
   bool prepared = false;
 };
 
-static int st_malloc(void** q, size_t bytes) {
+int st_malloc(void** q, size_t bytes) {
   if (hipMalloc(q, bytes) != hipSuccess) return CRK_ERR_HIP;
   crk_count_alloc_();
   return CRK_OK;
 }
 
-// the conv table of one stack (crk_net_conv_info) as this family's tables; CRK_ERR_UNSUPPORTED for what the kernel does not take
-static int st_add_net(StreamH* h, void* net, long long base, int in_ch, int out_ch, int aux_ch, StNet* out) {
+int st_add_net(StTables* h, void* net, long long base, int in_ch, int out_ch, int aux_ch, StNet* out) {
   if (!net || in_ch < 1 || in_ch > 128 || out_ch < 1 || out_ch > 128 || aux_ch < 0 || aux_ch > 128) return CRK_ERR_UNSUPPORTED;
   StNet n;
   memset(&n, 0, sizeof(n));
@@ -524,13 +397,18 @@ extern "C" int crk_stream_reserve(void* hh, int S, int C_max) {
   return CRK_OK;
 }
 
+int st_prepare_launch(const StPrep* d_preps, int nprep, int rows, const float* params, float* wt, void* stream) {
+  hipLaunchKernelGGL(stream_prepare_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, d_preps, nprep, params, wt);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
 extern "C" int crk_stream_prepare(void* hh, const float* params, unsigned long long version, void* stream) {
   StreamH* h = (StreamH*)hh;
   (void)version;  // (the caller's bookkeeping: one call per parameter version)
   if (!h || !params || !h->wt) return CRK_ERR_ARG;
-  hipLaunchKernelGGL(stream_prepare_kernel, dim3(h->rows), dim3(64), 0, (hipStream_t)stream, h->d_preps, (int)h->preps.size(),
-                     params, h->wt);
-  CRK_CHECK_LAUNCH();
+  const int rc = st_prepare_launch(h->d_preps, (int)h->preps.size(), h->rows, params, h->wt, stream);
+  if (rc != CRK_OK) return rc;
   h->p.params = params;
   h->prepared = true;
   return CRK_OK;

@@ -1,7 +1,8 @@
 """The live conversion loop on the MI355X: pushes of samples in, pushes of converted samples out.
 
 ``LiveConverter`` owns the four streaming stages - ``StreamingLogMel`` and ``StreamingF0`` (the front ends),
-``StreamingConverter`` and ``StreamingVocoder`` - and what connects them on the device (csrc/join_kernels.hip,
+``StreamingConverter`` (or, with ``lookahead=True``, ``LookaheadConverter`` for the recipe's default non-causal generators)
+and ``StreamingVocoder`` - and what connects them on the device (csrc/join_kernels.hip,
 DESIGN.md section 6m):
 
 ``FrameJoin`` (``crk_join_*``) pairs the rows of two inputs that arrive at different delays.  Log-mel frame t arrives
@@ -22,7 +23,7 @@ import torch
 from crank_amd import _lib
 from crank_amd._lib import check, stream_ptr
 from crank_amd._ragged import made, release, require_gpu
-from crank_amd.stream import StreamingConverter, check_stream_conf
+from crank_amd.stream import LookaheadConverter, StreamingConverter, check_lookahead_conf, check_stream_conf
 
 
 def join_capacities(fs, n_fft, hop, center, back_ms=300, ahead_ms=100, block_ms=80, max_samples=None):
@@ -205,16 +206,25 @@ class LiveConverter:
 
     The emitted samples do not depend on how the signal is cut into pushes when ``noise`` is given (zeros, or the caller's
     own tape); noise drawn on the device (``noise=None``) is drawn per push, so the waveform then depends on the cut.
-    Refused with NotImplementedError, naming the key: what ``check_stream_conf`` refuses, ``encoder_f0`` (it needs the
+    ``lookahead=True`` takes a generator built with ``causal: false`` (the recipe's default) instead: the conversion stage is
+    a ``LookaheadConverter`` that follows its input ``lookahead_frames(conf)`` frames behind (66 for the default shapes, 383
+    ms at 22.05 kHz with hop 128 - ``latency_ms`` counts them) and ends utterances itself under the join's end flag.  A push
+    that ends an utterance emits up to ``max_out = max_chunk + lookahead`` frames, so the vocoder stage, the noise argument
+    and the output buffers are ``max_out`` frames (``max_out * hop`` samples) wide; without the keyword ``max_out`` is
+    ``max_chunk``.  The samples are those of the offline forward of the whole utterance through the vocoder.
+
+    Refused with NotImplementedError, naming the key: what ``check_stream_conf`` (``check_lookahead_conf`` with
+    ``lookahead=True``) refuses, ``encoder_f0`` (it needs the
     unconverted rows, which ``StreamingF0`` does not emit in the same pass), an ``input_size`` that is not the layer's
     ``n_mels`` and an ``output_size`` that is not the vocoder's ``aux_channels``."""
 
     def __init__(self, G, layer, vocoder, n_streams, max_samples, minf0s=None, maxf0s=None, spk_lcf0_mean=None,
-                 spk_lcf0_std=None, scaler=None, **f0_grid):
+                 spk_lcf0_std=None, scaler=None, lookahead=False, **f0_grid):
         from crank_amd.world import StreamingF0
 
         conf = G.conf
-        check_stream_conf(conf, G.spkr_size)
+        self.lookahead = bool(lookahead)
+        (check_lookahead_conf if self.lookahead else check_stream_conf)(conf, G.spkr_size)
         if conf["encoder_f0"]:
             raise NotImplementedError("encoder_f0 = true: the encoder takes the unconverted lcf0 / uv rows, which StreamingF0 "
                                       "does not emit in the same pass")
@@ -267,8 +277,14 @@ class LiveConverter:
             if f0_grid:
                 raise ValueError(f"{sorted(f0_grid)}: the F0 grid of a model without decoder_f0")
             self.max_chunk = self.sl.max_frames
-        self.conv = StreamingConverter(G, S, self.max_chunk, dev)
-        self.sv = vocoder.streaming(S, self.max_chunk)
+        # the frames one push can hand to the vocoder: with look-ahead an end push flushes the frames the converter holds back
+        if self.lookahead:
+            self.conv = LookaheadConverter(G, S, self.max_chunk, dev)
+            self.max_out = self.conv.max_out
+        else:
+            self.conv = StreamingConverter(G, S, self.max_chunk, dev)
+            self.max_out = self.max_chunk
+        self.sv = vocoder.streaming(S, self.max_out)
         # what a push writes between the stages: made here, never in push
         self._nv = torch.zeros(S, dtype=torch.int32, device=dev)
         self._end = torch.zeros(S, dtype=torch.int32, device=dev)
@@ -276,8 +292,8 @@ class LiveConverter:
         self._first = torch.zeros(S, dtype=torch.int32, device=dev)  # (without a join: the frames emitted so far)
         self._goes_on = torch.zeros(S, dtype=torch.bool, device=dev)  # (without a join: the stream's end flag is 0)
         self._fr = self.sl.empty_outputs(S)
-        self._conv_out = self.conv.empty_outputs(S, self.max_chunk)
-        self._c = torch.zeros(S, self.max_chunk, D, device=dev)
+        self._conv_out = self.conv.empty_outputs(S) if self.lookahead else self.conv.empty_outputs(S, self.max_chunk)
+        self._c = torch.zeros(S, self.max_out, D, device=dev)
         self._zero_noise = None
         if self.decoder_f0:
             self._f0 = self.sf.empty_outputs(S)
@@ -292,8 +308,10 @@ class LiveConverter:
     @property
     def latency_ms(self):
         """The worst-case algorithmic delay from a sample to its converted sample: the later front end (half a window,
-        or F0's look-ahead plus a block), then the vocoder's look-ahead.  The length of a push and the push times add to it."""
-        return self._front_ms + 1000.0 * self.sv.lookahead * self.hop_size / self.fs
+        or F0's look-ahead plus a block), the generator's look-ahead when ``lookahead=True``, then the vocoder's look-ahead.
+        The length of a push and the push times add to it."""
+        frames = self.sv.lookahead + (self.conv.lookahead if self.lookahead else 0)
+        return self._front_ms + 1000.0 * frames * self.hop_size / self.fs
 
     def reset(self, streams=None):
         """``streams`` (all of them by default) start a new utterance in every stage; what they hold is dropped."""
@@ -315,9 +333,9 @@ class LiveConverter:
     def empty_outputs(self, S, decoded=False):
         """Output buffers of one push, in the form ``push(out=...)`` takes and returns; ``decoded``: also the decoded rows
         (scaled, as the generator emits them), their count and the utterance's frame index of the first one."""
-        out = self.sv.empty_outputs(S, self.max_chunk)
+        out = self.sv.empty_outputs(S, self.max_out)
         if decoded:
-            out.update(decoded=torch.empty(S, self.max_chunk, self.conf["output_size"], device=self.device),
+            out.update(decoded=torch.empty(S, self.max_out, self.conf["output_size"], device=self.device),
                        n_frames=torch.empty(S, dtype=torch.int32, device=self.device),
                        first=torch.empty(S, dtype=torch.int32, device=self.device))
         return out
@@ -333,8 +351,8 @@ class LiveConverter:
     def push(self, wave, org_spk, cv_spk, n_valid=None, end=None, noise=None, out=None):
         """wave (S, C) float32 samples on the GPU, S = ``n_streams``, C <= ``max_samples``; org_spk / cv_spk int32 (S,) on
         the GPU; n_valid, end: S host integers (default: C, 0) - the samples that count per stream and non-zero where this
-        push ends the stream's utterance; noise (S, max_chunk * hop) float32 or None (drawn on the device per push: the
-        waveform then depends on the cut).  Returns ``wave`` (S, (max_chunk + lookahead) * hop) and ``n_out`` (S,) int32 as
+        push ends the stream's utterance; noise (S, max_out * hop) float32 or None (drawn on the device per push: the
+        waveform then depends on the cut).  Returns ``wave`` (S, (max_out + the vocoder's lookahead) * hop) and ``n_out`` (S,) int32 as
         ``StreamingVocoder.push`` does; with ``out=`` buffers from ``empty_outputs(S, decoded=True)`` also ``decoded``,
         ``n_frames`` and ``first`` (the frame index of ``decoded[:, 0]`` in its utterance)."""
         if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.device.type != "cuda" or wave.dtype != torch.float32:
@@ -346,7 +364,7 @@ class LiveConverter:
         if nv_h.min() < 0 or nv_h.max() > C:
             raise ValueError(f"n_valid: 0 .. {C}")
         org_spk, cv_spk = _int32(org_spk, S, "org_spk"), _int32(cv_spk, S, "cv_spk")
-        N = self.max_chunk * self.hop_size
+        N = self.max_out * self.hop_size
         if noise is not None and (noise.device.type != "cuda" or noise.dtype != torch.float32 or tuple(noise.shape) != (S, N)):
             raise ValueError(f"noise: a float32 ({S}, {N}) tensor on the GPU")
         if out is None:
@@ -364,17 +382,21 @@ class LiveConverter:
             else:
                 feats, n, first, cond = fr["feats"], fr["n_frames"], self._first, None
             conv_out = self._conv_out if "decoded" not in out else dict(self._conv_out, decoded=out["decoded"])
-            dec = self.conv.push(feats, None, None, self._spk, n_valid=n, lcf0_uv=cond, out=conv_out)["decoded"]
+            if self.lookahead:  # the converter ends utterances itself and says which frames leave
+                res = self.conv.push(feats, None, None, self._spk, n_valid=n, end=self._end, lcf0_uv=cond, out=conv_out)
+                dec, n, first = res["decoded"], res["n_out"], res["first"]
+            else:
+                dec = self.conv.push(feats, None, None, self._spk, n_valid=n, lcf0_uv=cond, out=conv_out)["decoded"]
             feat_renorm(dec, self._scale, self._mean, self._vmean, self._vscale, n, self._c)
             res = self.sv.push(self._c, noise, n_valid=n, end=self._end, out={"wave": out["wave"], "n_out": out["n_out"]})
             if "n_frames" in out:
                 out["n_frames"].copy_(n)
                 out["first"].copy_(first)
-            if not self.decoder_f0:  # the frames emitted so far, for `first`: 0 again behind an end
+            if not self.decoder_f0 and not self.lookahead:  # the frames emitted so far, for `first`: 0 again behind an end
                 torch.eq(self._end, 0, out=self._goes_on)
                 self._first.add_(n).mul_(self._goes_on)
-            ended = [s for s in range(S) if end_h[s]]
-            if ended:  # the converter carries no end flag: its layers' history starts over
+            ended = [] if self.lookahead else [s for s in range(S) if end_h[s]]
+            if ended:  # the causal converter carries no end flag: its layers' history starts over
                 self.conv.reset(ended)
         out["wave"], out["n_out"] = res["wave"], res["n_out"]
         return out

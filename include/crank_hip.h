@@ -934,6 +934,38 @@ int crk_stream_push(void* st, const float* x, int ldx, const float* dec_cond, in
                     const long long* spk, const int* n_valid, int S, int C, float* decoded, long long* const* qidx,
                     float* const* encoded, void* stream);
 
+/* ---- look-ahead streaming conversion for non-causal generators (csrc/stream_la_kernels.hip) ----
+ * The same forward for a generator built without use_causal_conv, followed LA = crk_lstream_lookahead frames behind its
+ * input: the sum over every residual layer of the chain of (k - 1) / 2 * dilation.  After T frames of an utterance
+ * max(0, T - LA) of its frames have been emitted; a push with the end flag runs LA more steps on zero input, emits the rest
+ * and starts the stream over.  The emitted rows are the offline forward of the whole utterance and do not depend on how it
+ * is cut into pushes, bit for bit.  One launch per push, one workgroup per stream; the cost of a push is that of
+ * n_valid (+ LA under the end flag) steps of the causal kernel plus ring traffic.
+ *
+ * crk_lstream_create takes crk_stream_desc with causal = 0 and the stack handles as crk_stream_create does.
+ * CRK_ERR_UNSUPPORTED: causal != 0, what crk_stream_create refuses, an even kernel size.  The state per stream is each
+ * layer's last (k - 1) * dilation input rows, a frame counter, and rings [ring][frame mod capacity][row] for what waits
+ * for a delayed layer per frame: conditioning rows with the speaker of the push that delivered the frame, each stack's
+ * partially summed skip rows, enc[n] until dec[n + 1] arrives, quantized rows of the upper stacks, encoded / qidx until the
+ * decoded row exists.  crk_lstream_state_bytes counts all of it.
+ * crk_lstream_reserve / prepare / reset: as crk_stream_*; a reset stream's next frame is frame 0 of an utterance.
+ * crk_lstream_push: inputs as crk_stream_push, plus end [S] int32 on the device (NULL: no stream ends), non-zero where
+ * this push carries the utterance's last frames (n_valid may be 0).  Outputs have rows_out >= C + LA rows per stream:
+ * decoded [S][rows_out][out_ch], qidx[n] [S][rows_out] int64, encoded[n] [S][rows_out][emb_dim[n]]; row j is frame
+ * first[s] + j of the stream's utterance, rows at and past n_out[s] are not written; n_out, first [S] int32 on the device.
+ * The speaker of a frame is spk[s] of the push that delivered it.  Never allocates, never synchronises, reads nothing
+ * back, one launch: capturable.  CRK_ERR_UNSUPPORTED without a launch for S or C beyond what was reserved. */
+int crk_lstream_create(const crk_stream_desc* desc, void* const* enc_nets, void* const* dec_nets, void** handle);
+void crk_lstream_destroy(void* st);
+int crk_lstream_lookahead(void* st);
+int crk_lstream_reserve(void* st, int S, int C_max);
+long long crk_lstream_state_bytes(void* st, int S);
+int crk_lstream_prepare(void* st, const float* params, unsigned long long version, void* stream);
+int crk_lstream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_lstream_push(void* st, const float* x, int ldx, const float* dec_cond, int ldd, const float* enc_cond, int lde,
+                     const long long* spk, const int* n_valid, const int* end, int S, int C, int rows_out, float* decoded,
+                     long long* const* qidx, float* const* encoded, int* n_out, int* first, void* stream);
+
 /* ---- Frame join and the live loop's back-half affine (join_kernels.hip) -----------------------
  * crk_join_*: a two-input row join for up to n_streams streams.  Input A has rows of width_a floats, input B rows of
  * width_b floats (the live loop: log-mel frames and [lcf0, uv]); row k of A and row k of B of an utterance leave together
