@@ -1,5 +1,8 @@
-"""Plumbing the ragged-batch families share (world.py, griffin_lim.py, vocoder.py, bin/evaluate_mcd.py): offset tensors,
-input conversion, the grow-only workspace, the device check and the lifetime of a native handle."""
+"""Plumbing the ragged-batch and streaming families share (world.py, griffin_lim.py, vocoder.py, stream.py, live.py,
+net/module/mlfb.py, bin/evaluate_mcd.py): offset tensors, input conversion, the grow-only workspace, the device check, the
+lifetime of a native handle and the reset of a streaming handle's streams."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -48,6 +51,16 @@ def made(handle, create):
     if not handle:
         raise RuntimeError(f"libcrank_hip: {create} failed (unsupported configuration or HIP error)")
     return handle
+
+
+def reset_streams(handle, entry, streams, device):
+    """The body of a streaming class's ``reset``: the library's ``entry`` (``crk_*_reset``) on ``streams``, or on every
+    stream of ``handle`` when that is None, in the current stream of ``device``.  Validates no id: an id the handle does
+    not have is the library's CRK_ERR_ARG (a RuntimeError), raised before anything is zeroed."""
+    ids = None if streams is None else [int(s) for s in streams]
+    arr = None if ids is None else (ctypes.c_int * max(len(ids), 1))(*ids)
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), entry)(handle, arr, 0 if ids is None else len(ids), _lib.stream_ptr()), entry)
 
 
 def release(owner, attr, destroy):

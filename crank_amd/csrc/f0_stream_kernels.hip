@@ -363,20 +363,15 @@ extern "C" int crk_f0_stream_max_rounds(void* st) {
 
 extern "C" int crk_f0_stream_reset(void* st, const int* stream_ids, int n, void* stream) {
   F0Stream* h = static_cast<F0Stream*>(st);
-  if (!h || n < 0) return CRK_ERR_ARG;
-  hipStream_t q = (hipStream_t)stream;
+  if (!h) return CRK_ERR_ARG;
+  const int rc = crk_zero_stream_rows(h->g.state, sizeof(FsState), h->S, stream_ids, n, (hipStream_t)stream);
+  if (rc != CRK_OK) return rc;
+  // the host's copy of the counts
   if (!stream_ids) {
-    if (hipMemsetAsync(h->g.state, 0, (size_t)h->S * sizeof(FsState), q) != hipSuccess) return CRK_ERR_HIP;
     h->n.assign(h->S, 0);
     h->b.assign(h->S, 0);
-    return CRK_OK;
   }
-  for (int i = 0; i < n; ++i)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; ++i) {
-    if (hipMemsetAsync(h->g.state + stream_ids[i], 0, sizeof(FsState), q) != hipSuccess) return CRK_ERR_HIP;
-    h->n[stream_ids[i]] = h->b[stream_ids[i]] = 0;
-  }
+  for (int i = 0; stream_ids && i < n; ++i) h->n[stream_ids[i]] = h->b[stream_ids[i]] = 0;
   return CRK_OK;
 }
 

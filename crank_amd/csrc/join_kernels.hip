@@ -196,14 +196,8 @@ extern "C" int crk_join_max_frames(void* st) {
 
 extern "C" int crk_join_reset(void* st, const int* stream_ids, int n, void* stream) {
   FrameJoin* h = static_cast<FrameJoin*>(st);
-  if (!h || n < 0) return CRK_ERR_ARG;
-  hipStream_t q = (hipStream_t)stream;
-  if (!stream_ids) return hipMemsetAsync(h->g.state, 0, h->state_bytes, q) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
-  for (int i = 0; i < n; ++i)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; ++i)
-    if (hipMemsetAsync(h->g.state + stream_ids[i], 0, sizeof(JoinState), q) != hipSuccess) return CRK_ERR_HIP;
-  return CRK_OK;
+  if (!h) return CRK_ERR_ARG;
+  return crk_zero_stream_rows(h->g.state, sizeof(JoinState), h->S, stream_ids, n, (hipStream_t)stream);
 }
 
 extern "C" int crk_join_push(void* st, const float* a, int lda, const int* n_a, const float* b, int ldb, const int* n_b,

@@ -404,14 +404,8 @@ extern "C" int crk_logmel_stream_max_frames(void* st) {
 
 extern "C" int crk_logmel_stream_reset(void* st, const int* stream_ids, int n, void* stream) {
   LogMelStream* h = static_cast<LogMelStream*>(st);
-  if (!h || n < 0) return CRK_ERR_ARG;
-  hipStream_t q = (hipStream_t)stream;
-  if (!stream_ids) return hipMemsetAsync(h->g.counts, 0, (size_t)h->S * 16, q) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
-  for (int i = 0; i < n; ++i)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; ++i)
-    if (hipMemsetAsync(h->g.counts + 2 * stream_ids[i], 0, 16, q) != hipSuccess) return CRK_ERR_HIP;
-  return CRK_OK;
+  if (!h) return CRK_ERR_ARG;
+  return crk_zero_stream_rows(h->g.counts, 16, h->S, stream_ids, n, (hipStream_t)stream);  // a stream's two 64-bit counts
 }
 
 extern "C" int crk_logmel_stream_push(void* st, const float* x, int ldx, const int* n_valid, const int* end, int S, int C,

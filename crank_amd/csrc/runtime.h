@@ -1,5 +1,5 @@
 // What every kernel family's host side shares (runtime.hip): the process switches, the per-class HIP-event timing of
-// bench.py's roofline leg, the dynamic-LDS limit helper and the allocation counter.
+// bench.py's roofline leg, the dynamic-LDS limit helper, the streaming families' reset and the allocation counter.
 #pragma once
 #include "common.h"
 #include "switches.h"
@@ -30,5 +30,10 @@ inline int crk_raise_lds(int bytes, K*... kernels) {
       lds_raised_ = true;                                                     \
     }                                                                         \
   }
+
+// The reset of every streaming family: zeroes row i (bytes_per_stream bytes) of `base` for every i of the host array ids
+// [n], or all S rows where ids is null.  Every id is checked before the first memset: CRK_ERR_ARG for one outside 0 .. S-1,
+// nothing zeroed.
+int crk_zero_stream_rows(void* base, size_t bytes_per_stream, int S, const int* ids, int n, hipStream_t stream);
 
 long long crk_count_alloc_(void);  // net.hip: the allocation counter behind crk_debug_alloc_count

@@ -109,4 +109,15 @@ extern "C" int crk_prof_report(int cls, long long* count, double* total_ms, doub
   return CRK_OK;
 }
 
+int crk_zero_stream_rows(void* base, size_t bytes_per_stream, int S, const int* ids, int n, hipStream_t stream) {
+  if (!base || n < 0) return CRK_ERR_ARG;
+  if (!ids) return hipMemsetAsync(base, 0, bytes_per_stream * S, stream) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0 || ids[i] >= S) return CRK_ERR_ARG;
+  for (int i = 0; i < n; i++)
+    if (hipMemsetAsync((char*)base + (size_t)ids[i] * bytes_per_stream, 0, bytes_per_stream, stream) != hipSuccess)
+      return CRK_ERR_HIP;
+  return CRK_OK;
+}
+
 extern "C" const char* crk_version(void) { return "crank_hip 0.1 (gfx950)"; }

@@ -21,10 +21,11 @@
 // what an fp32 chain reads.)  The codebook search is built from the device bodies of vq_common.h - the ones every search
 // kernel of vq_kernels.hip is built from: norms, dot product, distance, (distance, then index) order, NaN pin and
 // straight-through value - so the indices are crk_vq_forward's on the same rows by construction.
-#include <string.h>
-
+//
+// Host side.  This file defines, once, what the entry points of this family and of stream_la_kernels.hip are made of and
+// stream_common.h declares: the table builder, the descriptor check, the first reserve's tables, the zeroed per-stream
+// buffer, the prepare launch, the common frees.  crk_stream_* at the end is that plus StP and the launch.
 #include "stream_common.h"
-#include "../../include/crank_hip.h"
 
 struct StP {
   StNet enc[ST_MAX_STACKS], dec[ST_MAX_STACKS];
@@ -112,12 +113,7 @@ __device__ void st_net(const StP& p, const StNet& n, int s, const float* in, int
   }
   for (int i = tid; i < nv * 64; i += ST_THREADS) g[(i >> 6) * ST_LD + (i & 63)] = fmaxf(skip[i] * n.skip_scale, 0.f);
   __syncthreads();
-  st_dense<FT>(W + n.w_last1, 64, 64, 1, 1, g, ST_LD, nv,
-               [&](int f, int co, float a) { skip[f * 64 + co] = fmaxf(P[n.b_last1 + co] + a, 0.f); });
-  __syncthreads();
-  st_dense<FT>(W + n.w_last2, n.out_ch, 64, 1, 1, skip, 64, nv,
-               [&](int f, int co, float a) { m.io[f * ST_LD + co] = P[n.b_last2 + co] + a; });
-  __syncthreads();
+  st_last<FT>(W, P, n, g, skip, nv, m);
 }
 
 
@@ -126,18 +122,12 @@ template <int FT>
 __device__ void st_tile(const StP& p, int s, long long r0, int nv, const StLds& m) {
   const int tid = threadIdx.x;
   const float* P = p.params;
-  {
-    const int ip = p.enc[0].in_pad, ic = p.enc[0].in_ch;
-    for (int i = tid; i < nv * ip; i += ST_THREADS) {
-      const int f = i / ip, c = i - f * ip;
-      m.io[f * ST_LD + c] = c < ic ? p.x[(r0 + f) * p.ldx + c] : 0.f;
+  st_load_input(p, r0, nv, m, [](int) { return true; });  // (every row of a causal tile has an input frame)
+  if (p.enc_f0)
+    for (int i = tid; i < nv * 4; i += ST_THREADS) {
+      const int f = i >> 2, c = i & 3;
+      m.cond[f * ST_LD + c] = c < 2 ? p.econd[(r0 + f) * p.lde + c] : 0.f;
     }
-    if (p.enc_f0)
-      for (int i = tid; i < nv * 4; i += ST_THREADS) {
-        const int f = i >> 2, c = i & 3;
-        m.cond[f * ST_LD + c] = c < 2 ? p.econd[(r0 + f) * p.lde + c] : 0.f;
-      }
-  }
   __syncthreads();
   for (int n = 0; n < p.nst; n++) {
     st_net<FT>(p, p.enc[n], s, m.io, nv, m);
@@ -188,7 +178,7 @@ __device__ void st_tile(const StP& p, int s, long long r0, int nv, const StLds& 
       const int f = i / ap, c = i - f * ap, e = c - p.dec_f0;
       float v = 0.f;
       if (c < p.dec_f0) v = p.dcond[(r0 + f) * p.ldd + c];
-      else if (e < p.spk_dim) v = p.spk_onehot ? (e == (int)spk ? 1.f : 0.f) : P[p.spk_off + spk * p.spk_dim + e];
+      else if (e < p.spk_dim) v = st_spk_value(p, P, spk, e);
       m.cond[f * ST_LD + c] = v;
     }
   }
@@ -204,16 +194,7 @@ __device__ void st_tile(const StP& p, int s, long long r0, int nv, const StLds& 
 
 __global__ __launch_bounds__(ST_THREADS) void stream_push_kernel(const StP p) {
   extern __shared__ __attribute__((aligned(16))) float st_lds[];
-  StLds m;
-  m.xw = st_lds;
-  m.g = m.xw + (ST_HALO + ST_TILE) * 64;
-  m.skip = m.g + ST_TILE * ST_LD;
-  m.cond = m.skip + ST_TILE * 64;
-  m.io = m.cond + ST_TILE * ST_LD;
-  m.red_d = m.io + ST_TILE * ST_LD;
-  m.red_i = reinterpret_cast<int*>(m.red_d + 4 * ST_TILE);
-  m.x2s = m.red_d + 8 * ST_TILE;
-  m.idxs = reinterpret_cast<int*>(m.red_d + 9 * ST_TILE);
+  const StLds m = st_carve(st_lds);
   const int s = blockIdx.x;
   int total = p.n_valid ? p.n_valid[s] : p.C;
   total = min(max(total, 0), p.C);
@@ -227,15 +208,9 @@ __global__ __launch_bounds__(ST_THREADS) void stream_push_kernel(const StP p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-struct StreamH : StTables {
-  StP p;
-  int S = 0, Cmax = 0;
-  float *wt = nullptr, *state = nullptr;
-  StLayer* d_layers = nullptr;
-  StPrep* d_preps = nullptr;
-  bool prepared = false;
-};
+struct StreamH : StHandle { StP p; };
 
+// ---- what both families' entry points are made of (stream_common.h)
 int st_malloc(void** q, size_t bytes) {
   if (hipMalloc(q, bytes) != hipSuccess) return CRK_ERR_HIP;
   crk_count_alloc_();
@@ -316,11 +291,12 @@ int st_add_net(StTables* h, void* net, long long base, int in_ch, int out_ch, in
   return CRK_OK;
 }
 
-extern "C" int crk_stream_create(const crk_stream_desc* desc_, void* const* enc_nets, void* const* dec_nets, void** handle) {
-  if (!desc_ || !enc_nets || !dec_nets || !handle) return CRK_ERR_ARG;
+int st_check_desc(const crk_stream_desc* d_, void* const* enc_nets, void* const* dec_nets, void** handle, bool causal, int* qsum_,
+                  int* d_aux_) {
+  if (!d_ || !enc_nets || !dec_nets || !handle) return CRK_ERR_ARG;
   *handle = nullptr;
-  const crk_stream_desc& d = *desc_;
-  if (d.n_stacks < 1 || d.n_stacks > ST_MAX_STACKS || !d.causal) return CRK_ERR_UNSUPPORTED;
+  const crk_stream_desc& d = *d_;
+  if (d.n_stacks < 1 || d.n_stacks > ST_MAX_STACKS || (d.causal != 0) != causal) return CRK_ERR_UNSUPPORTED;
   int qsum = 0;
   for (int n = 0; n < d.n_stacks; n++) {
     const int D = d.emb_dim[n];
@@ -331,22 +307,53 @@ extern "C" int crk_stream_create(const crk_stream_desc* desc_, void* const* enc_
   if (qsum > 128 || d.spk_dim < 0 || d_aux > 128 || d.n_spk < 1 || (d.spk_onehot && d.spk_dim != d.n_spk) ||
       (!d.spk_onehot && d.spk_dim > 0 && d.spk_off < 0))
     return CRK_ERR_UNSUPPORTED;
+  *qsum_ = qsum; *d_aux_ = d_aux;
+  return CRK_OK;
+}
+
+int st_reserve_tables(StHandle* h, int S, int C_max) {
+  if (!h) return CRK_ERR_ARG;
+  if (S < 1 || C_max < 1 || C_max > ST_MAX_CHUNK) return CRK_ERR_UNSUPPORTED;
+  if (h->wt) return CRK_OK;
+  int rc = st_malloc((void**)&h->wt, sizeof(float) * h->wt_floats);
+  if (rc == CRK_OK) rc = st_malloc((void**)&h->d_layers, sizeof(StLayer) * h->layers.size());
+  if (rc == CRK_OK) rc = st_malloc((void**)&h->d_preps, sizeof(StPrep) * h->preps.size());
+  if (rc != CRK_OK) return rc;
+  if (hipMemset(h->wt, 0, sizeof(float) * h->wt_floats) != hipSuccess ||
+      hipMemcpy(h->d_layers, h->layers.data(), sizeof(StLayer) * h->layers.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_preps, h->preps.data(), sizeof(StPrep) * h->preps.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return CRK_ERR_HIP;
+  return CRK_OK;
+}
+
+int st_zeroed(void** q, size_t bytes) {
+  *q = nullptr;
+  const int rc = st_malloc(q, bytes);
+  if (rc != CRK_OK) return rc;
+  if (hipMemset(*q, 0, bytes) == hipSuccess) return CRK_OK;
+  (void)hipFree(*q);
+  *q = nullptr;
+  return CRK_ERR_HIP;
+}
+
+void st_free_tables(StHandle* h) {
+  (void)hipFree(h->wt); (void)hipFree(h->state); (void)hipFree(h->d_layers); (void)hipFree(h->d_preps);
+}
+
+int st_prepare_launch(const StPrep* d_preps, int nprep, int rows, const float* params, float* wt, void* stream) {
+  hipLaunchKernelGGL(stream_prepare_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, d_preps, nprep, params, wt);
+  CRK_CHECK_LAUNCH();
+  return CRK_OK;
+}
+
+// ---- the causal family's entry points
+extern "C" int crk_stream_create(const crk_stream_desc* desc, void* const* enc_nets, void* const* dec_nets, void** handle) {
+  int qsum, d_aux;
+  int rc = st_check_desc(desc, enc_nets, dec_nets, handle, true, &qsum, &d_aux);
+  if (rc != CRK_OK) return rc;
   StreamH* h = new StreamH();
-  memset(&h->p, 0, sizeof(h->p));
-  StP& p = h->p;
-  p.nst = d.n_stacks; p.enc_f0 = d.enc_f0 ? 1 : 0; p.dec_f0 = d.dec_f0 ? 2 : 0; p.spk_dim = d.spk_dim;
-  p.spk_onehot = d.spk_onehot ? 1 : 0; p.n_spk = d.n_spk; p.spk_off = d.spk_off;
-  int rc = CRK_OK;
-  for (int n = 0; n < d.n_stacks && rc == CRK_OK; n++) {
-    p.emb_dim[n] = d.emb_dim[n]; p.emb_size[n] = d.emb_size[n]; p.cb_off[n] = d.cb_off[n];
-    rc = st_add_net(h, enc_nets[n], d.enc_base[n], n == 0 ? d.in_ch : d.emb_dim[n - 1], d.emb_dim[n],
-                    n == 0 && d.enc_f0 ? 2 : 0, &p.enc[n]);
-    if (rc == CRK_OK)
-      rc = st_add_net(h, dec_nets[n], d.dec_base[n], n == 0 ? qsum : d.emb_dim[n], n == 0 ? d.out_ch : d.emb_dim[n - 1],
-                      n == 0 ? d_aux : 0, &p.dec[n]);
-  }
+  rc = st_fill_model(h, h->p, *desc, enc_nets, dec_nets, qsum, d_aux);
   if (rc != CRK_OK) { delete h; return rc; }
-  p.state_stride = h->state_floats;
   *handle = h;
   return CRK_OK;
 }
@@ -354,7 +361,7 @@ extern "C" int crk_stream_create(const crk_stream_desc* desc_, void* const* enc_
 extern "C" void crk_stream_destroy(void* hh) {
   StreamH* h = (StreamH*)hh;
   if (!h) return;
-  (void)hipFree(h->wt); (void)hipFree(h->state); (void)hipFree(h->d_layers); (void)hipFree(h->d_preps);
+  st_free_tables(h);
   delete h;
 }
 
@@ -365,67 +372,30 @@ extern "C" long long crk_stream_state_bytes(void* hh, int S) {
 
 extern "C" int crk_stream_reserve(void* hh, int S, int C_max) {
   StreamH* h = (StreamH*)hh;
-  if (!h) return CRK_ERR_ARG;
-  if (S < 1 || C_max < 1 || C_max > ST_MAX_CHUNK) return CRK_ERR_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)stream_push_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st_lds_bytes()) !=
-        hipSuccess)
-      return CRK_ERR_HIP;
-    attr_set = true;
-  }
-  if (!h->wt) {
-    int rc = st_malloc((void**)&h->wt, sizeof(float) * h->wt_floats);
-    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_layers, sizeof(StLayer) * h->layers.size());
-    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_preps, sizeof(StPrep) * h->preps.size());
-    if (rc != CRK_OK) return rc;
-    if (hipMemset(h->wt, 0, sizeof(float) * h->wt_floats) != hipSuccess ||
-        hipMemcpy(h->d_layers, h->layers.data(), sizeof(StLayer) * h->layers.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->d_preps, h->preps.data(), sizeof(StPrep) * h->preps.size(), hipMemcpyHostToDevice) != hipSuccess)
-      return CRK_ERR_HIP;
-    h->p.wt = h->wt; h->p.layers = h->d_layers;
-  }
+  int rc = st_reserve_tables(h, S, C_max);
+  if (rc == CRK_OK) rc = crk_raise_lds((int)st_lds_bytes(), stream_push_kernel);
+  if (rc != CRK_OK) return rc;
   if (S > h->S) {  // more streams: a new, zeroed state (every stream starts over)
-    float* st = nullptr;
-    const int rc = st_malloc((void**)&st, sizeof(float) * h->state_floats * S);
+    float* st;
+    rc = st_zeroed((void**)&st, sizeof(float) * h->state_floats * S);
     if (rc != CRK_OK) return rc;
-    if (hipMemset(st, 0, sizeof(float) * h->state_floats * S) != hipSuccess) { (void)hipFree(st); return CRK_ERR_HIP; }
     (void)hipFree(h->state);
-    h->state = st; h->p.state = st; h->S = S;
+    h->state = st; h->S = S;
   }
   if (C_max > h->Cmax) h->Cmax = C_max;
-  return CRK_OK;
-}
-
-int st_prepare_launch(const StPrep* d_preps, int nprep, int rows, const float* params, float* wt, void* stream) {
-  hipLaunchKernelGGL(stream_prepare_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, d_preps, nprep, params, wt);
-  CRK_CHECK_LAUNCH();
   return CRK_OK;
 }
 
 extern "C" int crk_stream_prepare(void* hh, const float* params, unsigned long long version, void* stream) {
   StreamH* h = (StreamH*)hh;
   (void)version;  // (the caller's bookkeeping: one call per parameter version)
-  if (!h || !params || !h->wt) return CRK_ERR_ARG;
-  const int rc = st_prepare_launch(h->d_preps, (int)h->preps.size(), h->rows, params, h->wt, stream);
-  if (rc != CRK_OK) return rc;
-  h->p.params = params;
-  h->prepared = true;
-  return CRK_OK;
+  return h ? st_prepare(h, h->p, params, stream) : CRK_ERR_ARG;
 }
 
 extern "C" int crk_stream_reset(void* hh, const int* stream_ids, int n, void* stream) {
   StreamH* h = (StreamH*)hh;
-  if (!h || !h->state || n < 0) return CRK_ERR_ARG;
-  const size_t one = sizeof(float) * h->state_floats;
-  if (!stream_ids)
-    return hipMemsetAsync(h->state, 0, one * h->S, (hipStream_t)stream) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
-  for (int i = 0; i < n; i++)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; i++)
-    if (hipMemsetAsync(h->state + (size_t)stream_ids[i] * h->state_floats, 0, one, (hipStream_t)stream) != hipSuccess)
-      return CRK_ERR_HIP;
-  return CRK_OK;
+  if (!h) return CRK_ERR_ARG;
+  return crk_zero_stream_rows(h->state, sizeof(float) * h->state_floats, h->S, stream_ids, n, (hipStream_t)stream);
 }
 
 extern "C" int crk_stream_push(void* hh, const float* x, int ldx, const float* dec_cond, int ldd, const float* enc_cond, int lde,
@@ -433,16 +403,9 @@ extern "C" int crk_stream_push(void* hh, const float* x, int ldx, const float* d
                                long long* const* qidx, float* const* encoded, void* stream) {
   StreamH* h = (StreamH*)hh;
   if (!h) return CRK_ERR_ARG;
-  if (S < 1 || S > h->S || C < 1 || C > h->Cmax) return CRK_ERR_UNSUPPORTED;
-  if (!h->prepared || !x || !spk || !decoded || !qidx || !encoded || ldx < h->p.enc[0].in_ch) return CRK_ERR_ARG;
-  if ((h->p.dec_f0 && (!dec_cond || ldd < 2)) || (h->p.enc_f0 && (!enc_cond || lde < 2))) return CRK_ERR_ARG;
   StP p = h->p;
-  for (int n = 0; n < p.nst; n++) {
-    if (!qidx[n] || !encoded[n]) return CRK_ERR_ARG;
-    p.qidx[n] = qidx[n]; p.encoded[n] = encoded[n];
-  }
-  p.x = x; p.ldx = ldx; p.dcond = dec_cond; p.ldd = ldd; p.econd = enc_cond; p.lde = lde; p.spk = spk; p.n_valid = n_valid;
-  p.C = C; p.decoded = decoded;
+  const int rc = st_push_args(h, p, x, ldx, dec_cond, ldd, enc_cond, lde, spk, n_valid, S, C, decoded, qidx, encoded);
+  if (rc != CRK_OK) return rc;
   hipLaunchKernelGGL(stream_push_kernel, dim3(S), dim3(ST_THREADS), st_lds_bytes(), (hipStream_t)stream, p);
   CRK_CHECK_LAUNCH();
   return CRK_OK;

@@ -22,11 +22,12 @@
 //
 // Arithmetic: the device bodies of stream_common.h and vq_common.h, fp32, one fmaf chain per output element in (tap, input
 // channel) order: a frame's bits do not depend on how the utterance is cut into pushes.
+//
+// Host side: StHandle and the shared functions of stream_common.h (defined in stream_kernels.hip); this file adds the
+// delays and ring layout at create, the rings and frame counters at reserve / reset, and its own push arguments.
 #include <limits.h>
-#include <string.h>
 
 #include "stream_common.h"
-#include "../../include/crank_hip.h"
 
 struct LaRing { long long off; int cap, width; };  // off: floats from the stream's ring block
 
@@ -105,7 +106,7 @@ __device__ __forceinline__ void la_net(const LaP& p, const StNet& n, const LaTil
             v = row[c];
           } else if (speaker && e < p.spk_dim) {
             const int spk = __float_as_int(row[2]);
-            v = p.spk_onehot ? (e == spk ? 1.f : 0.f) : P[p.spk_off + (long long)spk * p.spk_dim + e];
+            v = st_spk_value(p, P, spk, e);
           }
         }
         m.cond[f * ST_LD + c] = v;
@@ -144,12 +145,7 @@ __device__ __forceinline__ void la_net(const LaP& p, const StNet& n, const LaTil
     g[f * ST_LD + (i & 63)] = la_in(fr, t.E) ? fmaxf(la_row(t, rskip, fr)[i & 63] * n.skip_scale, 0.f) : 0.f;
   }
   __syncthreads();
-  st_dense<FT>(W + n.w_last1, 64, 64, 1, 1, g, ST_LD, nv,
-               [&](int f, int co, float a) { m.skip[f * 64 + co] = fmaxf(P[n.b_last1 + co] + a, 0.f); });
-  __syncthreads();
-  st_dense<FT>(W + n.w_last2, n.out_ch, 64, 1, 1, m.skip, 64, nv,
-               [&](int f, int co, float a) { m.io[f * ST_LD + co] = P[n.b_last2 + co] + a; });
-  __syncthreads();
+  st_last<FT>(W, P, n, g, m.skip, nv, m);
 }
 
 // slots [t.u0, t.u0 + t.nv) of stream t.s; the first n_in of them take rows [r0, r0 + n_in) of the caller's inputs, the
@@ -159,12 +155,8 @@ __device__ __forceinline__ void la_tile(const LaP& p, const LaTile& t, long long
   const int tid = threadIdx.x, nv = t.nv;
   const float* P = p.params;
   const LaRing none = {0, 1, 0};
+  st_load_input(p, r0, nv, m, [&](int f) { return f < n_in; });
   {
-    const int ip = p.enc[0].in_pad, ic = p.enc[0].in_ch;
-    for (int i = tid; i < nv * ip; i += ST_THREADS) {
-      const int f = i / ip, c = i - f * ip;
-      m.io[f * ST_LD + c] = (c < ic && f < n_in) ? p.x[(r0 + f) * p.ldx + c] : 0.f;
-    }
     // the frames' conditioning rows, with the speaker of this push
     long long spk = p.spk[t.s];
     spk = spk < 0 ? 0 : (spk >= p.n_spk ? p.n_spk - 1 : spk);
@@ -273,16 +265,7 @@ __device__ __noinline__ void la_tile_short_call(const LaP& p, const LaTile& t, l
 template <bool SHORT>
 __global__ __launch_bounds__(ST_THREADS) void stream_la_push_kernel(const LaP p) {
   extern __shared__ __attribute__((aligned(16))) float st_lds[];
-  StLds m;
-  m.xw = st_lds;
-  m.g = m.xw + (ST_HALO + ST_TILE) * 64;
-  m.skip = m.g + ST_TILE * ST_LD;
-  m.cond = m.skip + ST_TILE * 64;
-  m.io = m.cond + ST_TILE * ST_LD;
-  m.red_d = m.io + ST_TILE * ST_LD;
-  m.red_i = reinterpret_cast<int*>(m.red_d + 4 * ST_TILE);
-  m.x2s = m.red_d + 8 * ST_TILE;
-  m.idxs = reinterpret_cast<int*>(m.red_d + 9 * ST_TILE);
+  const StLds m = st_carve(st_lds);
   const int s = blockIdx.x;
   int n_in = p.n_valid ? p.n_valid[s] : p.C;
   n_in = min(max(n_in, 0), p.C);
@@ -313,15 +296,11 @@ __global__ __launch_bounds__(ST_THREADS) void stream_la_push_kernel(const LaP p)
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-struct LaStreamH : StTables {
+struct LaStreamH : StHandle {
   LaP p;
   long long ring_floats = 0;
-  int S = 0, Cmax = 0;
-  float *wt = nullptr, *state = nullptr, *rings = nullptr;
+  float* rings = nullptr;
   int* count = nullptr;
-  StLayer* d_layers = nullptr;
-  StPrep* d_preps = nullptr;
-  bool prepared = false;
 };
 
 // sum of h over the layers of one net, and over all but its first layer (what its skip rows wait); -1 for an even kernel
@@ -336,36 +315,15 @@ static int la_net_delays(const LaStreamH* h, const StNet& n, int* all, int* tail
   return 0;
 }
 
-extern "C" int crk_lstream_create(const crk_stream_desc* desc_, void* const* enc_nets, void* const* dec_nets, void** handle) {
-  if (!desc_ || !enc_nets || !dec_nets || !handle) return CRK_ERR_ARG;
-  *handle = nullptr;
-  const crk_stream_desc& d = *desc_;
-  if (d.n_stacks < 1 || d.n_stacks > ST_MAX_STACKS || d.causal) return CRK_ERR_UNSUPPORTED;
-  int qsum = 0;
-  for (int n = 0; n < d.n_stacks; n++) {
-    const int D = d.emb_dim[n];
-    if ((D != 16 && D != 32 && D != 64 && D != 128) || d.emb_size[n] < 1 || d.cb_off[n] < 0) return CRK_ERR_UNSUPPORTED;
-    qsum += D;
-  }
-  const int d_aux = (d.dec_f0 ? 2 : 0) + d.spk_dim;
-  if (qsum > 128 || d.spk_dim < 0 || d_aux > 128 || d.n_spk < 1 || (d.spk_onehot && d.spk_dim != d.n_spk) ||
-      (!d.spk_onehot && d.spk_dim > 0 && d.spk_off < 0))
-    return CRK_ERR_UNSUPPORTED;
+extern "C" int crk_lstream_create(const crk_stream_desc* desc, void* const* enc_nets, void* const* dec_nets, void** handle) {
+  int qsum, d_aux;
+  int rc = st_check_desc(desc, enc_nets, dec_nets, handle, false, &qsum, &d_aux);
+  if (rc != CRK_OK) return rc;
+  const crk_stream_desc& d = *desc;
   LaStreamH* h = new LaStreamH();
-  memset(&h->p, 0, sizeof(h->p));
   LaP& p = h->p;
   const int nst = d.n_stacks;
-  p.nst = nst; p.enc_f0 = d.enc_f0 ? 1 : 0; p.dec_f0 = d.dec_f0 ? 2 : 0; p.spk_dim = d.spk_dim;
-  p.spk_onehot = d.spk_onehot ? 1 : 0; p.n_spk = d.n_spk; p.spk_off = d.spk_off;
-  int rc = CRK_OK;
-  for (int n = 0; n < nst && rc == CRK_OK; n++) {
-    p.emb_dim[n] = d.emb_dim[n]; p.emb_size[n] = d.emb_size[n]; p.cb_off[n] = d.cb_off[n];
-    rc = st_add_net(h, enc_nets[n], d.enc_base[n], n == 0 ? d.in_ch : d.emb_dim[n - 1], d.emb_dim[n],
-                    n == 0 && d.enc_f0 ? 2 : 0, &p.enc[n]);
-    if (rc == CRK_OK)
-      rc = st_add_net(h, dec_nets[n], d.dec_base[n], n == 0 ? qsum : d.emb_dim[n], n == 0 ? d.out_ch : d.emb_dim[n - 1],
-                      n == 0 ? d_aux : 0, &p.dec[n]);
-  }
+  rc = st_fill_model(h, p, d, enc_nets, dec_nets, qsum, d_aux);
   // the delays along the chain: a[n] / b[n] the sums of h of enc[n] / dec[n]; quantizer n works at delay at_q[n]
   int a[ST_MAX_STACKS], b[ST_MAX_STACKS], ta[ST_MAX_STACKS], tb[ST_MAX_STACKS], at_q[ST_MAX_STACKS];
   for (int n = 0; n < nst && rc == CRK_OK; n++)
@@ -391,7 +349,6 @@ extern "C" int crk_lstream_create(const crk_stream_desc* desc_, void* const* enc
     p.r_enc[n] = ring(d.emb_dim[n], p.la - at_q[n]);
     p.r_idx[n] = ring(1, p.la - at_q[n]);
   }
-  p.state_stride = h->state_floats;
   p.ring_stride = h->ring_floats;
   *handle = h;
   return CRK_OK;
@@ -400,8 +357,8 @@ extern "C" int crk_lstream_create(const crk_stream_desc* desc_, void* const* enc
 extern "C" void crk_lstream_destroy(void* hh) {
   LaStreamH* h = (LaStreamH*)hh;
   if (!h) return;
-  (void)hipFree(h->wt); (void)hipFree(h->state); (void)hipFree(h->rings); (void)hipFree(h->count); (void)hipFree(h->d_layers);
-  (void)hipFree(h->d_preps);
+  st_free_tables(h);
+  (void)hipFree(h->rings); (void)hipFree(h->count);
   delete h;
 }
 
@@ -417,40 +374,21 @@ extern "C" long long crk_lstream_state_bytes(void* hh, int S) {
 
 extern "C" int crk_lstream_reserve(void* hh, int S, int C_max) {
   LaStreamH* h = (LaStreamH*)hh;
-  if (!h) return CRK_ERR_ARG;
-  if (S < 1 || C_max < 1 || C_max > ST_MAX_CHUNK) return CRK_ERR_UNSUPPORTED;
-  // (per reserve, not once per process: the attribute belongs to the current device's copy of the kernels)
-  if (hipFuncSetAttribute((const void*)stream_la_push_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)st_lds_bytes()) != hipSuccess ||
-      hipFuncSetAttribute((const void*)stream_la_push_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)st_lds_bytes()) != hipSuccess)
-    return CRK_ERR_HIP;
-  if (!h->wt) {
-    int rc = st_malloc((void**)&h->wt, sizeof(float) * h->wt_floats);
-    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_layers, sizeof(StLayer) * h->layers.size());
-    if (rc == CRK_OK) rc = st_malloc((void**)&h->d_preps, sizeof(StPrep) * h->preps.size());
-    if (rc != CRK_OK) return rc;
-    if (hipMemset(h->wt, 0, sizeof(float) * h->wt_floats) != hipSuccess ||
-        hipMemcpy(h->d_layers, h->layers.data(), sizeof(StLayer) * h->layers.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(h->d_preps, h->preps.data(), sizeof(StPrep) * h->preps.size(), hipMemcpyHostToDevice) != hipSuccess)
-      return CRK_ERR_HIP;
-    h->p.wt = h->wt; h->p.layers = h->d_layers;
-  }
-  if (S > h->S) {  // more streams: a new, zeroed state (every stream starts over)
-    float *st = nullptr, *rg = nullptr;
+  int rc = st_reserve_tables(h, S, C_max);
+  if (rc == CRK_OK) rc = crk_raise_lds((int)st_lds_bytes(), stream_la_push_kernel<true>, stream_la_push_kernel<false>);
+  if (rc != CRK_OK) return rc;
+  if (S > h->S) {  // more streams: a new, zeroed state (every stream starts over); all three buffers or none
+    float *st, *rg = nullptr;
     int* cnt = nullptr;
-    const size_t st_bytes = sizeof(float) * (size_t)(h->state_floats > 0 ? h->state_floats : 1) * S;
-    int rc = st_malloc((void**)&st, st_bytes);
-    if (rc == CRK_OK) rc = st_malloc((void**)&rg, sizeof(float) * h->ring_floats * S);
-    if (rc == CRK_OK) rc = st_malloc((void**)&cnt, sizeof(int) * S);
-    if (rc != CRK_OK || hipMemset(st, 0, st_bytes) != hipSuccess ||
-        hipMemset(rg, 0, sizeof(float) * h->ring_floats * S) != hipSuccess || hipMemset(cnt, 0, sizeof(int) * S) != hipSuccess) {
+    rc = st_zeroed((void**)&st, sizeof(float) * (size_t)(h->state_floats > 0 ? h->state_floats : 1) * S);
+    if (rc == CRK_OK) rc = st_zeroed((void**)&rg, sizeof(float) * h->ring_floats * S);
+    if (rc == CRK_OK) rc = st_zeroed((void**)&cnt, sizeof(int) * S);
+    if (rc != CRK_OK) {
       (void)hipFree(st); (void)hipFree(rg); (void)hipFree(cnt);
-      return rc != CRK_OK ? rc : CRK_ERR_HIP;
+      return rc;
     }
     (void)hipFree(h->state); (void)hipFree(h->rings); (void)hipFree(h->count);
     h->state = st; h->rings = rg; h->count = cnt; h->S = S;
-    h->p.state = st; h->p.rings = rg; h->p.count = cnt;
   }
   if (C_max > h->Cmax) h->Cmax = C_max;
   return CRK_OK;
@@ -459,28 +397,14 @@ extern "C" int crk_lstream_reserve(void* hh, int S, int C_max) {
 extern "C" int crk_lstream_prepare(void* hh, const float* params, unsigned long long version, void* stream) {
   LaStreamH* h = (LaStreamH*)hh;
   (void)version;  // (the caller's bookkeeping: one call per parameter version)
-  if (!h || !params || !h->wt) return CRK_ERR_ARG;
-  const int rc = st_prepare_launch(h->d_preps, (int)h->preps.size(), h->rows, params, h->wt, stream);
-  if (rc != CRK_OK) return rc;
-  h->p.params = params;
-  h->prepared = true;
-  return CRK_OK;
+  return h ? st_prepare(h, h->p, params, stream) : CRK_ERR_ARG;
 }
 
 extern "C" int crk_lstream_reset(void* hh, const int* stream_ids, int n, void* stream) {
   LaStreamH* h = (LaStreamH*)hh;
-  if (!h || !h->state || n < 0) return CRK_ERR_ARG;
-  const size_t one = sizeof(float) * h->state_floats;
-  if (!stream_ids)
-    return (hipMemsetAsync(h->state, 0, one * h->S, (hipStream_t)stream) == hipSuccess &&
-            hipMemsetAsync(h->count, 0, sizeof(int) * h->S, (hipStream_t)stream) == hipSuccess) ? CRK_OK : CRK_ERR_HIP;
-  for (int i = 0; i < n; i++)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; i++)
-    if (hipMemsetAsync(h->state + (size_t)stream_ids[i] * h->state_floats, 0, one, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(h->count + stream_ids[i], 0, sizeof(int), (hipStream_t)stream) != hipSuccess)
-      return CRK_ERR_HIP;
-  return CRK_OK;
+  if (!h) return CRK_ERR_ARG;
+  const int rc = crk_zero_stream_rows(h->state, sizeof(float) * h->state_floats, h->S, stream_ids, n, (hipStream_t)stream);
+  return rc != CRK_OK ? rc : crk_zero_stream_rows(h->count, sizeof(int), h->S, stream_ids, n, (hipStream_t)stream);
 }
 
 extern "C" int crk_lstream_push(void* hh, const float* x, int ldx, const float* dec_cond, int ldd, const float* enc_cond, int lde,
@@ -489,18 +413,11 @@ extern "C" int crk_lstream_push(void* hh, const float* x, int ldx, const float* 
                                 void* stream) {
   LaStreamH* h = (LaStreamH*)hh;
   if (!h) return CRK_ERR_ARG;
-  if (S < 1 || S > h->S || C < 1 || C > h->Cmax) return CRK_ERR_UNSUPPORTED;
-  if (!h->prepared || !x || !spk || !decoded || !qidx || !encoded || !n_out || !first || ldx < h->p.enc[0].in_ch ||
-      rows_out < C + h->p.la)
-    return CRK_ERR_ARG;
-  if ((h->p.dec_f0 && (!dec_cond || ldd < 2)) || (h->p.enc_f0 && (!enc_cond || lde < 2))) return CRK_ERR_ARG;
   LaP p = h->p;
-  for (int n = 0; n < p.nst; n++) {
-    if (!qidx[n] || !encoded[n]) return CRK_ERR_ARG;
-    p.qidx[n] = qidx[n]; p.encoded[n] = encoded[n];
-  }
-  p.x = x; p.ldx = ldx; p.dcond = dec_cond; p.ldd = ldd; p.econd = enc_cond; p.lde = lde; p.spk = spk; p.n_valid = n_valid;
-  p.end = end; p.C = C; p.rows_out = rows_out; p.decoded = decoded; p.n_out = n_out; p.first = first;
+  const int rc = st_push_args(h, p, x, ldx, dec_cond, ldd, enc_cond, lde, spk, n_valid, S, C, decoded, qidx, encoded);
+  if (rc != CRK_OK) return rc;
+  if (!n_out || !first || rows_out < C + p.la) return CRK_ERR_ARG;
+  p.rings = h->rings; p.count = h->count; p.end = end; p.rows_out = rows_out; p.n_out = n_out; p.first = first;
   if (C <= LA_SHORT)
     hipLaunchKernelGGL(stream_la_push_kernel<true>, dim3(S), dim3(ST_THREADS), st_lds_bytes(), (hipStream_t)stream, p);
   else

@@ -324,14 +324,8 @@ extern "C" int crk_voc_stream_lookahead(void* st) {
 
 extern "C" int crk_voc_stream_reset(void* st, const int* stream_ids, int n, void* stream) {
   VocStream* h = static_cast<VocStream*>(st);
-  if (!h || n < 0) return CRK_ERR_ARG;
-  hipStream_t q = (hipStream_t)stream;
-  if (!stream_ids) return hipMemsetAsync(h->t_in, 0, (size_t)h->S * 4, q) == hipSuccess ? CRK_OK : CRK_ERR_HIP;
-  for (int i = 0; i < n; ++i)
-    if (stream_ids[i] < 0 || stream_ids[i] >= h->S) return CRK_ERR_ARG;
-  for (int i = 0; i < n; ++i)
-    if (hipMemsetAsync(h->t_in + stream_ids[i], 0, 4, q) != hipSuccess) return CRK_ERR_HIP;
-  return CRK_OK;
+  if (!h) return CRK_ERR_ARG;
+  return crk_zero_stream_rows(h->t_in, 4, h->S, stream_ids, n, (hipStream_t)stream);
 }
 
 extern "C" int crk_voc_stream_push(void* st, const float* c, const float* noise, const int* n_valid, const int* end, int S,

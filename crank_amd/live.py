@@ -22,7 +22,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import check, stream_ptr
-from crank_amd._ragged import made, release, require_gpu
+from crank_amd._ragged import made, release, require_gpu, reset_streams
 from crank_amd.stream import LookaheadConverter, StreamingConverter, check_lookahead_conf, check_stream_conf
 
 
@@ -106,16 +106,10 @@ class FrameJoin:
 
     def reset(self, streams=None):
         """``streams`` (all of them by default) drop what waits, start at pair 0 and clear their overflow flags."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_join_reset(self._handle, None, 0, stream_ptr()), "crk_join_reset")
-            else:
-                ids = [int(s) for s in streams]
-                if any(not 0 <= i < self.n_streams for i in ids):
-                    raise ValueError(f"streams {ids}: stream ids are 0 .. {self.n_streams - 1}")
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_join_reset(self._handle, arr, len(ids), stream_ptr()), "crk_join_reset")
+        ids = None if streams is None else [int(s) for s in streams]
+        if ids is not None and any(not 0 <= i < self.n_streams for i in ids):
+            raise ValueError(f"streams {ids}: stream ids are 0 .. {self.n_streams - 1}")
+        reset_streams(self._handle, "crk_join_reset", ids, self.device)
 
     def status(self):
         """Synchronises; raises if a ring of any stream lost rows since the stream's last reset."""

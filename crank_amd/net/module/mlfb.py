@@ -16,7 +16,7 @@ import torch
 
 from ... import _lib, ops
 from ..._lib import check, stream_ptr
-from ..._ragged import made, release, require_gpu
+from ..._ragged import made, release, require_gpu, reset_streams
 
 
 def slaney_mel_basis(sr, n_fft, n_mels, fmin, fmax):
@@ -143,14 +143,7 @@ class StreamingLogMel:
 
     def reset(self, streams=None):
         """``streams`` (all of them by default) start a new utterance; frames not emitted yet are dropped."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_logmel_stream_reset(self._handle, None, 0, stream_ptr()), "crk_logmel_stream_reset")
-            else:
-                ids = [int(s) for s in streams]
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_logmel_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_logmel_stream_reset")
+        reset_streams(self._handle, "crk_logmel_stream_reset", streams, self.device)
 
     def empty_outputs(self, S):
         """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""

@@ -24,6 +24,12 @@ causal kernel, the residual taken from the same frame's input, edges masked by p
 for what waits for a delayed layer (csrc/stream_la_kernels.hip, ``crk_lstream_*``) - and returns the
 offline forward of the whole utterance, bit for bit however it is cut.  ``LiveConverter(lookahead=True)`` is the live loop on it.
 
+Where things live: ``_Converter`` owns what the two classes share - the native handle of one family of entry points
+(``crk_stream_*`` / ``crk_lstream_*``), ``_prepare``, ``state_bytes``, ``reset`` (``_ragged.reset_streams``, the reset of
+every streaming class of the package) and ``_inputs``, the checks of a push's arguments; a class keeps its outputs
+(``empty_outputs``, ``LookaheadConverter._check_out``) and the library call of its ``push``.  On the native side
+csrc/stream_common.h holds the handle base and the functions both families' entry points are made of.
+
 What stays with the caller: ``encoder_f0`` conditioning (the same rows unconverted: ``StreamingF0`` with ``cv_spk = org_spk``),
 and ``use_raw`` models, which ``check_stream_conf`` refuses: feed them scaled features.
 """
@@ -33,7 +39,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import StreamDesc, check, stream_ptr
-from crank_amd._ragged import made, release, require_gpu
+from crank_amd._ragged import made, release, require_gpu, reset_streams
 
 MAX_STACKS = 3
 MAX_CHANNELS = 128      # inputs, outputs, conditioning and the last decoder's concatenated input (stream_kernels.hip)
@@ -126,65 +132,60 @@ def _stream_desc(G, causal):
     return d
 
 
-class StreamingConverter:
-    """``push`` runs generator ``G`` (a ``VQVAE2`` with ``causal: true``) on the next frames of up to ``n_streams``
-    independent streams, at most ``max_chunk`` frames each per push.  Stream i is row i of every argument."""
+class _Converter:
+    """What the two converters share: the native handle of one family (entry points ``<_prefix>_*``, a ``crk_stream_desc``
+    with ``causal = _causal``, configurations ``_check_conf`` lets through), its weights' preparation, ``reset`` and the
+    checks of a push's inputs.  A subclass adds its outputs and the one library call of ``push``."""
+    _prefix = _causal = _check_conf = _what = None
 
     def __init__(self, G, n_streams, max_chunk, device="cuda"):
         conf = G.conf
-        check_stream_conf(conf, G.spkr_size)
+        self._check_conf(conf, G.spkr_size)
         if n_streams < 1 or max_chunk < 1:
             raise ValueError(f"n_streams = {n_streams}, max_chunk = {max_chunk}: both must be at least 1")
         self.device = torch.device(device)
-        require_gpu(self.device, "streaming conversion", "the converter's device")
+        require_gpu(self.device, self._what, "the converter's device")
         self.G, self.conf, self.n_streams, self.max_chunk = G, conf, int(n_streams), int(max_chunk)
         self.nst = nst = conf["n_vq_stacks"]
         self.dims = [conf["emb_dim"][n] for n in range(nst)]
-        d = _stream_desc(G, causal=1)
+        d = _stream_desc(G, causal=self._causal)
         nets = ctypes.c_void_p * nst
         enc = nets(*[G.encoders[n].net.handle for n in range(nst)])
         dec = nets(*[G.decoders[n].net.handle for n in range(nst)])
         h = ctypes.c_void_p()
-        L = _lib.lib()
         with torch.cuda.device(self.device):
-            check(L.crk_stream_create(ctypes.byref(d), enc, dec, ctypes.byref(h)), "crk_stream_create")
-            self._handle = made(h, "crk_stream_create")
-            check(L.crk_stream_reserve(self._handle, self.n_streams, self.max_chunk), "crk_stream_reserve")
+            self._call("create", ctypes.byref(d), enc, dec, ctypes.byref(h))
+            self._handle = made(h, self._prefix + "_create")
+            self._call("reserve", self._handle, self.n_streams, self.max_chunk)
         self._prepared = None
         self._ptrs = ctypes.c_void_p * nst
 
+    def _call(self, name, *args):
+        """The family's entry point ``name``; RuntimeError unless it returns CRK_OK."""
+        entry = f"{self._prefix}_{name}"
+        check(getattr(_lib.lib(), entry)(*args), entry)
+
     def __del__(self):
-        release(self, "_handle", "crk_stream_destroy")
+        release(self, "_handle", self._prefix + "_destroy")
 
     @property
     def state_bytes(self):
-        return int(_lib.lib().crk_stream_state_bytes(self._handle, self.n_streams))
+        """What the handle keeps on the device for ``n_streams`` streams: layer history and, behind a look-ahead, frame
+        counters and the rings of what waits for a delayed layer."""
+        return int(getattr(_lib.lib(), self._prefix + "_state_bytes")(self._handle, self.n_streams))
 
     def _prepare(self):
         """Effective weights for the generator's current parameters; again after any parameter or codebook write."""
         G = self.G
         key = (G.version, G.codebook_epoch, G.flat.data_ptr())
         if key != self._prepared:
-            check(_lib.lib().crk_stream_prepare(self._handle, G.flat.data_ptr(), G.version, stream_ptr()), "crk_stream_prepare")
+            self._call("prepare", self._handle, G.flat.data_ptr(), G.version, stream_ptr())
             self._prepared = key
 
     def reset(self, streams=None):
-        """Zero the carried history of ``streams`` (all of them by default): their next frame is an utterance's first."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_stream_reset(self._handle, None, 0, stream_ptr()), "crk_stream_reset")
-            else:
-                ids = [int(s) for s in streams]
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_stream_reset")
-
-    def empty_outputs(self, S, C):
-        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
-        dev = self.device
-        return {"decoded": torch.empty(S, C, self.conf["output_size"], device=dev),
-                "qidx": [torch.empty(S, C, dtype=torch.int64, device=dev) for _ in range(self.nst)],
-                "encoded": [torch.empty(S, C, D, device=dev) for D in self.dims]}
+        """``streams`` (all of them by default) drop what they hold - the carried history, behind a look-ahead also the
+        frame count: their next frame is frame 0 of an utterance."""
+        reset_streams(self._handle, self._prefix + "_reset", streams, self.device)
 
     def _f32(self, t, S, C, last, what):
         if t is None:
@@ -193,16 +194,9 @@ class StreamingConverter:
             raise ValueError(f"{what}: a float32 ({S}, {C}, {last}) tensor on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
         return t.contiguous()
 
-    def push(self, feats, lcf0, uv, spkr, n_valid=None, enc_lcf0_uv=None, out=None, lcf0_uv=None):
-        """feats (S, C, input_size) scaled features, lcf0 / uv (S, C, 1) the scaled (already converted) F0 contour and the
-        voicing flags - or, with both of them None, lcf0_uv (S, C, 2) the two packed as ``FrameJoin`` emits them, which is
-        passed to the kernel as it is (giving both forms, or lcf0_uv to a model without ``decoder_f0``, is a ValueError) -,
-        spkr (S,) int64 target speakers, n_valid (S,)
-        frames that count per stream (default: C), enc_lcf0_uv (S, C, 2) the encoder's conditioning when ``encoder_f0``.
-        Returns ``decoded`` (S, C, output_size),
-        ``qidx`` [(S, C) int64 per stack, bottom first] and ``encoded`` [(S, C, emb_dim) per stack: the quantizer's input] -
-        the keys of ``VQVAE2.make_dict``.  Rows at and past ``n_valid`` are not written.  out: buffers to write into
-        (``empty_outputs``), e.g. the static ones of a captured graph."""
+    def _inputs(self, feats, lcf0, uv, spkr, n_valid, enc_lcf0_uv, lcf0_uv, end=None):
+        """The inputs of a push, checked: S, C, feats, the decoder's and the encoder's (S, C, 2) conditioning rows (None
+        where the model takes none) and n_valid, end as int32 (None stays None)."""
         S, C = int(feats.shape[0]), int(feats.shape[1])
         conf = self.conf
         feats = self._f32(feats, S, C, conf["input_size"], "feats")
@@ -218,21 +212,50 @@ class StreamingConverter:
         econd = self._f32(enc_lcf0_uv, S, C, 2, "enc_lcf0_uv") if conf["encoder_f0"] else None
         if spkr.device.type != "cuda" or spkr.dtype != torch.int64 or tuple(spkr.shape) != (S,):
             raise ValueError(f"spkr: an int64 ({S},) tensor on the GPU, got {spkr.dtype} {tuple(spkr.shape)} on {spkr.device}")
-        if n_valid is not None:
-            if n_valid.device.type != "cuda" or tuple(n_valid.shape) != (S,):
-                raise ValueError(f"n_valid: an integer ({S},) tensor on the GPU")
-            n_valid = n_valid.to(torch.int32).contiguous()
+        flags = []
+        for name, v in (("n_valid", n_valid), ("end", end)):
+            if v is not None:
+                if v.device.type != "cuda" or tuple(v.shape) != (S,):
+                    raise ValueError(f"{name}: an integer ({S},) tensor on the GPU")
+                v = v.to(torch.int32).contiguous()
+            flags.append(v)
+        return (S, C, feats, dcond, econd, *flags)
+
+
+class StreamingConverter(_Converter):
+    """``push`` runs generator ``G`` (a ``VQVAE2`` with ``causal: true``) on the next frames of up to ``n_streams``
+    independent streams, at most ``max_chunk`` frames each per push.  Stream i is row i of every argument."""
+    _prefix, _causal, _check_conf, _what = "crk_stream", 1, staticmethod(check_stream_conf), "streaming conversion"
+
+    def empty_outputs(self, S, C):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
+        dev = self.device
+        return {"decoded": torch.empty(S, C, self.conf["output_size"], device=dev),
+                "qidx": [torch.empty(S, C, dtype=torch.int64, device=dev) for _ in range(self.nst)],
+                "encoded": [torch.empty(S, C, D, device=dev) for D in self.dims]}
+
+    def push(self, feats, lcf0, uv, spkr, n_valid=None, enc_lcf0_uv=None, out=None, lcf0_uv=None):
+        """feats (S, C, input_size) scaled features, lcf0 / uv (S, C, 1) the scaled (already converted) F0 contour and the
+        voicing flags - or, with both of them None, lcf0_uv (S, C, 2) the two packed as ``FrameJoin`` emits them, which is
+        passed to the kernel as it is (giving both forms, or lcf0_uv to a model without ``decoder_f0``, is a ValueError) -,
+        spkr (S,) int64 target speakers, n_valid (S,)
+        frames that count per stream (default: C), enc_lcf0_uv (S, C, 2) the encoder's conditioning when ``encoder_f0``.
+        Returns ``decoded`` (S, C, output_size),
+        ``qidx`` [(S, C) int64 per stack, bottom first] and ``encoded`` [(S, C, emb_dim) per stack: the quantizer's input] -
+        the keys of ``VQVAE2.make_dict``.  Rows at and past ``n_valid`` are not written.  out: buffers to write into
+        (``empty_outputs``), e.g. the static ones of a captured graph."""
+        S, C, feats, dcond, econd, n_valid, _ = self._inputs(feats, lcf0, uv, spkr, n_valid, enc_lcf0_uv, lcf0_uv)
         out = self.empty_outputs(S, C) if out is None else out
         with torch.cuda.device(self.device):
             self._prepare()
-            check(_lib.lib().crk_stream_push(
-                self._handle, feats.data_ptr(), feats.shape[-1], _lib.ptr(dcond), 2, _lib.ptr(econd), 2, spkr.data_ptr(),
-                _lib.ptr(n_valid), S, C, out["decoded"].data_ptr(), self._ptrs(*[t.data_ptr() for t in out["qidx"]]),
-                self._ptrs(*[t.data_ptr() for t in out["encoded"]]), stream_ptr()), "crk_stream_push")
+            self._call("push", self._handle, feats.data_ptr(), feats.shape[-1], _lib.ptr(dcond), 2, _lib.ptr(econd), 2,
+                       spkr.data_ptr(), _lib.ptr(n_valid), S, C, out["decoded"].data_ptr(),
+                       self._ptrs(*[t.data_ptr() for t in out["qidx"]]), self._ptrs(*[t.data_ptr() for t in out["encoded"]]),
+                       stream_ptr())
         return out
 
 
-class LookaheadConverter:
+class LookaheadConverter(_Converter):
     """``push`` runs generator ``G`` (a ``VQVAE2`` with ``causal: false``, the recipe's default) on the next frames of up to
     ``n_streams`` independent streams, at most ``max_chunk`` frames each per push, and returns the frames whose whole
     future context has arrived: it follows its input ``lookahead = lookahead_frames(conf)`` frames behind (66 for the
@@ -241,60 +264,16 @@ class LookaheadConverter:
     cost of ``n_valid + lookahead`` frames - and starts the stream over.  What is emitted is the offline forward of the
     whole utterance, bit for bit however it is cut into pushes (csrc/stream_la_kernels.hip, ``crk_lstream_*``; DESIGN.md
     section 6n).  Stream i is row i of every argument.  There is no torch or CPU fallback."""
+    _prefix, _causal, _check_conf = "crk_lstream", 0, staticmethod(check_lookahead_conf)
+    _what = "look-ahead streaming conversion"
 
     def __init__(self, G, n_streams, max_chunk, device="cuda"):
-        conf = G.conf
-        check_lookahead_conf(conf, G.spkr_size)
-        if n_streams < 1 or max_chunk < 1:
-            raise ValueError(f"n_streams = {n_streams}, max_chunk = {max_chunk}: both must be at least 1")
-        self.device = torch.device(device)
-        require_gpu(self.device, "look-ahead streaming conversion", "the converter's device")
-        self.G, self.conf, self.n_streams, self.max_chunk = G, conf, int(n_streams), int(max_chunk)
-        self.nst = nst = conf["n_vq_stacks"]
-        self.dims = [conf["emb_dim"][n] for n in range(nst)]
-        self.lookahead = lookahead_frames(conf)
+        super().__init__(G, n_streams, max_chunk, device)
+        self.lookahead = lookahead_frames(self.conf)
         self.max_out = self.max_chunk + self.lookahead
-        d = _stream_desc(G, causal=0)
-        nets = ctypes.c_void_p * nst
-        enc = nets(*[G.encoders[n].net.handle for n in range(nst)])
-        dec = nets(*[G.decoders[n].net.handle for n in range(nst)])
-        h = ctypes.c_void_p()
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            check(L.crk_lstream_create(ctypes.byref(d), enc, dec, ctypes.byref(h)), "crk_lstream_create")
-            self._handle = made(h, "crk_lstream_create")
-            check(L.crk_lstream_reserve(self._handle, self.n_streams, self.max_chunk), "crk_lstream_reserve")
-        if int(L.crk_lstream_lookahead(self._handle)) != self.lookahead:
-            raise RuntimeError(f"crk_lstream_lookahead = {L.crk_lstream_lookahead(self._handle)}, not {self.lookahead}")
-        self._prepared = None
-        self._ptrs = ctypes.c_void_p * nst
-
-    def __del__(self):
-        release(self, "_handle", "crk_lstream_destroy")
-
-    @property
-    def state_bytes(self):
-        """Layer history, frame counters and the rings of what waits for a delayed layer, for ``n_streams`` streams."""
-        return int(_lib.lib().crk_lstream_state_bytes(self._handle, self.n_streams))
-
-    def _prepare(self):
-        """Effective weights for the generator's current parameters; again after any parameter or codebook write."""
-        G = self.G
-        key = (G.version, G.codebook_epoch, G.flat.data_ptr())
-        if key != self._prepared:
-            check(_lib.lib().crk_lstream_prepare(self._handle, G.flat.data_ptr(), G.version, stream_ptr()), "crk_lstream_prepare")
-            self._prepared = key
-
-    def reset(self, streams=None):
-        """``streams`` (all of them by default) drop what they hold: their next frame is frame 0 of an utterance."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_lstream_reset(self._handle, None, 0, stream_ptr()), "crk_lstream_reset")
-            else:
-                ids = [int(s) for s in streams]
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_lstream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_lstream_reset")
+        la = int(_lib.lib().crk_lstream_lookahead(self._handle))
+        if la != self.lookahead:
+            raise RuntimeError(f"crk_lstream_lookahead = {la}, not {self.lookahead}")
 
     def empty_outputs(self, S):
         """Output buffers of one push, in the form ``push(out=...)`` takes and returns: ``max_out`` rows per stream."""
@@ -304,8 +283,6 @@ class LookaheadConverter:
                 "encoded": [torch.empty(S, R, D, device=dev) for D in self.dims],
                 "n_out": torch.empty(S, dtype=torch.int32, device=dev),
                 "first": torch.empty(S, dtype=torch.int32, device=dev)}
-
-    _f32 = StreamingConverter._f32
 
     def _check_out(self, out, S):
         """Every buffer of ``out`` as ``empty_outputs(S)`` makes it: the kernel writes up to ``max_out`` rows per stream."""
@@ -332,36 +309,13 @@ class LookaheadConverter:
         first], ``encoded`` [(S, max_out, emb_dim) per stack] and ``n_out``, ``first`` (S,) int32 on the device: row j of
         every output is frame ``first + j`` of the stream's utterance, rows at and past ``n_out`` are not written.
         out: buffers to write into (``empty_outputs``), e.g. the static ones of a captured graph."""
-        S, C = int(feats.shape[0]), int(feats.shape[1])
-        conf = self.conf
-        feats = self._f32(feats, S, C, conf["input_size"], "feats")
-        dcond = None
-        if lcf0_uv is not None:
-            if lcf0 is not None or uv is not None:
-                raise ValueError("lcf0_uv: the packed rows replace lcf0 and uv; give one form, not both")
-            if not conf["decoder_f0"]:
-                raise ValueError("lcf0_uv: this model has decoder_f0 = false and takes no F0 rows")
-            dcond = self._f32(lcf0_uv, S, C, 2, "lcf0_uv")
-        elif conf["decoder_f0"]:
-            dcond = torch.cat([self._f32(lcf0, S, C, 1, "lcf0"), self._f32(uv, S, C, 1, "uv")], dim=-1)
-        econd = self._f32(enc_lcf0_uv, S, C, 2, "enc_lcf0_uv") if conf["encoder_f0"] else None
-        if spkr.device.type != "cuda" or spkr.dtype != torch.int64 or tuple(spkr.shape) != (S,):
-            raise ValueError(f"spkr: an int64 ({S},) tensor on the GPU, got {spkr.dtype} {tuple(spkr.shape)} on {spkr.device}")
-        flags = []
-        for name, v in (("n_valid", n_valid), ("end", end)):
-            if v is not None:
-                if v.device.type != "cuda" or tuple(v.shape) != (S,):
-                    raise ValueError(f"{name}: an integer ({S},) tensor on the GPU")
-                v = v.to(torch.int32).contiguous()
-            flags.append(v)
-        n_valid, end = flags
+        S, C, feats, dcond, econd, n_valid, end = self._inputs(feats, lcf0, uv, spkr, n_valid, enc_lcf0_uv, lcf0_uv, end)
         out = self.empty_outputs(S) if out is None else out
         self._check_out(out, S)
         with torch.cuda.device(self.device):
             self._prepare()
-            check(_lib.lib().crk_lstream_push(
-                self._handle, feats.data_ptr(), feats.shape[-1], _lib.ptr(dcond), 2, _lib.ptr(econd), 2, spkr.data_ptr(),
-                _lib.ptr(n_valid), _lib.ptr(end), S, C, self.max_out, out["decoded"].data_ptr(),
-                self._ptrs(*[t.data_ptr() for t in out["qidx"]]), self._ptrs(*[t.data_ptr() for t in out["encoded"]]),
-                out["n_out"].data_ptr(), out["first"].data_ptr(), stream_ptr()), "crk_lstream_push")
+            self._call("push", self._handle, feats.data_ptr(), feats.shape[-1], _lib.ptr(dcond), 2, _lib.ptr(econd), 2,
+                       spkr.data_ptr(), _lib.ptr(n_valid), _lib.ptr(end), S, C, self.max_out, out["decoded"].data_ptr(),
+                       self._ptrs(*[t.data_ptr() for t in out["qidx"]]), self._ptrs(*[t.data_ptr() for t in out["encoded"]]),
+                       out["n_out"].data_ptr(), out["first"].data_ptr(), stream_ptr())
         return out

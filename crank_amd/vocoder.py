@@ -15,7 +15,7 @@ import torch
 
 from crank_amd import _lib, ops
 from crank_amd._lib import check, stream_ptr
-from crank_amd._ragged import Workspace, made, offsets, release, require_gpu
+from crank_amd._ragged import Workspace, made, offsets, release, require_gpu, reset_streams
 
 MAX_AUX = 128
 MAX_SCALE = 16
@@ -342,16 +342,10 @@ class StreamingVocoder:
 
     def reset(self, streams=None):
         """``streams`` (all of them by default) start a new utterance; what they had not emitted yet is dropped."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_voc_stream_reset(self._handle, None, 0, stream_ptr()), "crk_voc_stream_reset")
-            else:
-                ids = [int(s) for s in streams]
-                if any(not 0 <= i < self.n_streams for i in ids):
-                    raise ValueError(f"streams {ids}: stream ids are 0 .. {self.n_streams - 1}")
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_voc_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_voc_stream_reset")
+        ids = None if streams is None else [int(s) for s in streams]
+        if ids is not None and any(not 0 <= i < self.n_streams for i in ids):
+            raise ValueError(f"streams {ids}: stream ids are 0 .. {self.n_streams - 1}")
+        reset_streams(self._handle, "crk_voc_stream_reset", ids, self.device)
 
     def empty_outputs(self, S, C):
         """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""

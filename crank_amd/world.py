@@ -28,7 +28,7 @@ import torch
 
 from crank_amd import _lib
 from crank_amd._lib import check, stream_ptr
-from crank_amd._ragged import Workspace, f64, made, offsets, release, require_gpu, size_of
+from crank_amd._ragged import Workspace, f64, made, offsets, release, require_gpu, reset_streams, size_of
 
 FFTL = 1024  # the only fftl the kernels implement (every mcep recipe uses it)
 K = FFTL // 2 + 1
@@ -859,14 +859,7 @@ class StreamingF0:
 
     def reset(self, streams=None):
         """``streams`` (all of them by default) return to their start state; blocks not emitted yet are dropped."""
-        L = _lib.lib()
-        with torch.cuda.device(self.device):
-            if streams is None:
-                check(L.crk_f0_stream_reset(self._handle, None, 0, stream_ptr()), "crk_f0_stream_reset")
-            else:
-                ids = [int(s) for s in streams]
-                arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-                check(L.crk_f0_stream_reset(self._handle, arr, len(ids), stream_ptr()), "crk_f0_stream_reset")
+        reset_streams(self._handle, "crk_f0_stream_reset", streams, self.device)
 
     def status(self):
         """Synchronises; raises if a Harvest event stream overflowed in a window of any stream since its last reset."""

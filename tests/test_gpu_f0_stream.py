@@ -431,3 +431,9 @@ def test_chain_into_the_converter_is_cut_independent_and_equals_the_offline_forw
         err = rel_err(a[s]["decoded"][None].cpu(), ref["decoded"].cpu(), ~above)
         print(f"chain stream {s}: decoded max |diff| / max |ref| = {err:.3e} on {int((~above).sum())} of {T} frames")
         assert err <= 1e-3, (s, err)
+
+
+def test_a_reset_with_an_id_out_of_range_is_the_librarys_error():
+    sf = make(16000, [(70, 400)], 1600, shiftms=5)
+    with pytest.raises(RuntimeError):
+        sf.reset([1])

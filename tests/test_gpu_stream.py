@@ -395,3 +395,119 @@ def test_refused_shapes_return_status_3_without_a_launch():
         h = ctypes.c_void_p()
         assert L.crk_stream_create(ctypes.byref(d), enc, dec, ctypes.byref(h)) == 3, field
         assert not h.value
+
+
+# ---------------------------------------------------------------------------------------------------- 10 one argument path
+def _family(kind):
+    """(the family's Dev of its small configuration - k333 causal, SMALL behind a look-ahead -, its converter class)."""
+    from crank_amd.stream import LookaheadConverter, StreamingConverter
+    from tests import stream_la_inputs as LI
+    from tests.test_gpu_stream_la import LaDev
+
+    if kind == "causal":
+        return Dev.of(**SI.VARIANTS["k333"]), StreamingConverter
+    return LaDev.of(**LI.SMALL), LookaheadConverter
+
+
+_BAD_S, _BAD_C = 2, 3
+_BAD_ARGS = {  # case -> (configuration keys on top of the family's, the message)
+    "feats_dtype": ({}, "feats: a float32 (2, 3, 80) tensor on the GPU, got torch.float64 (2, 3, 80) on cuda:0"),
+    "feats_width": ({}, "feats: a float32 (2, 3, 80) tensor on the GPU, got torch.float32 (2, 3, 79) on cuda:0"),
+    "spkr_shape": ({}, "spkr: an int64 (2,) tensor on the GPU, got torch.int64 (3,) on cuda:0"),
+    "n_valid_on_host": ({}, "n_valid: an integer (2,) tensor on the GPU"),
+    "both_f0_forms": ({}, "lcf0_uv: the packed rows replace lcf0 and uv; give one form, not both"),
+    "lcf0_uv_without_decoder_f0": (dict(decoder_f0=False), "lcf0_uv: this model has decoder_f0 = false and takes no F0 rows"),
+    "missing_enc_lcf0_uv": (dict(encoder_f0=True), "enc_lcf0_uv is required by this configuration"),
+    "no_streams": ({}, "n_streams = 0, max_chunk = 3: both must be at least 1"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_BAD_ARGS))
+@pytest.mark.parametrize("kind", ["causal", "lookahead"])
+def test_both_converters_refuse_the_same_bad_arguments(kind, case):
+    """The same ValueError, word for word, from either class, and nothing launched: the output buffers keep their fill."""
+    from crank_amd.net.module.vqvae2 import VQVAE2
+
+    dev, cls = _family(kind)
+    over, message = _BAD_ARGS[case]
+    assert dev.fx.conf["input_size"] == 80
+    G = VQVAE2(dict(dev.fx.conf, **over), spkr_size=SI.N_SPK).eval() if over else dev.G
+    if case == "no_streams":
+        with pytest.raises(ValueError) as e:
+            cls(G, 0, _BAD_C)
+        assert str(e.value) == message
+        return
+    conv = cls(G, _BAD_S, _BAD_C)
+    S, C = _BAD_S, _BAD_C
+    z = lambda *shape, **kw: torch.zeros(*shape, device="cuda", **kw)  # noqa: E731
+    args = dict(feats=z(S, C, 80), lcf0=z(S, C, 1), uv=z(S, C, 1), spkr=z(S, dtype=torch.int64))
+    if case == "feats_dtype":
+        args["feats"] = args["feats"].double()
+    elif case == "feats_width":
+        args["feats"] = z(S, C, 79)
+    elif case == "spkr_shape":
+        args["spkr"] = z(S + 1, dtype=torch.int64)
+    elif case == "n_valid_on_host":
+        args["n_valid"] = torch.full((S,), C, dtype=torch.int32)
+    elif case == "both_f0_forms":
+        args["lcf0_uv"] = z(S, C, 2)
+    elif case == "lcf0_uv_without_decoder_f0":
+        args.update(lcf0=None, uv=None, lcf0_uv=z(S, C, 2))
+    out = conv.empty_outputs(S, C) if kind == "causal" else conv.empty_outputs(S)
+    for t in [out["decoded"]] + out["qidx"] + out["encoded"]:
+        t.fill_(SENT_I)
+    with pytest.raises(ValueError) as e:
+        conv.push(out=out, **args)
+    assert str(e.value) == message
+    torch.cuda.synchronize()
+    assert all(bool((t == SENT_I).all()) for t in [out["decoded"]] + out["qidx"] + out["encoded"])
+
+
+def test_a_reset_with_an_id_out_of_range_zeroes_nothing():
+    """reset([0, n_streams]): RuntimeError, and stream 0 goes on as if nobody had asked - every id is checked before the
+    first row is zeroed.  5 frames, the refused reset, 5 more, against a converter that was never reset, bit for bit."""
+    dev, _ = _family("causal")
+    plan = [(3, 3), (2, 2)]
+    conv = dev.converter(2, 3)
+    head = run(conv, dev, plan, range(2))
+    with pytest.raises(RuntimeError):
+        conv.reset([0, 2])
+    rest = run(conv, dev, plan, range(2), start=[5, 5])
+    whole = run(dev.converter(2, 3), dev, plan + plan, range(2))
+    assert all(same(head[r], whole[r], 0, 5) and same(rest[r], whole[r], 5, 10) for r in range(2))
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_a_converter_on_a_second_device_after_one_on_the_first():
+    """The push kernel's dynamic-LDS limit is raised per reserve, on the device the converter lives on: a converter on
+    cuda:1 works in a process whose first converter was made on cuda:0.  Both against tests/stream_ref.py's float64
+    streaming reference under test_streaming_equals_the_offline_forwards' rules: identical indices, decoded and the
+    quantizers' inputs within 1e-3 of the largest reference value."""
+    from crank_amd.net.module.vqvae2 import VQVAE2
+    from crank_amd.stream import StreamingConverter
+    from tests.stream_ref import StreamRef
+
+    dev, _ = _family("causal")
+    fx, S2, C = dev.fx, 2, 3
+    dec_h, h = fx.dec_cond()
+    ref = []
+    for s in range(S2):
+        cond = torch.cat([dec_h[s, :C], fx.orac.spkr_embedding(h[s, :C]).detach()], -1)
+        ref.append(StreamRef(fx.orac).push(fx.x[s, :C], cond))
+    for name in ("cuda:0", "cuda:1"):
+        with torch.cuda.device(name):
+            G = VQVAE2(fx.conf, spkr_size=SI.N_SPK, device=name).eval()
+            G.load_state_dict(fx.state)
+            assert G.flat.device == torch.device(name)
+            conv = StreamingConverter(G, S2, C, device=name)
+            to = lambda t: t[:S2, :C].to(name).contiguous()  # noqa: E731
+            out = conv.push(to(fx.x), to(fx.lcf0), to(fx.uv), fx.spk[:S2].to(name))
+            torch.cuda.synchronize()
+        for s in range(S2):
+            d, q, e = ref[s]
+            assert fx.keep_dec[s, :C].any()
+            assert rel_err(out["decoded"][s].cpu().double(), d, fx.keep_dec[s, :C]) <= 1e-3, (name, s)
+            for n in range(fx.nst):
+                keep = torch.as_tensor(fx.keep_q[n][s, :C])
+                assert torch.equal(out["qidx"][n][s].cpu()[keep], q[n][keep]), (name, s, n)
+                assert rel_err(out["encoded"][n][s].cpu().double(), e[n], np.ones(C, bool)) <= 1e-3, (name, s, n)

@@ -435,3 +435,22 @@ def test_refused_shapes_return_status_3_without_a_write():
     nets = ctypes.c_void_p * 3
     d.n_stacks, d.causal = nst, 0
     assert L.crk_stream_create(ctypes.byref(d), nets(), nets(), ctypes.byref(h)) == 3
+
+
+# ---------------------------------------------------------------------------------------------------- 10 a refused reset
+def test_a_reset_with_an_id_out_of_range_zeroes_nothing():
+    """reset([0, n_streams]): RuntimeError, and stream 0 keeps its history and its frame count - every id is checked
+    before the first row of either is zeroed.  5 frames, the refused reset, 5 more with the end flag, against a converter
+    that was never reset, bit for bit (a reset stream 0 would emit an utterance of 5 frames, not of 10)."""
+    dev = LaDev.of(**LI.SMALL)
+    head = [((3, False),) * 2, ((2, False),) * 2]
+    tail = [((3, False),) * 2, ((2, True),) * 2]
+    conv = dev.converter(2, 3)
+    drive(conv, dev, range(2), head)
+    with pytest.raises(RuntimeError):
+        conv.reset([0, 2])
+    rest = drive(conv, dev, range(2), tail, start=[5, 5], taken=[5, 5])
+    whole = drive(dev.converter(2, 3), dev, range(2), head + tail)
+    for r in range(2):
+        assert len(rest[r]) == 1 and rest[r][0]["n"] == 10 and rest[r][0]["decoded"].shape[0] == 10
+        assert same(rest[r][0], whole[r][0]), r
