@@ -662,6 +662,10 @@ __global__ __launch_bounds__(256 * FH, 2) void stack2_fwd_kernel(const StackP p)
 int stack2_fwd_plan(StackP& p) {
   if ((p.ktaps != 3 && p.ktaps != 5) || p.max_off > SK_GUARD || p.aux_ch > 64 || p.L > 16) return CRK_ERR_UNSUPPORTED;
   if (p.ktaps == 3 && p.aux_ch > 0) return CRK_ERR_UNSUPPORTED;  // (no caller; keeps the instantiation count down)
+  // Dropout: the only instantiation that regenerates the keep mask is k = 5, no conditioning, not folded (launch_stack2_fwd).
+  // Every other stack with dropout is refused HERE, so that its route keeps the frame-split forward (any kernel size, with
+  // conditioning): a plan that accepted k = 3 launched the kernel without the mask, one that accepted conditioning failed at launch.
+  if (p.drop_p > 0.f && (p.ktaps != 5 || p.aux_ch > 0 || p.x_in)) return CRK_ERR_UNSUPPORTED;
   static int cfg_env = -1;
   if (cfg_env < 0) cfg_env = crk_sw().s2_cfg;
   // (ft, fh, ft1): tiles per wave of frame half 0, frame halves, tiles per wave of frame half 1.  CRK_S2_CFG = <ft><fh> or
@@ -728,8 +732,10 @@ int launch_stack2_fwd(const StackP& p, hipStream_t s) {
   int rc = CRK_OK;
   const bool fold = p.x_in != nullptr;
 #define S2_DISPATCH(KTV, AKCV) (fold ? s2_launch_shape<KTV, AKCV, false, true>(p, grid, s) : s2_launch_shape<KTV, AKCV, false, false>(p, grid, s))
-  if (p.ktaps == 3) rc = S2_DISPATCH(3, 0);
-  else if (p.drop_p > 0.f) {
+  if (p.ktaps == 3) {
+    if (p.drop_p > 0.f) return CRK_ERR_UNSUPPORTED;  // (no k = 3 kernel applies the mask: stack2_fwd_plan refuses it)
+    rc = S2_DISPATCH(3, 0);
+  } else if (p.drop_p > 0.f) {
     if (akc || fold) return CRK_ERR_UNSUPPORTED;
     rc = s2_launch_shape<5, 0, true, false>(p, grid, s);
   } else if (akc == 0) rc = S2_DISPATCH(5, 0);

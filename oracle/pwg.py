@@ -69,6 +69,25 @@ def bf16_emulation(on=True, accumulate="fp32"):
         _EMULATE_BF16, _ACCUMULATE = old
 
 
+# Dropout hook (TEST INFRASTRUCTURE): the HIP kernels never store a dropout mask, they regenerate it from an integer hash
+# of (seed, layer, element).  A test restates that hash (tests/dropout_ref.py) and installs `fn(block, x) -> dropped x`
+# here, so that a ResidualBlock multiplies its input by the very mask the kernels draw instead of calling F.dropout.
+# The product is formed in fp32 in front of the conv, i.e. before the bf16 emulation rounds the conv's operand - where the
+# kernels round it.
+_DROPOUT_HOOK = None
+
+
+@contextlib.contextmanager
+def dropout_hook(fn):
+    global _DROPOUT_HOOK
+    old = _DROPOUT_HOOK
+    _DROPOUT_HOOK = fn
+    try:
+        yield
+    finally:
+        _DROPOUT_HOOK = old
+
+
 def _conv_acc(x, w, b, padding, dilation):
     if _ACCUMULATE == "fp64":
         return F.conv1d(x.double(), w.double(), None if b is None else b.double(), padding=padding, dilation=dilation).float()
@@ -150,9 +169,13 @@ class Conv1d(nn.Conv1d):
             nn.init.constant_(self.bias, 0.0)
 
     def forward(self, x):
+        return self.conv_with(x, self.weight, self.bias)
+
+    def conv_with(self, x, w, b):
+        """This conv (geometry, current arithmetic) on explicit operands."""
         if _EMULATE_BF16:
-            return _EmuConv1d.apply(x, self.weight, self.bias, self.padding[0], self.dilation[0], self.grad_unscale)
-        return super().forward(x)
+            return _EmuConv1d.apply(x, w, b, self.padding[0], self.dilation[0], self.grad_unscale)
+        return F.conv1d(x, w, b, padding=self.padding[0], dilation=self.dilation[0])
 
 
 class Conv1d1x1(Conv1d):
@@ -204,7 +227,10 @@ class ResidualBlock(nn.Module):
 
     def forward(self, x, c):
         residual = x
-        x = F.dropout(x, p=self.dropout, training=self.training)
+        if _DROPOUT_HOOK is not None:
+            x = _DROPOUT_HOOK(self, x)
+        else:
+            x = F.dropout(x, p=self.dropout, training=self.training)
         x = self.conv(x)
         x = x[:, :, : residual.size(-1)] if self.use_causal_conv else x
         splitdim = 1

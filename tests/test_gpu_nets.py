@@ -91,33 +91,68 @@ def _oracle_run(orac, x, c, dy, aux_ch):
     return out, dy
 
 
-def _check_standalone(prod, orac, cin, B, T, precision, lengths=None, aux_ch=0, prod_call=None):
+def _standalone_refs(orac, cin, B, T, precision, aux_ch=0, mask_ctx=None):
+    """The CPU side of _check_standalone: inputs and oracle results of a case.  (x, c, dy, ref, e32, e32p, kink margin);
+    e32 / e32p are None outside precision "bf16".  mask_ctx: None, or a callable that returns a context manager under
+    which EVERY oracle evaluation runs (tests/dropout_ref.py masked: the oracle under the kernels' dropout mask)."""
+    import contextlib
+
+    from oracle import pwg as opwg
+
+    ctx = mask_ctx if mask_ctx is not None else contextlib.nullcontext
+    rs = np.random.RandomState(3)
+    c = torch.from_numpy(rs.standard_normal((B, aux_ch, T)).astype(np.float32)) if aux_ch else None
+    e32 = e32p = None
+    with ctx():
+        if precision == "bf16":
+            x = torch.from_numpy(np.random.RandomState(100).standard_normal((B, cin, T)).astype(np.float32))
+            with opwg.bf16_emulation(accumulate="fp64"):
+                ref, dy = _oracle_run(orac, x, c, None, aux_ch)
+            with opwg.bf16_emulation(accumulate="fp32"):
+                e32, _ = _oracle_run(orac, x, c, dy, aux_ch)
+            with opwg.bf16_emulation(accumulate="fp32-permuted"):
+                e32p, _ = _oracle_run(orac, x, c, dy, aux_ch)
+            margin = float("nan")
+        else:
+            x, margin = _pick_input_away_from_kinks(orac, B, cin, T, extra=c)
+            ref, dy = _oracle_run(orac, x, c, None, aux_ch)
+    return x, c, dy, ref, e32, e32p, margin
+
+
+def _x3_errors(got, ref):
+    """precision "bf16x3": {tensor: max error / scale} as _check_standalone asserts it."""
+    errs = {k: _rel(got[k], ref[k]) for k in ref}
+    # A weight_g gradient is the inner product <v, dW> / ||v|| of a row: it can cancel to a value far below the terms it
+    # sums (one output channel, three frames: ResidualParallelWaveGANDiscriminator T = 3 sits at 2e-4 of ITS OWN value
+    # with every other tensor at 2e-5), so its error is measured against what it is a sum of - ||dW|| of the row, which
+    # under weight normalisation (g ~ ||v||) is the row norm of the weight_v gradient - when that is the larger scale.
+    for k in ref:
+        kv = k[:-1] + "v"
+        if k.endswith("weight_g") and kv in ref:
+            rown = ref[kv].detach().double().flatten(1).norm(dim=1).max().item()
+            scale = max(ref[k].detach().abs().max().item(), rown) + 1e-12
+            errs[k] = (got[k].detach().cpu().double() - ref[k].detach().cpu().double()).abs().max().item() / scale
+    return errs
+
+
+def _check_standalone(prod, orac, cin, B, T, precision, lengths=None, aux_ch=0, prod_call=None, mask_ctx=None, pre_run=None):
     """precision "bf16x3": outputs, input gradients and every parameter gradient against the fp32 oracle, 2e-4 of
     scale.  precision "bf16" (the benchmarked arithmetic): against the oracle's bf16-emulation mode.  Rounding to
     bf16 is discontinuous, so two evaluations of the same arithmetic that only sum in a different order already
     disagree by percents in the gradients of an 8-layer net (oracle/pwg.py); the test therefore evaluates the
     emulation three ways on the CPU - float64 accumulation (the arithmetic's exact value), fp32, fp32 with permuted
     summation - and requires the kernel to lie as close to the float64 result as the fp32 evaluations do (relative
-    L2 error within 3x the larger of theirs).  A wrong operand, tap, halo row or rounding mode is off by O(1)."""
+    L2 error within 3x the larger of theirs).  A wrong operand, tap, halo row or rounding mode is off by O(1).
+    mask_ctx: see _standalone_refs; pre_run: called right before the HIP forward (a dropout test restarts the seed sequence)."""
+    import contextlib
+
     from crank_amd import ops
-    from oracle import pwg as opwg
 
     ops.set_precision(precision)
     _load_same(prod, orac)
-    rs = np.random.RandomState(3)
-    c = torch.from_numpy(rs.standard_normal((B, aux_ch, T)).astype(np.float32)) if aux_ch else None
-    if precision == "bf16":
-        x = torch.from_numpy(np.random.RandomState(100).standard_normal((B, cin, T)).astype(np.float32))
-        with opwg.bf16_emulation(accumulate="fp64"):
-            ref, dy = _oracle_run(orac, x, c, None, aux_ch)
-        with opwg.bf16_emulation(accumulate="fp32"):
-            e32, _ = _oracle_run(orac, x, c, dy, aux_ch)
-        with opwg.bf16_emulation(accumulate="fp32-permuted"):
-            e32p, _ = _oracle_run(orac, x, c, dy, aux_ch)
-        margin = float("nan")
-    else:
-        x, margin = _pick_input_away_from_kinks(orac, B, cin, T, extra=c)
-        ref, dy = _oracle_run(orac, x, c, None, aux_ch)
+    x, c, dy, ref, e32, e32p, margin = _standalone_refs(orac, cin, B, T, precision, aux_ch, mask_ctx)
+    if pre_run is not None:
+        pre_run()
     xp = x.cuda().requires_grad_(True)
     cp = c.cuda().requires_grad_(True) if aux_ch else None
     prod.zero_grad()
@@ -130,20 +165,23 @@ def _check_standalone(prod, orac, cin, B, T, precision, lengths=None, aux_ch=0, 
     for k in ref:
         if k not in got:
             got[k] = prod.grad_view(k[1:])
+    _compare_standalone(type(prod).__name__, got, ref, e32, e32p, margin, precision, B, T)
+    if precision == "bf16":
+        # and against the fp32 reference arithmetic: bf16-level agreement of the outputs
+        with torch.no_grad(), (mask_ctx if mask_ctx is not None else contextlib.nullcontext)():
+            yf = orac(x, c) if aux_ch else orac(x)
+        e32o = _rel(yp, yf)
+        print(f"   vs fp32 oracle: y {e32o:.2e} of scale")
+        assert e32o < TOL["bf16"], e32o
+    ops.set_precision("bf16")
+
+
+def _compare_standalone(name, got, ref, e32, e32p, margin, precision, B, T):
+    """_check_standalone's assertions on the tensors `got` of a HIP run (see there)."""
     if precision == "bf16x3":
-        errs = {k: _rel(got[k], ref[k]) for k in ref}
-        # A weight_g gradient is the inner product <v, dW> / ||v|| of a row: it can cancel to a value far below the terms it
-        # sums (one output channel, three frames: ResidualParallelWaveGANDiscriminator T = 3 sits at 2e-4 of ITS OWN value
-        # with every other tensor at 2e-5), so its error is measured against what it is a sum of - ||dW|| of the row, which
-        # under weight normalisation (g ~ ||v||) is the row norm of the weight_v gradient - when that is the larger scale.
-        for k in ref:
-            kv = k[:-1] + "v"
-            if k.endswith("weight_g") and kv in ref:
-                rown = ref[kv].detach().double().flatten(1).norm(dim=1).max().item()
-                scale = max(ref[k].detach().abs().max().item(), rown) + 1e-12
-                errs[k] = (got[k].detach().cpu().double() - ref[k].detach().cpu().double()).abs().max().item() / scale
+        errs = _x3_errors(got, ref)
         worst = max(errs, key=errs.get)
-        print(f"[{type(prod).__name__} bf16x3 B={B} T={T}] kink margin {margin:.1e} y {errs['y']:.2e} dx {errs['dx']:.2e} "
+        print(f"[{name} bf16x3 B={B} T={T}] kink margin {margin:.1e} y {errs['y']:.2e} dx {errs['dx']:.2e} "
               f"worst {worst} {errs[worst]:.2e}")
         bad = {k: v for k, v in errs.items() if not (v < TOL["bf16x3"])}
         assert not bad, bad
@@ -158,17 +196,10 @@ def _check_standalone(prod, orac, cin, B, T, precision, lengths=None, aux_ch=0, 
                 worst = (k, err / (noise + 1e-6), err)
         ny = max(_rl2(e32["y"], ref["y"]), _rl2(e32p["y"], ref["y"]))
         ndx = max(_rl2(e32["dx"], ref["dx"]), _rl2(e32p["dx"], ref["dx"]))
-        print(f"[{type(prod).__name__} bf16 vs bf16-emulating oracle (float64-accumulated) B={B} T={T}] relative L2: y kernel "
+        print(f"[{name} bf16 vs bf16-emulating oracle (float64-accumulated) B={B} T={T}] relative L2: y kernel "
               f"{_rl2(got['y'], ref['y']):.2e} / cpu fp32 {ny:.2e}; dx kernel {_rl2(got['dx'], ref['dx']):.2e} / cpu fp32 {ndx:.2e}; "
               f"largest kernel/cpu ratio {worst[1]:.2f} ({worst[0]}, {worst[2]:.2e})")
         assert not bad, bad
-        # and against the fp32 reference arithmetic: bf16-level agreement of the outputs
-        with torch.no_grad():
-            yf = orac(x, c) if aux_ch else orac(x)
-        e32o = _rel(yp, yf)
-        print(f"   vs fp32 oracle: y {e32o:.2e} of scale")
-        assert e32o < TOL["bf16"], e32o
-    ops.set_precision("bf16")
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
@@ -287,7 +318,7 @@ class _GenStack:
                 super().__init__()
                 self.stack = HipStack(KIND_GENERATOR, kw["in_channels"], kw["out_channels"], kw["kernel_size"], kw["layers"],
                                       stacks=kw["stacks"], aux_channels=kw["aux_channels"], bias=True,
-                                      use_causal_conv=kw.get("use_causal_conv", False))
+                                      use_causal_conv=kw.get("use_causal_conv", False), dropout=kw.get("dropout", 0.0))
                 self._alloc(self.stack.entries("", 0), self.stack.n_params, "cuda")
                 self.stack.bind(self, 0)
                 self.stack.init_parameters()
@@ -391,7 +422,10 @@ def test_plain_chain_split_forward_plain_backward(cfg, T):
     _check_split_forward(prod, orac, cfg["in_channels"], 0, 3, T, f"plain {cfg['kernel_size']}x{cfg['layers']}")
 
 
-def _check_split_forward(prod, orac, cin, aux, B, T, tag, orac_call=None):
+def _check_split_forward(prod, orac, cin, aux, B, T, tag, orac_call=None, mask_ctx=None, pre_run=None):
+    """mask_ctx / pre_run: as _check_standalone (pre_run is called before each of the two HIP forwards)."""
+    import contextlib
+
     from crank_amd import ops
 
     _load_same(prod, orac)
@@ -410,11 +444,14 @@ def _check_split_forward(prod, orac, cin, aux, B, T, tag, orac_call=None):
         def named_parameters(self, *a, **k):
             return self.m.named_parameters(*a, **k)
 
-    ref, dy = _oracle_run(O() if orac_call is not None else orac, x, c, None, aux)
+    with (mask_ctx if mask_ctx is not None else contextlib.nullcontext)():
+        ref, dy = _oracle_run(O() if orac_call is not None else orac, x, c, None, aux)
 
     def run(mode):
         ops.set_precision(mode)
         try:
+            if pre_run is not None:
+                pre_run()
             xp = x.cuda().requires_grad_(True)
             cp = c.cuda().requires_grad_(True) if aux else None
             prod.zero_grad()
