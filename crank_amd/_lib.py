@@ -75,6 +75,7 @@ SIGNATURES = {
     "crk_net_scratch_bytes": (LL, [P, I, I]),
     "crk_debug_alloc_count": (LL, []),
     "crk_debug_net_paths": (I, [P, I, I]),
+    "crk_debug_net_layout": (I, [P, I, I, ctypes.POINTER(c_int)]),
     "crk_debug_net_partials": (LL, [P, I, I, P, LL, P]),
     "crk_seed_next": (I, [P, P, P]),
     "crk_nets_wnorm_bwd": (I, [I, P, P]),

@@ -1106,6 +1106,41 @@ extern "C" int crk_debug_net_paths(void* h, int B, int T) {
   return (int)r.gen_split | (int)r.x3f << 1 | (int)r.disc_split << 2 | (int)(n->d.kind == 2 && r.fused) << 3;
 }
 
+// The layout of reserved shape (B, T), so that a test can assert that it runs the edge it is named after (tests/net_layout.py
+// restates the rules): out = {Gs, cpg_s, Gg, cpg, nseg of the shape's ShapeNeed, the ft stack2_bwd_plan chose, the window rows
+// of the plain-bf16 forward (stack2_fwd_kernel, or pstack2_kernel of a plain chain), 0}.  0 where a value does not apply: a
+// plain chain has no stack region, a stack without conditioning no sum segments, a route whose chain or forward is not
+// channel-split no ft / rows.  Host code only.  CRK_ERR_ARG: the shape is not reserved.
+extern "C" int crk_debug_net_layout(void* h, int B, int T, int* out) {
+  Net* n = (Net*)h;
+  const Shape* r = n ? find_shape(n, B, T) : nullptr;
+  if (!r || !out) return CRK_ERR_ARG;
+  const Route& rt = r->route[0];
+  const bool gated = n->d.kind != 2;
+  for (int i = 0; i < 8; i++) out[i] = 0;
+  if (gated) { out[0] = r->q.Gs; out[1] = r->q.cpg_s; }
+  out[2] = r->q.Gg; out[3] = r->q.cpg;
+  if (usum_floats(n, B, T) > 0) out[4] = r->q.nseg;
+  if (gated && (rt.gen_split || rt.disc_split)) {
+    StackBP b = stack_bwd_shape(n, B, T);
+    if (stack2_bwd_plan(b) == CRK_OK) out[5] = b.ft;
+  }
+  if (gated && (rt.fold_fwd || rt.blocks_s2)) {
+    StackP f = stack_fwd_shape(n, B, T);
+    if (rt.fold_fwd) {
+      f.x_in = reinterpret_cast<const float*>(n);  // (as route_of: folded)
+      f.in_ch = n->d.in_ch; f.kp_first = n->ents[n->idx_first].fw_kp;
+    } else f.drop_p = n->d.dropout;
+    if (stack2_fwd_plan(f) == CRK_OK) out[6] = 32 * (f.ft + (f.ft1 ? f.ft1 : f.ft)) * f.fh / 2;
+  }
+  if (!gated && rt.fused && rt.ps_fwd == CHAIN_PS2) {
+    PsP f = ps_base(n, B, T, nullptr);
+    f.cin = n->d.in_ch; f.L = r->ps.L[0];
+    if (pstack2_plan(f, r->ps.t[0]) == CRK_OK) out[6] = 32 * f.nw;
+  }
+  return CRK_OK;
+}
+
 // The weight-gradient partial sums of shape (B, T) as the last backward left them (tests compare launch forms on them):
 // returns their count and copies the first min(count, cap) floats to `out` (device memory); -1: the shape is not reserved.
 extern "C" long long crk_debug_net_partials(void* h, int B, int T, float* out, long long cap, void* stream) {

@@ -1017,6 +1017,12 @@ long long crk_debug_alloc_count(void);
  * The fallbacks compute the same values more slowly, as far as tests/test_gpu_per_layer.py and tests/test_gpu_fallback.py
  * compare them ("What reaches the per-layer kernels"); tests pin the bits at the benchmark shape. */
 int crk_debug_net_paths(void* net, int B, int T);
+/* The layout of reserved batch shape (B, T): out[0..7] = weight-gradient groups and 64-frame chunks per group of the gated
+ * blocks' region (Gs, cpg_s), groups and chunks per group of the generic region (Gg, cpg), per-utterance sum segments per
+ * group (nseg), the 64-frame tiles per window the channel-split data-gradient chain was planned with (ft), the window rows
+ * of the plain-bf16 channel-split forward, 0.  A value that does not apply to the net or its route is 0.  Tests assert the
+ * layout a case is named after before they compare values.  CRK_ERR_ARG: the shape is not reserved. */
+int crk_debug_net_layout(void* net, int B, int T, int* out);
 /* The weight-gradient partial sums (per group, before the weight-norm backward reduces them) the last backward of shape
  * (B, T) left in the handle: returns their count and copies the first min(count, cap) floats to `out` (device memory);
  * -1: the shape is not reserved.  Tests compare one launch over several nets with the single-net launches on them. */

@@ -98,6 +98,8 @@ CASES = [
     (6, 64, 500, 14),    # 40 groups of 13 chunks: groups begin and end inside utterances
     (6, 5, 333, 14),     # T not a multiple of 64; 30 chunks over 42 slots: every chunk its own group, 6 segments an utterance
     (8, 3, 140, 3),      # T not a multiple of 64, whole utterances per group
+    (8, 65, 193, 14),    # cond_embed_bwd_kernel gathers the utterance list in passes of 64: two passes, the second of one utterance
+    (8, 129, 100, 14),   # three passes
 ]
 # fp32 reassociation over <= 500 frames x 8 blocks.  The assertion is 4x (rounded up) the largest value measured in each
 # arithmetic, see the docstring below; a difference above 1e-4 would not be reassociation and needs an explanation.
@@ -116,7 +118,9 @@ def test_table_gradient_from_sums_equals_the_per_frame_one(mode, blocks, B, T, S
 
     (f64 = the float64 sum over frames of the per-frame path's dc.)  The largest value of each arithmetic is the case of
     3 utterances x 140 frames or of 5 x 333 in six segments each; 64 x 500 gives 2.7e-7 / 3.0e-7 / 3.1e-6 at 14 speakers
-    and the same at 100.  In bf16x3 the sums path multiplies (Waux_hi + Waux_lo) by the fp32 sum of dG_hi + dG_lo, which
+    and the same at 100.  The two cases that take two and three passes of cond_embed_bwd_kernel's utterance list (65 x 193,
+    129 x 100; added after the table) sit at its lower end: frame path 9.9e-8 ... 1.1e-7, sums path 2.2e-7 / 2.2e-7 /
+    2.6e-6, sums vs frame 2.3e-7 ... 2.5e-7 and 2.6e-6.  In bf16x3 the sums path multiplies (Waux_hi + Waux_lo) by the fp32 sum of dG_hi + dG_lo, which
     contains the lo x lo products the chain's three MFMAs (hi.hi + lo.hi + hi.lo) leave out - 2^-18 of a product at most,
     the size of the difference; the float64 reference is built from the chain's dc and inherits its omission.  Against the
     fp32 oracle the table's gradient sits at 1.4e-5 of scale (test_sums_path_parameter_gradients_vs_oracle_bf16x3), inside

@@ -298,7 +298,14 @@ cfgs = [dict(kind=KIND_GENERATOR, cin=128, cout=80, k=5, layers=8, stacks=4, aux
         # the planes of the weight gradient (dG, dX, dS) as 4-frame records (StackBP::rec); three more such shapes
         dict(kind=KIND_GENERATOR, cin=128, cout=80, k=5, layers=8, stacks=4, aux=34, B=4, T=504, drop=0.0),
         dict(kind=KIND_GENERATOR, cin=64, cout=64, k=3, layers=6, stacks=3, aux=0, B=2, T=240, drop=0.0),
-        dict(kind=KIND_RESIDUAL_D, cin=113, cout=1, k=5, layers=8, stacks=4, aux=0, B=2, T=496, drop=0.25)]
+        dict(kind=KIND_RESIDUAL_D, cin=113, cout=1, k=5, layers=8, stacks=4, aux=0, B=2, T=496, drop=0.25),
+        # the data-gradient chain planned at 192 rows (stack2_bwd_plan: ft = 3 - 259 / 260 / 259 workgroups at ft = 2; every
+        # shape above gets ft = 2; tests/test_net_layout_cpu.py pins the choice), and the plain chain's weight gradient in
+        # groups of 5 chunks against 4 per utterance (the last one 1 frame)
+        dict(kind=KIND_GENERATOR, cin=80, cout=64, k=5, layers=8, stacks=4, aux=0, B=37, T=500, drop=0.0),
+        dict(kind=KIND_GENERATOR, cin=64, cout=64, k=3, layers=6, stacks=3, aux=0, B=52, T=500, drop=0.0),
+        dict(kind=KIND_RESIDUAL_D, cin=113, cout=1, k=5, layers=8, stacks=4, aux=0, B=37, T=500, drop=0.0),
+        dict(kind=KIND_PLAIN, cin=80, cout=14, k=5, layers=8, stacks=1, aux=0, B=33, T=193, drop=0.0)]
 out = {}
 for i, c in enumerate(cfgs):
     torch.manual_seed(10 + i)
