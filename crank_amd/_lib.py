@@ -180,6 +180,13 @@ SIGNATURES = {
     "crk_wana_d4c": (I, [P, P, P, P, P, I, LL, LL, LL, D, P, P, P, LL, P]),
     "crk_wana_d4c_code": (I, [P, P, LL, P, P]),
     "crk_wana_d4c_frame_shapes": (I, [P, P, P, P, P, I, LL, LL, LL, D, P, P, P, P, P, LL, P]),
+    "crk_wana_stream_create": (I, [P, P, I, I, I, I, I, I, I, I, ctypes.POINTER(c_void_p)]),
+    "crk_wana_stream_destroy": (None, [P]),
+    "crk_wana_stream_state_bytes": (LL, [P]),
+    "crk_wana_stream_max_frames": (I, [P]),
+    "crk_wana_stream_reset": (I, [P, P, I, P]),
+    "crk_wana_stream_push": (I, [P, P, I, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P]),
+    "crk_wana_stream_status": (I, [P, P, P]),
     "crk_f0_create": (P, [I, I, P]),
     "crk_f0_destroy": (None, [P]),
     "crk_f0_reserve": (I, [P, LL]),

@@ -22,6 +22,7 @@
 // streams that have a j-th block ready in this push).  A push runs, per round, fs_window_kernel, crk_f0_harvest and
 // fs_finish_kernel, then fs_commit_kernel; a push with no ready block is the commit alone.  Nothing is read back.
 #include "runtime.h"
+#include "wana_frame.h"
 
 #include "../../include/crank_hip.h"
 #include <limits.h>
@@ -140,10 +141,7 @@ __global__ __launch_bounds__(FS_THREADS) void fs_window_kernel(FsGeom g, const f
     xwin[off + i] = sample(p);
     return;
   }
-  const int kmax = (int)fs_min(g.n_taps - 1, p);
-  double acc = 0.0;
-  for (int k = 0; k <= kmax; ++k) acc = fma(h[k], sample(p - k), acc);  // (wana_lowcut_kernel's chain)
-  xwin[off + i] = acc;
+  xwin[off + i] = wa_lowcut_sample(h, g.n_taps, p, sample);  // (wana_lowcut_kernel's chain)
 }
 
 struct FsFinish {

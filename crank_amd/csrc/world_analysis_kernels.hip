@@ -4,7 +4,8 @@
 // Replaces what the reference's evaluate_mcd.py runs on a converted waveform (crank.utils.low_cut_filter, sprocket
 // FeatureExtractor.analyze / .mcep / .npow: pyworld cheaptrick, pysptk sp2mc, sprocket spc2npow) except F0 estimation and
 // aperiodicity.  The oracle is the CPU restatement tests/world_analysis_ref.py; parity with pyworld / pysptk is unpinned.
-// Structure:
+// Structure; the arithmetic of a sample and of a frame is in wana_frame.h, one body each, which the
+// streaming kernels (wana_stream_kernels.hip) call too:
 //  * wana_lowcut_kernel: one thread per output sample, the taps in LDS, float32 in, float64 out, zero history at each
 //    utterance's start.
 //  * wana_offsets_kernel: one workgroup per utterance: every frame's shape integers (wa_shape) and the exclusive prefix
@@ -20,44 +21,9 @@
 #include "../../include/crank_hip.h"
 #include "signal_common.h"
 #include "wana.h"
+#include "wana_frame.h"
 
-#define WA_MAX_ORDER1 128
-#define WA_MAX_TAPS 256
 #define WA_TILE 256           // output samples per workgroup of the low-cut kernel
-#define WA_MAX_BOUND 172      // smoothing boundary at F0 = fs / 4
-#define WA_DEFAULT_F0 500.0
-#define WA_EPS 2.220446049250313e-16
-#define WA_NOISE 1e-12
-#define WA_Q1 (-0.15)
-
-// ---------------------------------------------------------------------------------------------------------- frame shape
-struct WaShape {
-  double cur;  // the F0 the frame is analysed at
-  int origin, half, dc, bound;
-};
-
-// Every integer a frame's shape hangs on, in plain IEEE float64 (no contraction): the restatement's frame_shapes forms
-// the same expressions, so both get the same integers also for F0 one ulp either side of a rounding point.  The clamps
-// never bind for finite F0 in [0, fs / 4]; they keep a frame with any other F0 inside its LDS arrays.
-__device__ WaShape wa_shape(double f0, long long i, int fs, double shiftms) {
-#pragma clang fp contract(off)
-  const double fsd = (double)fs;
-  const double floor_f0 = 3.0 * fsd / (W_N - 3.0);
-  WaShape s;
-  s.cur = (f0 <= floor_f0 || !(f0 == f0)) ? WA_DEFAULT_F0 : f0;
-  const double t = (double)i * shiftms / 1000.0;
-  const double o = t * fsd + 0.001;
-  s.origin = (int)fmin(o + 0.5, 2147483000.0);
-  const double h = 1.5 * fsd / s.cur;
-  s.half = (int)fmin(h + 0.5, 1e6);
-  s.dc = 2 + (int)fmin(s.cur * W_N / fsd, 1e6);
-  const double width = s.cur * 2.0 / 3.0;
-  s.bound = (int)fmin(width * W_N / fsd, 1e6) + 1;
-  s.half = max(1, min(s.half, W_N / 2 - 1));
-  s.dc = max(2, min(s.dc, W_N / 2));
-  s.bound = max(1, min(s.bound, WA_MAX_BOUND));
-  return s;
-}
 
 __global__ __launch_bounds__(W_THREADS) void wana_offsets_kernel(const double* __restrict__ f0,
                                                                  const long long* __restrict__ foff, int fs, double shiftms,
@@ -107,10 +73,8 @@ __global__ __launch_bounds__(WA_TILE) void wana_lowcut_kernel(const float* __res
   if (g >= S) return;
   const int u = w_find(soff, n_utts, g);
   const long long i = g - soff[u];
-  const int kmax = (int)min((long long)n_taps - 1, i);
-  double acc = 0.0;
-  for (int k = 0; k <= kmax; ++k) acc = fma(h[k], (double)x[g - k], acc);
-  y[g] = acc;
+  const float* xu = x + soff[u];
+  y[g] = wa_lowcut_sample(h, n_taps, i, [&](long long q) { return xu[q]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------- CheapTrick
@@ -124,151 +88,14 @@ struct WaFrame {
 };
 
 __global__ __launch_bounds__(W_THREADS) void wana_cheaptrick_kernel(WaFrame a) {
-#pragma clang fp contract(off)  // x w + noise and wav - w coef round as the restatement's do: on a locally constant signal
-                                // the mean removal cancels the signal and what is left is of the size of those roundings
-  __shared__ double2 Z[W_N];
-  __shared__ double tc[W_N / 2], ts[W_N / 2];
-  __shared__ double buf[W_N];      // the window, then the mirrored cumulative spectrum (at most 513 + 2 * 172 values)
-  __shared__ double pw[W_K + 7];   // power spectrum, then log spectrum, then liftered cepstrum
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
   const long long f = blockIdx.x;
   const int u = w_find(a.foff, a.n_utts, f);
   const long long S0 = a.soff[u], xlen = a.soff[u + 1] - S0;
   const double* xs = a.x + S0;
   const WaShape sh = wa_shape(a.f0[f], f - a.foff[u], a.fs, a.shiftms);
-  const long long roff = a.doff[f];
-  const double fsd = (double)a.fs, cur = sh.cur;
-  const int half = sh.half, n = 2 * half + 1;
-
-  w_stage_twiddles(tc, ts, a.twc, a.tws);
-  // the F0-adaptive window, unit energy
-  double e = 0.0;
-  for (int j = tid; j < n; j += W_THREADS) {
-    const double pos = (double)(j - half) / 1.5 / fsd;
-    const double w = 0.5 * cos(M_PI * pos * cur) + 0.5;
-    buf[j] = w;
-    e += w * w;
-  }
-  const double norm = sqrt(w_block_sum(e, red));
-  // windowed waveform (indices clamped to the signal) plus the stream's noise; the window-weighted mean removed
-  double wav[4], win[4], s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = tid + W_THREADS * r;
-    wav[r] = 0.0;
-    win[r] = 0.0;
-    if (j < n) {
-      const double w = buf[j] / norm;
-      const long long idx = max(0LL, min((long long)sh.origin + (j - half), xlen - 1));
-      const double xv = xlen > 0 ? xs[idx] : 0.0;
-      const double z = a.noise[min(roff + j, a.noise_len - 1)];
-      win[r] = w;
-      wav[r] = xv * w + z * WA_NOISE;
-      s1 += wav[r];
-      s2 += w;
-    }
-  }
-  s1 = w_block_sum(s1, red);
-  s2 = w_block_sum(s2, red);
-  const double coef = s1 / s2;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = tid + W_THREADS * r;
-    Z[w_brev(j)] = make_double2(j < n ? wav[r] - win[r] * coef : 0.0, 0.0);
-  }
-  __syncthreads();
-  w_fft(Z, tc, ts, -1.0);
-  for (int k = tid; k < W_K; k += W_THREADS) pw[k] = Z[k].x * Z[k].x + Z[k].y * Z[k].y;
-  __syncthreads();
-  // DC correction: the replica mirrored at F0 is added below it (all reads before the first write)
-  double rep[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int i = tid + W_THREADS * r;
-    rep[r] = i < sh.dc - 1 ? wa_interp(pw, sh.dc + 1, cur, -(fsd / W_N), (double)i * fsd / W_N) : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int i = tid + W_THREADS * r;
-    if (i < sh.dc - 1) pw[i] += rep[r];
-  }
-  __syncthreads();
-  // linear smoothing of width 2 F0 / 3: mirrored spectrum, its cumulative sum, two reads per bin.  The sum runs in one
-  // thread in the restatement's order: a band's level is the difference of two of its values, so a bin far below the
-  // frame's total power keeps only the digits both sums round alike (a scan that rounds otherwise was 1e-9 .. 2e-6 off
-  // in log sp on harmonic signals, where the two-FFT spread of the restatement is 1e-14 .. 1e-10).
-  const int b = sh.bound, len = W_K + 2 * b;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = tid + W_THREADS * r;
-    if (j < len) {
-      const int src = j < b ? b - j : (j < W_K - 1 + b ? j - b : (W_K - 1) - (j - (W_K - 1 + b)));
-      buf[j] = pw[src] * fsd / W_N;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double run = 0.0;
-#pragma unroll 8
-    for (int j = 0; j < len; ++j) {
-      run += buf[j];
-      buf[j] = run;
-    }
-  }
-  __syncthreads();
-  const double width = cur * 2.0 / 3.0;
-  const double x0 = -(b - 0.5) * fsd / W_N, dx = fsd / W_N;
-  for (int k = tid; k < W_K; k += W_THREADS) {
-    const double ax = (double)k / W_N * fsd - width / 2.0;
-    const double lo = wa_interp(buf, len, x0, dx, ax), hi = wa_interp(buf, len, x0, dx, ax + width);
-    const double z = a.noise[min(roff + n + k, a.noise_len - 1)];
-    pw[k] = log((hi - lo) / width + fabs(z) * WA_EPS);
-  }
-  __syncthreads();
-  // cepstrum of the even log spectrum; smoothing and recovery lifters
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = tid + W_THREADS * r;
-    Z[w_brev(j)] = make_double2(pw[j <= W_N / 2 ? j : W_N - j], 0.0);
-  }
-  __syncthreads();
-  w_fft(Z, tc, ts, -1.0);
-  double cl[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int k = tid + W_THREADS * r;
-    cl[r] = 0.0;
-    if (k < W_K) {
-      double sm = 1.0, cp = 1.0;
-      if (k > 0) {
-        const double q = (double)k / fsd;
-        sm = sin(M_PI * cur * q) / (M_PI * cur * q);
-        cp = (1.0 - 2.0 * WA_Q1) + 2.0 * WA_Q1 * cos(2.0 * M_PI * q * cur);
-      }
-      cl[r] = Z[k].x * sm * cp / W_N;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int k = tid + W_THREADS * r;
-    if (k < W_K) {
-      pw[k] = cl[r];
-      if (a.cep) a.cep[f * W_K + k] = cl[r];
-    }
-  }
-  if (!a.sp) return;
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = tid + W_THREADS * r;
-    Z[w_brev(j)] = make_double2(pw[j <= W_N / 2 ? j : W_N - j], 0.0);
-  }
-  __syncthreads();
-  w_fft(Z, tc, ts, -1.0);
-  for (int k = tid; k < W_K; k += W_THREADS) a.sp[f * W_K + k] = exp(Z[k].x);
+  const WaTables t{a.noise, a.noise_len, a.twc, a.tws, a.fs};
+  wa_cheaptrick_frame([&](long long idx) { return xs[idx]; }, xlen, sh, a.doff[f], t, a.sp ? a.sp + f * W_K : nullptr,
+                      a.cep ? a.cep + f * W_K : nullptr);
 }
 
 // mcep[f][m] = sum_k at[m][k] cep[f][k]: one wave per frame, lane l holds cep[l + 64 j]
@@ -278,23 +105,7 @@ __global__ __launch_bounds__(W_THREADS) void wana_mcep_kernel(const double* __re
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long long f = (long long)blockIdx.x * (W_THREADS / 64) + wv;
   if (f >= F) return;
-  double c[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const int k = lane + 64 * j;
-    c[j] = k < W_K ? cep[f * W_K + k] : 0.0;
-  }
-  for (int m = 0; m < m1; ++m) {
-    const double* row = at + (size_t)m * W_K;
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-      const int k = lane + 64 * j;
-      if (k < W_K) acc = fma(row[k], c[j], acc);
-    }
-    acc = w_wave_sum(acc);
-    if (lane == 0) mc[f * m1 + m] = acc;
-  }
+  wa_mcep_frame(cep + f * W_K, at, m1, lane, [&](int m, double v) { mc[f * m1 + m] = v; });
 }
 
 // ---------------------------------------------------------------------------------------------------------- power

@@ -20,6 +20,10 @@ each, and ``continuous_f0_batch`` the reference's ``convert_continuos_f0`` with 
 tests/harvest_ref.py; parity with pyworld is unpinned.  ``StreamingF0`` runs it on a window around
 each block of a live stream's frames and finishes the contour into the ``lcf0`` / ``uv`` rows streaming conversion takes
 (csrc/f0_stream_kernels.hip, crk_f0_stream_*; the definition is tests/f0_stream_ref.py).
+
+``StreamingMcep`` (``WorldAnalyzer.streaming``) is ``mcep_batch`` frame by frame from live streams of samples and F0 rows,
+bit for bit (csrc/wana_stream_kernels.hip, crk_wana_stream_*; the definition is tests/wana_stream_ref.py, DESIGN.md
+section 6o); ``analysis_capacities`` sizes its ring and its F0 queue.
 """
 import ctypes
 
@@ -492,6 +496,15 @@ class WorldAnalyzer:
             out.append(d)
         return out
 
+    def streaming(self, n_streams, max_samples, max_f0_in, f0_capacity=None, ring_capacity=None, f0_lag_ms=0.0, **kw):
+        """A ``StreamingMcep`` at this analyzer's fs, shiftms and device: ``mcep_batch`` frame by frame from live
+        streams.  Capacities not given are ``analysis_capacities`` for F0 rows that lag the signal by ``f0_lag_ms``;
+        ``kw``: dim, alpha, low_cut, max_utt_frames, scaler, use_mcep_0th."""
+        ring, queue = analysis_capacities(self.fs, self.shiftms, f0_lag_ms, max_samples, max_f0_in)
+        return StreamingMcep(self.fs, self.shiftms, n_streams, max_samples, max_f0_in,
+                             queue if f0_capacity is None else f0_capacity, ring if ring_capacity is None else ring_capacity,
+                             device=self.device, **kw)
+
     def analyze_mcep(self, wave, f0, dim=34, alpha=0.455, low_cut=70):
         """One utterance: evaluate_mcd.py's ``get_world_features`` with the F0 given."""
         return self.mcep_batch([wave], [f0], dim, alpha, low_cut)[0]
@@ -963,6 +976,211 @@ class StreamingF0:
                 out["lcf0"].data_ptr(), out["uv"].data_ptr(), out["n_frames"].data_ptr(), _lib.ptr(out.get("raw")),
                 _lib.ptr(out.get("cv_f0")), _lib.ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()),
                 "crk_f0_stream_push")
+        return out
+
+
+WINDOW_REACH = FFTL // 2 - 1  # the furthest a CheapTrick window reaches either side of its frame's origin
+
+
+def analysis_capacities(fs, shiftms, f0_lag_ms, max_samples, max_f0_in, reach=WINDOW_REACH):
+    """(ring_capacity, f0_capacity) of a ``StreamingMcep`` that can never set flag 1 or 2 while the F0 rows lag the signal
+    by at most ``f0_lag_ms`` and do not lead it.  With n the samples and ``rows`` the rows a stream holds after a push,
+    origin_k frame k's origin and L = ceil(f0_lag_ms fs / 1000): every frame with origin_k + L <= n has its row, no row
+    has origin_k > n, and an end push brings at most the rows the offline call takes (k shift <= n + shift).  Closed form,
+    with M = max(L, reach + 1) and C = max_samples:
+
+    * a frame leaves in the first push after which its row is there and n >= origin + reach + 1; before that push
+      n <= origin + M - 1, so after it n <= origin + M - 1 + C while the window starts at origin - reach or later: the
+      ring holds ``M - 1 + C + reach`` samples;
+    * before a push every frame with origin + M <= n has left, after it the rows reach k shift <= n + C + shift at the
+      most: the waiting rows have k shift within a closed span of C + M + shift - 0.499 (the 0.499: origins are k shift
+      + 0.001 rounded to nearest), ``floor((C + M - 0.499) / shift) + 2`` rows.
+
+    ``max_f0_in`` only bounds what a push can bring (at least one row).  tests/wana_stream_ref.py tries every history at
+    toy sizes (``reach`` is the toy's window)."""
+    fs, C = int(fs), int(max_samples)
+    shift = float(shiftms) / 1000.0 * fs
+    if not shift > 0.0 or C < 1 or int(max_f0_in) < 1 or not float(f0_lag_ms) >= 0.0 or int(reach) < 0:
+        raise ValueError("analysis_capacities: shiftms > 0, max_samples >= 1, max_f0_in >= 1, f0_lag_ms >= 0")
+    L = int(np.ceil(float(f0_lag_ms) * fs / 1000.0))
+    M = max(L, int(reach) + 1)
+    return M - 1 + C + int(reach), int(np.floor((C + M - 0.499) / shift)) + 2
+
+
+class StreamingMcep:
+    """``push`` takes the next samples and the next F0 rows of ``n_streams`` independent streams and returns the frames
+    ``WorldAnalyzer.mcep_batch`` writes for the whole utterance at the same contour, bit for bit, as soon as each frame's
+    window is complete (csrc/wana_stream_kernels.hip, ``crk_wana_stream_*``; the definition is tests/wana_stream_ref.py,
+    DESIGN.md section 6o).  Stream i is row i of every argument; row k of a stream's utterance is frame k.
+
+    Frame i leaves in the first push after which its F0 row has arrived and the stream holds ``origin_i + 512`` samples
+    (the longest half window plus one: readiness never depends on the F0), or in the push whose ``end`` flag is set, where
+    every waiting frame leaves with its window clamped at the stream's final length and the stream returns to its start
+    state.  ``feats`` are the rows a generator takes: columns ``first:`` of the mel-cepstrum (``first`` = 0 with
+    ``use_mcep_0th``, else 1), with ``scaler`` = (mean, scale) of ``dim + 1`` values as ``(mcep - mean) / scale`` in
+    float64, rounded once to float32.
+
+    The low-cut filtered signal (a power-of-two float64 ring of at least ``ring_capacity`` samples), the waiting F0 rows
+    (at most ``f0_capacity``), the counts and the randn draw offset stay on the device; ``n_valid``, ``n_f0`` and ``end`` are
+    device tensors and nothing is read back, so a push - four launches - can be captured in a graph.
+    ``analysis_capacities`` gives capacities that cannot overflow for a given F0 lag.  Sticky flags, raised by
+    ``status()``: 1 a frame's window start had left the ring (the frame is dropped and counted in ``n_dropped``), 2 the
+    F0 queue overflowed (the newest rows are dropped and counted), 4 an utterance outgrew ``max_utt_frames`` (the randn
+    table; the frame is emitted with the draw offset clamped), 8 rows past the end of the signal at an end push (dropped and counted),
+    16 an F0 row not finite, negative or above fs / 4 (analysed as unvoiced).  There is no torch or CPU fallback."""
+
+    FLAGS = {1: "a frame's window had left the sample ring (F0 rows came later than ring_capacity allows)",
+             2: "the F0 queue overflowed (f0_capacity)",
+             4: "an utterance drew past the randn table (max_utt_frames)",
+             8: "F0 rows past the end of the signal at an end push",
+             16: "an F0 row not finite, negative or above fs / 4"}
+
+    def __init__(self, fs, shiftms, n_streams, max_samples, max_f0_in, f0_capacity, ring_capacity, dim=34, alpha=0.455,
+                 low_cut=70, max_utt_frames=6000, scaler=None, use_mcep_0th=False, device="cuda"):
+        if int(fs) != fs or not 8000 <= int(fs) <= 192000:
+            raise ValueError(f"fs {fs}: the kernels take 8000 .. 192000 Hz")
+        if not float(shiftms) > 0.0:
+            raise ValueError(f"shiftms {shiftms}: must be positive")
+        order1 = int(dim) + 1
+        if not 1 <= order1 <= MAX_ORDER1:
+            raise ValueError(f"dim + 1 = {order1}: the kernels take 1 .. {MAX_ORDER1} coefficients")
+        if not abs(float(alpha)) < 1.0:
+            raise ValueError(f"alpha {alpha}: the all-pass constant must lie in (-1, 1)")
+        if not use_mcep_0th and order1 < 2:
+            raise ValueError("dim 0 without use_mcep_0th leaves no feature column")
+        sizes = dict(n_streams=n_streams, max_samples=max_samples, max_f0_in=max_f0_in, f0_capacity=f0_capacity,
+                     ring_capacity=ring_capacity, max_utt_frames=max_utt_frames)
+        for name, v in sizes.items():
+            if int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} = {v}: must be a positive integer")
+        if int(n_streams) > 65535 or max(int(f0_capacity), int(max_f0_in)) > 65536 or int(ring_capacity) > 1 << 26:
+            raise ValueError("at most 65535 streams, 65536 F0 rows and a ring of 2^26 samples")
+        if int(ring_capacity) < int(max_samples):
+            raise ValueError(f"ring_capacity {ring_capacity} below max_samples {max_samples}")
+        if int(max_utt_frames) * DRAWS_PER_FRAME > 1 << 31:
+            raise ValueError(f"max_utt_frames {max_utt_frames}: the randn table holds 2^31 draws")
+        self.device = torch.device(device)
+        require_gpu(self.device, "streaming WORLD analysis")
+        self.fs, self.shiftms, self.dim, self.alpha = int(fs), float(shiftms), int(dim), float(alpha)
+        self.low_cut, self.use_mcep_0th = low_cut, bool(use_mcep_0th)
+        self.first = 0 if self.use_mcep_0th else 1
+        self.n_streams, self.max_samples, self.max_f0_in = int(n_streams), int(max_samples), int(max_f0_in)
+        self.f0_capacity, self.ring_capacity, self.max_utt_frames = int(f0_capacity), int(ring_capacity), int(max_utt_frames)
+        self._mean = self._scale = None
+        if scaler is not None:
+            self._mean, self._scale = (f64(v, self.device).reshape(-1).contiguous() for v in scaler)
+            if self._mean.numel() != order1 or self._scale.numel() != order1:
+                raise ValueError(f"scaler: mean and scale of {order1} values each")
+        taps, n_taps = None, 0
+        if low_cut is not None:
+            from scipy.signal import firwin
+
+            n_taps = LOWCUT_TAPS
+            taps = (ctypes.c_double * n_taps)(*firwin(n_taps, low_cut / (self.fs // 2), pass_zero=False))
+        L = _lib.lib()
+        self._handle = self._wana = None
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            # a Wana handle of its own: its randn table is reserved once, here, and no offline call grows it
+            self._wana = made(L.crk_wana_create(self.fs, FFTL, self.shiftms, self.alpha, order1), "crk_wana_create")
+            check(L.crk_wana_stream_create(self._wana, taps, n_taps, self.n_streams, self.max_samples, self.max_f0_in,
+                                           self.f0_capacity, self.ring_capacity, self.max_utt_frames,
+                                           1 if self.use_mcep_0th else 0, ctypes.byref(h)), "crk_wana_stream_create")
+            self._handle = made(h, "crk_wana_stream_create")
+        self.max_frames = int(L.crk_wana_stream_max_frames(self._handle))
+
+    def __del__(self):
+        release(self, "_handle", "crk_wana_stream_destroy")
+        release(self, "_wana", "crk_wana_destroy")
+
+    @property
+    def state_bytes(self):
+        return int(_lib.lib().crk_wana_stream_state_bytes(self._handle))
+
+    def reset(self, streams=None):
+        """``streams`` (all of them by default) return to their start state; waiting frames are dropped, flags cleared."""
+        reset_streams(self._handle, "crk_wana_stream_reset", streams, self.device)
+
+    def flags(self):
+        """Synchronises; the sticky flag word of every stream (host list)."""
+        flags = (ctypes.c_int * self.n_streams)()
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_wana_stream_status(self._handle, flags, stream_ptr()), "crk_wana_stream_status")
+        return list(flags)
+
+    def status(self):
+        """Synchronises; raises if any stream has set a flag since its last reset."""
+        bad = {s: f for s, f in enumerate(self.flags()) if f}
+        if bad:
+            what = "; ".join(f"stream {s}: " + ", ".join(t for b, t in self.FLAGS.items() if f & b) for s, f in bad.items())
+            raise RuntimeError(f"streaming WORLD analysis: {what}")
+
+    def empty_outputs(self, S=None, sp=False):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns; ``sp`` (the spectral envelope) is
+        optional."""
+        S = self.n_streams if S is None else int(S)
+        dev, F = self.device, self.max_frames
+        out = {"mcep": torch.empty(S, F, self.dim + 1, dtype=torch.float64, device=dev),
+               "feats": torch.empty(S, F, self.dim + 1 - self.first, dtype=torch.float32, device=dev)}
+        if sp:
+            out["sp"] = torch.empty(S, F, K, dtype=torch.float64, device=dev)
+        for name in ("n_frames", "first", "n_dropped"):
+            out[name] = torch.empty(S, dtype=torch.int32, device=dev)
+        return out
+
+    def _dev_ints(self, v, S, what):
+        if v is None:
+            return None
+        if (not isinstance(v, torch.Tensor) or v.device.type != "cuda" or v.dtype != torch.int32
+                or tuple(v.shape) != (S,)):
+            raise ValueError(f"{what}: an int32 ({S},) tensor on the GPU (or None)")
+        return v.contiguous()
+
+    def push(self, x, f0, n_valid=None, n_f0=None, end=None, out=None):
+        """x (S, C) float32 samples and f0 (S, R) or (S, R, 1) float64 rows (raw contour, 0 = unvoiced) on the GPU, C <=
+        max_samples, R <= max_f0_in (either may be 0); n_valid, n_f0, end: int32 (S,) on the GPU or None (C, R, 0) - the
+        samples and rows that count per stream and non-zero where this push ends the stream's utterance.  Returns
+        ``mcep`` (S, max_frames, dim + 1) float64, ``feats`` (S, max_frames, dim + 1 - first) float32, ``sp`` (S,
+        max_frames, 513) float64 if ``out`` holds one, and ``n_frames``, ``first``, ``n_dropped`` int32 (S,): the frames
+        written at the start of each stream's rows; rows at and past ``n_frames`` are not written.  Anything refused
+        leaves outputs and state untouched.  out: buffers to write into (``empty_outputs``)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.device.type != "cuda" or x.dtype != torch.float32:
+            raise ValueError("x: a float32 (S, C) tensor on the GPU")
+        S, C = int(x.shape[0]), int(x.shape[1])
+        if S != self.n_streams:
+            raise ValueError(f"x: {S} rows for {self.n_streams} streams")
+        if C > self.max_samples:
+            raise ValueError(f"x: {C} samples per push, max_samples is {self.max_samples}")
+        if (not isinstance(f0, torch.Tensor) or f0.device.type != "cuda" or f0.dtype != torch.float64
+                or f0.dim() not in (2, 3) or f0.shape[0] != S or (f0.dim() == 3 and f0.shape[2] != 1)):
+            raise ValueError(f"f0: a float64 ({S}, R) or ({S}, R, 1) tensor on the GPU")
+        R = int(f0.shape[1])
+        if R > self.max_f0_in:
+            raise ValueError(f"f0: {R} rows per push, max_f0_in is {self.max_f0_in}")
+        x, f0 = x.contiguous(), f0.reshape(S, R).contiguous()
+        n_valid, n_f0, end = (self._dev_ints(v, S, what) for v, what in ((n_valid, "n_valid"), (n_f0, "n_f0"), (end, "end")))
+        if out is None:
+            out = self.empty_outputs(S)
+        else:
+            F = self.max_frames
+            for name, dt, w in (("mcep", torch.float64, self.dim + 1), ("feats", torch.float32, self.dim + 1 - self.first),
+                                ("sp", torch.float64, K)):
+                t = out.get(name)
+                if t is None and name == "sp":
+                    continue
+                if (t is None or t.device.type != "cuda" or t.dtype != dt or tuple(t.shape) != (S, F, w)
+                        or not t.is_contiguous()):
+                    raise ValueError(f"out[{name!r}]: {dt} ({S}, {F}, {w}) on the GPU (empty_outputs)")
+            for name in ("n_frames", "first", "n_dropped"):
+                t = out.get(name)
+                if t is None or t.device.type != "cuda" or t.dtype != torch.int32 or tuple(t.shape) != (S,):
+                    raise ValueError(f"out[{name!r}]: int32 ({S},) on the GPU (empty_outputs)")
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_wana_stream_push(
+                self._handle, x.data_ptr(), C, _lib.ptr(n_valid), C, f0.data_ptr(), R, _lib.ptr(n_f0), R, _lib.ptr(end), S,
+                _lib.ptr(self._mean), _lib.ptr(self._scale), out["mcep"].data_ptr(), _lib.ptr(out.get("sp")),
+                out["feats"].data_ptr(), out["n_frames"].data_ptr(), out["first"].data_ptr(), out["n_dropped"].data_ptr(),
+                stream_ptr()), "crk_wana_stream_push")
         return out
 
 

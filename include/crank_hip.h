@@ -856,6 +856,51 @@ int crk_f0_stream_push(void* st, void* f0h, const float* x, int ldx, const int* 
                        long long workspace_bytes, void* stream);
 int crk_f0_stream_status(void* st, int* flags, void* stream);
 
+/* ---- Streaming CheapTrick / mel-cepstrum analysis (csrc/wana_stream_kernels.hip) ---------------
+ * The frames crk_wana_mcep writes for a whole utterance, from a live stream: samples and F0 rows in, every frame out
+ * bit for bit as soon as its window is complete.  `wana` is a crk_wana_create handle (fs, shiftms, alpha, order1 are
+ * its own); it must outlive the stream handle, and crk_wana_stream_create reserves its randn table for
+ * max_utt_frames * 1536 draws (crk_wana_reserve; 1536 = the most one frame draws).  Per stream the handle keeps, on the
+ * device: the analysed signal y - the causal FIR taps (HOST float64, n_taps in 0 .. 255; 0: y = (double)x) with zero
+ * history at the utterance's start, by crk_wana_lowcut's arithmetic, each sample filtered once - in a power-of-two
+ * float64 ring of at least ring_capacity samples addressed by absolute position; the last raw samples the filter reaches;
+ * a queue of at most f0_capacity F0 rows (row k of an utterance is frame k) that have arrived and whose frames have not
+ * left; 64-bit counts of samples, rows and frames that left; the randn draw offset of the next frame; a sticky flag word.
+ * crk_wana_stream_create is the one call that allocates (it synchronises).  CRK_ERR_ARG: a null pointer, a size below 1,
+ * n_taps outside 0 .. 255, ring_capacity < max_samples; CRK_ERR_UNSUPPORTED: more than 65535 streams, f0_capacity or
+ * max_f0_in above 65536, ring_capacity above 2^26, max_utt_frames * 1536 above 2^31, use_mcep_0th == 0 with order1 == 1.
+ * crk_wana_stream_max_frames: f0_capacity, the most frames one push emits.  crk_wana_stream_reset: the streams in the
+ * HOST array stream_ids (NULL: all) return to their start state, flags cleared.
+ *
+ * crk_wana_stream_push: x fp32 [S][C] (row stride ldx), f0 double [S][R] (row stride ldf; raw contour, 0 = unvoiced);
+ * n_valid, n_f0, end DEVICE int32 [S] or NULL (C, R, 0; the counts are clamped to 0 .. C and 0 .. R).  The samples and
+ * rows are appended; then frame i of a stream leaves, in order, if its row has arrived and n >= origin_i + 512, origin_i
+ * crk_wana_frame_shapes' origin of frame i, n the samples so far - or, with end[s] != 0, every waiting frame leaves with
+ * its window clamped at n, and the stream returns to its start state.  Frame j to leave writes row j of mcep
+ * [S][max_frames][order1], of sp [S][max_frames][513] (optional) and of feats fp32 [S][max_frames][order1 - first]
+ * (first = 0 with use_mcep_0th, else 1): column m - first = mcep[m], or (mcep[m] - mean[m]) / scale[m] with mean / scale
+ * DEVICE double [order1] (both or neither), in float64 without contraction, rounded once.  Rows at and past n_frames[s]
+ * are not written.  n_frames, first, n_dropped DEVICE int32 [S] are written for every stream.  Sticky flags: 1 a frame's
+ * window start had left the ring (origin - half < n - ring_capacity): the frame is dropped and counted in n_dropped, its
+ * draws still consumed; 2 the queue overflowed: the newest rows that do not fit are dropped and counted; 4 a draw offset
+ * passed the reserved table: the kernel's clamp applies, the frame is emitted; 8 at an end push, rows k with
+ * k shift > n + shift (shift = shiftms / 1000 fs, what the offline call refuses) or rows with n == 0: dropped and
+ * counted; 16 an F0 row that is not finite, negative or above fs / 4: analysed as 0.  Judged before any launch, state
+ * and outputs untouched: CRK_ERR_ARG for S < 1, C or R < 0, a stride below its width, a null pointer (sp, mean / scale
+ * and the three int inputs excepted); CRK_ERR_UNSUPPORTED for S > n_streams, C > max_samples, R > max_f0_in.  Four
+ * launches whose grids depend on the handle and S alone; never allocates, never synchronises, reads nothing back:
+ * capturable.  crk_wana_stream_status synchronises and copies the flags of all n_streams streams to HOST int32. */
+int crk_wana_stream_create(void* wana, const double* taps, int n_taps, int n_streams, int max_samples, int max_f0_in,
+                           int f0_capacity, int ring_capacity, int max_utt_frames, int use_mcep_0th, void** handle);
+void crk_wana_stream_destroy(void* st);
+long long crk_wana_stream_state_bytes(void* st);
+int crk_wana_stream_max_frames(void* st);
+int crk_wana_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_wana_stream_push(void* st, const float* x, int ldx, const int* n_valid, int C, const double* f0, int ldf,
+                         const int* n_f0, int R, const int* end, int S, const double* mean, const double* scale,
+                         double* mcep, double* sp, float* feats, int* n_frames, int* first, int* n_dropped, void* stream);
+int crk_wana_stream_status(void* st, int* flags, void* stream);
+
 /* ---- Griffin-Lim waveform synthesis for log-mel models (csrc/griffin_lim_kernels.hip) ----
  * Replaces the reference's mlfb2wav (crank/utils/utils.py:94-107, 210-269: logmelspc_to_linearspc, griffin_lim -> librosa.griffinlim
  * with momentum 0.99, centred reflect-padded STFT, periodic Hann window; called by BaseTrainer._save_decoded_mlfb,
