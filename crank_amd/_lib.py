@@ -187,6 +187,13 @@ SIGNATURES = {
     "crk_wana_stream_reset": (I, [P, P, I, P]),
     "crk_wana_stream_push": (I, [P, P, I, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P]),
     "crk_wana_stream_status": (I, [P, P, P]),
+    "crk_wsyn_stream_create": (I, [P, I, I, I, I, I, I, D, I, LL, ctypes.POINTER(c_void_p)]),
+    "crk_wsyn_stream_destroy": (None, [P]),
+    "crk_wsyn_stream_state_bytes": (LL, [P]),
+    "crk_wsyn_stream_max_out": (I, [P]),
+    "crk_wsyn_stream_reset": (I, [P, P, I, P]),
+    "crk_wsyn_stream_push": (I, [P, P, P, P, P, P, I, P, I, I, P, P, P, P]),
+    "crk_wsyn_stream_status": (I, [P, P, P]),
     "crk_f0_create": (P, [I, I, P]),
     "crk_f0_destroy": (None, [P]),
     "crk_f0_reserve": (I, [P, LL]),

@@ -15,38 +15,12 @@
 //    both inverse transforms in four 1024-point fp64 LDS FFTs (two real sequences per complex transform); writes the
 //    pulse's response.
 //  * world_ola_kernel: one thread per output sample sums the responses that cover it, in pulse order (no atomics).
+// The arithmetic of the first four is csrc/world_frame.h's, one body each, shared with the streaming kernels
+// (world_stream_kernels.hip).
 #include "../../include/crank_hip.h"
-#include "signal_common.h"
+#include "world.h"
+#include "world_frame.h"
 #include <string.h>
-
-#define W_IRLEN 1024
-#define W_MAX_ORDER1 128
-#define W_CHUNK 2048
-#define W_SAFE 1e-12
-#define W_DEFAULT_F0 500.0
-
-struct World {
-  int fs, m1, bands, capacity;
-  double shiftms, fp, alpha;
-  double* tables;  // one device block: at [m1][W_IRLEN], wt [m1][W_K], tw cos [W_N/2], tw sin [W_N/2], dc [W_N]
-  const double *at, *wt, *twc, *tws, *dcw;
-  double* noise;
-  long long noise_len;
-};
-
-static int w_bands(int fs) { return (int)(fmin(15000.0, fs / 2.0 - 3000.0) / 3000.0); }
-
-// cos(x) for x in [0, pi] as the Taylor polynomial in x^2 (16 terms, Horner), each operation rounded on its own.
-// WORLD's delay takes sin as sqrt(1 - cos^2), which turns a last-bit difference of cos at small x into a large one of
-// sin; tests/world_synth_ref.py evaluates the same polynomial, so both get the same bits.
-static __constant__ double W_COS[16] = {1.0, -0.5, 0.041666666666666664, -0.001388888888888889, 2.48015873015873e-05, -2.755731922398589e-07, 2.08767569878681e-09, -1.1470745597729725e-11, 4.779477332387385e-14, -1.5619206968586225e-16, 4.110317623312165e-19, -8.896791392450574e-22, 1.6117375710961184e-24, -2.4795962632247976e-27, 3.279889237069838e-30, -3.7699876288159054e-33};
-__device__ double w_cos(double x) {
-#pragma clang fp contract(off)
-  const double x2 = x * x;
-  double r = W_COS[15];
-  for (int n = 14; n >= 0; --n) r = r * x2 + W_COS[n];
-  return r;
-}
 
 // ---------------------------------------------------------------------------------------------------------- per frame
 // mc2e of every frame of mcep (which 0) and rmcep (which 1): e[f * 2 + which].  One wave per item; lane l holds
@@ -61,34 +35,7 @@ __global__ __launch_bounds__(W_THREADS) void world_energy_kernel(const double* _
   const long long f = item >> 1;
   const double* mc = ((item & 1) ? rmcep : mcep) + f * m1;
   double* h = hs[wv];
-  double kc[W_IRLEN / 64];
-#pragma unroll
-  for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] = 0.0;
-  for (int i = 0; i < m1; ++i) {
-    const double v = mc[i];
-    const double* row = at + (size_t)i * W_IRLEN + lane;
-#pragma unroll
-    for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] = fma(row[64 * j], v, kc[j]);
-  }
-  const double c0 = __shfl(kc[0], 0);
-#pragma unroll
-  for (int j = 0; j < W_IRLEN / 64; ++j) kc[j] *= (double)(lane + 64 * j);
-  double h0 = exp(c0);
-  if (lane == 0) h[0] = h0;
-  double en = h0 * h0;
-  for (int n = 1; n < W_IRLEN; ++n) {
-    __builtin_amdgcn_wave_barrier();
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < W_IRLEN / 64; ++j) {
-      const int k = lane + 64 * j;
-      if (64 * j <= n && k >= 1 && k <= n) acc = fma(kc[j], h[n - k], acc);
-    }
-    const double hn = w_wave_sum(acc) / n;
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) h[n] = hn;
-    en = fma(hn, hn, en);
-  }
+  const double en = w_energy_row(mc, m1, at, h, lane);
   if (lane == 0) e[item] = en;
 }
 
@@ -100,30 +47,7 @@ __global__ void world_frame_kernel(const double* __restrict__ mcep, const double
   if (idx >= F * W_K) return;
   const long long f = idx / W_K;
   const int k = (int)(idx % W_K);
-  const double* mc = mcep + f * m1;
-  double acc = 0.0;
-  for (int i = 0; i < m1; ++i) {
-    double v = mc[i];
-    if (i == 0 && e) v += log(e[2 * f + 1] / e[2 * f]) / 2.0;
-    acc = fma(wt[(size_t)i * W_K + k], v, acc);
-  }
-  sp[idx] = exp(acc);
-  // WORLD DecodeAperiodicity: knots (0, -60 dB), (3000 b, cap[b-1]), (fs / 2, -1e-12); unvoiced frames 1 - 1e-12
-  const double* cp = cap + f * bands;
-  double mean = 0.0;
-  for (int b = 0; b < bands; ++b) mean += cp[b];
-  mean /= bands;
-  double a = 1.0 - W_SAFE;
-  if (!(mean > -0.5)) {
-    const double fk = (double)fs / W_N * k;
-    int j = 0;
-    while (j + 1 <= bands && 3000.0 * (j + 1) <= fk) ++j;  // the last knot at or below fk, at most `bands`
-    const double x0 = 3000.0 * j, x1 = j + 1 <= bands ? 3000.0 * (j + 1) : fs / 2.0;
-    const double y0 = j == 0 ? -60.0 : cp[j - 1], y1 = j + 1 <= bands ? cp[j] : -W_SAFE;
-    const double s = (fk - x0) / (x1 - x0);
-    a = pow(10.0, (y0 + s * (y1 - y0)) / 20.0);
-  }
-  ap[idx] = a;
+  w_frame_bin(mcep + f * m1, cap + f * bands, m1, bands, fs, k, wt, e ? e + 2 * f : nullptr, sp + idx, ap + idx);
 }
 
 // ---------------------------------------------------------------------------------------------------------- time base
@@ -147,40 +71,15 @@ __global__ __launch_bounds__(W_THREADS) void world_timebase_kernel(WTime a) {
     if (tid == 0) a.pcount[u] = 0;
     return;
   }
-  const double fsd = (double)a.fs, fp = a.fp, two_pi = 2.0 * M_PI;
-  const double lowest = (double)(a.fs / W_N) + 1.0;
+  const double fsd = (double)a.fs;
   const double* f0 = a.f0 + F0;
-  auto cf = [&](int j) {  // coarse F0 / vuv at knot j (j == T: the extrapolated point)
-    if (j < T) return f0[j] < lowest ? 0.0 : f0[j];
-    const double p = f0[T - 1] < lowest ? 0.0 : f0[T - 1], q = f0[T - 2] < lowest ? 0.0 : f0[T - 2];
-    return p * 2 - q;
-  };
-  auto cv = [&](int j) {
-    if (j < T) return cf(j) == 0.0 ? 0.0 : 1.0;
-    return (cf(T - 1) == 0.0 ? 0.0 : 1.0) * 2 - (cf(T - 2) == 0.0 ? 0.0 : 1.0);
-  };
+  auto row = [&](long long j) { return f0[j]; };
   double total = 0.0;  // thread 0's running phase
   long long base = 0;  // pulses written so far
   for (long long c0 = 0; c0 < Y; c0 += W_CHUNK) {
     const int n = (int)min((long long)W_CHUNK, Y - c0);
     for (int t = tid; t < n; t += W_THREADS) {
-      const long long i = c0 + t;
-      const double xi = (double)i / fsd;
-      int j = (int)(xi / fp);
-      j = max(0, min(j, T - 1));
-      while (j > 0 && (double)j * fp > xi) --j;
-      while (j + 1 < T && (double)(j + 1) * fp <= xi) ++j;
-      const double x0 = (double)j * fp, x1 = (double)(j + 1) * fp;
-      const double s = (xi - x0) / (x1 - x0);
-      const double v0 = cv(j), v1 = cv(j + 1);
-      const double v = v0 + s * (v1 - v0) > 0.5 ? 1.0 : 0.0;
-      double fr = W_DEFAULT_F0;
-      if (v != 0.0) {
-        const double g0 = cf(j), g1 = cf(j + 1);
-        fr = g0 + s * (g1 - g0);
-      }
-      ph[t] = two_pi * fr / fsd;
-      vv[t + 1] = (unsigned char)(v != 0.0);
+      ph[t] = w_phase_increment(c0 + t, T, a.fs, a.fp, row, &vv[t + 1]);
     }
     __syncthreads();
     if (tid == 0) {
@@ -190,13 +89,13 @@ __global__ __launch_bounds__(W_THREADS) void world_timebase_kernel(WTime a) {
       }
     }
     __syncthreads();
-    for (int t = tid; t < n; t += W_THREADS) wr[t + 1] = fmod(ph[t], two_pi);
+    for (int t = tid; t < n; t += W_THREADS) wr[t + 1] = w_wrap(ph[t]);
     __syncthreads();
     // pulse at sample i = c0 + t - 1 when |wrap[i + 1] - wrap[i]| > pi (t >= 1 in the first chunk)
     const int per = W_CHUNK / W_THREADS, t0 = tid * per, t1 = min(t0 + per, n);
     const int tstart = c0 == 0 ? 1 : 0;
     int mine = 0;
-    for (int t = max(t0, tstart); t < t1; ++t) mine += fabs(wr[t + 1] - wr[t]) > M_PI;
+    for (int t = max(t0, tstart); t < t1; ++t) mine += w_is_pulse(wr[t], wr[t + 1]);
     cnt[tid] = mine;
     __syncthreads();
     if (tid == 0) {
@@ -210,10 +109,9 @@ __global__ __launch_bounds__(W_THREADS) void world_timebase_kernel(WTime a) {
     __syncthreads();
     long long at = base + cnt[tid];
     for (int t = max(t0, tstart); t < t1; ++t) {
-      if (fabs(wr[t + 1] - wr[t]) > M_PI) {
-        const double y1 = wr[t] - two_pi, y2 = wr[t + 1];
+      if (w_is_pulse(wr[t], wr[t + 1])) {
         a.ppos[S0 + at] = (int)(c0 + t - 1);
-        a.pshift[S0 + at] = -y1 / (y2 - y1) / fsd;
+        a.pshift[S0 + at] = w_pulse_shift(wr[t], wr[t + 1], fsd);
         a.pvuv[S0 + at] = vv[t];
         ++at;
       }
@@ -248,20 +146,11 @@ struct WPulse {
   const double* sp; const double* ap;
   const long long* foff; const long long* soff; const long long* poff; int n_utts;
   const int* ppos; const double* pshift; const unsigned char* pvuv;
-  const double* noise; long long noise_len;
-  const double* twc; const double* tws; const double* dcw;
+  WPulseTables t;
   double* resp; long long p0;
-  int fs; double fp;
 };
 
 __global__ __launch_bounds__(W_THREADS) void world_pulse_kernel(WPulse a) {
-#pragma clang fp contract(off)  // 1 - c * c below: a fused c * c would differ from the restatement at small angles
-  __shared__ double2 Z[W_N];
-  __shared__ double2 Yb[W_N];
-  __shared__ double env[W_K], rat[W_K];
-  __shared__ double tc[W_N / 2], ts[W_N / 2];
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
   const long long p = a.p0 + blockIdx.x;
   const int u = w_find(a.poff, a.n_utts, p);
   const long long pu0 = a.poff[u], pu1 = a.poff[u + 1];
@@ -273,112 +162,10 @@ __global__ __launch_bounds__(W_THREADS) void world_pulse_kernel(WPulse a) {
   const long long nbase = s - a.ppos[a.soff[u]];
   const long long F0 = a.foff[u];
   const int T = (int)(a.foff[u + 1] - F0);
-  double* out = a.resp + (size_t)blockIdx.x * W_N;
-
-  w_stage_twiddles(tc, ts, a.twc, a.tws);
-  // envelope and aperiodic ratio at t = s / fs (WORLD GetSpectralEnvelope / GetAperiodicRatio)
-  const double q = (double)s / (double)a.fs / a.fp;
-  const int lo = min(T - 1, (int)floor(q)), hi = min(T - 1, (int)ceil(q));
-  const double w1 = q - lo;
-  const double* sl = a.sp + (F0 + lo) * W_K;
-  const double* sh = a.sp + (F0 + hi) * W_K;
-  const double* al = a.ap + (F0 + lo) * W_K;
-  const double* ah = a.ap + (F0 + hi) * W_K;
-  for (int k = tid; k < W_K; k += W_THREADS) {
-    const double ql = fmax(0.001, fmin(0.999999999999, al[k]));
-    if (lo == hi) {
-      env[k] = fabs(sl[k]);
-      rat[k] = ql * ql;
-    } else {
-      const double qh = fmax(0.001, fmin(0.999999999999, ah[k]));
-      env[k] = (1.0 - w1) * fabs(sl[k]) + w1 * fabs(sh[k]);
-      const double r = (1.0 - w1) * ql + w1 * qh;
-      rat[k] = r * r;
-    }
-  }
-  __syncthreads();
-  const bool per_on = vuv > 0.5 && rat[0] <= 0.999 && ns > 0;
-  if (ns <= 0) {  // the last pulse of an utterance: no noise, periodic part times sqrt(0)
-    for (int i = tid; i < W_N; i += W_THREADS) out[i] = 0.0;
-    return;
-  }
-  // both log amplitudes as one complex even sequence: FFT -> (periodic cepstrum, aperiodic cepstrum)
-  for (int n = tid; n < W_N; n += W_THREADS) {
-    const int k = n <= W_N / 2 ? n : W_N - n;
-    const double la = per_on ? log(env[k] * (1.0 - rat[k]) + W_SAFE) / 2.0 : 0.0;
-    const double lb = vuv != 0.0 ? log(env[k] * rat[k] + W_SAFE) / 2.0 : log(env[k] + W_SAFE) / 2.0;
-    Z[w_brev(n)] = make_double2(la, lb);
-  }
-  __syncthreads();
-  w_fft(Z, tc, ts, -1.0);
-  // fold (c0, 2 c_1 .. 2 c_{N/2-1}, c_{N/2}, zeros) and transform both folded cepstra at once
-  for (int n = tid; n < W_N; n += W_THREADS) {
-    double2 c = make_double2(0.0, 0.0);
-    if (n <= W_N / 2) {
-      const double g = (n == 0 || n == W_N / 2) ? 1.0 : 2.0;
-      c = make_double2(g * Z[n].x, g * Z[n].y);
-    }
-    Yb[w_brev(n)] = c;
-  }
-  __syncthreads();
-  w_fft(Yb, tc, ts, -1.0);
-  // zero-mean noise of min(ns, N) samples from the fixed randn stream, zero padded
-  const int m = min(ns, W_N);
-  double part = 0.0;
-  for (int n = tid; n < m; n += W_THREADS) part += a.noise[min(nbase + n, a.noise_len - 1)];
-  const double mean = w_block_sum(part, red) / m;
-  for (int n = tid; n < W_N; n += W_THREADS)
-    Z[w_brev(n)] = make_double2(n < m ? a.noise[min(nbase + n, a.noise_len - 1)] - mean : 0.0, 0.0);
-  __syncthreads();
-  w_fft(Z, tc, ts, -1.0);
-  // spectra: periodic P = exp(A / N) e^{-i theta}, aperiodic Q = exp(B / N) * noise; V = P + i Q, Hermitian halves
-  const double coef = 2.0 * M_PI * shift * a.fs / W_N;
-  double2 P[3], Q[3];  // k = tid + 256 r
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int k = tid + W_THREADS * r;
-    if (k > W_N / 2) break;
-    const double2 yk = Yb[k], ym = Yb[(W_N - k) & (W_N - 1)];
-    const double Ar = 0.5 * (yk.x + ym.x), Ai = 0.5 * (yk.y - ym.y);
-    const double dr = yk.x - ym.x, di = yk.y + ym.y;
-    const double Br = 0.5 * di, Bi = -0.5 * dr;
-    double2 pk = make_double2(0.0, 0.0);
-    if (per_on) {
-      const double ea = exp(Ar / W_N), re = ea * cos(Ai / W_N), im = ea * sin(Ai / W_N);
-      const double c = w_cos(coef * k), sn = sqrt(fmax(1.0 - c * c, 0.0));
-      pk = make_double2(re * c + im * sn, im * c - re * sn);
-    }
-    const double eb = exp(Br / W_N), mr = eb * cos(Bi / W_N), mi = eb * sin(Bi / W_N);
-    const double2 nzk = Z[k];
-    double2 qk = make_double2(mr * nzk.x - mi * nzk.y, mr * nzk.y + mi * nzk.x);
-    if (k == 0 || k == W_N / 2) { pk.y = 0.0; qk.y = 0.0; }  // a real inverse transform ignores them
-    P[r] = pk;
-    Q[r] = qk;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int k = tid + W_THREADS * r;
-    if (k > W_N / 2) break;
-    const double2 pk = P[r], qk = Q[r];
-    Z[w_brev(k)] = make_double2(pk.x - qk.y, pk.y + qk.x);
-    if (k > 0 && k < W_N / 2) Z[w_brev(W_N - k)] = make_double2(pk.x + qk.y, -pk.y + qk.x);
-  }
-  __syncthreads();
-  w_fft(Z, tc, ts, 1.0);
-  // fftshift; the periodic part's DC removal; (periodic sqrt(ns) + aperiodic) / N
-  double dcp = 0.0;
-  if (per_on) {
-    for (int n = tid; n < W_N / 2; n += W_THREADS) dcp += Z[n].x;
-    dcp = w_block_sum(dcp, red);
-  }
-  const double sq = sqrt((double)ns);
-  for (int i = tid; i < W_N; i += W_THREADS) {
-    const double2 v = Z[(i + W_N / 2) & (W_N - 1)];
-    double per = 0.0;
-    if (per_on) per = i < W_N / 2 ? -dcp * a.dcw[i] : v.x - dcp * a.dcw[i];
-    out[i] = (per * sq + v.y) / W_N;
-  }
+  const double* sp = a.sp + F0 * W_K;
+  const double* ap = a.ap + F0 * W_K;
+  w_pulse_response(s, T, ns, shift, vuv, nbase, a.t, [&](long long j) { return sp + j * W_K; },
+                   [&](long long j) { return ap + j * W_K; }, a.resp + (size_t)blockIdx.x * W_N);
 }
 
 // y[g] += the responses of the chunk's pulses that cover sample g, in pulse order
@@ -586,7 +373,7 @@ extern "C" int crk_world_synthesis(void* h, const double* f0, const double* mcep
   for (long long p0 = 0; p0 < P; p0 += w->capacity) {
     const long long np = std::min((long long)w->capacity, P - p0);
     WPulse a{ws.sp, ws.ap, frame_offsets, sample_offsets, ws.poff, n_utts, ws.ppos, ws.pshift, ws.pvuv,
-             w->noise, w->noise_len, w->twc, w->tws, w->dcw, ws.resp, p0, w->fs, w->fp};
+             WPulseTables{w->noise, w->noise_len, w->twc, w->tws, w->dcw, w->fs, w->fp}, ws.resp, p0};
     world_pulse_kernel<<<dim3((unsigned)np), dim3(W_THREADS), 0, st>>>(a);
     CRK_CHECK_LAUNCH();
     world_ola_kernel<<<dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, st>>>(

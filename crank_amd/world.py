@@ -24,6 +24,10 @@ each block of a live stream's frames and finishes the contour into the ``lcf0`` 
 ``StreamingMcep`` (``WorldAnalyzer.streaming``) is ``mcep_batch`` frame by frame from live streams of samples and F0 rows,
 bit for bit (csrc/wana_stream_kernels.hip, crk_wana_stream_*; the definition is tests/wana_stream_ref.py, DESIGN.md
 section 6o); ``analysis_capacities`` sizes its ring and its F0 queue.
+
+``StreamingWorldSynthesizer`` (``WorldSynthesizer.streaming``) is ``synthesis_batch`` sample by sample from live streams of
+frame rows, bit for bit (csrc/world_stream_kernels.hip, crk_wsyn_stream_*; the definition is tests/wsyn_stream_ref.py,
+DESIGN.md section 6p); ``synthesis_capacities`` sizes its row queue, its sample ring and what one push can add and emit.
 """
 import ctypes
 
@@ -208,6 +212,12 @@ class WorldSynthesizer:
             out.append((p, ns, shift[s0:s0 + c].cpu().numpy(), vuv[s0:s0 + c].cpu().numpy().astype(np.float64)))
             s0 += n
         return out
+
+    def streaming(self, n_streams, max_rows_in, order1, **kw):
+        """A ``StreamingWorldSynthesizer`` at this synthesizer's fs, shiftms, alpha and device (with a handle of its
+        own: no call on this object can move the table a captured push reads)."""
+        kw.setdefault("device", self.device)
+        return StreamingWorldSynthesizer(self.fs, self.shiftms, n_streams, max_rows_in, order1, self.alpha, **kw)
 
     # -- eval outputs
     def vocode_eval_outputs(self, outputs, clip=True):
@@ -1181,6 +1191,241 @@ class StreamingMcep:
                 _lib.ptr(self._mean), _lib.ptr(self._scale), out["mcep"].data_ptr(), _lib.ptr(out.get("sp")),
                 out["feats"].data_ptr(), out["n_frames"].data_ptr(), out["first"].data_ptr(), out["n_dropped"].data_ptr(),
                 stream_ptr()), "crk_wana_stream_push")
+        return out
+
+
+def longest_pulse_interval(fs, shiftms, fftl=FFTL):
+    """The most samples between two consecutive pulses of WORLD's time base away from an utterance's last frame.  A
+    pulse lies at i where the phase total crosses a multiple of 2 pi inside sample i + 1's increment, so an interval is
+    one more than the longest run of increments that sum to less than one cycle.  The slowest steady contour is the
+    lowest F0 the time base keeps, L = fs // fftl + 1 (anything below is unvoiced and pulses at 500 Hz): fs / L
+    increments per cycle.  Next to an unvoiced row a voiced row's F0 is interpolated down to half over the voiced half
+    of the frame (frame fraction s < 0.5 falling, s > 0.5 rising; s = 0.5 is unvoiced); such a ramp falls short of L by
+    L times the sum of min(s, 1 - s) over its samples: h (h + 1) / (2 shift) increments' worth with h = floor(shift / 2)
+    when the frame holds a whole number `shift` of samples (a sample at s = 0.5 counted on both sides: its fraction is a
+    rounded quotient), and below shift / 8 + 1 / 2 otherwise.  A run holds two ramps
+    (one each end) and no more: between two others lies a whole unvoiced frame, whose 500 Hz repay both while 500 >=
+    1.25 L.  So with d the two ramps' shortfall a run has fewer than fs / L + d increments: the interval is at most
+    ceil(fs / L + d)."""
+    fs, shift = int(fs), float(shiftms) / 1000.0 * int(fs)
+    lowest = fs // int(fftl) + 1
+    if not 500.0 >= 1.25 * lowest:
+        raise ValueError(f"fs {fs}: the lowest F0 {lowest} Hz is too close to the unvoiced pulse rate")
+    if shift == int(shift):
+        h = int(shift) // 2
+        d = h * (h + 1) / shift
+    else:
+        d = shift / 4.0 + 1.0
+    return int(np.ceil(fs / lowest + d))
+
+
+def synthesis_capacities(fs, shiftms, max_rows_in, f0_ceil=1000.0, fftl=FFTL):
+    """Capacities of a ``StreamingWorldSynthesizer`` that can never set flag 1, 2, 32 or 64 while every F0 row lies within
+    ``f0_ceil``: a dict of ``rows`` (the row queue), ``ring`` (the sample ring), ``pulses`` (the pulses one push adds)
+    and ``out`` (the samples one push emits, ``max_out``).  Closed forms, with shift = shiftms fs / 1000 samples per
+    frame, r = max_rows_in, a = fftl / 2 - 1 and b = fftl / 2 (a pulse at s covers s - a .. s + b), I =
+    ``longest_pulse_interval`` and n(R) = ceil((R - 1) shift) the time front after R rows:
+
+    * the front's own comparison of rounded times puts n(R) at that value or one past it, so a push moves the front by
+      at most D = ceil(r shift) + 1, an end push by at most D_end = floor((r + 1) shift) (to y_length(R + r) = floor((R +
+      r) shift); 1 more where shift is no whole number and the product can round up to one);
+    * the pending pulse P has no successor among the n samples with a phase, and its successor comes within I: P >=
+      n - 1 - I.  No sample at or past P - a has left, so before a push at most I + 1 + a samples with a phase are
+      held.  A push needs the ring up to the reach of the last pulse it can find, n' - 2 + b, an end push up to
+      y_length: ``ring`` = I + a + max(D + b, D_end + 1);
+    * at an end everything held leaves: ``out`` = I + 1 + a + D_end (a push that does not end emits at most D + I);
+    * a held row is one the pending pulse or the front still reads, from floor(P / fs / fp) on, a rounded quotient that
+      can fall one below floor(P / shift); with n >= (R - 1) shift that is 2 + ceil((I + 1) / shift) rows, and a push
+      brings r more: ``rows``;
+    * a push adds at most the pulses it finds (and at an end the pending one besides).  D increments at no more than F =
+      max(f0_ceil, 500) Hz (unvoiced samples pulse at 500 Hz) cross floor(D F / fs) + 1 multiples at the most.  In an
+      utterance's last frame the extrapolated knot reaches 2 f0_ceil - or goes negative, which is slower: its
+      increments sum to at most f0_ceil (shift + (shift + 1) / 2) / fs cycles, or 500 shift / fs: ``pulses`` = max(floor(D F
+      / fs) + 1, floor(((D_end - shift) F + max(f0_ceil (3 shift + 1) / 2, 500 shift)) / fs) + 2).
+
+    tests/test_wsyn_stream_cpu.py walks row histories at toy sizes (``fftl`` is the toy's) and finds, for each capacity,
+    a history that overflows one unit less."""
+    fs, r, N = int(fs), int(max_rows_in), int(fftl)
+    shift = float(shiftms) / 1000.0 * fs
+    if not shift >= 2.0 or r < 1 or not 0.0 < float(f0_ceil) <= fs / 4.0 or N < 4:
+        raise ValueError("synthesis_capacities: shiftms fs / 1000 >= 2, max_rows_in >= 1, 0 < f0_ceil <= fs / 4")
+    a, b = N // 2 - 1, N // 2
+    interval = longest_pulse_interval(fs, shiftms, N)
+    D = int(np.ceil(r * shift)) + 1
+    D_end = int(np.floor((r + 1) * shift)) + (0 if shift == int(shift) else 1)
+    F = max(float(f0_ceil), 500.0)
+    last = max(float(f0_ceil) * (3.0 * shift + 1.0) / 2.0, 500.0 * shift)
+    return {"rows": 2 + int(np.ceil((interval + 1) / shift)) + r,
+            "ring": interval + a + max(D + b, D_end + 1),
+            "pulses": max(int(np.floor(D * F / fs)) + 1, int(np.floor(((D_end - shift) * F + last) / fs)) + 2),
+            "out": interval + 1 + a + D_end}
+
+
+class StreamingWorldSynthesizer:
+    """``push`` takes the next frame rows of ``n_streams`` independent streams - F0, mel-cepstrum, coded aperiodicity, and
+    the rmcep rows with ``power_mod`` - and returns the samples ``WorldSynthesizer.synthesis_batch`` writes for the whole
+    utterance, bit for bit under any cut, as soon as no pulse can reach them any more (csrc/world_stream_kernels.hip,
+    ``crk_wsyn_stream_*``; the definition is tests/wsyn_stream_ref.py).  Stream i is row i of every
+    argument; row k of a stream's utterance is frame k.
+
+    After a push with R rows so far the time base has run over every sample whose frame is at most R - 2 (its next row
+    is there).  A pulse at i is found when sample i + 1 has its phase and added when its successor is found, which gives
+    its noise size.  Sample i leaves once i + 511 < B, B the pending pulse (found, not added) or else the last sample
+    with a phase: readiness depends on the contour, so the count comes back as a device int32.  The push whose ``end``
+    flag is set runs the front to ``y_length(R)`` with the offline clamp and extrapolated knot, adds the last pulse with
+    noise size 0, emits every sample and returns the stream to its start state.
+
+    The open rows, the phase carry, the pending pulse and a float64 ring of the samples still open stay on the device;
+    ``n_rows`` and ``end`` are device tensors and nothing is read back, so a push - five launches, six with
+    ``power_mod`` - can be captured in a graph.  ``capacities`` defaults to ``synthesis_capacities`` (which cannot
+    overflow within ``f0_ceil``); the randn table is reserved once, for ``max_utt_samples``, on a handle of the stream's
+    own.  Sticky flags, raised by ``status()``: 1 the sample ring overflowed, 2 the row queue overflowed (the newest rows
+    are dropped and counted in ``n_dropped``), 4 an utterance outgrew ``max_utt_samples`` (the noise offset is clamped),
+    8 an end push on a stream holding a single row (dropped and counted; nothing leaves), 16 an F0 row not finite,
+    negative or above ``f0_ceil`` (synthesised as unvoiced), 32 a push found more pulses than its budget, 64 more samples
+    were ready than ``max_out``.  There is no torch or CPU fallback."""
+
+    FLAGS = {1: "the sample ring overflowed (capacities['ring'])",
+             2: "the row queue overflowed (capacities['rows'])",
+             4: "an utterance's noise offsets passed the randn table (max_utt_samples)",
+             8: "an end push on a stream holding one row",
+             16: "an F0 row not finite, negative or above f0_ceil",
+             32: "a push found more pulses than its budget (capacities['pulses'])",
+             64: "more samples were ready than max_out (capacities['out'])"}
+
+    def __init__(self, fs, shiftms, n_streams, max_rows_in, order1, alpha, power_mod=False, f0_ceil=1000.0,
+                 max_utt_samples=1 << 21, capacities=None, device="cuda"):
+        if int(fs) != fs or n_bands(int(fs)) < 1 or int(fs) > 192000:
+            raise ValueError(f"fs {fs}: WORLD's coded aperiodicity needs 12000 < fs <= 192000 Hz")
+        if not float(shiftms) * int(fs) / 1000.0 >= 2.0:
+            raise ValueError(f"shiftms {shiftms}: a frame must hold at least 2 samples")
+        if not 1 <= int(order1) <= MAX_ORDER1:
+            raise ValueError(f"order1 {order1}: the kernels take 1 .. {MAX_ORDER1} coefficients")
+        if not abs(float(alpha)) < 1.0:
+            raise ValueError(f"alpha {alpha}: the all-pass constant must lie in (-1, 1)")
+        if not 0.0 < float(f0_ceil) <= int(fs) / 4.0:
+            raise ValueError(f"f0_ceil {f0_ceil}: must lie in (0, fs / 4]")
+        if capacities is None:
+            capacities = synthesis_capacities(fs, shiftms, max_rows_in, f0_ceil)
+        caps = {k: capacities[k] for k in ("rows", "ring", "pulses", "out")}
+        sizes = dict(n_streams=n_streams, max_rows_in=max_rows_in, max_utt_samples=max_utt_samples, **caps)
+        for name, v in sizes.items():
+            if int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} = {v}: must be a positive integer")
+        if (int(n_streams) > 65535 or int(max_rows_in) > 4096 or int(caps["rows"]) > 65536 or int(caps["pulses"]) > 65535
+                or max(int(caps["ring"]), int(caps["out"])) > 1 << 24 or int(max_utt_samples) > 1 << 31):
+            raise ValueError("at most 65535 streams, 4096 rows a push, 65536 queued rows, 65535 pulses a push, a ring and "
+                             "an output of 2^24 samples, utterances of 2^31 samples")
+        if int(caps["rows"]) < 2 or int(caps["ring"]) < FFTL:
+            raise ValueError(f"capacities: at least 2 rows and a ring of {FFTL} samples")
+        self.device = torch.device(device)
+        require_gpu(self.device, "streaming WORLD synthesis")
+        self.fs, self.shiftms, self.alpha, self.order1 = int(fs), float(shiftms), float(alpha), int(order1)
+        self.bands = n_bands(self.fs)
+        self.n_streams, self.max_rows_in, self.power_mod = int(n_streams), int(max_rows_in), bool(power_mod)
+        self.f0_ceil, self.max_utt_samples = float(f0_ceil), int(max_utt_samples)
+        self.capacities = {k: int(v) for k, v in caps.items()}
+        L = _lib.lib()
+        self._handle = self._world = None
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            # a World handle of its own: its randn table is reserved once, here, and no offline call grows it
+            self._world = made(L.crk_world_create(self.fs, FFTL, self.shiftms, self.alpha, self.order1, self.bands, 1),
+                               "crk_world_create")
+            c = self.capacities
+            check(L.crk_wsyn_stream_create(self._world, self.n_streams, self.max_rows_in, c["rows"], c["ring"], c["pulses"],
+                                           c["out"], self.f0_ceil, 1 if self.power_mod else 0, self.max_utt_samples,
+                                           ctypes.byref(h)), "crk_wsyn_stream_create")
+            self._handle = made(h, "crk_wsyn_stream_create")
+        self.max_out = int(L.crk_wsyn_stream_max_out(self._handle))
+
+    def __del__(self):
+        release(self, "_handle", "crk_wsyn_stream_destroy")
+        release(self, "_world", "crk_world_destroy")
+
+    def state_bytes(self):
+        return int(_lib.lib().crk_wsyn_stream_state_bytes(self._handle))
+
+    def reset(self, streams=None):
+        """``streams`` (all of them by default) return to their start state; open samples are dropped, flags cleared."""
+        reset_streams(self._handle, "crk_wsyn_stream_reset", streams, self.device)
+
+    def flags(self):
+        """Synchronises; the sticky flag word of every stream (host list)."""
+        flags = (ctypes.c_int * self.n_streams)()
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_wsyn_stream_status(self._handle, flags, stream_ptr()), "crk_wsyn_stream_status")
+        return list(flags)
+
+    def status(self):
+        """Synchronises; raises if any stream has set a flag since its last reset."""
+        bad = {s: f for s, f in enumerate(self.flags()) if f}
+        if bad:
+            what = "; ".join(f"stream {s}: " + ", ".join(t for b, t in self.FLAGS.items() if f & b) for s, f in bad.items())
+            raise RuntimeError(f"streaming WORLD synthesis: {what}")
+
+    def empty_outputs(self):
+        """Output buffers of one push, in the form ``push(out=...)`` takes and returns."""
+        S, dev = self.n_streams, self.device
+        return {"y": torch.empty(S, self.max_out, dtype=torch.float64, device=dev),
+                "n_samples": torch.empty(S, dtype=torch.int32, device=dev),
+                "n_dropped": torch.empty(S, dtype=torch.int32, device=dev)}
+
+    def _rows(self, t, S, R, width, what):
+        shape = (S, R) if width is None else (S, R, width)
+        ok = isinstance(t, torch.Tensor) and t.device.type == "cuda" and t.dtype == torch.float64
+        if ok and width is None and tuple(t.shape) == (S, R, 1):
+            t = t.reshape(S, R)
+        if not ok or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: a float64 {shape} tensor on the GPU")
+        return t.contiguous()
+
+    def _dev_ints(self, v, S, what):
+        if v is None:
+            return None
+        if (not isinstance(v, torch.Tensor) or v.device.type != "cuda" or v.dtype != torch.int32
+                or tuple(v.shape) != (S,)):
+            raise ValueError(f"{what}: an int32 ({S},) tensor on the GPU (or None)")
+        return v.contiguous()
+
+    def push(self, f0, mcep, codeap, rmcep=None, n_rows=None, end=None, out=None, clip=False):
+        """f0 (S, R) or (S, R, 1), mcep (S, R, order1), codeap (S, R, bands) and, with ``power_mod``, rmcep (S, R, order1):
+        float64 on the GPU, R <= max_rows_in (R may be 0); n_rows, end: int32 (S,) on the GPU or None (R, 0) - the rows
+        that count per stream and non-zero where this push ends the stream's utterance.  Returns ``y`` (S, max_out)
+        float64 (not clipped; ``clip=True`` clamps to [-1, 1] as ``world2wav`` does) and ``n_samples``, ``n_dropped``
+        int32 (S,): the samples written at the start of each stream's row and the rows dropped; columns at and past
+        ``n_samples`` are not written.  Anything refused raises ValueError before any launch and leaves outputs and
+        state untouched.  out: buffers to write into (``empty_outputs``)."""
+        S = self.n_streams
+        if not isinstance(f0, torch.Tensor) or f0.dim() not in (2, 3) or f0.shape[0] != S:
+            raise ValueError(f"f0: a float64 ({S}, R) or ({S}, R, 1) tensor on the GPU")
+        R = int(f0.shape[1])
+        if R > self.max_rows_in:
+            raise ValueError(f"f0: {R} rows per push, max_rows_in is {self.max_rows_in}")
+        if (rmcep is not None) != self.power_mod:
+            raise ValueError("rmcep: given exactly when the handle was made with power_mod")
+        f0 = self._rows(f0, S, R, None, "f0")
+        mcep = self._rows(mcep, S, R, self.order1, "mcep")
+        codeap = self._rows(codeap, S, R, self.bands, "codeap")
+        if rmcep is not None:
+            rmcep = self._rows(rmcep, S, R, self.order1, "rmcep")
+        n_rows, end = (self._dev_ints(v, S, what) for v, what in ((n_rows, "n_rows"), (end, "end")))
+        if out is None:
+            out = self.empty_outputs()
+        else:
+            t = out.get("y")
+            if (t is None or t.device.type != "cuda" or t.dtype != torch.float64 or tuple(t.shape) != (S, self.max_out)
+                    or not t.is_contiguous()):
+                raise ValueError(f"out['y']: float64 ({S}, {self.max_out}) on the GPU (empty_outputs)")
+            for name in ("n_samples", "n_dropped"):
+                t = out.get(name)
+                if t is None or t.device.type != "cuda" or t.dtype != torch.int32 or tuple(t.shape) != (S,):
+                    raise ValueError(f"out[{name!r}]: int32 ({S},) on the GPU (empty_outputs)")
+        with torch.cuda.device(self.device):
+            check(_lib.lib().crk_wsyn_stream_push(
+                self._handle, f0.data_ptr(), mcep.data_ptr(), codeap.data_ptr(), _lib.ptr(rmcep), _lib.ptr(n_rows), R,
+                _lib.ptr(end), S, 1 if clip else 0, out["y"].data_ptr(), out["n_samples"].data_ptr(),
+                out["n_dropped"].data_ptr(), stream_ptr()), "crk_wsyn_stream_push")
         return out
 
 

@@ -901,6 +901,54 @@ int crk_wana_stream_push(void* st, const float* x, int ldx, const int* n_valid, 
                          double* mcep, double* sp, float* feats, int* n_frames, int* first, int* n_dropped, void* stream);
 int crk_wana_stream_status(void* st, int* flags, void* stream);
 
+/* ---- Streaming WORLD synthesis (csrc/world_stream_kernels.hip) ----------------------------------
+ * The samples crk_world_synthesis writes for a whole utterance, from a live stream of frame rows: F0, mel-cepstrum, coded
+ * aperiodicity (and rmcep with power modification) in, every sample out bit for bit as soon as no pulse can reach it.
+ * `world` is a crk_world_create handle of the stream's own (fs, shiftms, alpha, order1, bands are its); it must outlive
+ * the stream handle and no other call may use it: crk_wsyn_stream_create reserves its randn table for max_utt_samples
+ * values (crk_world_reserve) and a captured push reads that table.  Per stream the handle keeps, on the device: a queue of
+ * at most row_capacity frame rows (F0, sp [513], ap [513]; row k of an utterance is frame k, at k % row_capacity); the
+ * time base's float64 phase total, the last sample's wrapped phase and vuv; 64-bit counts of rows, samples with a phase
+ * and samples that left; the utterance's first pulse; the pending pulse (found, not yet added); a power-of-two float64
+ * ring of at least ring_capacity samples addressed by absolute position; a sticky flag word; and per push a list of
+ * max_pulses + 1 pulses and max_pulses responses of 1024 doubles.  crk_wsyn_stream_create is the one call that allocates
+ * (it synchronises).  CRK_ERR_ARG: a null pointer, n_streams, max_rows_in, max_pulses, max_out or max_utt_samples below 1,
+ * row_capacity below 2, ring_capacity below 1024, f0_ceil not in (0, fs / 4]; CRK_ERR_UNSUPPORTED: more than 65535
+ * streams, max_rows_in above 4096, row_capacity above 65536, ring_capacity or max_out above 2^24, max_pulses above 65535,
+ * max_utt_samples above 2^31, fewer than 2 samples per frame.  crk_wsyn_stream_max_out: the most samples one push emits.
+ * crk_wsyn_stream_reset: the streams in the HOST array stream_ids (NULL: all) return to their start state, ring zeroed,
+ * flags cleared.
+ *
+ * crk_wsyn_stream_push: f0 double [S][R] (Hz, 0 = unvoiced), mcep [S][R][order1], codeap [S][R][bands], rmcep
+ * [S][R][order1] (given exactly when the handle has power_mod, R > 0), all contiguous DEVICE float64; n_rows, end DEVICE
+ * int32 [S] or NULL (R, 0; n_rows is clamped to 0 .. R).  The rows are appended; the time base runs over every sample
+ * whose frame is at most rows - 2 (at an end: to y_length(rows) with the offline clamp and extrapolated knot); a pulse at
+ * i is found when sample i + 1 has its phase and added when its successor is found (at an end the last one with noise
+ * size 0); sample i leaves, in order, once i + 511 < B, B the pending pulse or else the last sample with a phase; at an
+ * end every sample below y_length leaves and the stream returns to its start state.  The j-th sample to leave is y
+ * [S][max_out] column j (clamped to [-1, 1] with clip != 0); columns at and past n_samples[s] are not written.
+ * n_samples, n_dropped DEVICE int32 [S] are written for every stream.  Sticky flags: 1 a push needed more than
+ * ring_capacity samples of ring (adds past it are lost); 2 the row queue overflowed: the newest rows are dropped and
+ * counted in n_dropped; 4 a pulse's noise offset passed max_utt_samples: the kernel's clamp applies; 8 an end push on a
+ * stream holding one row: the row is dropped and counted, nothing leaves (an end on an empty stream is a no-op); 16 an F0
+ * row not finite, negative or above f0_ceil: synthesised as 0; 32 a push found more pulses than max_pulses (the last are
+ * lost); 64 more samples were ready than max_out (the rest are lost).  Every index into queue, ring, list and responses
+ * is masked or clamped.  Judged before any launch, state and outputs untouched: CRK_ERR_ARG for S < 1, R < 0, a null
+ * pointer (n_rows, end excepted; the row inputs only when R > 0), rmcep missing with power_mod or given without;
+ * CRK_ERR_UNSUPPORTED for S > n_streams, R > max_rows_in.  Five launches, six with power_mod, whose grids depend on the
+ * handle and S alone; never allocates, never synchronises, reads nothing back, no atomics: capturable.
+ * crk_wsyn_stream_status synchronises and copies the flags of all n_streams streams to HOST int32. */
+int crk_wsyn_stream_create(void* world, int n_streams, int max_rows_in, int row_capacity, int ring_capacity, int max_pulses,
+                           int max_out, double f0_ceil, int power_mod, long long max_utt_samples, void** handle);
+void crk_wsyn_stream_destroy(void* st);
+long long crk_wsyn_stream_state_bytes(void* st);
+int crk_wsyn_stream_max_out(void* st);
+int crk_wsyn_stream_reset(void* st, const int* stream_ids, int n, void* stream);
+int crk_wsyn_stream_push(void* st, const double* f0, const double* mcep, const double* codeap, const double* rmcep,
+                         const int* n_rows, int R, const int* end, int S, int clip, double* y, int* n_samples,
+                         int* n_dropped, void* stream);
+int crk_wsyn_stream_status(void* st, int* flags, void* stream);
+
 /* ---- Griffin-Lim waveform synthesis for log-mel models (csrc/griffin_lim_kernels.hip) ----
  * Replaces the reference's mlfb2wav (crank/utils/utils.py:94-107, 210-269: logmelspc_to_linearspc, griffin_lim -> librosa.griffinlim
  * with momentum 0.99, centred reflect-padded STFT, periodic Hann window; called by BaseTrainer._save_decoded_mlfb,
